@@ -17,11 +17,15 @@ Linear / Conv law drawn on the GPU, adapter to_out ~ N(0, 0.02^2)), resident in 
 are independent: they shard over ranks with no per-step collective; rank 0 draws the weights and broadcasts them once
 as one flat buffer over RCCL.
 
-Prints ONE JSON line (rank 0) with the contract fields plus
+A plain run sets up, warms up, times exactly K steps (one window) and prints ONE JSON line (rank 0) with the contract
+fields (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`, ...); `--dump-outputs DIR` then also writes
+the latents the last timed step produced as DIR/latents.npy (float32).  With `--full` the line carries in addition
   "roofline":     live HIP-event timing of the dominant kernel class over one instrumented eager step,
   "cpu_baseline": the CPU oracle (fp32, unfused torch graph = the reference's op graph) timed on the host cores on ONE
                   CFG UNet forward of this same workload (rank 0, N = 1 only), and `parity`: the HIP forward compared
-                  with that oracle forward on the same weights and inputs.
+                  with that oracle forward on the same weights and inputs,
+  "stream_modes": the other residual-stream mode timed and checked beside the timed one,
+and the timed window is repeated (`--windows`, 5 by default) with the median window reported.
 """
 import argparse
 import json
@@ -46,6 +50,8 @@ PARITY_ABS_TOL = 4.0e-3
 # rounding patterns, the RMS is stable to 1 % (3.6 - 3.7e-4 on the config-2 forward since round 3) -- the gate that catches a real
 # numerical regression
 PARITY_RMS_TOL = 4.5e-4
+# --dump-outputs writes at most this many bytes in all (a fixed, seeded sample of an output above it)
+DUMP_MAX_BYTES = 64 << 20
 
 SD15 = dict(sample_size=64, in_channels=4, out_channels=4, block_out_channels=(320, 640, 1280, 1280),
             layers_per_block=2, cross_attention_dim=768, num_attention_heads=8, norm_num_groups=32,
@@ -91,6 +97,31 @@ def sample_inputs(index, frames, h_lat, ip):
     return d
 
 
+def host_threads(cap=32):
+    """threads for the CPU oracle: the cores this process may run on, no more than OMP_NUM_THREADS when that is set
+    (os.cpu_count() counts the whole host, and a pool sized by it oversubscribes a CPU quota), at most `cap`."""
+    n = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+    omp = os.environ.get("OMP_NUM_THREADS", "")
+    if omp.isdigit() and int(omp) > 0:
+        n = min(n, int(omp))
+    return max(1, min(cap, n))
+
+
+def dump_outputs(out_dir, arrays, seed=0):
+    """`--dump-outputs DIR`: each array as DIR/<name>.npy in float32.  Above DUMP_MAX_BYTES in all, every array is
+    replaced by the same fixed, seeded sample of its flattened elements (same shape and seed -> same positions)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(a.numel() * 4 for a in arrays.values())
+    for name, a in arrays.items():
+        a = a.detach().float().cpu()
+        if total > DUMP_MAX_BYTES:
+            n = max(1, a.numel() * DUMP_MAX_BYTES // total)
+            idx = torch.randperm(a.numel(), generator=torch.Generator().manual_seed(seed))[:n].sort().values
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, f"{name}.npy"), a.numpy())
+
+
 def cpu_baseline_and_parity(model, ip_sd, frames, h_lat, dev, n_forwards=3):
     """`n_forwards` CFG UNet forwards (B = 2) of this workload through the CPU oracle on the host cores, with the HIP
     model's weights; the MEDIAN time is the baseline, and the forward is compared with the HIP forward of the
@@ -122,7 +153,7 @@ def cpu_baseline_and_parity(model, ip_sd, frames, h_lat, dev, n_forwards=3):
         ie = torch.randn(2, 1024, generator=g).half().float()
         added, added_d = {"image_embeds": ie}, {"image_embeds": ie.to(dev)}
     t = torch.tensor([481, 481])
-    cores = min(32, os.cpu_count() or 1)
+    cores = host_threads()
     torch.set_num_threads(cores)
     try:
         with torch.no_grad():
@@ -205,7 +236,7 @@ def latent_parity(args, model, dev):
     ou.load_state_dict({k: v.detach().float().cpu() for k, v in model.state_dict().items()})
     ou.eval()
     oblocks.Attention._sdpa = lambda self, q, k, v: F.scaled_dot_product_attention(q, k, v, scale=self.scale)
-    cores = min(32, os.cpu_count() or 1)
+    cores = host_threads()
     torch.set_num_threads(cores)
     g = torch.Generator().manual_seed(21)
     h16 = lambda t: t.half().float()
@@ -464,9 +495,15 @@ def main():
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--latent-parity", type=int, default=0,
                     help="N > 0: compare the final latents of N DDIM steps with the CPU oracle's pipeline and exit")
-    ap.add_argument("--windows", type=int, default=5,
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: repeated timed windows, the instrumented eager step "
+                         "(roofline, kernel classes, --shapes), the other residual-stream mode, the CPU-oracle baseline "
+                         "and the parity gate (exit code 3 on failure)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed (the latents) as DIR/<name>.npy")
+    ap.add_argument("--windows", type=int, default=None,
                     help="the K-step timed window is repeated this many times (each bracketed by barrier + synchronize); "
-                         "the line reports the MEDIAN window, and min / max as `window_ms_per_step`")
+                         "the line reports the MEDIAN window, and min / max as `window_ms_per_step` (default 1, 5 with --full)")
     ap.add_argument("--cpu-forwards", type=int, default=3, help="oracle forwards timed for cpu_baseline (median)")
     ap.add_argument("--train", action="store_true",
                     help="time the ADAPTER TRAINING STEP instead (SURVEY 8 f4: forward + backward + one all-reduce of the "
@@ -479,13 +516,21 @@ def main():
                          "minutes of host time at 32 f x 768^2; profiles/r5_parity_configs.jsonl)")
     ap.add_argument("--precise", action="store_true",
                     help="time the step with the PRECISE residual stream (fp16 hi + lo pairs between the modules, DESIGN 2.1; "
-                         "blocks.set_precise_stream); without it the default single-GPU run times the default stream and adds "
-                         "the precise mode's ms_per_step and parity beside it (`stream_modes`)")
+                         "blocks.set_precise_stream); without it the default single-GPU run times the default stream, and with "
+                         "--full adds the precise mode's ms_per_step and parity beside it (`stream_modes`)")
     ap.add_argument("--dry-run", action="store_true",
                     help="rehearse the multi-rank plumbing on a box WITHOUT GPUs: launcher, rendezvous, gloo group, flat "
                          "weight broadcast, pair sharding, timed loop with a stub step, MAX all-reduce, JSON line "
                          "(marked \"dry_run\": true; not a measurement)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.windows is None:
+        args.windows = 5 if args.full else 1
+    if args.shapes and not args.full:
+        ap.error("--shapes needs --full (it comes from the instrumented eager step)")
+    if args.dump_outputs and (args.train or args.latent_parity or args.parity_only or args.dry_run):
+        ap.error("--dump-outputs applies to the timed inference step only")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -607,11 +652,14 @@ def main():
                               lambda: st["step_idx"].zero_(), torch.cuda.synchronize, world, dev)
         elapsed = sorted(windows)[len(windows) // 2]
         finite = bool(torch.isfinite(st["latents"]).all().item())
+        # ---- what the last timed step computed, before anything below advances the same buffers
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, {"latents": st["latents"]})
 
-        # ---- live per-kernel-class roofline (rank 0): one instrumented eager step behind a GPU backlog so that
+        # ---- live per-kernel-class roofline (rank 0, --full): one instrumented eager step behind a GPU backlog so that
         #      the event pairs bracket back-to-back kernels, not host launch gaps
         roof, classes = None, None
-        if rank == 0:
+        if rank == 0 and args.full:
             load_group(groups[0])
             torch.cuda._sleep(int(2.0e8))   # ~0.1 s device-side spin (not one of our kernels): the host runs ahead
             # (single-stream for this one step: the event pairs must bracket one kernel each.  The timed replays above are
@@ -669,10 +717,10 @@ def main():
                     roof["peak_measured_source"] = f"profiles/{name} (MFMA-saturating loop / stream copy, this pool)"
                     break
 
-        # ---- the OTHER residual-stream mode, timed the same way over two windows (default single-GPU run only): the line
+        # ---- the OTHER residual-stream mode, timed the same way over two windows (--full single-GPU run only): the line
         #      carries ms_per_step and parity of both modes
         other_mode = None
-        if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.no_graph:
+        if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not args.no_graph:
             prev = hblocks.set_precise_stream(not hblocks.precise_stream())
             try:
                 load_group(groups[0])
@@ -698,7 +746,7 @@ def main():
     graph = None
     t_gpu_done = time.time()
     cpu_base, parity = None, None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu_base, parity = cpu_baseline_and_parity(model, ip_sd, F, h_lat, dev, n_forwards=args.cpu_forwards)
         parity["tolerance"], parity["rms_tolerance"] = PARITY_ABS_TOL, PARITY_RMS_TOL
         parity["parity_ok"] = bool(parity["max_abs_err"] <= PARITY_ABS_TOL and parity["rms_err"] <= PARITY_RMS_TOL)
@@ -741,7 +789,7 @@ def main():
             "ms_per_step": ms, "window_ms_per_step": {"n": len(windows), "median": ms,
                                                       "min": min(windows) / (len(groups) * args.steps) * 1e3,
                                                       "max": max(windows) / (len(groups) * args.steps) * 1e3},
-            "higher_is_better": True, "scaling": "weak" if not args.pairs else "strong",
+            "higher_is_better": True, "scaling": "weak" if not args.pairs else "strong", "full": bool(args.full),
             "ranks_in_rccl_group": (dist.get_world_size() if world > 1 else 1),
             "vs_baseline": None, "dtype": "f16", "data": "synthetic",
             "config": {"workload": f"SD-v1.5 + motion-adapter-v1-5-2 + I2V-Adapter topology, {F}f x {args.size}x{args.size}, "

@@ -574,7 +574,7 @@ def test_config4_two_sample_cfg_forward_vs_oracle(dev, pair_ip):
     compare(got[sel], one, abs_tol=FWD_ABS_TOL, name="config 4: sample 0 inside a two-sample forward vs alone")
 
 
-def test_rccl_world_size_1_weight_broadcast_full_model():
+def test_rccl_world_size_1_weight_broadcast_full_model(dev):
     """the RCCL branch of bench.py on ONE GPU: `init_process_group("nccl", world_size=1, device_id=cuda:0)`, the flat
     2.76 GB state-dict broadcast of the SD-1.5-width model on the device, the MAX all-reduce of the elapsed time and the
     barrier.  (The 8-GPU run is the driver's; this exercises RCCL initialisation and the device flatten path.)  In a child

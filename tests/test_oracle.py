@@ -175,7 +175,13 @@ def test_add_noise_known_answer():
         sa = sa.unsqueeze(-1)
     assert torch.all(torch.eq(noised[:, 0], x[:, 0] * sa))
     gold = load_file(os.path.join(GOLD, "oracle_outputs.safetensors"))["ddpm_sqrt_alphas_cumprod"]
-    assert torch.equal(sch.alphas_cumprod ** 0.5, gold)
+    # the golden schedule was recorded on one host: torch.linspace's float32 betas round differently with the CPU kernel
+    # torch picks for the host (AVX-512 / AVX2 / scalar), which moves entries of the cumulative product by an ulp or two
+    # (2 on the scalar kernel) -- the pin is a few float32 ulps, not bit equality across hosts
+    got = sch.alphas_cumprod ** 0.5
+    assert got.dtype == gold.dtype == torch.float32 and bool((got > 0).all()) and bool((gold > 0).all())
+    ulps = int((got.view(torch.int32).long() - gold.view(torch.int32).long()).abs().max())   # positive floats order as ints
+    assert ulps <= 4, f"sqrt(alphas_cumprod) is {ulps} float32 ulps off the golden schedule"
     assert abs(float(sch.betas[0]) - 1e-4) < 1e-10 and abs(float(sch.betas[-1]) - 0.02) < 1e-8
 
 

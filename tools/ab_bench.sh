@@ -9,7 +9,7 @@ mkdir -p gpurun_out
 for r in $(seq 1 "$rounds"); do
   for v in A B; do
     lib=$A; [ $v = B ] && lib=$B
-    I2V_LIB_PATH="$(realpath "$lib")" python bench.py --no-cpu-baseline --steps 20 --warmup 3 "$@" 2>/dev/null | python -c "
+    I2V_LIB_PATH="$(realpath "$lib")" python bench.py --full --no-cpu-baseline --steps 20 --warmup 3 "$@" 2>/dev/null | python -c "
 import json,sys; d=json.loads(sys.stdin.read()); print('$v', round(d['value'],3), round(d['ms_per_step'],3), {k: v['ms'] for k, v in d['kernel_classes'].items() if v['ms'] > 1})"
   done
 done

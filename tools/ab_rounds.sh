@@ -6,7 +6,8 @@ name=$1
 for r in $(seq 1 ${2:-2}); do
   for v in A B; do
     dir=.; [ $v = A ] && dir=.ab_old/$name
-    (cd $dir && python bench.py --no-cpu-baseline --steps 20 --warmup 3 2>/dev/null) | python -c "
+    full=--full; grep -q -- '"--full"' $dir/bench.py || full=      # a tree from before --full measures everything anyway
+    (cd $dir && python bench.py $full --no-cpu-baseline --steps 20 --warmup 3 2>/dev/null) | python -c "
 import json,sys; d=json.loads(sys.stdin.read()); print('$v', round(d['value'],3), round(d['ms_per_step'],3), {k: v['ms'] for k, v in d['kernel_classes'].items() if v['ms'] > 1})"
   done
 done

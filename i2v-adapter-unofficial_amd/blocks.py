@@ -1067,6 +1067,14 @@ class DDIMScheduler:
         cfg.update(overrides)
         return cls(**cfg)
 
+    @classmethod
+    def from_config(cls, config: dict, **overrides):
+        """diffusers' `SchedulerMixin.from_config`: a config dict (another scheduler's `.config`, a parsed scheduler_config.json)
+        + keyword overrides; keys starting with `_` and keys this scheduler does not know are ignored."""
+        cfg = {k: v for k, v in dict(config).items() if not k.startswith("_")}
+        cfg.update(overrides)
+        return cls(**cfg)
+
     def save_pretrained(self, save_directory: str):
         import json
         import os
@@ -1114,6 +1122,153 @@ class DDIMScheduler:
             a_p = self.alphas_cumprod[prev_t] if prev_t >= 0 else self.final_alpha_cumprod
             out.append(float(eta) * float((((1 - a_p) / (1 - a_t)) * (1 - a_t / a_p)) ** 0.5))
         return out
+
+    def add_noise(self, original_samples, noise, timesteps):
+        ac = self.alphas_cumprod.to(device=original_samples.device, dtype=original_samples.dtype)
+        timesteps = timesteps.to(original_samples.device)
+        sa = (ac[timesteps] ** 0.5).flatten()
+        sb = ((1 - ac[timesteps]) ** 0.5).flatten()
+        while sa.dim() < original_samples.dim():
+            sa, sb = sa.unsqueeze(-1), sb.unsqueeze(-1)
+        return sa * original_samples + sb * noise
+
+
+class DPMSolverMultistepScheduler:
+    """DPM-Solver++(2M) for the captured step: the host side of `i2v_dpm_cfg_step` (the reference's pipeline accepts
+    DPMSolverMultistepScheduler, pipe:25-32, 83-90).  A restatement of diffusers 0.24.0's DPMSolverMultistepScheduler (the version
+    the reference's requirements pin; unpinned, as DDIMScheduler above) for the configuration the kernel implements:
+    algorithm_type="dpmsolver++", solver_type="midpoint", solver_order 1 or 2, epsilon prediction, lower_order_final=True,
+    no thresholding, no Karras sigmas, lambda_min_clipped=-inf, timestep_spacing linspace / leading / trailing.  Any other value
+    of one of those keys raises NotImplementedError; keys it does not know are ignored (so another scheduler's config loads).
+
+    The beta defaults are this repository's DDIMScheduler's (scaled_linear 0.00085 .. 0.012, 1000 train steps, steps_offset=1),
+    not diffusers' (linear 0.0001 .. 0.02, steps_offset=0): `DPMSolverMultistepScheduler()` is the SD-1.5 schedule.
+
+    Deterministic, so the whole step stays one captured hipGraph; its one piece of state is the previous step's data prediction,
+    which the pipeline keeps on the device (`x0_prev`).  `scale_model_input` is the identity and `add_noise` is DDIM's."""
+
+    order = 1
+    init_noise_sigma = 1.0
+    _SUPPORTED = {"algorithm_type": ("dpmsolver++",), "solver_type": ("midpoint",), "solver_order": (1, 2),
+                  "prediction_type": ("epsilon",), "lower_order_final": (True,), "thresholding": (False,),
+                  "use_karras_sigmas": (False,), "timestep_spacing": ("linspace", "leading", "trailing"),
+                  "lambda_min_clipped": (-math.inf,)}
+
+    def __init__(self, num_train_timesteps=1000, beta_start=0.00085, beta_end=0.012, beta_schedule="scaled_linear",
+                 trained_betas=None, solver_order=2, prediction_type="epsilon", thresholding=False,
+                 algorithm_type="dpmsolver++", solver_type="midpoint", lower_order_final=True, use_karras_sigmas=False,
+                 lambda_min_clipped=-math.inf, timestep_spacing="linspace", steps_offset=1, **_unused):
+        self.config = dict(num_train_timesteps=num_train_timesteps, beta_start=beta_start, beta_end=beta_end,
+                           beta_schedule=beta_schedule, solver_order=solver_order, prediction_type=prediction_type,
+                           thresholding=thresholding, algorithm_type=algorithm_type, solver_type=solver_type,
+                           lower_order_final=lower_order_final, use_karras_sigmas=use_karras_sigmas,
+                           lambda_min_clipped=lambda_min_clipped, timestep_spacing=timestep_spacing, steps_offset=steps_offset)
+        for key, allowed in self._SUPPORTED.items():
+            v = self.config[key]
+            if not any(v == a and isinstance(v, bool) == isinstance(a, bool) for a in allowed):
+                raise NotImplementedError(f"DPMSolverMultistepScheduler: {key}={v!r} is not supported (supported: "
+                                          f"{', '.join(repr(a) for a in allowed)})")
+        if trained_betas is not None:
+            raise NotImplementedError("DPMSolverMultistepScheduler: trained_betas is not supported")
+        if beta_schedule == "scaled_linear":
+            self.betas = torch.linspace(beta_start ** 0.5, beta_end ** 0.5, num_train_timesteps, dtype=torch.float32) ** 2
+        elif beta_schedule == "linear":
+            self.betas = torch.linspace(beta_start, beta_end, num_train_timesteps, dtype=torch.float32)
+        else:
+            raise NotImplementedError(f"DPMSolverMultistepScheduler: beta_schedule={beta_schedule!r} is not supported")
+        self.num_train_timesteps = num_train_timesteps
+        self.solver_order = solver_order
+        self.alphas_cumprod = torch.cumprod(1.0 - self.betas, dim=0)
+        self.steps_offset = steps_offset
+        self.timestep_spacing = timestep_spacing
+        self.num_inference_steps = None
+        self.timesteps = torch.arange(num_train_timesteps - 1, -1, -1, dtype=torch.int64)
+
+    @classmethod
+    def from_config(cls, config: dict, **overrides):
+        """diffusers' `SchedulerMixin.from_config` (`DPMSolverMultistepScheduler.from_config(pipe.scheduler.config)`): keys starting
+        with `_` and unknown keys are ignored."""
+        cfg = {k: v for k, v in dict(config).items() if not k.startswith("_")}
+        cfg.update(overrides)
+        return cls(**cfg)
+
+    @classmethod
+    def from_pretrained(cls, pretrained_model_path: str, subfolder: Optional[str] = None, **overrides):
+        """scheduler_config.json (of any scheduler class: an SD-1.5 checkpoint ships PNDM's) + keyword overrides."""
+        import json
+        import os
+        path = os.path.join(pretrained_model_path, subfolder) if subfolder else pretrained_model_path
+        with open(os.path.join(path, "scheduler_config.json")) as f:
+            return cls.from_config(json.load(f), **overrides)
+
+    def save_pretrained(self, save_directory: str):
+        import json
+        import os
+        os.makedirs(save_directory, exist_ok=True)
+        with open(os.path.join(save_directory, "scheduler_config.json"), "w") as f:
+            json.dump({"_class_name": "DPMSolverMultistepScheduler", **self.config}, f, indent=2, sort_keys=True)
+
+    def set_timesteps(self, num_inference_steps: int, device=None):
+        """N timesteps from T - 1 down (the N + 1 point grid without its last point, or `trailing`), and the noise levels
+        sigma(t) = sqrt((1 - a_t) / a_t) of each plus a final sigma(0): the last step lands on alphas_cumprod[0]."""
+        import numpy as np
+        T, N = self.num_train_timesteps, num_inference_steps
+        if self.timestep_spacing == "linspace":
+            ts = np.linspace(0, T - 1, N + 1).round()[::-1][:-1].copy().astype(np.int64)
+        elif self.timestep_spacing == "leading":
+            ratio = T // (N + 1)
+            ts = (np.arange(0, N + 1) * ratio).round()[::-1][:-1].copy().astype(np.int64)
+            ts += self.steps_offset
+        else:
+            ts = np.arange(T, 0, -T / N).round().copy().astype(np.int64)
+            ts -= 1
+        self.timesteps = torch.from_numpy(ts)
+        self.num_inference_steps = len(ts)
+        ac = self.alphas_cumprod.double()
+        self.sigmas = torch.cat([((1 - ac[self.timesteps]) / ac[self.timesteps]) ** 0.5, ((1 - ac[:1]) / ac[:1]) ** 0.5])
+
+    def scale_model_input(self, sample, timestep=None):
+        return sample
+
+    def step_orders(self, timesteps):
+        """the solver order of each step of `timesteps` (the full list, or a tail of it: frame_similarity_sample_ratio < 1)"""
+        start, n = self._start_index(timesteps), len(self.timesteps)
+        return [1 if (self.solver_order == 1 or k == 0 or (i == n - 1 and n < 15)) else 2
+                for k, i in enumerate(range(start, start + len(timesteps)))]
+
+    def _start_index(self, timesteps):
+        full = [int(v) for v in self.timesteps]
+        sub = [int(v) for v in timesteps]
+        if not sub or sub[0] not in full or full[full.index(sub[0]):full.index(sub[0]) + len(sub)] != sub:
+            raise ValueError("timesteps must be a tail of the scheduler's timesteps (set_timesteps first)")
+        return full.index(sub[0])
+
+    def step_coefficients(self, timesteps, eta: float = 0.0) -> torch.Tensor:
+        """[len(timesteps), 6] fp32 rows {a_s0, s_s0, s_t / s_s0, c_cur, c_prev, order} of `i2v_dpm_cfg_step`, built in float64.
+        Row k is the step from s0 = timesteps[k] (full-list index i) to the next entry's noise level (sigma(0) after the last):
+            x0 = (x - s_s0 eps) / a_s0,   x_t = (s_t / s_s0) x + c_cur x0 + c_prev x0_prev,
+        a = 1 / sqrt(sigma^2 + 1), s = sigma a, lambda = log a - log s, h = lambda_t - lambda_s0; order 1: c_cur = a_t (1 - e^-h),
+        c_prev = 0; order 2 (midpoint, r0 = (lambda_s0 - lambda_s1) / h with s1 the previous full-list entry):
+        c_cur = a_t (1 - e^-h) (1 + 1 / (2 r0)), c_prev = -a_t (1 - e^-h) / (2 r0).  A step is first order if solver_order is 1,
+        if it is the first step executed since set_timesteps, or if it is the last of a full list shorter than 15
+        (lower_order_final).  `eta` is ignored: the reference passes it only to a scheduler whose step takes it (pipe:184-199)."""
+        sig = [float(v) for v in self.sigmas]
+        alpha = lambda s: 1.0 / math.sqrt(s * s + 1.0)
+        lam = lambda s: math.log(alpha(s)) - math.log(s * alpha(s))
+        start = self._start_index(timesteps)
+        rows = []
+        for (k, order), i in zip(enumerate(self.step_orders(timesteps)), range(start, start + len(timesteps))):
+            s0, st = sig[i], sig[i + 1]
+            a_s0, a_t = alpha(s0), alpha(st)
+            h = lam(st) - lam(s0)
+            phi = a_t * -math.expm1(-h)
+            if order == 1:
+                c_cur, c_prev = phi, 0.0
+            else:
+                r0 = (lam(s0) - lam(sig[i - 1])) / h
+                c_cur, c_prev = phi * (1.0 + 0.5 / r0), -phi * 0.5 / r0
+            rows.append([a_s0, s0 * a_s0, (st * a_t) / (s0 * a_s0), c_cur, c_prev, float(order)])
+        return torch.tensor(rows, dtype=torch.float64).to(torch.float32)
 
     def add_noise(self, original_samples, noise, timesteps):
         ac = self.alphas_cumprod.to(device=original_samples.device, dtype=original_samples.dtype)

@@ -1,5 +1,5 @@
 // Layout edges (NCHW <-> token-major), timestep embedding, SiLU, row repeat / 2-D copy, and the two halves of
-// the DDIM + classifier-free-guidance step that bracket the UNet call.  All pure HBM traffic.
+// the DDIM (or DPM-Solver++) + classifier-free-guidance step that bracket the UNet call.  All pure HBM traffic.
 #include "common.h"
 
 namespace {
@@ -166,6 +166,74 @@ __global__ __launch_bounds__(256) void ddim_step_kernel(float* __restrict__ late
     const float x = latents[i];
     const float x0 = (x - sb_t * eps) / sa_t;
     latents[i] = sa_p * x0 + sb_p * eps;
+  }
+}
+
+// DPM-Solver++ (2M, midpoint) update with the same CFG combine, one pass over the latents, V consecutive pixels of one
+// (image, channel) per thread (V = 4: 16-byte latents / x0_prev accesses).  Row {a_s0, s_s0, s_t / s_s0, c_cur, c_prev, order}:
+//   x0 = (x - s_s0 eps) / a_s0;  x_t = (s_t / s_s0) x + c_cur x0 + c_prev x0_prev;  x0_prev := x0.
+// A first-order row (order 1, c_prev = 0) never reads x0_prev: its contents before the first step of a sample are undefined.
+template <int V>
+__device__ __forceinline__ void load_f32v(const float* p, float (&v)[V]) {
+  if constexpr (V == 4) {
+    const f32x4 t = *reinterpret_cast<const f32x4*>(p);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) v[j] = t[j];
+  } else {
+#pragma unroll
+    for (int j = 0; j < V; ++j) v[j] = p[j];
+  }
+}
+
+template <int V>
+__device__ __forceinline__ void store_f32v(float* p, const float (&v)[V]) {
+  if constexpr (V == 4) {
+    *reinterpret_cast<f32x4*>(p) = f32x4{v[0], v[1], v[2], v[3]};
+  } else {
+#pragma unroll
+    for (int j = 0; j < V; ++j) p[j] = v[j];
+  }
+}
+
+template <typename NP, int V>
+__global__ __launch_bounds__(256) void dpm_step_kernel(float* __restrict__ latents, float* __restrict__ x0_prev,
+                                                       const NP* __restrict__ np, int64_t ld_np, const float* __restrict__ coef,
+                                                       int n_steps, const int32_t* __restrict__ step_index, float guidance,
+                                                       int b, int f, int c, int hw, int copies) {
+  const int hwv = hw / V;
+  const int64_t groups = (int64_t)b * f * c * hwv;
+  const float* cf = coef + 6 * (int64_t)min(max(*step_index, 0), n_steps - 1);
+  const float a_s0 = cf[0], s_s0 = cf[1], ratio = cf[2], c_cur = cf[3], c_prev = cf[4];
+  const bool second = cf[5] > 1.5f;
+  const int64_t bf = (int64_t)b * f;
+  for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < groups; g += (int64_t)gridDim.x * 256) {
+    const int p0 = (int)(g % hwv) * V;
+    const int64_t t = g / hwv;
+    const int ch = (int)(t % c);
+    const int64_t img = t / c;  // b * f + fr
+    float x[V], x0[V], out[V];
+    load_f32v<V>(latents + g * V, x);
+#pragma unroll
+    for (int j = 0; j < V; ++j) {
+      float eps;
+      if (copies == 2) {
+        const float u = (float)np[(img * hw + p0 + j) * ld_np + ch];
+        const float cnd = (float)np[((bf + img) * hw + p0 + j) * ld_np + ch];
+        eps = u + guidance * (cnd - u);
+      } else {
+        eps = (float)np[(img * hw + p0 + j) * ld_np + ch];
+      }
+      x0[j] = (x[j] - s_s0 * eps) / a_s0;
+      out[j] = ratio * x[j] + c_cur * x0[j];
+    }
+    if (second) {
+      float xp[V];
+      load_f32v<V>(x0_prev + g * V, xp);
+#pragma unroll
+      for (int j = 0; j < V; ++j) out[j] += c_prev * xp[j];
+    }
+    store_f32v<V>(x0_prev + g * V, x0);
+    store_f32v<V>(latents + g * V, out);
   }
 }
 
@@ -381,6 +449,38 @@ extern "C" int i2v_ddim_cfg_step(float* latents, const void* noise_pred, int32_t
                        c, hw, cfg_copies);
   hipLaunchKernelGGL(bump_step_kernel, dim3(1), dim3(64), 0, s, step_index, n_steps);
   return i2v_check_launch("i2v_ddim_cfg_step");
+}
+
+template <int V>
+static void launch_dpm_step(float* latents, float* x0_prev, const void* noise_pred, int32_t np_is_f32, int64_t ld_np,
+                            const float* coef, int32_t n_steps, int32_t* step_index, float guidance_scale, int32_t b, int32_t f,
+                            int32_t c, int32_t hw, int32_t cfg_copies, hipStream_t s) {
+  const dim3 grid(ew_blocks((int64_t)b * f * c * (hw / V))), block(256);
+  if (np_is_f32)
+    hipLaunchKernelGGL((dpm_step_kernel<float, V>), grid, block, 0, s, latents, x0_prev, reinterpret_cast<const float*>(noise_pred),
+                       ld_np, coef, n_steps, step_index, guidance_scale, b, f, c, hw, cfg_copies);
+  else
+    hipLaunchKernelGGL((dpm_step_kernel<f16, V>), grid, block, 0, s, latents, x0_prev, reinterpret_cast<const f16*>(noise_pred),
+                       ld_np, coef, n_steps, step_index, guidance_scale, b, f, c, hw, cfg_copies);
+}
+
+extern "C" int i2v_dpm_cfg_step(float* latents, float* x0_prev, const void* noise_pred, int32_t np_is_f32, int64_t ld_np,
+                                const float* coef, int32_t n_steps, int32_t* step_index, float guidance_scale, int32_t b,
+                                int32_t f, int32_t c, int32_t hw, int32_t cfg_copies, i2v_stream_t stream) {
+  I2V_CHECK_ARG(latents && x0_prev && noise_pred && coef && step_index && b > 0 && f > 0 && c > 0 && hw > 0 && ld_np >= c &&
+                    n_steps > 0,
+                "i2v_dpm_cfg_step: bad arguments");
+  I2V_CHECK_ARG(cfg_copies == 1 || cfg_copies == 2, "i2v_dpm_cfg_step: cfg_copies must be 1 or 2");
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const bool vec4 = hw % 4 == 0 && (reinterpret_cast<uintptr_t>(latents) & 15) == 0 && (reinterpret_cast<uintptr_t>(x0_prev) & 15) == 0;
+  if (vec4)
+    launch_dpm_step<4>(latents, x0_prev, noise_pred, np_is_f32, ld_np, coef, n_steps, step_index, guidance_scale, b, f, c, hw,
+                       cfg_copies, s);
+  else
+    launch_dpm_step<1>(latents, x0_prev, noise_pred, np_is_f32, ld_np, coef, n_steps, step_index, guidance_scale, b, f, c, hw,
+                       cfg_copies, s);
+  hipLaunchKernelGGL(bump_step_kernel, dim3(1), dim3(64), 0, s, step_index, n_steps);
+  return i2v_check_launch("i2v_dpm_cfg_step");
 }
 
 extern "C" int i2v_first_frame_prior_f32(const float* cond, const float* mask_uniform, const float* noise, float* latents,

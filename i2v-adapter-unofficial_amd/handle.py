@@ -30,7 +30,7 @@ ENTRY_IDS = {name: i for i, name in enumerate((
     "i2v_gemm_f16", "i2v_attention_f16", "i2v_temporal_attention_f16", "i2v_motion_attn_f16", "i2v_cross_attn_fused_f16", "i2v_ln_qkv_f16",
     "i2v_ff_fused_f16", "i2v_groupnorm_f16", "i2v_layernorm_f16", "i2v_groupnorm_fold_f16", "i2v_nchw_to_tokens", "i2v_tokens_to_nchw",
     "i2v_timestep_embedding", "i2v_silu_f16", "i2v_repeat_rows_f16", "i2v_copy3d_f16", "i2v_select_row_f16",
-    "i2v_pack_ctx_fragments_f16", "i2v_ddim_prep", "i2v_ddim_cfg_step"))}
+    "i2v_pack_ctx_fragments_f16", "i2v_ddim_prep", "i2v_ddim_cfg_step", "i2v_dpm_cfg_step"))}
 IO_SAMPLE, IO_TIMESTEPS, IO_CONTEXT, IO_IMAGE_EMBEDS, IO_OUT = range(5)
 RELOC_ARENA, RELOC_WEIGHT, RELOC_IO = range(3)
 _INT_TYPES = (C.c_int32, C.c_int64, C.c_int)
@@ -289,7 +289,7 @@ def record_forward_plan(unet, sample, timesteps, encoder_hidden_states, image_em
 
 # ---- the whole denoising loop (pipe:663-700) for a host without Python: a per-sample preparation plan and a per-step plan whose
 #      per-sample buffers are named like weights
-STEP_LATENTS, STEP_COND, STEP_INDEX, STEP_COEF = range(4)          # io slots of a step plan
+STEP_LATENTS, STEP_COND, STEP_INDEX, STEP_COEF, STEP_HISTORY = range(5)   # io slots of a step plan (STEP_HISTORY: DPM-Solver++ only)
 PREP_CONTEXT, PREP_TIMESTEPS, PREP_IMAGE_EMBEDS = range(3)         # io slots of a preparation plan
 
 
@@ -318,14 +318,21 @@ def record_step_plan(pipe, st):
     pipeline routes it (projected context, the step's row of the time-embedding table, the CFG prefix computed once), CFG combine +
     DDIM update (i2v_ddim_cfg_step) -- as a launch plan.  `st` is a PREPARED pipeline state (static buffers, `ctx_proj`, `temb_table`).
     io: STEP_LATENTS fp32 [B, F, C, H, W] (in / out), STEP_COND fp32 [B, C, H, W], STEP_INDEX int32 [1] (in / out: advanced by the
-    step), STEP_COEF fp32 [T, 4]; the per-sample buffers are weights named `sample#...` (`sample_buffers`)."""
-    keep = (st["latents"].clone(), st["step_idx"].clone())
+    step), STEP_COEF fp32 [T, 4]; the per-sample buffers are weights named `sample#...` (`sample_buffers`).
+    With a DPMSolverMultistepScheduler the step ends in i2v_dpm_cfg_step: STEP_COEF is fp32 [T, 6] and STEP_HISTORY fp32 [B, F, C, H, W]
+    (= st["x0_prev"], in / out: the previous step's data prediction; not read by the first step of a sample)."""
+    hist = st.get("x0_prev")
+    keep = (st["latents"].clone(), st["step_idx"].clone(), None if hist is None else hist.clone())
 
     def restore():
         st["latents"].copy_(keep[0])
         st["step_idx"].copy_(keep[1])
-    blob, weights = record_plan(lambda: pipe._step(st), unet=pipe.unet, restore=restore, problem=_step_problem(st),
-                                io={STEP_LATENTS: st["latents"], STEP_COND: st["cond"], STEP_INDEX: st["step_idx"], STEP_COEF: st["coef"]},
+        if hist is not None:
+            hist.copy_(keep[2])
+    io = {STEP_LATENTS: st["latents"], STEP_COND: st["cond"], STEP_INDEX: st["step_idx"], STEP_COEF: st["coef"]}
+    if hist is not None:
+        io[STEP_HISTORY] = hist
+    blob, weights = record_plan(lambda: pipe._step(st), unet=pipe.unet, restore=restore, problem=_step_problem(st), io=io,
                                 extra_persistent=lambda: sample_buffers(pipe.unet, st))
     restore()
     return blob, weights
@@ -492,6 +499,9 @@ def export_denoiser(pipe, out_dir, *, num_frames, latent_height, latent_width, b
     unet = pipe.unet
     dev = unet.device
     sch = pipe.scheduler
+    if pipe._scheduler_kind() != "ddim":
+        raise NotImplementedError("export_denoiser writes the DDIM loop (manifest `ddim_coefficients`, four io slots per step); "
+                                  "a DPM-Solver++ step plan comes from record_step_plan")
     sch.set_timesteps(num_inference_steps)
     ts = sch.timesteps
     B, F, hh, ww = batch, num_frames, latent_height, latent_width

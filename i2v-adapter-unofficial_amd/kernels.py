@@ -1027,6 +1027,34 @@ def ddim_cfg_step(latents, noise_pred, coef, step_index, guidance_scale, cfg_cop
     return latents
 
 
+def dpm_cfg_step(latents, x0_prev, noise_pred, coef, step_index, guidance_scale, cfg_copies):
+    """In-place DPM-Solver++ (2M) update of latents fp32 [B, F, C, H, W] from noise_pred tokens (fp32, or fp16)
+    [cfg_copies * B * F, H, W, ld]; x0_prev fp32 like the latents (the previous step's data prediction: read by second-order
+    rows, written by every row); coef fp32 [steps, 6] (`DPMSolverMultistepScheduler.step_coefficients`); step_index device
+    int32 scalar (advanced by one, wrapping to 0 at the end of the table)."""
+    lib = _lib.load()
+    _req(latents, "latents", dtype=torch.float32)
+    _req(x0_prev, "x0_prev", dtype=torch.float32)
+    _req(noise_pred, "noise_pred", dtype=None)
+    if noise_pred.dtype not in (torch.float32, f16):
+        raise TypeError("noise_pred must be fp32 or fp16")
+    _req(coef, "coef", dtype=torch.float32)
+    _req(step_index, "step_index", dtype=torch.int32)
+    b, f, c, h, w = latents.shape
+    if tuple(x0_prev.shape) != tuple(latents.shape) or not x0_prev.is_contiguous() or not latents.is_contiguous():
+        raise ValueError(f"latents and x0_prev must be contiguous {tuple(latents.shape)}")
+    if noise_pred.dim() != 4 or not noise_pred.is_contiguous() or noise_pred.shape[0] != cfg_copies * b * f or \
+            noise_pred.shape[1] != h or noise_pred.shape[2] != w or noise_pred.shape[3] < c:
+        raise ValueError(f"noise_pred must be contiguous [{cfg_copies * b * f}, {h}, {w}, >={c}]")
+    if coef.dim() != 2 or coef.shape[1] != 6 or not coef.is_contiguous():
+        raise ValueError("coef must be contiguous [steps, 6]")
+    _lib.check(lib.i2v_dpm_cfg_step(_p(latents), _p(x0_prev), _p(noise_pred), 1 if noise_pred.dtype == torch.float32 else 0,
+                                    noise_pred.shape[3], _p(coef), coef.shape[0],
+                                    _p(step_index), float(guidance_scale), b, f, c, h * w, cfg_copies, _stream()),
+               "i2v_dpm_cfg_step")
+    return latents
+
+
 # ---------------------------------------------------------------------------------------------- backward (SURVEY 8 f4)
 def transpose_tokens(x, batch_len, out=None):
     """[B * L, C] token-major -> [B, C, pad8(L)] channel-major (zero-filled pad): the K^T / Q^T / dO^T operands of the

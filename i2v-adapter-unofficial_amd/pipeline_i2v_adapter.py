@@ -3,7 +3,8 @@
 `get_timesteps` :529-536, `__call__` :538-719, loop :663-700).
 
 One DDIM step = frame-0 overwrite + CFG duplicate + layout edge (i2v_ddim_prep), timestep embedding, the UNet,
-CFG combine + DDIM update (i2v_ddim_cfg_step).  The whole step is captured ONCE as a hipGraph (through
+CFG combine + DDIM update (i2v_ddim_cfg_step; with a DPMSolverMultistepScheduler the DPM-Solver++(2M) update,
+i2v_dpm_cfg_step, which also keeps the previous data prediction on the device).  The whole step is captured ONCE as a hipGraph (through
 torch.cuda.CUDAGraph on the stream the ctypes launches go to) and replayed for every timestep: the step's
 scalars (t, sqrt(a_t), ...) are read on the device from small tables indexed by a device-side step counter, so
 there is no per-step host<->device traffic and no per-step sync (the reference syncs once per step on
@@ -21,7 +22,7 @@ import torch
 
 from . import kernels as K
 from ._lib import HipLibraryError
-from .blocks import DDIMScheduler
+from .blocks import DDIMScheduler, DPMSolverMultistepScheduler
 from .image_processor import VaeImageProcessor, tensor2vid
 from .unet_motion_cross_frame_attn import UNetMotionCrossFrameAttnModel
 
@@ -31,6 +32,10 @@ from .unet_motion_cross_frame_attn import UNetMotionCrossFrameAttnModel
 CFG_SHARED = os.environ.get("I2V_CFG_SHARED", "1") != "0"
 
 f16 = torch.float16
+
+# diffusers schedulers the reference's pipeline accepts (pipe:25-32, 83-90) that this build does not: each needs what the
+# captured step has no room for (sigma-scaled inputs and prior, per-step host noise, 3-4 history tensors)
+UNSUPPORTED_SCHEDULERS = ("EulerDiscreteScheduler", "EulerAncestralDiscreteScheduler", "LMSDiscreteScheduler", "PNDMScheduler")
 
 
 class I2VAdapterPipelineOutput:
@@ -68,7 +73,7 @@ class I2VAdapterPipeline:
     model_cpu_offload_seq = "text_encoder->image_encoder->unet->vae"
 
     def __init__(self, vae=None, text_encoder=None, tokenizer=None, unet=None, motion_adapter=None,
-                 i2v_adapter=None, scheduler: Optional[DDIMScheduler] = None, feature_extractor=None,
+                 i2v_adapter=None, scheduler=None, feature_extractor=None,
                  image_encoder=None):
         if unet is None:
             raise ValueError("`unet` is required")
@@ -78,6 +83,7 @@ class I2VAdapterPipeline:
         self.vae, self.text_encoder, self.tokenizer = vae, text_encoder, tokenizer
         self.motion_adapter, self.i2v_adapter = motion_adapter, i2v_adapter
         self.scheduler = scheduler if scheduler is not None else DDIMScheduler()
+        self._scheduler_kind()
         self.feature_extractor, self.image_encoder = feature_extractor, image_encoder
         if vae is not None:                                                                  # pipe:110-111
             self.vae_scale_factor = 2 ** (len(vae.config["block_out_channels"]) - 1)
@@ -163,6 +169,15 @@ class I2VAdapterPipeline:
         return latents.to(device=device, dtype=torch.float32) * self.scheduler.init_noise_sigma
 
     # ------------------------------------------------------------------------------------------ one step
+    def _scheduler_kind(self):
+        """"dpmsolver++" for a DPMSolverMultistepScheduler (the i2v_dpm_cfg_step update), "ddim" for any other scheduler object
+        (the DDIM update, as before); the reference's other schedulers by class name raise."""
+        name = type(self.scheduler).__name__
+        if name in UNSUPPORTED_SCHEDULERS:
+            raise NotImplementedError(f"{name} is not supported by this build: use DDIMScheduler or DPMSolverMultistepScheduler "
+                                      "(e.g. DPMSolverMultistepScheduler.from_config(pipe.scheduler.config))")
+        return "dpmsolver++" if isinstance(self.scheduler, DPMSolverMultistepScheduler) else "ddim"
+
     def _step(self, st):
         """One iteration of pipe:666-697 as kernel launches on the current stream (captured into a hipGraph)."""
         unet = self.unet
@@ -174,19 +189,24 @@ class I2VAdapterPipeline:
         y = unet._fwd_tokens(x, None, True, st.get("ctx_proj") or st["ctx_text"], st["ctx_ip"],
                              st["num_frames"], cfg_shared=CFG_SHARED and st["copies"] == 2, temb_proj=temb_proj,
                              forward_upsample_size=any(s % (2 ** unet.num_upsamplers) for s in st["latents"].shape[-2:]))   # pipe:676-683, unet:1304-1311
-        K.ddim_cfg_step(st["latents"], y, st["coef"], st["step_idx"], st["guidance"], st["copies"])  # pipe:686-691
+        if isinstance(self.scheduler, DPMSolverMultistepScheduler):
+            K.dpm_cfg_step(st["latents"], st["x0_prev"], y, st["coef"], st["step_idx"], st["guidance"], st["copies"])
+        else:
+            K.ddim_cfg_step(st["latents"], y, st["coef"], st["step_idx"], st["guidance"], st["copies"])  # pipe:686-691
 
     def _graph_key(self, st):
         """everything a captured step has baked in besides the contents of the static buffers: shapes, the Python
-        scalars passed as launch arguments (guidance, IP scales) and the identity / version of every weight (the packed
-        kernel-layout copies are rebuilt when a parameter changes, and a graph captured before that reads the old ones)"""
+        scalars passed as launch arguments (guidance, IP scales), the identity / version of every weight (the packed
+        kernel-layout copies are rebuilt when a parameter changes, and a graph captured before that reads the old ones) and the
+        scheduler's update (a scheduler swapped between calls re-captures)"""
         unet = self.unet
         wsig = hash(tuple((p.data_ptr(), p._version) for p in unet.parameters()))
         ips = tuple((a.ip_num_tokens, float(a.ip_scale)) for a in unet._cross_attention_layers())
         shp = lambda t: None if t is None else (tuple(t.shape), t.dtype)
         from .blocks import precise_stream      # (a captured step keeps the residual-stream mode it was captured in)
         return (tuple(st["latents"].shape), st["copies"], st["num_frames"], st["guidance"], shp(st["t_table"]),
-                shp(st["ctx_text"]), shp(st["ctx_ip"]), str(st["latents"].device), wsig, ips, precise_stream())
+                shp(st["ctx_text"]), shp(st["ctx_ip"]), str(st["latents"].device), wsig, ips, precise_stream(),
+                self._scheduler_kind(), shp(st["coef"]))
 
     def _run_steps(self, st, n_steps, use_graph):
         if not use_graph:
@@ -316,6 +336,7 @@ class I2VAdapterPipeline:
                     negative_image_embeds = torch.zeros_like(image_embeds)                      # pipe:343
                 image_embeds = torch.cat([negative_image_embeds, image_embeds])                 # pipe:621-622
 
+        dpm = self._scheduler_kind() == "dpmsolver++"
         self.scheduler.set_timesteps(num_inference_steps)                                       # pipe:630-631
         timesteps, _ = self.get_timesteps(num_inference_steps, frame_similarity_sample_ratio)
 
@@ -343,24 +364,29 @@ class I2VAdapterPipeline:
             ctx_text=prompt_embeds.to(dev, f16).contiguous(),
             ctx_ip=self.unet._project_image_embeds(
                 {"image_embeds": image_embeds.to(dev)} if image_embeds is not None else None))
+        if dpm:
+            # the previous step's data prediction: the first step of a sample is first order and does not read it
+            st["x0_prev"] = torch.empty_like(latents)
         # K / V^T of the prompt (+ image) context for all 16 cross-attention layers: once per sample, not once per step
         # (projected where it is consumed: a graph-cache hit projects straight into the graph's static buffers)
-        if callback is None and eta == 0.0:
+        # (DPM-Solver++ has no stochastic form here: the reference passes `eta` only to a scheduler whose step takes it,
+        # pipe:184-199, so it is ignored and the steps stay captured)
+        if callback is None and (eta == 0.0 or dpm):
             st["latents"] = self._run_steps(st, len(timesteps), use_graph)
         else:
             # eager steps: a per-step host hook (pipe:693-697), and / or the stochastic DDIM update (eta > 0, pipe:550, 659-660:
             # sigma_t is out of the direction coefficient -- `step_coefficients(timesteps, eta)` -- and comes back as fresh noise,
             # one draw of the latents' shape per step from `generator` as diffusers' scheduler draws it)
-            if eta != 0.0 and use_graph:
+            if eta != 0.0 and use_graph and not dpm:
                 import warnings
                 warnings.warn("eta > 0: the stochastic DDIM update draws fresh noise on the host every step, so the steps run as "
                               "eager launches instead of the captured hipGraph (about 2x the step time)", RuntimeWarning, stacklevel=2)
-            sigmas = self.scheduler.step_sigmas(timesteps, eta)
+            sigmas = None if dpm else self.scheduler.step_sigmas(timesteps, eta)
             st["ctx_proj"] = self.unet.project_context(st["ctx_text"], st["ctx_ip"])
             st["temb_table"] = self.unet.project_time_table(st["t_table"])
             for i, t in enumerate(timesteps):                                                   # pipe:666-697
                 self._step(st)
-                if eta > 0:
+                if eta > 0 and not dpm:
                     z = _draw(torch.randn, tuple(st["latents"].shape), generator, dev).to(torch.float32).contiguous()
                     K.axpby(st["latents"], z, 1.0, sigmas[i])
                 if callback is not None and i % callback_steps == 0:
@@ -376,6 +402,22 @@ class I2VAdapterPipeline:
         if not return_dict:
             return (video,)
         return I2VAdapterPipelineOutput(frames=video)
+
+
+SCHEDULERS = ("ddim", "dpmsolver++")
+
+
+def load_scheduler(model_path, kind="ddim"):
+    """the evaluation driver's scheduler (`--scheduler`) from `<model_path>/scheduler/scheduler_config.json`: "ddim" as the
+    reference builds it (pipe:755-757), "dpmsolver++" the same config as a DPMSolverMultistepScheduler (DPM-Solver++(2M),
+    linspace spacing, steps_offset=1)."""
+    if kind == "ddim":
+        return DDIMScheduler.from_pretrained(model_path, subfolder="scheduler", clip_sample=False,
+                                             timestep_spacing="linspace", steps_offset=1)          # pipe:755-757
+    if kind == "dpmsolver++":
+        return DPMSolverMultistepScheduler.from_pretrained(model_path, subfolder="scheduler", timestep_spacing="linspace",
+                                                           steps_offset=1)
+    raise ValueError(f"unknown scheduler {kind!r}: one of {', '.join(SCHEDULERS)}")
 
 
 def main(argv=None):
@@ -420,6 +462,8 @@ def main(argv=None):
     parser.add_argument("--height", type=int, default=None)
     parser.add_argument("--width", type=int, default=None)
     parser.add_argument("--seed", type=int, default=0)
+    parser.add_argument("--scheduler", choices=SCHEDULERS, default="ddim",
+                        help="ddim (the reference's) or dpmsolver++ (DPM-Solver++(2M): 15-20 steps instead of 25-50)")
     args = parser.parse_args(argv)
     if args.task_name is None:
         logger.error("Checkpoint `task_name` must be specified.")
@@ -442,8 +486,7 @@ def main(argv=None):
     device = torch.device("cuda")                                # there is no CPU path (the reference falls back to it)
     unet2d = UNet2DConditionModel.from_pretrained(os.path.join(args.model_path, "unet"))         # pipe:751
     vae = AutoencoderKL.from_pretrained(os.path.join(args.model_path, "vae"))                    # pipe:754
-    scheduler = DDIMScheduler.from_pretrained(args.model_path, subfolder="scheduler", clip_sample=False,
-                                              timestep_spacing="linspace", steps_offset=1)       # pipe:755-757
+    scheduler = load_scheduler(args.model_path, args.scheduler)                                 # pipe:755-757
 
     eval_data_dir = os.path.dirname(args.eval_data_path)                                         # pipe:759-768
     eval_data_df = pd.read_csv(args.eval_data_path)

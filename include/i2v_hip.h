@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define I2V_ABI_VERSION 9
+#define I2V_ABI_VERSION 10
 
 #define I2V_OK 0
 #define I2V_ERR_INVALID_ARG (-1)
@@ -489,6 +489,20 @@ int i2v_ddim_prep(float* latents, const float* cond, void* model_in, int32_t b, 
 int i2v_ddim_cfg_step(float* latents, const void* noise_pred, int32_t np_is_f32, int64_t ld_np, const float* coef, int32_t n_steps,
                       int32_t* step_index, float guidance_scale, int32_t b, int32_t f, int32_t c, int32_t hw,
                       int32_t cfg_copies, i2v_stream_t stream);
+
+/* (ABI 10) The DPM-Solver++ (2M, midpoint, data prediction) form of the step half, for DPMSolverMultistepScheduler: the same
+ * CFG combine and the same layouts as i2v_ddim_cfg_step (i2v_ddim_prep is reused unchanged: scale_model_input is the identity), then
+ *   x0 = (x - s_s0 eps) / a_s0;  x_t = (s_t / s_s0) x + c_cur x0 + c_prev x0_prev;  x0_prev := x0
+ * and *step_index advances / wraps as in the DDIM step.
+ * coef fp32 [n_steps][6] = {a_s0, s_s0, s_t / s_s0, c_cur, c_prev, order}, with a = 1 / sqrt(sigma^2 + 1), s = sigma a,
+ * lambda = log a - log s, h = lambda_t - lambda_s0 and, for order 2, r0 = (lambda_s0 - lambda_s1) / h:
+ *   order 1: c_cur = a_t (1 - e^-h), c_prev = 0;
+ *   order 2: c_cur = a_t (1 - e^-h) (1 + 1 / (2 r0)), c_prev = -a_t (1 - e^-h) / (2 r0).
+ * x0_prev fp32 [b, f, c, hw]: the previous step's data prediction.  A row with order 1 does not read it (its contents before the
+ * first step of a sample do not matter); every row writes it. */
+int i2v_dpm_cfg_step(float* latents, float* x0_prev, const void* noise_pred, int32_t np_is_f32, int64_t ld_np, const float* coef,
+                     int32_t n_steps, int32_t* step_index, float guidance_scale, int32_t b, int32_t f, int32_t c, int32_t hw,
+                     int32_t cfg_copies, i2v_stream_t stream);
 
 /* First-frame-similarity prior and the initial add_noise of the sampling loop, pipe:647-656:
  *   prior   = mask * GaussianBlur3x3(cond) + (1 - mask) * cond, mask = (mask_uniform < strength), per frame (pipe:648-654)

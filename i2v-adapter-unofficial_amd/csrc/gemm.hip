@@ -364,22 +364,22 @@ int vector_epilogue_ok(const i2v_gemm_params& p) {
 
 extern "C" int64_t i2v_gemm_workspace_bytes(const i2v_gemm_params* pp) {
   if (pp == nullptr || pp->M <= 0 || pp->N <= 0 || pp->K <= 0) return 0;
-  return i2v_gemm_big_workspace_bytes(*pp, vector_epilogue_ok(*pp));
+  return i2v_gemm_big_plan(*pp, vector_epilogue_ok(*pp)).workspace_bytes;
 }
 
 extern "C" int i2v_gemm_ln_supported(const i2v_gemm_params* pp) {
   if (pp == nullptr || pp->M <= 0 || pp->N <= 0 || pp->K <= 0) return 0;
-  return i2v_gemm_big_ln_ok(*pp, vector_epilogue_ok(*pp));
+  return i2v_gemm_big_plan(*pp, vector_epilogue_ok(*pp)).ln_fold ? 1 : 0;
 }
 
 extern "C" int i2v_gemm_batch_supported(const i2v_gemm_params* pp) {
   if (pp == nullptr || pp->M <= 0 || pp->N <= 0 || pp->K <= 0) return 0;
-  return i2v_gemm_big_unsplit_ok(*pp, vector_epilogue_ok(*pp));
+  return i2v_gemm_big_plan(*pp, vector_epilogue_ok(*pp)).form == GemmBigForm::Tile ? 1 : 0;
 }
 
 extern "C" int32_t i2v_gemm_gn_partial_rows(const i2v_gemm_params* pp) {
   if (pp == nullptr) return 0;
-  return i2v_gemm_big_gn_rows(*pp, vector_epilogue_ok(*pp));
+  return i2v_gemm_big_plan(*pp, vector_epilogue_ok(*pp)).gn_rows;
 }
 
 extern "C" int i2v_gemm_f16(const i2v_gemm_params* pp, i2v_stream_t stream) {
@@ -457,6 +457,7 @@ extern "C" int i2v_gemm_f16(const i2v_gemm_params* pp, i2v_stream_t stream) {
   }
 
   int vec4 = vector_epilogue_ok(p);
+  const GemmBigPlan big_plan = i2v_gemm_big_plan(p, vec4);   // which form of the 8-wave kernel (gemm_big.hip) runs this, if any
   if (p.rowvec && p.rowvec_period > 0)
     I2V_CHECK_ARG(p.store_mode != I2V_STORE_ROWPERM && p.store_mode != I2V_STORE_VT &&
                       (p.rowvec_period & (p.rowvec_period - 1)) == 0,
@@ -464,7 +465,7 @@ extern "C" int i2v_gemm_f16(const i2v_gemm_params* pp, i2v_stream_t stream) {
                   "row index: an integer modulo there cost the 256-row kernels 40 %%) and a row-major / VT_T store");
   if (p.ln_wsum) {
     I2V_CHECK_ARG(aligned_to(p.ln_wsum, 16) && p.ln_eps > 0.f, "i2v_gemm_f16: ln_wsum must be 16-byte aligned, ln_eps > 0");
-    if (!i2v_gemm_big_ln_ok(p, vec4))
+    if (!big_plan.ln_fold)
       I2V_FAIL(I2V_ERR_INVALID_ARG, "i2v_gemm_f16: LayerNorm-folded GEMM is not implemented for this problem "
                "(M %d N %d K %d, epilogue %d, store %d): ask i2v_gemm_ln_supported() first", p.M, p.N, p.K, p.epilogue,
                p.store_mode);
@@ -472,13 +473,13 @@ extern "C" int i2v_gemm_f16(const i2v_gemm_params* pp, i2v_stream_t stream) {
 
   if (p.gn_partial) {
     I2V_CHECK_ARG(aligned_to(p.gn_partial, 8), "i2v_gemm_f16: gn_partial must be 8-byte aligned");
-    if (!i2v_gemm_big_gn_rows(p, vec4))
+    if (!big_plan.gn_rows)
       I2V_FAIL(I2V_ERR_INVALID_ARG, "i2v_gemm_f16: GroupNorm partials (gn_partial) are not implemented for this problem (M %d N %d K %d, "
                "groups %d): ask i2v_gemm_gn_partial_rows() first", p.M, p.N, p.K, p.gn_groups);
   }
   if (p.rows_per_w > 0 || p.a_perm_frames > 0) {
     I2V_CHECK_ARG(p.rows_per_w >= 0 && p.a_perm_frames >= 0 && p.w_batch_stride >= 0, "i2v_gemm_f16: negative batch / permutation field");
-    if (!i2v_gemm_big_unsplit_ok(p, vec4))
+    if (big_plan.form != GemmBigForm::Tile)
       I2V_FAIL(I2V_ERR_INVALID_ARG, "i2v_gemm_f16: per-batch weights / the permuted A gather are not implemented for this "
                "problem (M %d N %d K %d, rows_per_w %d, a_perm %d x %d): they need the 8-wave kernel with full row tiles",
                p.M, p.N, p.K, p.rows_per_w, p.a_perm_frames, p.a_perm_hw);
@@ -497,7 +498,7 @@ extern "C" int i2v_gemm_f16(const i2v_gemm_params* pp, i2v_stream_t stream) {
   }
   // large problems whose N is a multiple of 320 go to the 8-wave LDS-DMA kernel (gemm_big.hip)
   {
-    const int big = i2v_gemm_big_try(p, vec4, reinterpret_cast<hipStream_t>(stream));
+    const int big = i2v_gemm_big_launch(p, vec4, big_plan, reinterpret_cast<hipStream_t>(stream));
     if (big != 0) return big < 0 ? big : I2V_OK;
   }
   if (p.store_mode == I2V_STORE_VT_T) vec4 = 0;   // the generic kernel stores this mode element by element

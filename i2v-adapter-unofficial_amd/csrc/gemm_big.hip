@@ -13,6 +13,7 @@
 // instruction for 8-row group j fetches logical chunk (l & 7) ^ ((row >> 1) & 7) of row 8 j + (l >> 3) (guide rule 21).
 // Masked lanes (row >= M, conv halo) carry an out-of-range buffer offset: LDS-DMA cannot skip a lane, but the
 // descriptor's range check makes it write zeros.
+#include <algorithm>
 #include <cstdlib>
 #include <utility>
 
@@ -766,7 +767,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void gemm_big_kernel(cons
         if constexpr (HILO) xlo[j][q] = __builtin_bit_cast(f16x8, __builtin_amdgcn_raw_buffer_load_b128(rs_xl, off, 0, 0));
       }
     };
-    // (no residual behind a folded LayerNorm: those GEMMs feed q / k / v / the feed-forward; i2v_gemm_big_ln_ok refuses it)
+    // (no residual behind a folded LayerNorm: those GEMMs feed q / k / v / the feed-forward; the planner's ln_fold_ok refuses it)
     if (EPI != I2V_EPI_GEGLU) {
       static_for<(RES_AHEAD < MI ? RES_AHEAD : MI)>([&](auto jc) { fetch_rows(jc); });
     }
@@ -981,166 +982,6 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void gemm_big_kernel(cons
   }   // persistent tile loop
 }
 
-// Persistent launch (I2V_GEMM_PERSIST=1; OFF by default): one workgroup per CU walks the tiles, the next tile's first K
-// tile already in flight under the current epilogue.  Measured on the step's shapes (round 2, same box): the in-kernel
-// timeline loses its 2.4-2.8 us first-tile wait, but a cache-warm 131072 x 2560 x 320 GEGLU gains only 2 %, the K = 640
-// GEGLU loses 2.5 %, N = K = 320 gains 7 %, the whole step: 59.3 vs 59.3 ms.  The hardware's own workgroup turnover
-// already hides what the loop hides; what bounds these kernels is the K loop itself (2.3-2.8 us per 64-deep K tile
-// against 1.3 at the clock the chip holds under this load: one 72 KiB stage in flight does not cover the DMA's tail
-// latency, and LDS has no room for a third stage).  Kept as an A/B switch.
-int persist_mode() {   // 0 (default) never, 1 every eligible plain GEMM, 2 only the LayerNorm-folded row-major GEMMs
-  static const int mode = getenv("I2V_GEMM_PERSIST") ? atoi(getenv("I2V_GEMM_PERSIST")) : 0;
-  return mode;
-}
-int persistent_grid(int ntiles) {
-  static const int cus = [] {
-    if (persist_mode() == 0) return 0;
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-      return 0;
-    return n;
-  }();
-  return (cus > 0 && ntiles > cus) ? cus : ntiles;
-}
-// Round 3, per flavour (tools/gemm4_ab.py under I2V_GEMM_PERSIST=0 / 1 / 2): on one box the walk gained 3 - 14 % on the
-// LayerNorm-folded GEMMs with plain row-major stores (131072 x 960 x 320: 156 -> 134 us) and lost on residual / GEGLU / V^T
-// epilogues; on two other boxes mode 2 (those GEMMs only) measured 155.7 vs 159.2 us on that shape and 54.05 vs 54.09 ms
-// on the whole step -- no reproducible gain, so the default stays 0.
-bool want_persistent(const i2v_gemm_params& p) {
-  const int mode = persist_mode();
-  if (mode == 1) return true;
-  return mode == 2 && p.ln_wsum != nullptr && p.epilogue == I2V_EPI_NONE && p.store_mode == I2V_STORE_ROWMAJOR;
-}
-
-template <int BM, int BK, int NS, int AMODE, bool FAST>
-int launch_big_mode(const i2v_gemm_params& p, hipStream_t s) {
-  const int tiles_m = (int)i2v_cdiv(p.M, BM), tiles_n = p.N / BIG_BN;
-  const int ntiles = tiles_m * tiles_n;
-  const dim3 grid(FAST ? persistent_grid(ntiles) : ntiles), block(512);
-#define I2V_BIG_LAUNCH(EPI, STORE, LNF) \
-  hipLaunchKernelGGL((gemm_big_kernel<BM, BK, NS, AMODE, EPI, STORE, false, true, LNF, FAST>), grid, block, 0, s, p, tiles_n, 0, ntiles)
-#define I2V_BIG_LAUNCH_HILO(STORE) \
-  hipLaunchKernelGGL((gemm_big_kernel<BM, BK, NS, AMODE, I2V_EPI_NONE, STORE, false, true, false, false, 320, 8, false, true>), grid, block, 0, s, \
-                     p, tiles_n, 0, ntiles)
-  const bool hilo = p.residual_lo != nullptr || p.c_lo != nullptr;      // (vetted by i2v_gemm_f16: EPI_NONE, row-major / row-permuted)
-  if (p.ln_wsum != nullptr) {   // LayerNorm-folded epilogues (i2v_gemm_big_ln_ok has vetted the combination)
-    if constexpr (AMODE == I2V_A_PLAIN) {
-      if (p.epilogue == I2V_EPI_GEGLU)
-        I2V_BIG_LAUNCH(I2V_EPI_GEGLU, I2V_STORE_ROWMAJOR, true);
-      else if (p.store_mode == I2V_STORE_VT_T)
-        I2V_BIG_LAUNCH(I2V_EPI_NONE, I2V_STORE_VT_T, true);
-      else if (p.store_mode == I2V_STORE_ROWPERM)
-        I2V_BIG_LAUNCH(I2V_EPI_NONE, I2V_STORE_ROWPERM, true);
-      else
-        I2V_BIG_LAUNCH(I2V_EPI_NONE, I2V_STORE_ROWMAJOR, true);
-    }
-    const int rc = i2v_check_launch("i2v_gemm_f16(big, LayerNorm fold)");
-    return rc < 0 ? rc : 1;
-  }
-  if (p.epilogue == I2V_EPI_GEGLU) {
-    if constexpr (AMODE == I2V_A_PLAIN) I2V_BIG_LAUNCH(I2V_EPI_GEGLU, I2V_STORE_ROWMAJOR, false);
-  } else if (hilo) {               // the precise residual stream (residual_lo / c_lo): plain row-major / row-permuted stores
-    if constexpr (!FAST) {
-      if (p.store_mode == I2V_STORE_ROWPERM) {
-        if constexpr (AMODE == I2V_A_PLAIN) I2V_BIG_LAUNCH_HILO(I2V_STORE_ROWPERM);
-      } else {
-        I2V_BIG_LAUNCH_HILO(I2V_STORE_ROWMAJOR);
-      }
-    }
-  } else if (p.store_mode == I2V_STORE_ROWPERM) {
-    if constexpr (AMODE == I2V_A_PLAIN) I2V_BIG_LAUNCH(I2V_EPI_NONE, I2V_STORE_ROWPERM, false);
-  } else if (p.store_mode == I2V_STORE_VT) {
-    if constexpr (AMODE == I2V_A_PLAIN) I2V_BIG_LAUNCH(I2V_EPI_NONE, I2V_STORE_VT, false);
-  } else if (p.store_mode == I2V_STORE_VT_T) {
-    if constexpr (AMODE == I2V_A_PLAIN) I2V_BIG_LAUNCH(I2V_EPI_NONE, I2V_STORE_VT_T, false);
-  } else if (AMODE == I2V_A_CONV3X3 && p.gn_partial != nullptr) {      // + GroupNorm partials of the result (vetted by i2v_gemm_gn_partial_rows)
-    if constexpr (AMODE == I2V_A_CONV3X3 && !FAST)
-      hipLaunchKernelGGL((gemm_big_kernel<BM, BK, NS, AMODE, I2V_EPI_NONE, I2V_STORE_ROWMAJOR, false, true, false, false, 320, 8, true>), grid,
-                         block, 0, s, p, tiles_n, 0, ntiles);
-  } else {
-    I2V_BIG_LAUNCH(I2V_EPI_NONE, I2V_STORE_ROWMAJOR, false);
-  }
-#undef I2V_BIG_LAUNCH
-#undef I2V_BIG_LAUNCH_HILO
-  const int rc = i2v_check_launch("i2v_gemm_f16(big)");
-  return rc < 0 ? rc : 1;
-}
-
-// Two workgroups of 4 waves per CU: 128 x 320 x 32 tiles (see the NW template parameter).  Measured 5 - 40 % slower on every
-// flavour (below), so the instantiations are compiled only into the A/B library (tools/build_variant.sh --variants).
-#ifdef I2V_VARIANTS
-template <int AMODE>
-int launch_big4(const i2v_gemm_params& p, hipStream_t s) {
-  constexpr int BM = 128;
-  const int tiles_m = (int)i2v_cdiv(p.M, BM), tiles_n = p.N / BIG_BN;
-  const int ntiles = tiles_m * tiles_n;
-  const dim3 grid(ntiles), block(256);
-#define I2V_BIG4_LAUNCH(EPI, STORE, LNF) \
-  hipLaunchKernelGGL((gemm_big_kernel<BM, 32, 2, AMODE, EPI, STORE, false, false, LNF, false, 320, 4>), grid, block, 0, s, p, tiles_n, 0, ntiles)
-  if (p.ln_wsum != nullptr) {
-    if constexpr (AMODE == I2V_A_PLAIN) {
-      if (p.epilogue == I2V_EPI_GEGLU)
-        I2V_BIG4_LAUNCH(I2V_EPI_GEGLU, I2V_STORE_ROWMAJOR, true);
-      else if (p.store_mode == I2V_STORE_VT_T)
-        I2V_BIG4_LAUNCH(I2V_EPI_NONE, I2V_STORE_VT_T, true);
-      else if (p.store_mode == I2V_STORE_ROWPERM)
-        I2V_BIG4_LAUNCH(I2V_EPI_NONE, I2V_STORE_ROWPERM, true);
-      else
-        I2V_BIG4_LAUNCH(I2V_EPI_NONE, I2V_STORE_ROWMAJOR, true);
-    }
-  } else if (p.epilogue == I2V_EPI_GEGLU) {
-    if constexpr (AMODE == I2V_A_PLAIN) I2V_BIG4_LAUNCH(I2V_EPI_GEGLU, I2V_STORE_ROWMAJOR, false);
-  } else if (p.store_mode == I2V_STORE_ROWPERM) {
-    if constexpr (AMODE == I2V_A_PLAIN) I2V_BIG4_LAUNCH(I2V_EPI_NONE, I2V_STORE_ROWPERM, false);
-  } else if (p.store_mode == I2V_STORE_VT) {
-    if constexpr (AMODE == I2V_A_PLAIN) I2V_BIG4_LAUNCH(I2V_EPI_NONE, I2V_STORE_VT, false);
-  } else if (p.store_mode == I2V_STORE_VT_T) {
-    if constexpr (AMODE == I2V_A_PLAIN) I2V_BIG4_LAUNCH(I2V_EPI_NONE, I2V_STORE_VT_T, false);
-  } else {
-    I2V_BIG4_LAUNCH(I2V_EPI_NONE, I2V_STORE_ROWMAJOR, false);
-  }
-#undef I2V_BIG4_LAUNCH
-  const int rc = i2v_check_launch("i2v_gemm_f16(big, 4-wave)");
-  return rc < 0 ? rc : 1;
-}
-
-// Which un-split problems take the 4-wave / two-workgroups-per-CU form: NONE by default.  Measured in round 3 on every
-// GEMM flavour of the step (tools/gemm4_ab.py, same box, profiles/r3_gemm_4wave_ab.txt): 5 - 40 % SLOWER on all of them
-// (131072 x 2560 x 320 GEGLU + LayerNorm 368 -> 386 us, 8192 x 1280 x 5120 + residual 104 -> 145 us, whole step 58.2 ->
-// 64.5 ms).  The overlap of one tile's epilogue with the other's MFMAs does not pay for what the 128 x 320 x 32 tile costs:
-// 91 FLOP per staged byte instead of 146 against a CU's ~70 GB/s LDS-DMA intake, and a barrier every 40 MFMAs per wave.
-// I2V_GEMM_4W=1 selects it for every eligible plain GEMM (kept as a tested A/B switch).
-bool use_4wave(const i2v_gemm_params& p, int plan_rows) {
-  static const int mode = getenv("I2V_GEMM_4W") ? atoi(getenv("I2V_GEMM_4W")) : 0;
-  (void)plan_rows;
-  return mode == 1 && p.a_mode == I2V_A_PLAIN && p.N % BIG_BN == 0 && p.K % 32 == 0;
-}
-#endif
-
-// 3x3 convolutions whose channel count is not a multiple of 320 (the VAE: 128 / 256 / 512): column tiles of 256 or 128
-template <int BM, int BN>
-int launch_big_conv_bn(const i2v_gemm_params& p, hipStream_t s) {
-  const int tiles_m = (int)i2v_cdiv(p.M, BM), tiles_n = p.N / BN;
-  const int ntiles = tiles_m * tiles_n;
-  hipLaunchKernelGGL((gemm_big_kernel<BM, 64, 2, I2V_A_CONV3X3, I2V_EPI_NONE, I2V_STORE_ROWMAJOR, false, true, false, false, BN>),
-                     dim3(ntiles), dim3(512), 0, s, p, tiles_n, 0, ntiles);
-  const int rc = i2v_check_launch("i2v_gemm_f16(big conv)");
-  return rc < 0 ? rc : 1;
-}
-
-// Pipeline shape: two 64-deep stages.  Four 32-deep stages (three tiles in flight, <BM, 32, 4, ...>) measured 5-12 %
-// slower on every shape of the step (profiles/r1_tile_sweep.txt), and again in round 3 on the full-chip 16 x 16 level
-// (tools/l2_ab.py: 8192 x 1280 x 1280 40.6 -> 45.5 us, x 2560 70.7 -> 78.5): with every CU busy the extra barriers cost more
-// than the third tile in flight gives.  Deeper pipelines pay only where the chip is NOT full (deep_plan below).
-template <int BM>
-int launch_big(const i2v_gemm_params& p, int vec4, hipStream_t s) {
-  (void)vec4;
-  if (p.a_mode == I2V_A_CONV3X3) return launch_big_mode<BM, 64, 2, I2V_A_CONV3X3, false>(p, s);
-  if (p.a2 == nullptr && p.M % BM == 0 && want_persistent(p) && persistent_grid(1 << 20) != (1 << 20) && !p.residual_lo && !p.c_lo)
-    return launch_big_mode<BM, 64, 2, I2V_A_PLAIN, true>(p, s);
-  return launch_big_mode<BM, 64, 2, I2V_A_PLAIN, false>(p, s);
-}
-
 // ---- split-K: sum the fp32 partial tiles and apply the fused epilogue (bias / time-embedding vector / residual)
 __global__ __launch_bounds__(256) void splitk_reduce_kernel(const i2v_gemm_params p, const int splits, const int vec4) {
   const int64_t groups = (int64_t)p.M * (p.N / 4);
@@ -1156,14 +997,55 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const i2v_gemm_param
   }
 }
 
-// number of K splits the split path would use (0: not a split-K problem)
-int splitk_plan(const i2v_gemm_params& p, int vec4, int* kps_out) {
-  if (p.N % BIG_BN != 0 || !vec4 || p.epilogue != I2V_EPI_NONE || p.store_mode != I2V_STORE_ROWMAJOR) return 0;
+// ================================================ host side ================================================
+// Three parts: the switches, the dispatch plan (which form of gemm_big_kernel runs a problem, with what grid / splits /
+// workspace: i2v_gemm_big_plan, the only place that decides) and the launch table (launch_form, the only place that spells
+// the kernel's template arguments).
+
+// The I2V_GEMM_* switches of this file (README, "switches"), read once per process.
+struct GemmBigSwitches {
+  int big;        // I2V_GEMM_BIG: unset = decide per problem, 0 = never this kernel, 256 / 128 = force that tile height
+  int splitk;     // I2V_GEMM_SPLITK [1]: 0 = report no split-K workspace (callers then attach none, so nothing is split)
+  int split256;   // I2V_GEMM_SPLIT256 [1]: 256-row tiles with K split.  0 off, 1 convolutions with >= 90 K tiles and the 8 x 8 level's
+                  // plain GEMMs with >= 64, 2 every eligible problem
+  int deep;       // I2V_GEMM_DEEP [2]: deep-pipeline form.  0 off, 1 only where the 128 / 256-row tiles fill < 40 % of the chip,
+                  // 2 every eligible problem
+  int persist;    // I2V_GEMM_PERSIST [0]: persistent tile walk.  0 never, 1 every eligible plain GEMM, 2 only the LayerNorm-folded
+                  // row-major GEMMs
+  int four_wave;  // I2V_GEMM_4W [0]: 1 = the 4-wave / two-workgroups-per-CU form for every eligible plain GEMM (variants library only)
+};
+const GemmBigSwitches& switches() {
+  static const GemmBigSwitches sw = [] {
+    auto env = [](const char* name, int unset) { return getenv(name) ? atoi(getenv(name)) : unset; };
+    return GemmBigSwitches{env("I2V_GEMM_BIG", -1),    env("I2V_GEMM_SPLITK", 1),  env("I2V_GEMM_SPLIT256", 1),
+                           env("I2V_GEMM_DEEP", 2),    env("I2V_GEMM_PERSIST", 0), env("I2V_GEMM_4W", 0)};
+  }();
+  return sw;
+}
+// tuning values that were settled by measurement (the rules that use them say how)
+constexpr int BIG_MIN_K = 128;           // plain GEMMs: a single K tile cannot hide its own DMA latency
+constexpr int SPLIT256_MIN_TILES = 16;   // 256-row split-K: the 8 x 8 level (16 tiles) and up
+constexpr int DEEP_MIN_KT = 10, DEEP_MAX_KT = 63;   // deep pipeline: K tiles of the chain it is worth building for
+constexpr bool BIG_VAE_TILES = true;     // 256 / 128-column tiles for the VAE's 3x3 convolutions
+
+struct SplitPlan {
+  int splits = 0, kps = 0;   // splits == 0: not a split-K problem
+};
+SplitPlan even_splits(int nkt, int splits) {   // `splits` ranges of K tiles, none empty
+  SplitPlan sp;
+  sp.kps = (int)i2v_cdiv(nkt, splits);
+  sp.splits = (int)i2v_cdiv(nkt, sp.kps);
+  return sp.splits < 2 ? SplitPlan{} : sp;
+}
+
+// 128-row tiles with K split: too few output tiles for the chip and a long K
+SplitPlan splitk_plan(const i2v_gemm_params& p, int vec4) {
+  if (p.N % BIG_BN != 0 || !vec4 || p.epilogue != I2V_EPI_NONE || p.store_mode != I2V_STORE_ROWMAJOR) return {};
   const int nkt = (p.K + 63) / 64;
   const int64_t t128 = i2v_cdiv(p.M, 128) * (p.N / BIG_BN);
   // measured: K = 1280 (20 K tiles) loses to the unsplit generic kernel (the reduce pass costs more than it saves);
   // K >= 2560 gains 1.6 - 2.3x (8 x 8 level convs 316 -> 654 TFLOP/s)
-  if (nkt < 40 || t128 > 128) return 0;
+  if (nkt < 40 || t128 > 128) return {};
   int splits = (int)(256 / t128);
   // (the weight gradients of the training step contract over every token: 320 x 320 x 65536 = 3 tiles with 1024 K tiles each.
   //  Eight splits left them on 24 workgroups, 138 us; plain GEMMs with >= 256 K tiles -- none on the inference path -- may take 64:
@@ -1171,11 +1053,8 @@ int splitk_plan(const i2v_gemm_params& p, int vec4, int* kps_out) {
   const int cap = (p.a_mode == I2V_A_PLAIN && nkt >= 256) ? 64 : 8;
   if (splits > cap) splits = cap;
   if (splits > nkt / 8) splits = nkt / 8;
-  if (splits < 2) return 0;
-  const int kps = (int)i2v_cdiv(nkt, splits);
-  splits = (int)i2v_cdiv(nkt, kps);          // no empty split
-  if (kps_out) *kps_out = kps;
-  return splits;
+  if (splits < 2) return {};
+  return even_splits(nkt, splits);
 }
 
 // 256-row tiles with K split in two to four: problems whose 256-row tiles fill only a quarter to half of the chip (the 16 x 16
@@ -1186,288 +1065,336 @@ int splitk_plan(const i2v_gemm_params& p, int vec4, int* kps_out) {
 // conv 8192 x 1280 x 23040 425.7 -> 382.8 us, x 17280 329.4 -> 298.5, x 11520 + residual 232.7 -> 227.4, x 5760 130.2 -> 121.5;
 // GEMM 8192 x 1280 x 5120 + residual 122.9 -> 129.9 (the partials cost more than its 80 K tiles give back).  Whole step, same
 // box: 54.84 -> 54.13 ms with the 16 x 16 level's convolutions, 54.02 -> 53.76 with the 8 x 8 level's too (tiles >= 16),
-// 52.12 -> 51.99 with the plain GEMMs as well.  Default (I2V_GEMM_SPLIT256 unset / 1): convolutions with >= 90 K tiles and the
-// 8 x 8 level's plain GEMMs with >= 64; 2: every eligible GEMM; 0: off.
-int splitk256_plan(const i2v_gemm_params& p, int vec4, int* kps_out) {
-  static const int on = getenv("I2V_GEMM_SPLIT256") ? atoi(getenv("I2V_GEMM_SPLIT256")) : 1;
-  if (!on) return 0;
-  const int64_t t256_ = (int64_t)(p.M / 256 > 0 ? p.M / 256 : 1) * (p.N / BIG_BN);
-  if (on == 1 && p.a_mode == I2V_A_CONV3X3 && (p.K + 63) / 64 < 90) return 0;
-  if (on == 1 && p.a_mode != I2V_A_CONV3X3 && t256_ > 32) return 0;   // plain GEMMs: the 8 x 8 level only (52.12 -> 51.99 ms)
-  if (p.N % BIG_BN != 0 || !vec4 || p.epilogue != I2V_EPI_NONE || p.store_mode != I2V_STORE_ROWMAJOR || p.M % 256 != 0) return 0;
-  if (p.a2 != nullptr || p.rows_per_w > 0 || p.a_perm_frames > 0 || p.ln_wsum != nullptr) return 0;
+// 52.12 -> 51.99 with the plain GEMMs as well.  Hence the default (GemmBigSwitches::split256 == 1).
+SplitPlan splitk256_plan(const i2v_gemm_params& p, int vec4) {
+  const int on = switches().split256;
+  if (!on) return {};
   const int nkt = (p.K + 63) / 64;
   const int64_t t256 = (int64_t)(p.M / 256) * (p.N / BIG_BN);
-  static const int min_t = getenv("I2V_GEMM_SPLIT256_MINT") ? atoi(getenv("I2V_GEMM_SPLIT256_MINT")) : 16;
-  if (nkt < 64 || t256 < min_t || t256 > 128) return 0;
+  if (on == 1 && p.a_mode == I2V_A_CONV3X3 && nkt < 90) return {};
+  if (on == 1 && p.a_mode != I2V_A_CONV3X3 && t256 > 32) return {};   // plain GEMMs: the 8 x 8 level only (52.12 -> 51.99 ms)
+  if (p.N % BIG_BN != 0 || !vec4 || p.epilogue != I2V_EPI_NONE || p.store_mode != I2V_STORE_ROWMAJOR || p.M % 256 != 0) return {};
+  if (p.a2 != nullptr || p.rows_per_w > 0 || p.a_perm_frames > 0 || p.ln_wsum != nullptr) return {};
+  if (nkt < 64 || t256 < SPLIT256_MIN_TILES || t256 > 128) return {};
   int splits = (int)(256 / t256);
   if (splits > 8) splits = 8;
   if (splits > nkt / 8) splits = nkt / 8;
-  const int kps = (int)i2v_cdiv(nkt, splits);
-  splits = (int)i2v_cdiv(nkt, kps);
-  if (splits < 2) return 0;
-  if (kps_out) *kps_out = kps;
-  return splits;
-}
-
-int launch_split256(const i2v_gemm_params& p, int vec4, int splits, int kps, hipStream_t s) {
-  const int tiles_m = p.M / 256, tiles_n = p.N / BIG_BN;
-  const dim3 grid(tiles_m * tiles_n, splits), block(512);
-  if (p.a_mode == I2V_A_CONV3X3)
-    hipLaunchKernelGGL((gemm_big_kernel<256, 64, 2, I2V_A_CONV3X3, I2V_EPI_NONE, I2V_STORE_ROWMAJOR, true>), grid, block, 0, s, p,
-                       tiles_n, kps, tiles_m * tiles_n);
-  else
-    hipLaunchKernelGGL((gemm_big_kernel<256, 64, 2, I2V_A_PLAIN, I2V_EPI_NONE, I2V_STORE_ROWMAJOR, true>), grid, block, 0, s, p,
-                       tiles_n, kps, tiles_m * tiles_n);
-  const int64_t groups = (int64_t)p.M * (p.N / 4);
-  const int blocks = (int)(i2v_cdiv(groups, 256) < 2048 ? i2v_cdiv(groups, 256) : 2048);
-  hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, s, p, splits, vec4);
-  const int rc = i2v_check_launch("i2v_gemm_f16(split-K, 256-row tiles)");
-  return rc < 0 ? rc : 1;
-}
-
-int launch_split(const i2v_gemm_params& p, int vec4, int splits, int kps, hipStream_t s) {
-  const int tiles_m = (int)i2v_cdiv(p.M, 128), tiles_n = p.N / BIG_BN;
-  const dim3 grid(tiles_m * tiles_n, splits), block(512);
-  if (p.a_mode == I2V_A_CONV3X3)
-    hipLaunchKernelGGL((gemm_big_kernel<128, 64, 2, I2V_A_CONV3X3, I2V_EPI_NONE, I2V_STORE_ROWMAJOR, true>), grid, block, 0, s, p,
-                       tiles_n, kps, tiles_m * tiles_n);
-  else
-    hipLaunchKernelGGL((gemm_big_kernel<128, 64, 2, I2V_A_PLAIN, I2V_EPI_NONE, I2V_STORE_ROWMAJOR, true>), grid, block, 0, s, p,
-                       tiles_n, kps, tiles_m * tiles_n);
-  const int64_t groups = (int64_t)p.M * (p.N / 4);
-  const int blocks = (int)(i2v_cdiv(groups, 256) < 2048 ? i2v_cdiv(groups, 256) : 2048);
-  hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, s, p, splits, vec4);
-  const int rc = i2v_check_launch("i2v_gemm_f16(split-K)");
-  return rc < 0 ? rc : 1;
+  return even_splits(nkt, splits);
 }
 
 // Deep-pipeline form for the problems that cannot fill the chip (the 8 x 8 level: 2048 rows): their K loop is a chain of
 // nkt DMA round trips (1.3 - 1.5 us each with one tile in flight, whatever the tile size), so the tile is made SMALLER --
 // 128 x 128 (32 KiB stages, four of them) or 128 x 256 (48 KiB, three) -- and the freed LDS holds two or three more K tiles
 // in flight: the chain advances at round trip / 3 (or / 2), and the smaller tiles also spread the problem over more CUs.
-// Returns the column tile (128 / 256) or 0.  I2V_GEMM_DEEP=0 turns it off.
-int deep_plan(const i2v_gemm_params& p, int vec4) {
-  static const int on = getenv("I2V_GEMM_DEEP") ? atoi(getenv("I2V_GEMM_DEEP")) : 1;
-  if (!on || !vec4) return 0;
+// Returns the column tile (128 / 256) or 0.
+int deep_cols(const i2v_gemm_params& p, int vec4) {
+  if (!switches().deep || !vec4) return 0;
   if (p.a_mode != I2V_A_PLAIN || p.epilogue != I2V_EPI_NONE || p.store_mode == I2V_STORE_VT_T || p.ln_wsum != nullptr) return 0;
   if (p.rows_per_w > 0 || p.a_perm_frames > 0 || p.c_is_f32) return 0;
-  static const int min_kt = getenv("I2V_GEMM_DEEP_MINKT") ? atoi(getenv("I2V_GEMM_DEEP_MINKT")) : 10;
-  if (p.N % 128 != 0 || (p.K + 63) / 64 < min_kt) return 0;
+  if (p.N % 128 != 0 || (p.K + 63) / 64 < DEEP_MIN_KT) return 0;
   const int64_t tm = i2v_cdiv(p.M, 128);
   if (tm * (p.N / 128) <= 256) return 128;
   if (p.N % 256 == 0 && tm * (p.N / 256) <= 256) return 256;
   return 0;
 }
 
-template <int BN, int NS>
-int launch_deep(const i2v_gemm_params& p, hipStream_t s) {
-  const int tiles_m = (int)i2v_cdiv(p.M, 128), tiles_n = p.N / BN;
-  const int ntiles = tiles_m * tiles_n;
-#define I2V_DEEP_LAUNCH(STORE) \
-  hipLaunchKernelGGL((gemm_big_kernel<128, 64, NS, I2V_A_PLAIN, I2V_EPI_NONE, STORE, false, true, false, false, BN>), \
-                     dim3(ntiles), dim3(512), 0, s, p, tiles_n, 0, ntiles)
-  if (p.residual_lo != nullptr || p.c_lo != nullptr) {
-    if (p.store_mode == I2V_STORE_ROWPERM)
-      hipLaunchKernelGGL((gemm_big_kernel<128, 64, NS, I2V_A_PLAIN, I2V_EPI_NONE, I2V_STORE_ROWPERM, false, true, false, false, BN, 8, false, true>),
-                         dim3(ntiles), dim3(512), 0, s, p, tiles_n, 0, ntiles);
-    else
-      hipLaunchKernelGGL((gemm_big_kernel<128, 64, NS, I2V_A_PLAIN, I2V_EPI_NONE, I2V_STORE_ROWMAJOR, false, true, false, false, BN, 8, false, true>),
-                         dim3(ntiles), dim3(512), 0, s, p, tiles_n, 0, ntiles);
-  } else if (p.store_mode == I2V_STORE_ROWPERM)
-    I2V_DEEP_LAUNCH(I2V_STORE_ROWPERM);
-  else if (p.store_mode == I2V_STORE_VT)
-    I2V_DEEP_LAUNCH(I2V_STORE_VT);
-  else
-    I2V_DEEP_LAUNCH(I2V_STORE_ROWMAJOR);
-#undef I2V_DEEP_LAUNCH
-  const int rc = i2v_check_launch("i2v_gemm_f16(big, deep pipeline)");
-  return rc < 0 ? rc : 1;
+bool a16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
+bool lo_stream(const i2v_gemm_params& p) { return p.residual_lo != nullptr || p.c_lo != nullptr; }   // the precise residual stream
+// the caller attached an fp32 scratch that holds `splits` partial results
+bool workspace_holds(const i2v_gemm_params& p, int splits) {
+  return p.workspace && p.workspace_bytes >= (int64_t)splits * p.M * p.N * (int64_t)sizeof(float) && a16(p.workspace);
 }
 
-}  // namespace
-
-int64_t i2v_gemm_big_workspace_bytes(const i2v_gemm_params& p, int vec4) {
-  static const int off = getenv("I2V_GEMM_SPLITK") ? (atoi(getenv("I2V_GEMM_SPLITK")) == 0) : 0;
-  if (off) return 0;
-  int splits = splitk_plan(p, vec4, nullptr);
-  const int s256 = splitk256_plan(p, vec4, nullptr);
-  if (s256 > splits) splits = s256;
-  return splits ? (int64_t)splits * p.M * p.N * (int64_t)sizeof(float) : 0;
-}
-
-namespace {
-// columns per tile for this problem: 320 (UNet), or for 3x3 convolutions 256 / 128 (VAE channel counts); 0 = none
-int big_bn(const i2v_gemm_params& p) {
-  if (p.c_is_f32) return 0;   // fp32 results exist in the generic kernel only (narrow outputs)
-  if (p.N % BIG_BN == 0) return BIG_BN;
-  if (p.a_mode == I2V_A_PLAIN) return deep_plan(p, 1) ? -1 : 0;   // -1: the deep-pipeline form (128 / 256 columns) or nothing
-  static const int vae = getenv("I2V_GEMM_BIG_VAE") ? atoi(getenv("I2V_GEMM_BIG_VAE")) : 1;
-  if (vae && p.a_mode == I2V_A_CONV3X3 && p.epilogue == I2V_EPI_NONE && p.store_mode == I2V_STORE_ROWMAJOR && !p.residual_lo && !p.c_lo) {
-    if (p.N % 256 == 0) return 256;
-    if (p.N % 128 == 0) return 128;
+// form, tile and splits of one problem (plan.form stays None: not for this kernel).  The answer depends on the attached
+// workspace: a problem that splits K with one may run un-split (or on the generic kernel) without.
+void plan_form(const i2v_gemm_params& p, int vec4, GemmBigPlan& plan) {
+  using Form = GemmBigForm;
+  const GemmBigSwitches& sw = switches();
+  const bool conv = p.a_mode == I2V_A_CONV3X3;
+  auto set = [&plan](Form form, int rows, int cols, int stages, SplitPlan sp = {}) {
+    plan.form = form, plan.rows = rows, plan.cols = cols, plan.stages = stages, plan.splits = sp.splits, plan.kps = sp.kps;
+  };
+  if (sw.big == 0) return;
+  if (p.c_is_f32) return;   // fp32 results exist in the generic kernel only (narrow outputs)
+  // columns per tile: 320 (UNet), or for 3x3 convolutions 256 / 128 (VAE channel counts); plain GEMMs with other widths have
+  // the deep-pipeline form (128 / 256 columns) or nothing
+  const int dcols = deep_cols(p, vec4);
+  int cols = 0;
+  if (p.N % BIG_BN == 0) {
+    cols = BIG_BN;
+  } else if (p.a_mode == I2V_A_PLAIN) {
+    if (!dcols) return;
+  } else if (BIG_VAE_TILES && conv && p.epilogue == I2V_EPI_NONE && p.store_mode == I2V_STORE_ROWMAJOR && !lo_stream(p)) {
+    cols = p.N % 256 == 0 ? 256 : p.N % 128 == 0 ? 128 : 0;
+    if (!cols) return;
+  } else {
+    return;
   }
-  return 0;
-}
-
-// dispatch decision for one problem: 0 = not for this kernel, 256 / 128 = tile height, -1 = split-K (*splits, *kps set)
-int big_plan(const i2v_gemm_params& p, int vec4, int* splits_out, int* kps_out) {
-  static const int mode = getenv("I2V_GEMM_BIG") ? atoi(getenv("I2V_GEMM_BIG")) : -1;  // 0 off, 256 / 128 force
-  if (mode == 0) return 0;
-  const int bn = big_bn(p);
-  if (bn == 0) return 0;
+  const bool deep_only = cols == 0;
   // the kernel addresses each operand through a buffer descriptor with 32-bit byte offsets (< 2 GiB per operand) and
   // moves whole BK-deep K tiles (K, the concat split and the conv channel count must be multiples of 64)
-  if (p.K % 64 != 0 || (p.a2 != nullptr && p.k_split % 64 != 0)) return 0;
-  if ((int64_t)p.N * p.ldw >= (1ll << 30)) return 0;
-  if (p.a_mode == I2V_A_CONV3X3) {
-    if (p.cin % 64 != 0 || (int64_t)p.n_img * p.in_h * p.in_w * p.lda >= (1ll << 30)) return 0;
-    if (p.conv_kblock != 0 && p.conv_kblock != 64) return 0;
+  if (p.K % 64 != 0 || (p.a2 != nullptr && p.k_split % 64 != 0)) return;
+  if ((int64_t)p.N * p.ldw >= (1ll << 30)) return;
+  if (conv) {
+    if (p.cin % 64 != 0 || (int64_t)p.n_img * p.in_h * p.in_w * p.lda >= (1ll << 30)) return;
+    if (p.conv_kblock != 0 && p.conv_kblock != 64) return;
   } else if ((int64_t)p.M * p.lda >= (1ll << 30) || (int64_t)p.M * p.lda2 >= (1ll << 30)) {
-    return 0;
+    return;
   }
   // the specialised epilogue handles the vector (8-byte) forms only; anything else stays on the generic kernel
-  if (!vec4 || p.epilogue == I2V_EPI_GELU) return 0;
-  if (p.a_mode == I2V_A_CONV3X3 && (p.epilogue != I2V_EPI_NONE || p.store_mode != I2V_STORE_ROWMAJOR)) return 0;
-  if (p.epilogue == I2V_EPI_GEGLU && p.store_mode != I2V_STORE_ROWMAJOR) return 0;
+  if (!vec4 || p.epilogue == I2V_EPI_GELU) return;
+  if (conv && (p.epilogue != I2V_EPI_NONE || p.store_mode != I2V_STORE_ROWMAJOR)) return;
+  if (p.epilogue == I2V_EPI_GEGLU && p.store_mode != I2V_STORE_ROWMAJOR) return;
   if (p.store_mode == I2V_STORE_ROWMAJOR || p.store_mode == I2V_STORE_ROWPERM) {
     // the row-contiguous epilogue moves 16 bytes per lane
-    auto a16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-    if (p.ldc % 8 != 0 || !a16(p.c)) return 0;
-    if (p.residual && (p.ldr % 8 != 0 || !a16(p.residual))) return 0;
-    if (!a16(p.residual_lo) || !a16(p.c_lo)) return 0;
-    if (p.rowvec && (p.ld_rowvec % 8 != 0 || !a16(p.rowvec))) return 0;
+    if (p.ldc % 8 != 0 || !a16(p.c)) return;
+    if (p.residual && (p.ldr % 8 != 0 || !a16(p.residual))) return;
+    if (!a16(p.residual_lo) || !a16(p.c_lo)) return;
+    if (p.rowvec && (p.ld_rowvec % 8 != 0 || !a16(p.rowvec))) return;
   }
-  if (p.rowvec && p.M >= (1 << 24)) return 0;   // the epilogue's reciprocal division of the row index is exact below 2^24
+  if (p.rowvec && p.M >= (1 << 24)) return;   // the epilogue's reciprocal division of the row index is exact below 2^24
   // the row-contiguous epilogue prefetches ONE added operand (residual or row vector) and addresses C and it with 32-bit
   // byte offsets (buffer ops)
-  if (p.residual && p.rowvec && p.epilogue != I2V_EPI_GEGLU) return 0;
+  if (p.residual && p.rowvec && p.epilogue != I2V_EPI_GEGLU) return;
   const int64_t rv_rows = p.rowvec_period > 0 ? p.rowvec_period : (p.M - 1) / (p.rows_per_vec > 0 ? p.rows_per_vec : 1) + 1;
   if ((int64_t)p.M * p.ldc >= (1ll << 30) || (p.residual && (int64_t)p.M * p.ldr >= (1ll << 30)) ||
       (p.rowvec && rv_rows * p.ld_rowvec >= (1ll << 30)))
-    return 0;
+    return;
   if (p.rows_per_w > 0 || p.a_perm_frames > 0) {
     // per-batch weights / the permuted A gather exist only in the full-tile DMA path of the un-split kernel
-    if (p.a_mode != I2V_A_PLAIN || p.a2 != nullptr || p.M % 256 != 0) return 0;
+    if (p.a_mode != I2V_A_PLAIN || p.a2 != nullptr || p.M % 256 != 0) return;
     if (p.rows_per_w > 0 && (p.rows_per_w % 256 != 0 || p.M % p.rows_per_w != 0 ||
                              (int64_t)(p.M / p.rows_per_w) * p.w_batch_stride >= (1ll << 30)))
-      return 0;
+      return;
     if (p.a_perm_frames > 0) {
       const int f = p.a_perm_frames;
       if ((f & (f - 1)) != 0 || f > 64 || p.a_perm_hw <= 0 || p.a_perm_hw % (64 / f) != 0 ||
           ((int64_t)f * p.a_perm_hw) % 256 != 0 || p.M % (f * p.a_perm_hw) != 0)
-        return 0;
+        return;
     }
   }
-  const int64_t tn = bn > 0 ? p.N / bn : i2v_cdiv(p.N, BIG_BN);
-  const int64_t t256 = i2v_cdiv(p.M, 256) * tn, t128 = i2v_cdiv(p.M, 128) * tn;
-  if (mode == 256 || mode == 128) return bn > 0 ? mode : 0;
-  static const int min_k = getenv("I2V_GEMM_BIG_MINK") ? atoi(getenv("I2V_GEMM_BIG_MINK")) : 128;
-  if (p.a_mode != I2V_A_CONV3X3 && p.K < min_k) return 0;   // a single K tile cannot hide its own DMA latency
+  if (sw.big == 256 || sw.big == 128) {   // forced tile height (the column tile must exist)
+    if (!deep_only) set(Form::Tile, sw.big, cols, 2);
+    return;
+  }
+  if (!conv && p.K < BIG_MIN_K) return;
+  // 256-row tiles with K split, when the caller supplied the fp32 scratch
+  const SplitPlan sp256 = splitk256_plan(p, vec4);
+  if (sp256.splits && workspace_holds(p, sp256.splits)) return set(Form::SplitK, 256, BIG_BN, 2, sp256);
   // one 8-wave block per CU: a tile count just above a multiple of 256 wastes most of the last round.  Pick the
   // tile height by (fill of the last round) x (measured relative rate: 256-row 1.0, 128-row 0.82,
   // profiles/r1_tile_sweep.txt); below 40 % the 3-blocks-per-CU kernel of gemm.hip is faster.
-  {   // 256-row tiles with K split (returns -2)
-    int kps256 = 0;
-    const int s256 = splitk256_plan(p, vec4, &kps256);
-    if (s256 && p.workspace && p.workspace_bytes >= (int64_t)s256 * p.M * p.N * (int64_t)sizeof(float) &&
-        (reinterpret_cast<uintptr_t>(p.workspace) % 16) == 0) {
-      if (splits_out) *splits_out = s256;
-      if (kps_out) *kps_out = kps256;
-      return -2;
-    }
-  }
+  const int64_t tn = deep_only ? i2v_cdiv(p.N, BIG_BN) : p.N / cols;
+  const int64_t t256 = i2v_cdiv(p.M, 256) * tn, t128 = i2v_cdiv(p.M, 128) * tn;
   const double e256 = (double)t256 / (double)(i2v_cdiv(t256, 256) * 256);
   const double e128 = 0.82 * (double)t128 / (double)(i2v_cdiv(t128, 256) * 256);
-  if (bn == BIG_BN || bn == -1) {   // a single, partial round of tiles and a chain of >= 10 K tiles: the deep-pipeline form
-    static const int deep_mode = getenv("I2V_GEMM_DEEP") ? atoi(getenv("I2V_GEMM_DEEP")) : 2;
-    static const int max_kt = getenv("I2V_GEMM_DEEP_MAXKT") ? atoi(getenv("I2V_GEMM_DEEP_MAXKT")) : 63;
-    const int dbn = deep_plan(p, vec4);
-    if (dbn && (p.K + 63) / 64 <= max_kt && (deep_mode == 2 || bn == -1 || (e256 < 0.40 && e128 < 0.40)))
-      return -3 - (dbn == 256 ? 1 : 0);   // -3: 128-column tiles, -4: 256-column tiles
-    if (bn == -1) return 0;
+  if (cols == BIG_BN || deep_only) {   // a single, partial round of tiles and a chain of >= 10 K tiles: the deep-pipeline form
+    if (dcols && (p.K + 63) / 64 <= DEEP_MAX_KT && (sw.deep == 2 || deep_only || (e256 < 0.40 && e128 < 0.40)))
+      return set(Form::Deep, 128, dcols, dcols == 256 ? 3 : 4);
+    if (deep_only) return;
   }
-  if (e256 >= e128 && e256 >= 0.40) return 256;
-  if (e128 >= 0.40) return 128;
-  if (bn != BIG_BN) return 0;   // (split-K exists for 320-column tiles only)
-
+  // Pipeline shape of the tile form: two 64-deep stages.  Four 32-deep stages (three tiles in flight) measured 5-12 %
+  // slower on every shape of the step (profiles/r1_tile_sweep.txt), and again in round 3 on the full-chip 16 x 16 level
+  // (tools/l2_ab.py: 8192 x 1280 x 1280 40.6 -> 45.5 us, x 2560 70.7 -> 78.5): with every CU busy the extra barriers cost more
+  // than the third tile in flight gives.  Deeper pipelines pay only where the chip is NOT full (the deep form above).
+  if (e256 >= e128 && e256 >= 0.40) return set(Form::Tile, 256, cols, 2);
+  if (e128 >= 0.40) return set(Form::Tile, 128, cols, 2);
+  if (cols != BIG_BN) return;   // (split-K exists for 320-column tiles only)
   // too few output tiles for the chip: split K when the caller supplied the fp32 scratch
-  int kps = 0;
-  const int splits = splitk_plan(p, vec4, &kps);
-  if (splits && p.workspace && p.workspace_bytes >= (int64_t)splits * p.M * p.N * (int64_t)sizeof(float) &&
-      (reinterpret_cast<uintptr_t>(p.workspace) % 16) == 0) {
-    if (splits_out) *splits_out = splits;
-    if (kps_out) *kps_out = kps;
-    return -1;
-  }
-  return 0;
+  const SplitPlan sp128 = splitk_plan(p, vec4);
+  if (sp128.splits && workspace_holds(p, sp128.splits)) return set(Form::SplitK, 128, BIG_BN, 2, sp128);
 }
-}  // namespace
 
 // LayerNorm-folded problems (ln_wsum set) run only on the un-split 8-wave kernel, through the epilogues that
 // implement the fold: the row-contiguous staged stores (row-major / row-permuted, plain or GEGLU) and the fast V^T form.
-int i2v_gemm_big_ln_ok(const i2v_gemm_params& p, int vec4) {
-  const int plan = big_plan(p, vec4, nullptr, nullptr);
-  if (plan != 256 && plan != 128) return 0;
-  if (p.a_mode != I2V_A_PLAIN || p.a2 != nullptr) return 0;   // the K loop must stream whole rows of ONE source
-  if (p.rowvec && p.rowvec_period > 0 && (p.rowvec_period & (p.rowvec_period - 1)) != 0) return 0;
-  if (p.residual) return 0;   // no consumer of a folded LayerNorm adds a residual; the LNF epilogues do not carry the path
+bool ln_fold_ok(const i2v_gemm_params& p, const GemmBigPlan& plan) {
+  if (plan.form != GemmBigForm::Tile) return false;
+  if (p.a_mode != I2V_A_PLAIN || p.a2 != nullptr) return false;   // the K loop must stream whole rows of ONE source
+  if (p.rowvec && p.rowvec_period > 0 && (p.rowvec_period & (p.rowvec_period - 1)) != 0) return false;
+  if (p.residual) return false;   // no consumer of a folded LayerNorm adds a residual; the LNF epilogues do not carry the path
   if (p.store_mode == I2V_STORE_ROWMAJOR || p.store_mode == I2V_STORE_ROWPERM)
-    return (p.epilogue == I2V_EPI_NONE || (p.epilogue == I2V_EPI_GEGLU && !p.rowvec)) ? 1 : 0;
+    return p.epilogue == I2V_EPI_NONE || (p.epilogue == I2V_EPI_GEGLU && !p.rowvec);
   if (p.store_mode == I2V_STORE_VT_T)
-    return (p.vt_len % 8 == 0 && p.M % 8 == 0 && p.vt_ld % 8 == 0 && (reinterpret_cast<uintptr_t>(p.c) & 15) == 0 &&
-            (!p.rowvec || (p.rowvec_period >= 8 && (p.rowvec_period & (p.rowvec_period - 1)) == 0 && p.ld_rowvec % 8 == 0)))
-               ? 1 : 0;
-  return 0;
+    return p.vt_len % 8 == 0 && p.M % 8 == 0 && p.vt_ld % 8 == 0 && a16(p.c) &&
+           (!p.rowvec || (p.rowvec_period >= 8 && (p.rowvec_period & (p.rowvec_period - 1)) == 0 && p.ld_rowvec % 8 == 0));
+  return false;
 }
 
 // rows per block of the GroupNorm partials the un-split convolution's epilogue writes (gn_partial), 0: not this problem
-int i2v_gemm_big_gn_rows(const i2v_gemm_params& p, int vec4) {
-  const int plan = big_plan(p, vec4, nullptr, nullptr);
-  if (plan != 256 && plan != 128) return 0;
-  if (p.a_mode != I2V_A_CONV3X3 || big_bn(p) != BIG_BN || p.epilogue != I2V_EPI_NONE || p.store_mode != I2V_STORE_ROWMAJOR) return 0;
+int gn_partial_rows(const i2v_gemm_params& p, const GemmBigPlan& plan) {
+  if (plan.form != GemmBigForm::Tile || plan.cols != BIG_BN) return 0;
+  if (p.a_mode != I2V_A_CONV3X3 || p.epilogue != I2V_EPI_NONE || p.store_mode != I2V_STORE_ROWMAJOR) return 0;
   if (p.residual || p.ln_wsum || p.c_is_f32 || p.rows_per_w > 0 || p.a_perm_frames > 0) return 0;
   // the partials describe acc + bias + rowvec: with an output scale the stored tensor is another one
   if (p.out_scale != 1.0f) return 0;
   if (p.gn_groups <= 0 || p.N % p.gn_groups != 0) return 0;
   const int cpg = p.N / p.gn_groups, hw = p.out_h * p.out_w;
-  if (cpg <= 0 || BIG_BN % cpg != 0 || p.M % plan != 0 || hw % plan != 0) return 0;
-  if (p.rowvec && (p.rowvec_period > 0 || p.rows_per_vec <= 0 || p.rows_per_vec % plan != 0)) return 0;
-  return plan;
+  if (cpg <= 0 || BIG_BN % cpg != 0 || p.M % plan.rows != 0 || hw % plan.rows != 0) return 0;
+  if (p.rowvec && (p.rowvec_period > 0 || p.rows_per_vec <= 0 || p.rows_per_vec % plan.rows != 0)) return 0;
+  return plan.rows;
 }
 
-// 1 if the 8-wave kernel takes this problem un-split (per-batch weights and the permuted A gather exist only there)
-int i2v_gemm_big_unsplit_ok(const i2v_gemm_params& p, int vec4) {
-  const int plan = big_plan(p, vec4, nullptr, nullptr);
-  return plan == 256 || plan == 128;
+// Persistent walk (I2V_GEMM_PERSIST; OFF by default): one workgroup per CU walks the tiles, the next tile's first K
+// tile already in flight under the current epilogue.  Measured on the step's shapes (round 2, same box): the in-kernel
+// timeline loses its 2.4-2.8 us first-tile wait, but a cache-warm 131072 x 2560 x 320 GEGLU gains only 2 %, the K = 640
+// GEGLU loses 2.5 %, N = K = 320 gains 7 %, the whole step: 59.3 vs 59.3 ms.  The hardware's own workgroup turnover
+// already hides what the loop hides; what bounds these kernels is the K loop itself (2.3-2.8 us per 64-deep K tile
+// against 1.3 at the clock the chip holds under this load: one 72 KiB stage in flight does not cover the DMA's tail
+// latency, and LDS has no room for a third stage).  Kept as an A/B switch.
+// Round 3, per flavour (tools/gemm4_ab.py under I2V_GEMM_PERSIST=0 / 1 / 2): on one box the walk gained 3 - 14 % on the
+// LayerNorm-folded GEMMs with plain row-major stores (131072 x 960 x 320: 156 -> 134 us) and lost on residual / GEGLU / V^T
+// epilogues; on two other boxes mode 2 (those GEMMs only) measured 155.7 vs 159.2 us on that shape and 54.05 vs 54.09 ms
+// on the whole step -- no reproducible gain, so the default stays 0.
+// The walk exists for plain A from one source with whole row tiles (the kernel's FAST form).
+bool want_persistent(const i2v_gemm_params& p, const GemmBigPlan& plan) {
+  const int mode = switches().persist;
+  if (plan.form != GemmBigForm::Tile || plan.cols != BIG_BN || p.a_mode != I2V_A_PLAIN) return false;
+  if (p.a2 != nullptr || p.M % plan.rows != 0 || lo_stream(p)) return false;
+  return mode == 1 || (mode == 2 && p.ln_wsum != nullptr && p.epilogue == I2V_EPI_NONE && p.store_mode == I2V_STORE_ROWMAJOR);
+}
+int persistent_grid(int ntiles) {   // (the CU count is looked up at the first launch, not by the planner)
+  static const int cus = [] {
+    int dev = 0, n = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
+      return 0;
+    return n;
+  }();
+  return (cus > 0 && ntiles > cus) ? cus : ntiles;
+}
+
+// Which un-split problems take the 4-wave / two-workgroups-per-CU form (128 x 320 x 32 tiles, see the NW template parameter;
+// compiled only into the A/B library, tools/build_variant.sh --variants): NONE by default.  Measured in round 3 on every
+// GEMM flavour of the step (tools/gemm4_ab.py, same box, profiles/r3_gemm_4wave_ab.txt): 5 - 40 % SLOWER on all of them
+// (131072 x 2560 x 320 GEGLU + LayerNorm 368 -> 386 us, 8192 x 1280 x 5120 + residual 104 -> 145 us, whole step 58.2 ->
+// 64.5 ms).  The overlap of one tile's epilogue with the other's MFMAs does not pay for what the 128 x 320 x 32 tile costs:
+// 91 FLOP per staged byte instead of 146 against a CU's ~70 GB/s LDS-DMA intake, and a barrier every 40 MFMAs per wave.
+// I2V_GEMM_4W=1 selects it for every eligible plain GEMM (kept as a tested A/B switch); it has no hi + lo epilogue.
+bool want_4wave(const i2v_gemm_params& p, const GemmBigPlan& plan) {
+#ifdef I2V_VARIANTS
+  return switches().four_wave == 1 && plan.form == GemmBigForm::Tile && plan.cols == BIG_BN && p.a_mode == I2V_A_PLAIN &&
+         p.K % 32 == 0 && !lo_stream(p);
+#else
+  return false;
+#endif
+}
+
+// ---- the launch table
+// what a kernel adds to the plain epilogue; at most one of them per problem
+enum BigExtra { EXTRA_NONE = 0, EXTRA_LNF = 1, EXTRA_HILO = 2, EXTRA_GNS = 4 };
+
+// The instantiations of gemm_big_kernel that exist, per tile geometry: everything else is refused by the planner (or, for
+// ln_wsum / gn_partial, by i2v_gemm_f16 through the plan's ln_fold / gn_rows).
+template <int BN, int NS, int AMODE, bool SPLIT, bool FAST, int NW>
+constexpr bool big_kernel_exists(int epi, int store, int extra) {
+  constexpr bool plain_a = AMODE == I2V_A_PLAIN;
+  constexpr bool tile320 = BN == BIG_BN && NS == 2 && !SPLIT;   // the tile form proper: every epilogue lives here
+  constexpr bool deep = NS > 2;
+  const bool rowmajor = store == I2V_STORE_ROWMAJOR, rowperm = store == I2V_STORE_ROWPERM;
+  if (epi == I2V_EPI_GEGLU) return tile320 && plain_a && rowmajor && (extra == EXTRA_NONE || extra == EXTRA_LNF);
+  if (epi != I2V_EPI_NONE) return false;
+  switch (extra) {
+    case EXTRA_NONE: return rowmajor || (plain_a && (tile320 || (deep && store != I2V_STORE_VT_T)));
+    case EXTRA_LNF:  return tile320 && plain_a && store != I2V_STORE_VT;
+    case EXTRA_HILO: return (tile320 || deep) && !FAST && NW == 8 && (rowmajor || (rowperm && plain_a));
+    case EXTRA_GNS:  return tile320 && !plain_a && !FAST && NW == 8 && rowmajor;
+    default: return false;
+  }
+}
+
+// calls f(std::integral_constant<int, V>) for the V that equals v; false if none does
+template <int... Vs, class F>
+bool with_constant(int v, F&& f) {
+  return ((v == Vs ? (f(std::integral_constant<int, Vs>{}), true) : false) || ...);
+}
+
+// Launches the instantiation of one tile geometry that p's epilogue / store / LayerNorm fold / hi + lo / GroupNorm partials
+// select.  Returns 1, or < 0 on error.
+template <int BM, int BN, int NS, int AMODE, bool SPLIT = false, bool FAST = false, int NW = 8>
+int launch_form(const i2v_gemm_params& p, const GemmBigPlan& plan, hipStream_t s, const char* what) {
+  constexpr int BK = NW == 8 ? 64 : 32;
+  const int tiles_n = p.N / BN, ntiles = (int)i2v_cdiv(p.M, BM) * tiles_n;
+  const dim3 grid(FAST ? persistent_grid(ntiles) : ntiles, SPLIT ? plan.splits : 1), block(NW * 64);
+  // (split-K: the kernel writes fp32 partials; the reduce pass adds residual_lo and writes c_lo)
+  const int extra = (p.ln_wsum ? EXTRA_LNF : 0) | (lo_stream(p) && !SPLIT ? EXTRA_HILO : 0) | (p.gn_partial ? EXTRA_GNS : 0);
+  bool launched = false;
+  with_constant<I2V_EPI_NONE, I2V_EPI_GEGLU>(p.epilogue, [&](auto epi) {
+    with_constant<I2V_STORE_ROWMAJOR, I2V_STORE_ROWPERM, I2V_STORE_VT, I2V_STORE_VT_T>(p.store_mode, [&](auto store) {
+      with_constant<EXTRA_NONE, EXTRA_LNF, EXTRA_HILO, EXTRA_GNS>(extra, [&](auto ex) {
+        constexpr int EPI = decltype(epi)::value, STORE = decltype(store)::value, EX = decltype(ex)::value;
+        if constexpr (big_kernel_exists<BN, NS, AMODE, SPLIT, FAST, NW>(EPI, STORE, EX)) {
+          hipLaunchKernelGGL((gemm_big_kernel<BM, BK, NS, AMODE, EPI, STORE, SPLIT, NW == 8, EX == EXTRA_LNF, FAST, BN, NW,
+                                              EX == EXTRA_GNS, EX == EXTRA_HILO>),
+                             grid, block, 0, s, p, tiles_n, plan.kps, ntiles);
+          launched = true;
+        }
+      });
+    });
+  });
+  if (!launched)
+    I2V_FAIL(I2V_ERR_UNSUPPORTED, "%s: no kernel for epilogue %d, store %d, ln_wsum %d, hi + lo %d, gn_partial %d", what,
+             p.epilogue, p.store_mode, p.ln_wsum != nullptr, (int)lo_stream(p), p.gn_partial != nullptr);
+  const int rc = i2v_check_launch(what);
+  return rc < 0 ? rc : 1;
+}
+
+// the plan's tile height as a template argument
+template <int BN, int NS, int AMODE, bool SPLIT = false, bool FAST = false>
+int launch_rows(const i2v_gemm_params& p, const GemmBigPlan& plan, hipStream_t s, const char* what) {
+  return plan.rows == 256 ? launch_form<256, BN, NS, AMODE, SPLIT, FAST>(p, plan, s, what)
+                          : launch_form<128, BN, NS, AMODE, SPLIT, FAST>(p, plan, s, what);
+}
+
+}  // namespace
+
+GemmBigPlan i2v_gemm_big_plan(const i2v_gemm_params& p, int vec4) {
+  GemmBigPlan plan;
+  if (switches().splitk != 0) {   // what the caller allocates: the larger of the two split plans, whichever form runs in the end
+    const int splits = std::max(splitk_plan(p, vec4).splits, splitk256_plan(p, vec4).splits);
+    plan.workspace_bytes = (int64_t)splits * p.M * p.N * (int64_t)sizeof(float);
+  }
+  plan_form(p, vec4, plan);
+  plan.four_wave = want_4wave(p, plan);
+  plan.persistent = !plan.four_wave && want_persistent(p, plan);
+  plan.ln_fold = ln_fold_ok(p, plan);
+  plan.gn_rows = gn_partial_rows(p, plan);
+  return plan;
 }
 
 #ifdef I2V_VARIANTS
 int i2v_gemm_alt_try(const i2v_gemm_params& p, hipStream_t s);   // variants/gemm_alt.hip: short-K problems, alternating wave groups
 #endif
 
-int i2v_gemm_big_try(const i2v_gemm_params& p, int vec4, hipStream_t s) {
-  int splits = 0, kps = 0;
-  const int plan = big_plan(p, vec4, &splits, &kps);
-  const int bn = big_bn(p);
+int i2v_gemm_big_launch(const i2v_gemm_params& p, int vec4, const GemmBigPlan& plan, hipStream_t s) {
+  constexpr int PLAIN = I2V_A_PLAIN, CONV = I2V_A_CONV3X3;
+  const bool conv = p.a_mode == I2V_A_CONV3X3;
+  switch (plan.form) {
+    case GemmBigForm::None:
+      return 0;
+    case GemmBigForm::Tile:
+      // 3x3 convolutions whose channel count is not a multiple of 320 (the VAE: 128 / 256 / 512): column tiles of 256 or 128
+      if (plan.cols == 256) return launch_rows<256, 2, CONV>(p, plan, s, "i2v_gemm_f16(big conv)");
+      if (plan.cols == 128) return launch_rows<128, 2, CONV>(p, plan, s, "i2v_gemm_f16(big conv)");
 #ifdef I2V_VARIANTS
-  if (bn == BIG_BN && (plan == 256 || plan == 128)) {
-    const int rc = i2v_gemm_alt_try(p, s);
-    if (rc != 0) return rc;
+      if (const int rc = i2v_gemm_alt_try(p, s); rc != 0) return rc;
+      if (plan.four_wave) return launch_form<128, BIG_BN, 2, PLAIN, false, false, 4>(p, plan, s, "i2v_gemm_f16(big, 4-wave)");
+#endif
+      if (conv) return launch_rows<BIG_BN, 2, CONV>(p, plan, s, "i2v_gemm_f16(big)");
+      if (plan.persistent && persistent_grid(1 << 20) != (1 << 20))   // (the CU count is known)
+        return launch_rows<BIG_BN, 2, PLAIN, false, true>(p, plan, s, "i2v_gemm_f16(big, persistent)");
+      return launch_rows<BIG_BN, 2, PLAIN>(p, plan, s, "i2v_gemm_f16(big)");
+    case GemmBigForm::Deep:
+      return plan.cols == 256 ? launch_form<128, 256, 3, PLAIN>(p, plan, s, "i2v_gemm_f16(big, deep pipeline)")
+                              : launch_form<128, 128, 4, PLAIN>(p, plan, s, "i2v_gemm_f16(big, deep pipeline)");
+    case GemmBigForm::SplitK: {
+      const int rc = conv ? launch_rows<BIG_BN, 2, CONV, true>(p, plan, s, "i2v_gemm_f16(split-K)")
+                          : launch_rows<BIG_BN, 2, PLAIN, true>(p, plan, s, "i2v_gemm_f16(split-K)");
+      if (rc < 0) return rc;
+      const int64_t groups = (int64_t)p.M * (p.N / 4);
+      const int blocks = (int)(i2v_cdiv(groups, 256) < 2048 ? i2v_cdiv(groups, 256) : 2048);
+      hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, s, p, plan.splits, vec4);
+      const int rc2 = i2v_check_launch("i2v_gemm_f16(split-K reduce)");
+      return rc2 < 0 ? rc2 : 1;
+    }
   }
-#endif
-  if (bn == 256 && plan == 256) return launch_big_conv_bn<256, 256>(p, s);
-  if (bn == 256 && plan == 128) return launch_big_conv_bn<128, 256>(p, s);
-  if (bn == 128 && plan == 256) return launch_big_conv_bn<256, 128>(p, s);
-  if (bn == 128 && plan == 128) return launch_big_conv_bn<128, 128>(p, s);
-#ifdef I2V_VARIANTS
-  if ((plan == 256 || plan == 128) && use_4wave(p, plan)) return launch_big4<I2V_A_PLAIN>(p, s);
-#endif
-  if (plan == 256) return launch_big<256>(p, vec4, s);
-  if (plan == 128) return launch_big<128>(p, vec4, s);
-  if (plan == -1) return launch_split(p, vec4, splits, kps, s);
-  if (plan == -2) return launch_split256(p, vec4, splits, kps, s);
-  if (plan == -3) return launch_deep<128, 4>(p, s);
-  if (plan == -4) return launch_deep<256, 3>(p, s);
   return 0;
 }

@@ -131,18 +131,26 @@ __device__ __forceinline__ void gemm_store4(const i2v_gemm_params& p, const int 
   }
 }
 
-// implemented in gemm_big.hip: 256-thread-pair (8-wave) LDS-DMA kernel for N % 320 == 0; returns 1 if it took the
-// problem, 0 if the caller should use the generic kernel, < 0 on error.
-int i2v_gemm_big_try(const i2v_gemm_params& p, int vec4, hipStream_t s);
-int i2v_gemm_big_gn_rows(const i2v_gemm_params& p, int vec4);
+// gemm_big.hip: the 8-wave LDS-DMA kernel (N % 320 == 0, the VAE's 128 / 256-column convolutions, the deep-pipeline form of
+// under-filled plain GEMMs).  Which form of it runs a problem is decided once, by i2v_gemm_big_plan, and read everywhere else.
+enum class GemmBigForm { None, Tile, SplitK, Deep };   // None: the generic kernel's problem
+struct GemmBigPlan {
+  GemmBigForm form = GemmBigForm::None;
+  int rows = 0, cols = 0, stages = 0;   // tile height (256 / 128), width (320 / 256 / 128), LDS stages (2; Deep: 3 / 4)
+  int splits = 0, kps = 0;              // SplitK: K ranges (blockIdx.y) and 64-deep K tiles per range
+  int64_t workspace_bytes = 0;          // fp32 scratch with which K would be split (0: no split); what callers allocate
+  bool persistent = false;              // Tile: one workgroup per CU walks the tiles (I2V_GEMM_PERSIST)
+  bool four_wave = false;               // Tile: the 4-wave / two-workgroups-per-CU form (variants library, I2V_GEMM_4W)
+  bool ln_fold = false;                 // this form implements the LayerNorm fold (ln_wsum) for p's epilogue
+  int gn_rows = 0;                      // rows per block of the GroupNorm partials its epilogue can write (gn_partial); 0: none
+};
+// Pure host arithmetic (no device call).  The form depends on whether p.workspace is attached; workspace_bytes does not.
+GemmBigPlan i2v_gemm_big_plan(const i2v_gemm_params& p, int vec4);
+// returns 1 if it launched, 0 if plan.form is None (the caller uses the generic kernel), < 0 on error
+int i2v_gemm_big_launch(const i2v_gemm_params& p, int vec4, const GemmBigPlan& plan, hipStream_t s);
 // conv_thin.hip: 3x3 convolutions with <= 16 output channels (same return convention)
 int i2v_conv_thin_try(const i2v_gemm_params& p, hipStream_t s);
-// 1 if gemm_big.hip takes this problem AND implements the LayerNorm fold (ln_wsum) for its epilogue
-int i2v_gemm_big_ln_ok(const i2v_gemm_params& p, int vec4);
-int i2v_gemm_big_unsplit_ok(const i2v_gemm_params& p, int vec4);
-// fp32 scratch bytes with which gemm_big.hip would split K for this problem (0: no split)
-int64_t i2v_gemm_big_workspace_bytes(const i2v_gemm_params& p, int vec4);
 // implemented in gemm_ws.hip: the weight-stationary kernel for K = 320 row-major projections with >= 16384 rows (W slices in
-// registers, A streamed through three LDS stages); same return convention as i2v_gemm_big_try
+// registers, A streamed through three LDS stages); same return convention as i2v_gemm_big_launch
 int i2v_gemm_ws_try(const i2v_gemm_params& p, hipStream_t s);
 int i2v_gemm_ws_ok(const i2v_gemm_params& p);

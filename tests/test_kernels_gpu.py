@@ -464,6 +464,7 @@ def _variants_env(**switches):
     instantiations): they are not in the default library, only in the A/B build `bash tools/build_variant.sh --variants`
     (-> .ab_libs/variants.so, selected through I2V_LIB_PATH).  Skips when that library has not been built."""
     import os
+    import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     lib = os.path.join(root, ".ab_libs", "variants.so")
     if not os.path.exists(lib):

@@ -204,6 +204,7 @@ SIGNATURES = {
     "i2v_gemm_f16": (C.c_int, [C.POINTER(GemmParams), _P]),
     "i2v_gemm_ln_supported": (C.c_int, [C.POINTER(GemmParams)]),
     "i2v_gemm_batch_supported": (C.c_int, [C.POINTER(GemmParams)]),
+    "i2v_gemm_upconv_fold_supported": (C.c_int, [C.POINTER(GemmParams)]),
     "i2v_gemm_workspace_bytes": (C.c_int64, [C.POINTER(GemmParams)]),
     "i2v_gemm_gn_partial_rows": (C.c_int32, [C.POINTER(GemmParams)]),
     "i2v_attention_f16": (C.c_int, [C.POINTER(AttnParams), _P]),

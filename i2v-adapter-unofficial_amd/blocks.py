@@ -114,6 +114,41 @@ def pack_conv3x3(weight: torch.Tensor, cin_pad: Optional[int] = None) -> torch.T
     return w.reshape(co, 9 * ci).to(f16).contiguous()
 
 
+def pack_upconv_fold(weight: torch.Tensor, dtype=f16) -> torch.Tensor:
+    """[Cout, Cin, 3, 3] -> [4, Cout, 4 * Cin]: the weights of conv3x3(nearest-2x(x)) as four 2x2 convolutions of x itself, one per
+    output parity (`K.conv3x3(..., w_folded=)`, i2v_gemm_params.upsample = 2).  Output pixel (2 i + py, 2 j + px) reads the 2 x 2
+    source pixels (i + py - 1 + ty, j + px - 1 + tx); the taps ky that land on source row ty are
+        py = 0: ty = 0 <- {0}, ty = 1 <- {1, 2};   py = 1: ty = 0 <- {0, 1}, ty = 1 <- {2}
+    (columns the same with px / kx), and their weights are summed -- in fp32 (fp64 for an fp64 weight), rounded to `dtype` once.
+    Matrix ph = 2 py + px, column k = t * Cin + ci with t = 2 ty + tx, or, when Cin % 64 == 0 (`K.conv_k_block`),
+    channel-block-major k = ((ci // 64) * 4 + t) * 64 + ci % 64."""
+    co, ci = weight.shape[:2]
+    w = weight.detach()
+    w = w.double() if w.dtype == torch.float64 else w.float()
+    rows = (((0,), (1, 2)), ((0, 1), (2,)))                      # [parity][source row of the 2 x 2 window] -> 3x3 taps
+    phases = []
+    for py in range(2):
+        for px in range(2):
+            taps = []
+            for ty in range(2):
+                for tx in range(2):
+                    acc = None
+                    for ky in rows[py][ty]:
+                        for kx in rows[px][tx]:
+                            acc = w[:, :, ky, kx] if acc is None else acc + w[:, :, ky, kx]
+                    taps.append(acc)
+            phases.append(torch.stack(taps, dim=1))               # [co, tap, ci]
+    f = torch.stack(phases, dim=0)                                # [phase, co, tap, ci]
+    if K.conv_k_block(ci):
+        f = f.reshape(4, co, 4, ci // 64, 64).permute(0, 1, 3, 2, 4)   # [phase, co, channel block, tap, 64]
+    return f.reshape(4, co, 4 * ci).to(dtype).contiguous()
+
+
+# the up-sampling convolutions run with the nearest-2x folded into the weights (four taps per output parity instead of nine)
+# wherever the library takes the problem in that form; I2V_UPCONV_FOLD=0 keeps the 9-tap gather everywhere (same-box A/B)
+UPCONV_FOLD = os.environ.get("I2V_UPCONV_FOLD", "1") != "0"
+
+
 def pack_geglu(weight, bias):
     """rows (value_i, gate_i) interleaved so that the gate pair lands in one lane of the GEMM epilogue."""
     inner = weight.shape[0] // 2
@@ -421,13 +456,20 @@ class Upsample2D(HipModule):
         self.conv = nn.Conv2d(channels, out_channels, 3, padding=1)
 
     def _pack(self):
-        return dict(w=pack_conv3x3(self.conv.weight), b=w16(self.conv.bias))
+        p = LazyPack(w=pack_conv3x3(self.conv.weight), b=w16(self.conv.bias))
+        p.lazy("w_fold", lambda: pack_upconv_fold(self.conv.weight))      # (inference only: built on first use)
+        return p
 
     def _fwd(self, x, output_size=None):
         # output_size: the skip tensor's size when the latent size is not a multiple of 8 (unet:1304-1311, 1414-1415): 2x or 2x - 1
         p = self.packed()
-        return K.conv3x3(x, p["w"], p["b"], upsample=True,          # (read by conv_shortcut resnets only: no low half needed)
-                         output_size=None if output_size is None else tuple(int(v) for v in output_size))
+        size = None if output_size is None else tuple(int(v) for v in output_size)
+        # exactly 2x: four pre-summed taps per output parity.  2x - 1 stays on the 9-tap gather: its last row / column has no
+        # ky = 2 / kx = 2 neighbour, which a pre-summed weight cannot express.
+        if (UPCONV_FOLD and size in (None, (2 * x.shape[1], 2 * x.shape[2]))
+                and K.upconv_fold_supported(x.shape, self.conv.out_channels)):
+            return K.conv3x3(x, p["w"], p["b"], upsample=True, w_folded=p["w_fold"])
+        return K.conv3x3(x, p["w"], p["b"], upsample=True, output_size=size)   # (read by conv_shortcut resnets only: no low half needed)
 
     def forward(self, hidden_states, output_size=None, scale: float = 1.0):
         return from_tokens(self._fwd(to_tokens(hidden_states), output_size), hidden_states.dtype)

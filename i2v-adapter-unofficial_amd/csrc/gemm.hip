@@ -377,6 +377,11 @@ extern "C" int i2v_gemm_batch_supported(const i2v_gemm_params* pp) {
   return i2v_gemm_big_plan(*pp, vector_epilogue_ok(*pp)).form == GemmBigForm::Tile ? 1 : 0;
 }
 
+extern "C" int i2v_gemm_upconv_fold_supported(const i2v_gemm_params* pp) {
+  if (pp == nullptr || pp->M <= 0 || pp->N <= 0 || pp->K <= 0 || pp->a_mode != I2V_A_CONV3X3 || pp->upsample != 2) return 0;
+  return i2v_gemm_big_plan(*pp, vector_epilogue_ok(*pp)).form == GemmBigForm::Tile ? 1 : 0;
+}
+
 extern "C" int32_t i2v_gemm_gn_partial_rows(const i2v_gemm_params* pp) {
   if (pp == nullptr) return 0;
   return i2v_gemm_big_plan(*pp, vector_epilogue_ok(*pp)).gn_rows;
@@ -395,7 +400,9 @@ extern "C" int i2v_gemm_f16(const i2v_gemm_params* pp, i2v_stream_t stream) {
   I2V_CHECK_ARG(p.lda % 8 == 0, "i2v_gemm_f16: lda (%lld) must be a multiple of 8", (long long)p.lda);
   if (p.a_mode == I2V_A_CONV3X3) {
     I2V_CHECK_ARG(p.a2 == nullptr, "i2v_gemm_f16: conv mode takes a single source");
-    I2V_CHECK_ARG(p.cin > 0 && p.cin % 8 == 0 && p.K == 9 * p.cin, "i2v_gemm_f16: conv needs cin %% 8 == 0, K == 9 cin");
+    I2V_CHECK_ARG(p.upsample >= 0 && p.upsample <= 2, "i2v_gemm_f16: upsample must be 0, 1 or 2 (got %d)", p.upsample);
+    I2V_CHECK_ARG(p.cin > 0 && p.cin % 8 == 0 && p.K == (p.upsample == 2 ? 4 : 9) * p.cin,
+                  "i2v_gemm_f16: conv needs cin %% 8 == 0, K == 9 cin (4 cin with the up-sampling folded into the weights)");
     I2V_CHECK_ARG(p.stride == 1 || p.stride == 2, "i2v_gemm_f16: conv stride must be 1 or 2");
     I2V_CHECK_ARG(!(p.upsample && p.stride != 1), "i2v_gemm_f16: upsample conv must have stride 1");
     I2V_CHECK_ARG(!p.asym_pad || (p.stride == 2 && !p.upsample), "i2v_gemm_f16: asym_pad needs stride 2, no upsample");
@@ -407,7 +414,7 @@ extern "C" int i2v_gemm_f16(const i2v_gemm_params* pp, i2v_stream_t stream) {
     // upsample: nearest to 2 in, or to 2 in - 1 (unet:1304-1311, 1414-1415 `forward_upsample_size`: the skip tensor of a level whose
     // size was odd before its stride-2 down-sampler; F.interpolate(size=2 in - 1, mode="nearest") reads source floor(i in / (2 in - 1))
     // = i >> 1, the same gather, with the zero padding at the smaller image's border)
-    I2V_CHECK_ARG((p.out_h == eh || (p.upsample && p.out_h == eh - 1)) && (p.out_w == ew || (p.upsample && p.out_w == ew - 1)),
+    I2V_CHECK_ARG((p.out_h == eh || (p.upsample == 1 && p.out_h == eh - 1)) && (p.out_w == ew || (p.upsample == 1 && p.out_w == ew - 1)),
                   "i2v_gemm_f16: conv output size mismatch (%d x %d vs %d x %d)", p.out_h, p.out_w, eh, ew);
     I2V_CHECK_ARG((int64_t)p.n_img * p.out_h * p.out_w == p.M, "i2v_gemm_f16: conv M != n_img*out_h*out_w");
     I2V_CHECK_ARG(p.lda >= p.cin, "i2v_gemm_f16: conv pixel stride lda < cin");
@@ -477,6 +484,10 @@ extern "C" int i2v_gemm_f16(const i2v_gemm_params* pp, i2v_stream_t stream) {
       I2V_FAIL(I2V_ERR_INVALID_ARG, "i2v_gemm_f16: GroupNorm partials (gn_partial) are not implemented for this problem (M %d N %d K %d, "
                "groups %d): ask i2v_gemm_gn_partial_rows() first", p.M, p.N, p.K, p.gn_groups);
   }
+  if (p.a_mode == I2V_A_CONV3X3 && p.upsample == 2 && big_plan.form != GemmBigForm::Tile)
+    I2V_FAIL(I2V_ERR_INVALID_ARG, "i2v_gemm_f16: the folded up-sampling convolution (upsample = 2) is not implemented for this problem "
+             "(M %d N %d cin %d, %d x %d -> %d x %d, rows_per_w %d): ask i2v_gemm_upconv_fold_supported() first", p.M, p.N, p.cin,
+             p.in_h, p.in_w, p.out_h, p.out_w, p.rows_per_w);
   if (p.rows_per_w > 0 || p.a_perm_frames > 0) {
     I2V_CHECK_ARG(p.rows_per_w >= 0 && p.a_perm_frames >= 0 && p.w_batch_stride >= 0, "i2v_gemm_f16: negative batch / permutation field");
     if (big_plan.form != GemmBigForm::Tile)

@@ -102,13 +102,22 @@ __device__ __forceinline__ int big_lds_addr(int row, int kchunk) {
 // TWO workgroups share a CU -- the two waves of a SIMD then belong to DIFFERENT output tiles at unrelated phases, and one
 // tile's prologue (first DMA wait) and epilogue (LayerNorm apply, GELU, transposes, stores: as long as the K loop itself
 // when K = 320) run beside the other tile's MFMAs instead of stopping the CU.
+// UPF: the nearest-2x up-sampling convolution with the up-sampling folded into the weights (i2v_gemm_params.upsample == 2): the
+// 3 x 3 taps of output pixel (2 i + py, 2 j + px) over the up-sampled grid touch 2 x 2 source pixels, so each of the four
+// output parities ("phases") is a 2 x 2 convolution of the SOURCE image with pre-summed weights: K = 4 cin instead of 9 cin.
+// Rows are ordered (phase, image, i, j); phase ph = 2 py + px owns rows [ph M / 4, (ph + 1) M / 4) and its own weight matrix
+// (rows_per_w = M / 4), tap t = 2 ty + tx reads source pixel (i + py - 1 + ty, j + px - 1 + tx), and the row-contiguous store
+// sends row m to output pixel (2 i + py, 2 j + px).  M / 4 is a multiple of BM, so the phase is uniform per tile.
 template <int BM, int BK, int NS, int AMODE, int EPI, int STORE, bool SPLIT = false, bool STAGGER = true, bool LNF = false,
-          bool FAST = false, int BNT = 320, int NW = 8, bool GNS = false, bool HILO = false>
+          bool FAST = false, int BNT = 320, int NW = 8, bool GNS = false, bool HILO = false, bool UPF = false>
 __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void gemm_big_kernel(const i2v_gemm_params p, const int tiles_n,
                                                                             const int kps, const int ntiles) {
   static_assert(NS == 2 || (NS <= 4 && !FAST && !SPLIT && NW == 8),
                 "the cross-tile prefetch of the persistent tile loop, the LayerNorm fold and split-K are written for two stages");
   static_assert(NW == 8 || (NW == 4 && !STAGGER && !SPLIT), "4-wave workgroups: one M-wave, no stagger partner, no split-K");
+  static_assert(!UPF || (AMODE == I2V_A_CONV3X3 && EPI == I2V_EPI_NONE && STORE == I2V_STORE_ROWMAJOR && !SPLIT && !LNF && !FAST &&
+                         !GNS && !HILO && NW == 8),
+                "the folded up-sampling convolution is an un-split conv with the plain row-contiguous store");
   constexpr int BN = BNT;
   constexpr int WNC = BN / 4;               // columns per N-wave: 80 / 64 / 32
   constexpr int WM = BM / (NW / 4), MI = WM / 16, NI = WNC / 16;
@@ -180,6 +189,18 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void gemm_big_kernel(cons
   const unsigned w_lane = (unsigned)((r0 * (int)p.ldw + lane_k) * 2);
   // conv: output pixel of each of the lane's AG rows (first pixel of its image, oy, ox)
   auto conv_rows = [&](int tm0, int (&cp)[AG], int (&cy)[AG], int (&cx)[AG]) {
+    if constexpr (UPF) {   // (cy, cx) = the source pixel of tap 0 of the row's phase
+      const int mq = M >> 2, ph = tm0 / mq, ihw = p.in_h * p.in_w;
+#pragma unroll
+      for (int i = 0; i < AG; ++i) {
+        const int mm = tm0 - ph * mq + r0 + RSTEP * i;
+        const int img = mm / ihw, rem = mm - img * ihw, sy = rem / p.in_w;
+        cp[i] = img * ihw;
+        cy[i] = sy - 1 + (ph >> 1);
+        cx[i] = rem - sy * p.in_w - 1 + (ph & 1);
+      }
+      return;
+    }
 #pragma unroll
     for (int i = 0; i < AG; ++i) {
       const int m = tm0 + r0 + RSTEP * i;
@@ -204,19 +225,26 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void gemm_big_kernel(cons
       // lambdas it ended up in scratch memory -- two scratch loads + stores per issue inside the K loop, conv class
       // 12.5 -> 17.5 ms per step
       int tap, ci;
-      if (p.conv_kblock) {   // channel-block-major: the 9 taps of a 64-channel block, then the next block
+      if (UPF && p.conv_kblock) {   // folded up-sampling: 4 taps per 64-channel block
+        tap = kt & 3;
+        ci = (kt >> 2) * BK;
+      } else if (p.conv_kblock) {   // channel-block-major: the 9 taps of a 64-channel block, then the next block
         tap = kt % 9;
         ci = (kt / 9) * BK;
       } else {               // tap-major; cin % BK == 0, so a K tile never straddles taps
         tap = kb / p.cin;
         ci = kb - tap * p.cin;
       }
-      const int dy = tap / 3, dx = tap - dy * 3;
+      const int dy = UPF ? tap >> 1 : tap / 3, dx = UPF ? tap & 1 : tap - dy * 3;
 #pragma unroll
       for (int i = 0; i < AG; ++i) {
         int iy, ix;
         bool ok;
-        if (p.upsample) {
+        if (UPF) {
+          iy = cy[i] + dy;
+          ix = cx[i] + dx;
+          ok = (iy >= 0) && (ix >= 0) && (iy < p.in_h) && (ix < p.in_w);
+        } else if (p.upsample) {
           const int uy = cy[i] - 1 + dy, ux = cx[i] - 1 + dx;
           ok = (uy >= 0) && (ux >= 0) && (uy < p.out_h) && (ux < p.out_w);      // (out = 2 in, or 2 in - 1: forward_upsample_size)
           iy = uy >> 1;
@@ -700,6 +728,9 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void gemm_big_kernel(cons
     const int out_col0 = EPI == I2V_EPI_GEGLU ? (n0 >> 1) + wn * (WNC / 2) : n0 + wn * WNC;
     // One 8-column task of the 16-row block j: (valid, row m, destination row, first column)
     constexpr int QN = (NT + 63) / 64;
+    // UPF: row m = (phase, image, i, j) goes to output pixel (2 i + py, 2 j + px) (row indices < 2^24: checked by the planner)
+    const int up_mq = UPF ? M >> 2 : 1, up_ph = UPF ? m0 / up_mq : 0, up_ihw = UPF ? p.in_h * p.in_w : 1;
+    const float up_inv_ihw = UPF ? uniform_f(1.0f / (float)up_ihw) : 0.f, up_inv_w = UPF ? uniform_f(1.0f / (float)p.in_w) : 0.f;
     auto task = [&](int j, int q, int& m, int& m_out, int& n) {
       const int t = lane + 64 * q;
       const int row = t / TPR, c = t - row * TPR;
@@ -710,6 +741,12 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void gemm_big_kernel(cons
         const int b = m / per, rem = m - b * per;
         const int pix = rem / p.frames, f = rem - pix * p.frames;
         m_out = (b * p.frames + f) * p.hw + pix;
+      }
+      if constexpr (UPF) {
+        const int mm = m - up_ph * up_mq;
+        const int img = fast_div(mm, up_ihw, up_inv_ihw), rem = mm - img * up_ihw;
+        const int sy = fast_div(rem, p.in_w, up_inv_w), sx = rem - sy * p.in_w;
+        m_out = (img * p.out_h + 2 * sy + (up_ph >> 1)) * p.out_w + 2 * sx + (up_ph & 1);
       }
       n = out_col0 + c * 8;
       return t < NT && m < M;
@@ -728,8 +765,9 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void gemm_big_kernel(cons
     // ONE added operand per problem: the residual (out-projections, conv2, proj_out) or the row-vector table (time
     // embedding, positional table, per-image bias of a folded GroupNorm) -- big_plan sends a problem with both to the
     // generic kernel -- so one set of prefetch registers serves either (two sets spilled 150-290 registers per lane)
-    const bool has_res = !LNF && EPI != I2V_EPI_GEGLU && resid != nullptr;
-    const bool has_rv = EPI != I2V_EPI_GEGLU && !has_res && rowvec != nullptr;
+    // (UPF: bias only -- no added operand, so no prefetch registers beside the phase store's row arithmetic)
+    const bool has_res = !UPF && !LNF && EPI != I2V_EPI_GEGLU && resid != nullptr;
+    const bool has_rv = !UPF && EPI != I2V_EPI_GEGLU && !has_res && rowvec != nullptr;
     const bool has_add = has_res || has_rv;
     const int n_out_cols = EPI == I2V_EPI_GEGLU ? N / 2 : N;
     const auto rs_c = __builtin_amdgcn_make_buffer_rsrc(C, 0, (int)((((int64_t)M - 1) * p.ldc + n_out_cols) * 2), 0x00020000);
@@ -768,7 +806,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void gemm_big_kernel(cons
       }
     };
     // (no residual behind a folded LayerNorm: those GEMMs feed q / k / v / the feed-forward; the planner's ln_fold_ok refuses it)
-    if (EPI != I2V_EPI_GEGLU) {
+    if (EPI != I2V_EPI_GEGLU && !UPF) {
       static_for<(RES_AHEAD < MI ? RES_AHEAD : MI)>([&](auto jc) { fetch_rows(jc); });
     }
     __builtin_amdgcn_s_barrier();                         // every wave has left the K loop: the stages are free
@@ -871,7 +909,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void gemm_big_kernel(cons
     I2V_STAMP(3);
     static_for<MI>([&](auto jc) {
       constexpr int j = decltype(jc)::value;
-      if constexpr (j + RES_AHEAD < MI && EPI != I2V_EPI_GEGLU) {
+      if constexpr (j + RES_AHEAD < MI && EPI != I2V_EPI_GEGLU && !UPF) {
         fetch_rows(std::integral_constant<int, j + RES_AHEAD>{});
       }
       static_for<NI>([&](auto ic) {
@@ -893,7 +931,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void gemm_big_kernel(cons
         const f32x4 hi = *reinterpret_cast<const f32x4*>(stg + row * LDS_LD + c * 8 + 4);
         float v[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
         if (EPI != I2V_EPI_GEGLU) {
-          if (has_add) {
+          if (!UPF && has_add) {
 #pragma unroll
             for (int e = 0; e < 8; ++e) v[e] += (float)xpre[j][q][e];
             if constexpr (HILO) {
@@ -1028,6 +1066,9 @@ constexpr int SPLIT256_MIN_TILES = 16;   // 256-row split-K: the 8 x 8 level (16
 constexpr int DEEP_MIN_KT = 10, DEEP_MAX_KT = 63;   // deep pipeline: K tiles of the chain it is worth building for
 constexpr bool BIG_VAE_TILES = true;     // 256 / 128-column tiles for the VAE's 3x3 convolutions
 
+// the up-sampling convolution with the nearest-2x folded into four phase weight matrices (i2v_gemm_params.upsample == 2)
+bool upconv_fold(const i2v_gemm_params& p) { return p.a_mode == I2V_A_CONV3X3 && p.upsample == 2; }
+
 struct SplitPlan {
   int splits = 0, kps = 0;   // splits == 0: not a split-K problem
 };
@@ -1040,6 +1081,7 @@ SplitPlan even_splits(int nkt, int splits) {   // `splits` ranges of K tiles, no
 
 // 128-row tiles with K split: too few output tiles for the chip and a long K
 SplitPlan splitk_plan(const i2v_gemm_params& p, int vec4) {
+  if (upconv_fold(p)) return {};   // (the reduce pass has no phase store)
   if (p.N % BIG_BN != 0 || !vec4 || p.epilogue != I2V_EPI_NONE || p.store_mode != I2V_STORE_ROWMAJOR) return {};
   const int nkt = (p.K + 63) / 64;
   const int64_t t128 = i2v_cdiv(p.M, 128) * (p.N / BIG_BN);
@@ -1160,7 +1202,16 @@ void plan_form(const i2v_gemm_params& p, int vec4, GemmBigPlan& plan) {
   if ((int64_t)p.M * p.ldc >= (1ll << 30) || (p.residual && (int64_t)p.M * p.ldr >= (1ll << 30)) ||
       (p.rowvec && rv_rows * p.ld_rowvec >= (1ll << 30)))
     return;
-  if (p.rows_per_w > 0 || p.a_perm_frames > 0) {
+  const bool fold = upconv_fold(p);
+  if (fold) {
+    // Folded up-sampling convolution: one weight matrix per output parity through rows_per_w = M / 4, whole 256-row tiles per
+    // phase (a tile must not straddle phases), bias only (the up-sampler has no residual, row vector, low half or GroupNorm
+    // partials), exactly 2x, row indices below 2^24 (the store's reciprocal division).  Only this kernel implements it.
+    if (p.K != 4 * p.cin || p.stride != 1 || p.out_h != 2 * p.in_h || p.out_w != 2 * p.in_w) return;
+    if (p.M % 4 != 0 || p.rows_per_w != p.M / 4 || p.rows_per_w % 256 != 0 || p.a_perm_frames > 0 || p.M >= (1 << 24)) return;
+    if (p.w_batch_stride < (int64_t)p.N * p.ldw || 4 * p.w_batch_stride >= (1ll << 30)) return;
+    if (p.residual || p.rowvec || lo_stream(p) || p.gn_partial || p.ln_wsum) return;
+  } else if (p.rows_per_w > 0 || p.a_perm_frames > 0) {
     // per-batch weights / the permuted A gather exist only in the full-tile DMA path of the un-split kernel
     if (p.a_mode != I2V_A_PLAIN || p.a2 != nullptr || p.M % 256 != 0) return;
     if (p.rows_per_w > 0 && (p.rows_per_w % 256 != 0 || p.M % p.rows_per_w != 0 ||
@@ -1197,6 +1248,11 @@ void plan_form(const i2v_gemm_params& p, int vec4, GemmBigPlan& plan) {
   // slower on every shape of the step (profiles/r1_tile_sweep.txt), and again in round 3 on the full-chip 16 x 16 level
   // (tools/l2_ab.py: 8192 x 1280 x 1280 40.6 -> 45.5 us, x 2560 70.7 -> 78.5): with every CU busy the extra barriers cost more
   // than the third tile in flight gives.  Deeper pipelines pay only where the chip is NOT full (the deep form above).
+  // (Folded up-sampling convolutions, upsample == 2, take the same rule.  Its one close call is the 8 x 8 -> 16 x 16 up-sampler,
+  //  8192 x 1280 x 5120: 128 tiles of 256 rows fill half the chip, 256 tiles of 128 rows all of it.  Measured, same process,
+  //  alternating: 128-row tiles 97.6 us (1100 TFLOP/s executed), 256-row tiles 129.8 us -- the rule's choice stands.  Split-K was
+  //  not built for this form: the reduce pass has no phase store, and 80 K tiles are below the 90 from which the 9-tap
+  //  convolutions split.)
   if (e256 >= e128 && e256 >= 0.40) return set(Form::Tile, 256, cols, 2);
   if (e128 >= 0.40) return set(Form::Tile, 128, cols, 2);
   if (cols != BIG_BN) return;   // (split-K exists for 320-column tiles only)
@@ -1280,7 +1336,7 @@ bool want_4wave(const i2v_gemm_params& p, const GemmBigPlan& plan) {
 
 // ---- the launch table
 // what a kernel adds to the plain epilogue; at most one of them per problem
-enum BigExtra { EXTRA_NONE = 0, EXTRA_LNF = 1, EXTRA_HILO = 2, EXTRA_GNS = 4 };
+enum BigExtra { EXTRA_NONE = 0, EXTRA_LNF = 1, EXTRA_HILO = 2, EXTRA_GNS = 4, EXTRA_UPF = 8 };
 
 // The instantiations of gemm_big_kernel that exist, per tile geometry: everything else is refused by the planner (or, for
 // ln_wsum / gn_partial, by i2v_gemm_f16 through the plan's ln_fold / gn_rows).
@@ -1297,6 +1353,7 @@ constexpr bool big_kernel_exists(int epi, int store, int extra) {
     case EXTRA_LNF:  return tile320 && plain_a && store != I2V_STORE_VT;
     case EXTRA_HILO: return (tile320 || deep) && !FAST && NW == 8 && (rowmajor || (rowperm && plain_a));
     case EXTRA_GNS:  return tile320 && !plain_a && !FAST && NW == 8 && rowmajor;
+    case EXTRA_UPF:  return NS == 2 && !SPLIT && !plain_a && !FAST && NW == 8 && rowmajor;   // (every column tile of the conv)
     default: return false;
   }
 }
@@ -1315,15 +1372,16 @@ int launch_form(const i2v_gemm_params& p, const GemmBigPlan& plan, hipStream_t s
   const int tiles_n = p.N / BN, ntiles = (int)i2v_cdiv(p.M, BM) * tiles_n;
   const dim3 grid(FAST ? persistent_grid(ntiles) : ntiles, SPLIT ? plan.splits : 1), block(NW * 64);
   // (split-K: the kernel writes fp32 partials; the reduce pass adds residual_lo and writes c_lo)
-  const int extra = (p.ln_wsum ? EXTRA_LNF : 0) | (lo_stream(p) && !SPLIT ? EXTRA_HILO : 0) | (p.gn_partial ? EXTRA_GNS : 0);
+  const int extra = (p.ln_wsum ? EXTRA_LNF : 0) | (lo_stream(p) && !SPLIT ? EXTRA_HILO : 0) | (p.gn_partial ? EXTRA_GNS : 0) |
+                    (upconv_fold(p) ? EXTRA_UPF : 0);
   bool launched = false;
   with_constant<I2V_EPI_NONE, I2V_EPI_GEGLU>(p.epilogue, [&](auto epi) {
     with_constant<I2V_STORE_ROWMAJOR, I2V_STORE_ROWPERM, I2V_STORE_VT, I2V_STORE_VT_T>(p.store_mode, [&](auto store) {
-      with_constant<EXTRA_NONE, EXTRA_LNF, EXTRA_HILO, EXTRA_GNS>(extra, [&](auto ex) {
+      with_constant<EXTRA_NONE, EXTRA_LNF, EXTRA_HILO, EXTRA_GNS, EXTRA_UPF>(extra, [&](auto ex) {
         constexpr int EPI = decltype(epi)::value, STORE = decltype(store)::value, EX = decltype(ex)::value;
         if constexpr (big_kernel_exists<BN, NS, AMODE, SPLIT, FAST, NW>(EPI, STORE, EX)) {
           hipLaunchKernelGGL((gemm_big_kernel<BM, BK, NS, AMODE, EPI, STORE, SPLIT, NW == 8, EX == EXTRA_LNF, FAST, BN, NW,
-                                              EX == EXTRA_GNS, EX == EXTRA_HILO>),
+                                              EX == EXTRA_GNS, EX == EXTRA_HILO, EX == EXTRA_UPF>),
                              grid, block, 0, s, p, tiles_n, plan.kps, ntiles);
           launched = true;
         }
@@ -1331,8 +1389,8 @@ int launch_form(const i2v_gemm_params& p, const GemmBigPlan& plan, hipStream_t s
     });
   });
   if (!launched)
-    I2V_FAIL(I2V_ERR_UNSUPPORTED, "%s: no kernel for epilogue %d, store %d, ln_wsum %d, hi + lo %d, gn_partial %d", what,
-             p.epilogue, p.store_mode, p.ln_wsum != nullptr, (int)lo_stream(p), p.gn_partial != nullptr);
+    I2V_FAIL(I2V_ERR_UNSUPPORTED, "%s: no kernel for epilogue %d, store %d, ln_wsum %d, hi + lo %d, gn_partial %d, folded up-sampling %d",
+             what, p.epilogue, p.store_mode, p.ln_wsum != nullptr, (int)lo_stream(p), p.gn_partial != nullptr, (int)upconv_fold(p));
   const int rc = i2v_check_launch(what);
   return rc < 0 ? rc : 1;
 }

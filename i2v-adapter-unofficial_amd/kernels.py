@@ -6,6 +6,7 @@ torch.empty and launches the HIP kernel on torch's current stream through ctypes
 torch ops and nothing falls back to the CPU: a CPU tensor or a missing library raises.
 """
 import ctypes as C
+import functools
 import os
 from typing import Optional
 
@@ -209,8 +210,34 @@ def conv_k_block(cin: int) -> int:
     return 64 if cin % 64 == 0 and os.environ.get("I2V_CONV_KBLOCK", "1") != "0" else 0
 
 
+def _upconv_fold_params(p, n, h, wd, cin, cout):
+    """the fields of the folded up-sampling convolution (i2v_gemm_params.upsample = 2): four phase matrices [Cout, 4 Cin]"""
+    p.a_mode, p.lda = I2V_A_CONV3X3, cin
+    p.M, p.N, p.K, p.ldw, p.ldc = 4 * n * h * wd, cout, 4 * cin, 4 * cin, cout
+    p.epilogue, p.store_mode, p.out_scale = I2V_EPI_NONE, I2V_STORE_ROWMAJOR, 1.0
+    p.n_img, p.in_h, p.in_w, p.cin = n, h, wd, cin
+    p.out_h, p.out_w, p.stride, p.upsample = 2 * h, 2 * wd, 1, 2
+    p.conv_kblock = conv_k_block(cin)
+    p.w_batch_stride, p.rows_per_w = cout * 4 * cin, n * h * wd
+
+
+@functools.lru_cache(maxsize=None)
+def _upconv_fold_query(n, h, wd, cin, cout, kblock):
+    p = GemmParams()
+    _upconv_fold_params(p, n, h, wd, cin, cout)
+    p.a = p.w = p.c = p.bias = 1 << 40          # (a query tests pointers for null and alignment only)
+    return bool(_lib.load().i2v_gemm_upconv_fold_supported(C.byref(p)))
+
+
+def upconv_fold_supported(x_shape, cout):
+    """whether the library runs the up-sampling convolution of a token-major image of shape x_shape = (N, H, W, Cin) to Cout
+    channels in the folded form (`conv3x3(..., w_folded=)`: four taps per output parity instead of nine); launches nothing"""
+    n, h, wd, cin = (int(v) for v in x_shape)
+    return _upconv_fold_query(n, h, wd, cin, int(cout), conv_k_block(cin))
+
+
 def conv3x3(x, w_packed, bias=None, *, stride=1, upsample=False, rowvec=None, rows_per_vec=0, residual=None,
-            out_scale=1.0, asym_pad=False, out_f32=False, gn_stats_groups=0, precise=False, output_size=None):
+            out_scale=1.0, asym_pad=False, out_f32=False, gn_stats_groups=0, precise=False, output_size=None, w_folded=None):
     """3x3 / pad 1 convolution of a token-major image x [N, H, W, Cin] with w_packed [Cout, 9 * Cin]
     (k ordered as `blocks.pack_conv3x3` lays it out: tap-major, or channel-block-major when Cin % 64 == 0, see
     conv_k_block); optional nearest-2x upsampling of the input first.  asym_pad (stride 2): no
@@ -222,12 +249,36 @@ def conv3x3(x, w_packed, bias=None, *, stride=1, upsample=False, rowvec=None, ro
     precise: as `gemm` (the result and the residual are tensors of the precise residual stream).
     output_size (upsample only): (2 H, 2 W) or one less in either dimension -- `F.interpolate(size=output_size, mode="nearest")`
     in front of the convolution, the reference's forward_upsample_size path for latent sizes that are not multiples of 8
-    (unet:1304-1311, 1414-1415)."""
+    (unet:1304-1311, 1414-1415).
+    w_folded (upsample only, exactly 2x, bias only): [4, Cout, 4 * Cin] from `blocks.pack_upconv_fold` -- the up-sampling folded
+    into the weights, one 2x2 convolution of the source image per output parity (i2v_gemm_params.upsample = 2); w_packed is then
+    not read.  Ask `upconv_fold_supported` first: a problem the library does not take in this form is an error."""
     lib = _lib.load()
     _req(x, "x")
     if x.dim() != 4 or not x.is_contiguous():
         raise ValueError(f"x must be a contiguous [N, H, W, C] tensor, got {tuple(x.shape)}")
     n, h, wd, cin = x.shape
+    if w_folded is not None:
+        if (not upsample or stride != 1 or asym_pad or rowvec is not None or residual is not None or out_scale != 1.0 or out_f32
+                or gn_stats_groups or precise):
+            raise ValueError("w_folded belongs to a plain up-sampling convolution (bias only)")
+        if output_size is not None and tuple(int(v) for v in output_size) != (2 * h, 2 * wd):
+            raise ValueError(f"w_folded: the folded form up-samples to exactly {(2 * h, 2 * wd)}, not {tuple(output_size)}")
+        _req(w_folded, "w_folded")
+        cout = w_folded.shape[1] if w_folded.dim() == 3 else 0
+        if tuple(w_folded.shape) != (4, cout, 4 * cin) or not w_folded.is_contiguous():
+            raise ValueError(f"w_folded must be a contiguous [4, Cout, {4 * cin}] tensor, got {tuple(w_folded.shape)}")
+        out = torch.empty((n, 2 * h, 2 * wd, cout), dtype=f16, device=x.device)
+        p = GemmParams()
+        _upconv_fold_params(p, n, h, wd, cin, cout)
+        p.a, p.w, p.c = _p(x), _p(w_folded), _p(out)
+        if bias is not None:
+            _req(bias, "bias")
+            if bias.numel() != cout or not bias.is_contiguous():
+                raise ValueError("bias must be a contiguous vector of Cout elements")
+            p.bias = _p(bias)
+        _lib.check(lib.i2v_gemm_f16(C.byref(p), _stream()), "i2v_gemm_f16(conv3x3, folded up-sampling)")
+        return out
     w_packed, ldw = _mat(w_packed, "w_packed")
     cout, K = w_packed.shape
     if K != 9 * cin:

@@ -2,7 +2,7 @@
 
 `with KernelProfile() as prof:` wraps every C-ABI wrapper of `kernels` with a pair of events recorded on torch's
 current stream (the stream the ctypes launches go to) and the ALGORITHMIC work of the call:
-  flops: gemm 2 M N K; conv3x3 2 M Cout 9 Cin; attention 4 Lq Lk C Bq; temporal attention 4 F F C pixels; fused motion
+  flops: gemm 2 M N K; conv3x3 2 M Cout 9 Cin (2 M Cout 4 Cin where the up-sampling is folded into the weights: the work executed); attention 4 Lq Lk C Bq; temporal attention 4 F F C pixels; fused motion
          attention sub-block 2 M C 3C + 4 M F C; fused text cross-attention 2 M C C + 4 M Lk C
   bytes: operands read once + result written once (fp16), GroupNorm 2 reads + 1 write, LayerNorm 1 read + 1 write
 (the counting rules of SURVEY.md Appendix B / section 8d).  Only used outside the timed region.
@@ -34,6 +34,9 @@ def _work_conv(args, kw, out):
     if isinstance(out, tuple):        # (result, GroupNorm partials from the epilogue or None): gn_stats_groups
         out, stats = out
     M = out.shape[0] * out.shape[1] * out.shape[2]
+    wf = kw.get("w_folded")
+    if wf is not None:                # up-sampling folded into the weights: four taps per output pixel are executed, not nine
+        return ("conv3x3", 2.0 * M * wf.shape[1] * wf.shape[2], _numel_bytes(x, wf, out), f"{M}x{wf.shape[1]}x{wf.shape[2]} up4")
     return ("conv3x3", 2.0 * M * w.shape[0] * w.shape[1], _numel_bytes(x, w, kw.get("residual"), out),
             f"{M}x{w.shape[0]}x{w.shape[1]}" + (" s2" if kw.get("stride", 1) == 2 else "")
             + (" up" if kw.get("upsample") else "") + (" +res" if kw.get("residual") is not None else "")

@@ -111,7 +111,16 @@ typedef struct i2v_gemm_params {
   float out_scale;
   /* I2V_A_CONV3X3 geometry: input image [n_img, in_h, in_w, cin] fp16 (pixel stride = lda elements),
      3x3 kernel, padding 1, `stride` 1 or 2; `upsample` = 1 applies nearest-2x to the input first
-     (Upsample2D).  `asym_pad` = 1 (stride 2 only): no padding at the top / left and one zero row / column at the
+     (Upsample2D).
+     `upsample` = 2: the same convolution of the nearest-2x up-sampled input (out = exactly 2 in) with the up-sampling FOLDED INTO
+     THE WEIGHTS: the 3x3 taps of output pixel (2 i + py, 2 j + px) touch only 2 x 2 source pixels, so each output parity
+     ("phase" ph = 2 py + px) is a 2x2 convolution of the source image, K = 4 * cin.  w holds four matrices [N, 4 * cin], matrix ph
+     at w + ph * w_batch_stride, rows_per_w = M / 4; column k = t * cin + ci (conv_kblock = 64: ((ci / 64) * 4 + t) * 64 + ci % 64)
+     of tap t = 2 ty + tx multiplies source pixel (i + py - 1 + ty, j + px - 1 + tx) (outside the image: zero) and holds the sum of
+     the 3x3 taps (ky, kx) that land on it: rows py = 0: ty = 0 <- ky 0, ty = 1 <- ky 1 + 2; py = 1: ty = 0 <- ky 0 + 1,
+     ty = 1 <- ky 2; columns the same with px / kx.  Bias only (no residual, rowvec, gn_partial, residual_lo / c_lo); the 8-wave
+     kernel only: i2v_gemm_upconv_fold_supported() tells whether a problem qualifies.
+     `asym_pad` = 1 (stride 2 only): no padding at the top / left and one zero row / column at the
      bottom / right = diffusers Downsample2D(padding=0) of the VAE encoder (F.pad(x, (0, 1, 0, 1)) + conv stride 2).
      M = n_img * out_h * out_w. */
   int32_t n_img, in_h, in_w, cin, out_h, out_w, stride, upsample, asym_pad;
@@ -164,6 +173,8 @@ int i2v_gemm_f16(const i2v_gemm_params* p, i2v_stream_t stream);
 int i2v_gemm_ln_supported(const i2v_gemm_params* p);
 /* 1 if i2v_gemm_f16 accepts this problem with rows_per_w / a_perm_frames set (pointers are not dereferenced), else 0. */
 int i2v_gemm_batch_supported(const i2v_gemm_params* p);
+/* 1 if i2v_gemm_f16 accepts this I2V_A_CONV3X3 problem with upsample = 2 (pointers are not dereferenced), else 0. */
+int i2v_gemm_upconv_fold_supported(const i2v_gemm_params* p);
 /* bytes of `workspace` with which i2v_gemm_f16 would split K for this problem (0: it would not split). */
 int64_t i2v_gemm_workspace_bytes(const i2v_gemm_params* p);
 /* rows per block of the GroupNorm partials i2v_gemm_f16 would write for this problem with gn_partial set (gn_groups must be set;

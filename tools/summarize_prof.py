@@ -13,9 +13,9 @@ with open(dst, "w") as o:
         o.write(f"# library_source_stamp {bench.source_stamp()}\n")
     except Exception as e:
         o.write(f"# library_source_stamp unknown ({e})\n")
-    o.write(f"{'kernel':90s} {'calls':>7s} {'total_ms':>10s} {'avg_us':>10s} {'pct':>7s}\n")
+    o.write(f"{'kernel':100s} {'calls':>7s} {'total_ms':>10s} {'avg_us':>10s} {'pct':>7s}\n")
     for r in rows[:45]:
-        name = re.sub(r"\(anonymous namespace\)::", "", r["Name"])[:90]
-        o.write(f"{name:90s} {int(r['Calls']):7d} {float(r['TotalDurationNs']) / 1e6:10.2f} "
+        name = re.sub(r"\(anonymous namespace\)::", "", r["Name"])[:100]   # (the last template argument tells the folded up-sampling form apart)
+        o.write(f"{name:100s} {int(r['Calls']):7d} {float(r['TotalDurationNs']) / 1e6:10.2f} "
                 f"{float(r['AverageNs']) / 1e3:10.1f} {float(r['Percentage']):7.2f}\n")
 print(open(dst).read()[:3000])

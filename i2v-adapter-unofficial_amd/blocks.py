@@ -993,6 +993,17 @@ class DownBlockMotion(nn.Module):
         return from_tokens(x, dt), tuple(from_tokens(s, dt) for s in states)
 
 
+def freeu_scales(block):
+    """(b, s) of FreeU for an up block, or None: enabled as in the reference (unet:453-459) when the block's four attributes
+    s1, s2, b1, b2 (`UNetMotionCrossFrameAttnModel.enable_freeu`) are all truthy, and applied by the blocks with resolution_idx 0
+    (b1, s1) and 1 (b2, s2) only (diffusers apply_freeu)."""
+    s1, s2 = getattr(block, "s1", None), getattr(block, "s2", None)
+    b1, b2 = getattr(block, "b1", None), getattr(block, "b2", None)
+    if not (s1 and s2 and b1 and b2):
+        return None
+    return {0: (float(b1), float(s1)), 1: (float(b2), float(s2))}.get(block.resolution_idx)
+
+
 class UpBlockMotion(nn.Module):
     """A11 (unet:122-137)."""
 
@@ -1017,9 +1028,12 @@ class UpBlockMotion(nn.Module):
         self.resolution_idx = resolution_idx
 
     def _fwd(self, x, res_tuple, temb_act, num_frames, upsample_size=None):
+        fu = freeu_scales(self)
         for resnet, motion in zip(self.resnets, self.motion_modules):
             skip = res_tuple[-1]
             res_tuple = res_tuple[:-1]
+            if fu is not None:                           # apply_freeu ahead of the concatenation (one launch, new tensors)
+                x, skip = K.freeu(x, skip, *fu)
             x = resnet._fwd(x, temb_act, x2=skip)        # torch.cat([x, skip], 1) never materialised (unet:478)
             x = motion._fwd(x, num_frames)
         if self.upsamplers is not None:

@@ -31,6 +31,18 @@ ENTRY_IDS = {name: i for i, name in enumerate((
     "i2v_ff_fused_f16", "i2v_groupnorm_f16", "i2v_layernorm_f16", "i2v_groupnorm_fold_f16", "i2v_nchw_to_tokens", "i2v_tokens_to_nchw",
     "i2v_timestep_embedding", "i2v_silu_f16", "i2v_repeat_rows_f16", "i2v_copy3d_f16", "i2v_select_row_f16",
     "i2v_pack_ctx_fragments_f16", "i2v_ddim_prep", "i2v_ddim_cfg_step", "i2v_dpm_cfg_step"))}
+# ENTRY_IDS is the table as it stood at ABI 10 and stays that table (tests/test_dpm_solver.py pins i2v_dpm_cfg_step as its last id).
+# Entry points added since continue the numbering of `enum Entry` here; `entry_id` / `ENTRY_NAMES` cover both.
+LATER_ENTRY_IDS = {name: len(ENTRY_IDS) + i for i, name in enumerate((
+    "i2v_freeu_f16",))}                                             # ABI 11
+ENTRY_NAMES = {i: n for n, i in {**ENTRY_IDS, **LATER_ENTRY_IDS}.items()}
+
+
+def entry_id(name):
+    """id of a launch entry point in csrc/handle.hip `enum Entry`, or None when a plan cannot carry it"""
+    return ENTRY_IDS.get(name, LATER_ENTRY_IDS.get(name))
+
+
 IO_SAMPLE, IO_TIMESTEPS, IO_CONTEXT, IO_IMAGE_EMBEDS, IO_OUT = range(5)
 RELOC_ARENA, RELOC_WEIGHT, RELOC_IO = range(3)
 _INT_TYPES = (C.c_int32, C.c_int64, C.c_int)
@@ -56,9 +68,9 @@ class _RecordingLib:
         launches = bool(argtypes) and argtypes[-1] is C.c_void_p and res is C.c_int and not name.startswith("i2v_unet_")
         if not launches:
             return fn
-        if name not in ENTRY_IDS:
+        if entry_id(name) is None:
             def refuse(*a, _n=name):
-                raise _lib.HipLibraryError(f"{_n} is not an entry point a launch plan can carry (handle.ENTRY_IDS / csrc/handle.hip)")
+                raise _lib.HipLibraryError(f"{_n} is not an entry point a launch plan can carry (handle.entry_id / csrc/handle.hip)")
             return refuse
 
         def call(*args, _n=name, _fn=fn, _at=argtypes):
@@ -93,7 +105,7 @@ class _RecordingLib:
                 slots.append(struct.pack("<d", float(arg)))          # (the C side reads a float slot as a double)
             else:
                 raise TypeError(f"{name}: a launch plan carries pointers, integers and floats, not {at}")
-        self.ops.append((ENTRY_IDS[name], sbytes, slots, ptrs))
+        self.ops.append((entry_id(name), sbytes, slots, ptrs))
 
 
 def persistent_tensors(unet):

@@ -1106,6 +1106,31 @@ def dpm_cfg_step(latents, x0_prev, noise_pred, coef, step_index, guidance_scale,
     return latents
 
 
+def freeu(hidden, skip, b, s):
+    """FreeU on the operands of an up block's skip concatenation (i2v_freeu_f16; diffusers apply_freeu, unet:453-478): hidden
+    [N, H, W, C1], skip [N, H, W, C2] fp16 token-major -> (hidden', skip'), new tensors.  hidden'[..., :C1 // 2] = hidden * b, the
+    other channels copied; skip' = skip with its four lowest spatial frequencies scaled by s.  A hidden tensor of the precise residual
+    stream (`lo_of(hidden)`) is scaled as hi + lo and comes back with a fresh low half."""
+    lib = _lib.load()
+    _req(hidden, "hidden")
+    _req(skip, "skip")
+    if hidden.dim() != 4 or skip.dim() != 4 or tuple(hidden.shape[:3]) != tuple(skip.shape[:3]):
+        raise ValueError(f"hidden {tuple(hidden.shape)} and skip {tuple(skip.shape)} must be [N, H, W, C1] and [N, H, W, C2]")
+    if not hidden.is_contiguous() or not skip.is_contiguous():
+        raise ValueError("hidden and skip must be contiguous")
+    n, hh, ww, c1 = hidden.shape
+    lo = lo_of(hidden)
+    if lo is not None and (lo.shape != hidden.shape or lo.stride() != hidden.stride() or lo.dtype != f16):
+        raise ValueError("the low half of a stream tensor must be laid out like the tensor")
+    h_out, s_out = torch.empty_like(hidden), torch.empty_like(skip)
+    lo_out = None if lo is None else torch.empty_like(hidden)
+    _lib.check(lib.i2v_freeu_f16(_p(hidden), _p(lo), _p(h_out), _p(lo_out), _p(skip), _p(s_out), n, hh, ww, c1, skip.shape[3],
+                                 float(b), float(s), _stream()), "i2v_freeu_f16")
+    if lo_out is not None:
+        h_out._i2v_lo = lo_out
+    return h_out, s_out
+
+
 # ---------------------------------------------------------------------------------------------- backward (SURVEY 8 f4)
 def transpose_tokens(x, batch_len, out=None):
     """[B * L, C] token-major -> [B, C, pad8(L)] channel-major (zero-filled pad): the K^T / Q^T / dO^T operands of the

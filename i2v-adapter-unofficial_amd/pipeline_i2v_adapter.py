@@ -99,6 +99,18 @@ class I2VAdapterPipeline:
     def disable_vae_slicing(self):
         self._vae_slicing = False
 
+    def enable_freeu(self, s1: float, s2: float, b1: float, b2: float):
+        """pipe:155-176: FreeU (https://arxiv.org/abs/2309.11497) on the UNet's first two up blocks -- s1 / s2 attenuate the low
+        frequencies of the skip features of stage 1 / 2, b1 / b2 amplify half of the backbone channels (SD-1.5: 0.9, 0.2, 1.2, 1.4).
+        The step stays one captured hipGraph (six i2v_freeu_f16 launches in it)."""
+        if getattr(self, "unet", None) is None:
+            raise ValueError("The pipeline must have `unet` for using FreeU.")
+        self.unet.enable_freeu(s1=s1, s2=s2, b1=b1, b2=b2)
+
+    def disable_freeu(self):
+        """pipe:179-181."""
+        self.unet.disable_freeu()
+
     def decode_latents(self, latents):
         """pipe:300-320: latents (B, F, 4, h, w) -> video (B, F, 3, 8h, 8w) float32 through the HIP VAE decoder."""
         if self.vae is None:
@@ -198,7 +210,8 @@ class I2VAdapterPipeline:
         """everything a captured step has baked in besides the contents of the static buffers: shapes, the Python
         scalars passed as launch arguments (guidance, IP scales), the identity / version of every weight (the packed
         kernel-layout copies are rebuilt when a parameter changes, and a graph captured before that reads the old ones) and the
-        scheduler's update (a scheduler swapped between calls re-captures)"""
+        scheduler's update (a scheduler swapped between calls re-captures) and FreeU's four scales (launch arguments: enabling,
+        changing or disabling FreeU re-captures)"""
         unet = self.unet
         wsig = hash(tuple((p.data_ptr(), p._version) for p in unet.parameters()))
         ips = tuple((a.ip_num_tokens, float(a.ip_scale)) for a in unet._cross_attention_layers())
@@ -206,7 +219,7 @@ class I2VAdapterPipeline:
         from .blocks import precise_stream      # (a captured step keeps the residual-stream mode it was captured in)
         return (tuple(st["latents"].shape), st["copies"], st["num_frames"], st["guidance"], shp(st["t_table"]),
                 shp(st["ctx_text"]), shp(st["ctx_ip"]), str(st["latents"].device), wsig, ips, precise_stream(),
-                self._scheduler_kind(), shp(st["coef"]))
+                self._scheduler_kind(), shp(st["coef"]), unet.freeu_signature())
 
     def _run_steps(self, st, n_steps, use_graph):
         if not use_graph:
@@ -464,6 +477,8 @@ def main(argv=None):
     parser.add_argument("--seed", type=int, default=0)
     parser.add_argument("--scheduler", choices=SCHEDULERS, default="ddim",
                         help="ddim (the reference's) or dpmsolver++ (DPM-Solver++(2M): 15-20 steps instead of 25-50)")
+    parser.add_argument("--freeu", type=float, nargs=4, default=None, metavar=("S1", "S2", "B1", "B2"),
+                        help="enable FreeU with these scales (SD-1.5: 0.9 0.2 1.2 1.4); off by default, as in the reference driver")
     args = parser.parse_args(argv)
     if args.task_name is None:
         logger.error("Checkpoint `task_name` must be specified.")
@@ -502,6 +517,8 @@ def main(argv=None):
         pipe.load_ip_adapter(args.ip_adapter_path, subfolder="models", weight_name="ip-adapter_sd15.bin")
     pipe.to(device, torch.float16)
     pipe.enable_vae_slicing()                                                                    # pipe:787
+    if args.freeu is not None:
+        pipe.enable_freeu(*args.freeu)
 
     sample_save_dir = os.path.join(args.samples_root, args.task_name, f"epoch_{args.checkpoint_epoch}")
     os.makedirs(sample_save_dir, exist_ok=True)

@@ -524,6 +524,9 @@ class UNetAdapterTrainer:
         reference's training step passes them, train_image_to_video.py:843); returns the prediction as tokens fp32
         [B * F, H, W, 8] (4 channels + zeros)."""
         u = self.unet
+        if any(fs is not None for fs in u.freeu_signature()):
+            raise NotImplementedError("FreeU (enable_freeu) is a sampling-time switch: the training step has no backward of "
+                                      "i2v_freeu_f16 -- call unet.disable_freeu() before training")
         b, F, c, hh, ww = sample.shape
         p = u.packed()
         t = timestep if torch.is_tensor(timestep) else torch.tensor([timestep])

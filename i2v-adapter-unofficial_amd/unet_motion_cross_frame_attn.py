@@ -17,7 +17,7 @@ from torch import nn
 from . import kernels as K
 from ._lib import HipLibraryError
 from .blocks import (Attention, DownBlockMotion, Downsample2D, HipModule, ImageProjection, MotionAdapter,
-                     ProjectedContext, ProjectedTemb, ResnetBlock2D, TimestepEmbedding, Timesteps, UpBlockMotion,
+                     ProjectedContext, ProjectedTemb, ResnetBlock2D, TimestepEmbedding, Timesteps, UpBlockMotion, freeu_scales,
                      Upsample2D, _as_f16_matrix, _motion, from_tokens, pack_conv3x3, precise_stream, to_tokens, w16)
 from .checkpoint import PretrainedMixin
 from .i2v_adapter import I2VAdapterModule, I2VAdapterTransformer2DModel
@@ -135,9 +135,12 @@ class CrossFrameAttnUpBlockMotion(nn.Module):
         self.resolution_idx = resolution_idx
 
     def _fwd(self, x, res_tuple, temb_act, enable, ctx_text, ctx_ip, num_frames, upsample_size=None):
+        fu = freeu_scales(self)
         for resnet, attn, motion in zip(self.resnets, self.attentions, self.motion_modules):
             skip = res_tuple[-1]
             res_tuple = res_tuple[:-1]
+            if fu is not None:                                    # apply_freeu (unet:453-478): one launch, new tensors
+                x, skip = K.freeu(x, skip, *fu)
             x = resnet._fwd(x, temb_act, x2=skip)                 # cat([x, skip], 1) (unet:478) never materialised
             x = attn._fwd(x, enable, num_frames, ctx_text, ctx_ip)
             x = motion._fwd(x, num_frames)
@@ -605,6 +608,25 @@ class UNetMotionCrossFrameAttnModel(PretrainedMixin, HipModule):
                 self._packed = self._pack()
             self._packed_key = key
         return self._packed
+
+    def enable_freeu(self, s1: float, s2: float, b1: float, b2: float) -> None:
+        """unet:1213-1219 (https://arxiv.org/abs/2309.11497): the four scales as attributes of every up block.  The blocks with
+        resolution_idx 0 (b1, s1) and 1 (b2, s2) then scale the first half of the backbone channels by b and the four lowest
+        spatial frequencies of each skip tensor by s ahead of every skip concatenation (i2v_freeu_f16); a zero or None among the
+        four leaves FreeU off, as in the reference.  The values are launch arguments: a captured step is re-captured."""
+        for blk in self.up_blocks:
+            blk.s1, blk.s2, blk.b1, blk.b2 = s1, s2, b1, b2
+
+    def disable_freeu(self) -> None:
+        """unet:1221-1228."""
+        for blk in self.up_blocks:
+            for k in ("s1", "s2", "b1", "b2"):
+                if getattr(blk, k, None) is not None:
+                    setattr(blk, k, None)
+
+    def freeu_signature(self):
+        """what FreeU bakes into the launches of a forward: (b, s) of every up block that applies it (None where it does not)"""
+        return tuple(freeu_scales(blk) for blk in self.up_blocks)
 
     def _cross_attention_layers(self):
         """the spatial blocks' attn2 modules, in attn_processors order."""

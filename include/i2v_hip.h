@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define I2V_ABI_VERSION 10
+#define I2V_ABI_VERSION 11
 
 #define I2V_OK 0
 #define I2V_ERR_INVALID_ARG (-1)
@@ -514,6 +514,21 @@ int i2v_ddim_cfg_step(float* latents, const void* noise_pred, int32_t np_is_f32,
 int i2v_dpm_cfg_step(float* latents, float* x0_prev, const void* noise_pred, int32_t np_is_f32, int64_t ld_np, const float* coef,
                      int32_t n_steps, int32_t* step_index, float guidance_scale, int32_t b, int32_t f, int32_t c, int32_t hw,
                      int32_t cfg_copies, i2v_stream_t stream);
+
+/* (ABI 11) FreeU (pipe:155-181 enable_freeu; unet:453-478, 1213-1227: diffusers 0.24 apply_freeu / fourier_filter with threshold 1) on the
+ * two operands of an up block's skip concatenation, before `cat([hidden, skip], 1)` (unet:478); one launch, new tensors out (neither
+ * input is modified, and no output may alias its input).  hidden [n, h, w, c1], skip [n, h, w, c2] fp16 token-major, dense.
+ *   hidden_out[..., :c1 / 2] = hidden[..., :c1 / 2] * b (fp32 product, rounded once); the other channels are copied bit for bit.
+ *   skip_out = Re(ifftn(ifftshift(mask * fftshift(fftn(skip))))) over (h, w), mask = s on [h/2-1 : h/2+1, w/2-1 : w/2+1] and 1 elsewhere.
+ *     The box holds the four frequencies (k, l) in {0, -1}^2, so
+ *       skip_out = skip + (s - 1) / (h w) * Re( sum_{(k, l)} X[k, l] e^{+2 pi i (k y / h + l x / w)} ),  X = DFT of the plane:
+ *     seven fp32 sums per (image, channel) plane and one rounding of the corrected value.
+ * hidden_lo / hidden_out_lo: NULL together, or the low halves of the precise residual stream's fp16 pair (i2v_gemm_params.c_lo):
+ * the product is then taken of hi + lo and written as a pair, and the copied channels keep both halves.
+ * I2V_ERR_INVALID_ARG ("not implemented for this problem") for h < 2 or w < 2 -- the reference's box slice wraps there and the
+ * four-frequency form does not hold --, h or w > 256, c1 or c2 not a multiple of 8. */
+int i2v_freeu_f16(const void* hidden, const void* hidden_lo, void* hidden_out, void* hidden_out_lo, const void* skip, void* skip_out,
+                  int32_t n, int32_t h, int32_t w, int32_t c1, int32_t c2, float b, float s, i2v_stream_t stream);
 
 /* First-frame-similarity prior and the initial add_noise of the sampling loop, pipe:647-656:
  *   prior   = mask * GaussianBlur3x3(cond) + (1 - mask) * cond, mask = (mask_uniform < strength), per frame (pipe:648-654)

@@ -1169,6 +1169,7 @@ inline int ew_grid(int64_t n) {
   return (int)(b < 65535 * 4 ? (b > 0 ? b : 1) : 65535 * 4);
 }
 
+// tests/attn_bwd_reference.py forms() mirrors these choices (and i2v_attention_lse_f32's, the (KS, DT) classes): it must follow them
 template <int KS, int DT>
 int launch_bwd(const i2v_attn_bwd_params& p, hipStream_t s) {
   const float c = p.scale * LOG2E;

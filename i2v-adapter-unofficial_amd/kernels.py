@@ -390,8 +390,10 @@ def attention(q, k, vt, *, batch_q, lq, lk, heads, head_dim, kv_group=1, scale=N
               acc_scale=1.0, return_lse=False):
     """Flash attention forward.  q [batch_q * lq, >= heads*head_dim] (row-strided view is fine),
     k [batch_kv * lk, ...], vt [batch_kv, heads*head_dim, >= pad8(lk)], returns [batch_q * lq, heads*head_dim]
-    (return_lse: the pair (out, fp32 [batch_q, heads, lq] log2-sum-exp of the scaled logits), written by the same pass: what
-    attention_bwd otherwise recomputes)."""
+    return_lse: the pair (out, fp32 [batch_q, heads, lq] log2-sum-exp of the scaled logits): what attention_bwd otherwise
+    recomputes.  True: the statistic of the logits the backward recomputes (attention_lse, a second launch).  "fused": the one
+    the forward kernel writes in the same pass; it belongs to the kernel's own logits (Q scaled and rounded to fp16 before
+    Q K^T) and is off by up to ~1e-3 of max|lse|: a backward fed with it recomputes rows of P that sum to 2^(-error), not 1."""
     lib = _lib.load()
     q, ldq = _mat(q, "q")
     k, ldk = _mat(k, "k")
@@ -423,9 +425,14 @@ def attention(q, k, vt, *, batch_q, lq, lk, heads, head_dim, kv_group=1, scale=N
     if return_lse:
         if accumulate:
             raise ValueError("return_lse is not combined with accumulate")
-        lse = torch.empty((batch_q, heads, lq), dtype=torch.float32, device=q.device)
-        p.lse = _p(lse)
+        if return_lse == "fused":
+            lse = torch.empty((batch_q, heads, lq), dtype=torch.float32, device=q.device)
+            p.lse = _p(lse)
+        elif return_lse is not True:
+            raise ValueError(f"return_lse must be False, True or 'fused', got {return_lse!r}")
     _lib.check(lib.i2v_attention_f16(C.byref(p), _stream()), "i2v_attention_f16")
+    if return_lse and lse is None:
+        lse = attention_lse(q, k, batch_q=batch_q, lq=lq, lk=lk, heads=heads, head_dim=head_dim, kv_group=kv_group, scale=p.scale)
     return (out, lse) if return_lse else out
 
 

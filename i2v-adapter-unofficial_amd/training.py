@@ -142,8 +142,9 @@ class AdapterBlockTrainer:
         proj = K.gemm(n1, w["w_qkq"])                                                # [q1 | k1 | q_adapter]
         q1, k1, qa = proj[:, :c], proj[:, c:2 * c], proj[:, 2 * c:]
         v1 = K.gemm(n1, w["w_v1"])
-        # (return_lse: the forward kernel writes each row's log2-sum-exp beside O; the backward sweeps take it from the tape
-        #  instead of recomputing Q K^T for it)
+        # (return_lse: each row's log2-sum-exp is made beside O, once, and both backward sweeps take it from the tape; it is
+        #  attention_lse's, the statistic of the logits the backward recomputes, not the forward kernel's own "fused" one:
+        #  with that one the rows of the backward's P do not sum to 1, tests/test_attention_bwd_edges_gpu.py)
         o1, lse1 = K.attention(q1, k1, K.transpose_tokens(v1, L), batch_q=n_img, lq=L, lk=L, heads=heads, head_dim=d,
                                return_lse=True)
         first = torch.empty((clips, L, c), dtype=f16, device=x.device)

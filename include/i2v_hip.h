@@ -207,7 +207,9 @@ typedef struct i2v_attn_params {
   float acc_scale;
   float* lse;     /* optional (ABI 6): fp32 [batch_q][heads][lq], the log2-sum-exp of the scaled logits of every query row,
                      written by the forward pass itself (what i2v_attention_lse_f32 recomputes; the training step keeps it
-                     for i2v_attention_bwd_f16).  NULL: not written.  Not combined with accumulate.                       */
+                     for i2v_attention_bwd_f16).  NULL: not written.  Not combined with accumulate.  It is the statistic of
+                     the kernel's own logits (Q is scaled and rounded to fp16 before Q K^T): within 1e-3 of max|lse| of
+                     i2v_attention_lse_f32's, which is the one that makes the backward's recomputed rows of P sum to 1.    */
 } i2v_attn_params;
 
 int i2v_attention_f16(const i2v_attn_params* p, i2v_stream_t stream);

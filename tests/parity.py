@@ -28,6 +28,8 @@ if ROOT not in sys.path:
 REL_TOL_MODULE = 2e-3
 REL_TOL_UNET = 3e-3
 REL_TOL_TRAJECTORY = 3.3e-3
+# gradients of the training kernels and modules (tests/test_training_gpu.py, tests/test_attention_bwd_edges_gpu.py)
+GRAD_REL_TOL = 2.5e-3     # measured 2.5e-4 .. 1.2e-3 of the largest reference gradient entry
 # SD-1.5 + AnimateDiff motion adapter + I2V-Adapter topology (unet:703-726 defaults with cross_attention_dim = 768):
 # the model bench.py times (BASELINE configs[1..4])
 SD15 = dict(sample_size=64, in_channels=4, out_channels=4, block_out_channels=(320, 640, 1280, 1280),

@@ -1138,6 +1138,46 @@ def freeu(hidden, skip, b, s):
     return h_out, s_out
 
 
+def vae_tile_blend(tile, out, oy, ox, blend_extent, limit, up=None, left=None, upleft=None, c=None):
+    """One tile of the tiled VAE into the stitched image (i2v_vae_tile_blend; diffusers tiled_decode / tiled_encode): tile
+    [N, th, tw, ld] token-major, fp32 (the decoder's conv_out) or fp16 (quant_conv), is blended over its first `blend_extent` rows
+    with the last rows of `up` [N, up_h, tw, ld] and over its first columns with the last columns of `left` [N, th, left_w, ld]
+    (`upleft` [N, up_h, left_w, ld] enters their common corner), cropped to limit x limit and written to
+    out[:, :, oy : oy + min(th, limit), ox : ox + min(tw, limit)] of the fp32 NCHW image `out` [N, c, H, W].  The neighbours are the
+    RAW tiles (the closed form of diffusers' in-place blends, include/i2v_hip.h); nothing else of `out` is written."""
+    lib = _lib.load()
+    _req(tile, "tile", dtype=None)
+    if tile.dtype not in (torch.float32, f16):
+        raise TypeError("tile must be fp16 or fp32")
+    if tile.dim() != 4 or not tile.is_contiguous():
+        raise ValueError("tile must be contiguous [N, th, tw, ld]")
+    n, th, tw, ld = tile.shape
+    c = ld if c is None else c
+    _req(out, "out", dtype=torch.float32)
+    if out.dim() != 4 or not out.is_contiguous() or out.shape[0] != n or out.shape[1] != c:
+        raise ValueError(f"out must be contiguous fp32 [{n}, {c}, H, W], got {tuple(out.shape)}")
+    up_h = left_w = 0
+    if up is not None:
+        up_h = up.shape[1] if up.dim() == 4 else 0
+        want = (n, up_h, tw, ld)
+        if up.dtype != tile.dtype or tuple(up.shape) != want or not up.is_contiguous() or not up.is_cuda:
+            raise ValueError(f"up must be a contiguous {tile.dtype} device tensor [{n}, up_h, {tw}, {ld}], got {tuple(up.shape)}")
+    if left is not None:
+        left_w = left.shape[2] if left.dim() == 4 else 0
+        want = (n, th, left_w, ld)
+        if left.dtype != tile.dtype or tuple(left.shape) != want or not left.is_contiguous() or not left.is_cuda:
+            raise ValueError(f"left must be a contiguous {tile.dtype} device tensor [{n}, {th}, left_w, {ld}], got {tuple(left.shape)}")
+    if upleft is not None and up is not None and left is not None:
+        if upleft.dtype != tile.dtype or tuple(upleft.shape) != (n, up_h, left_w, ld) or not upleft.is_contiguous() or \
+                not upleft.is_cuda:
+            raise ValueError(f"upleft must be a contiguous {tile.dtype} device tensor [{n}, {up_h}, {left_w}, {ld}], got "
+                             f"{tuple(upleft.shape)}")
+    _lib.check(lib.i2v_vae_tile_blend(_p(tile), _p(up), _p(left), _p(upleft), 1 if tile.dtype == torch.float32 else 0, n, th, tw, ld,
+                                      c, up_h, left_w, int(blend_extent), int(limit), _p(out), out.shape[2], out.shape[3], int(oy),
+                                      int(ox), _stream()), "i2v_vae_tile_blend")
+    return out
+
+
 # ---------------------------------------------------------------------------------------------- backward (SURVEY 8 f4)
 def transpose_tokens(x, batch_len, out=None):
     """[B * L, C] token-major -> [B, C, pad8(L)] channel-major (zero-filled pad): the K^T / Q^T / dO^T operands of the

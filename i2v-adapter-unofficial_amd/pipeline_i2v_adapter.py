@@ -99,6 +99,22 @@ class I2VAdapterPipeline:
     def disable_vae_slicing(self):
         self._vae_slicing = False
 
+    def enable_vae_tiling(self):
+        """pipe:139-147: decode (and encode) images larger than one VAE tile -- `vae.tile_sample_min_size` pixels on a side, 512 for
+        the SD VAE -- tile by tile with cross-faded seams (`AutoencoderKL.tiled_decode` / `tiled_encode`): peak VAE memory becomes that
+        of one tile, and, as in the reference, the frames differ from the untiled ones (every tile has its own GroupNorm statistics
+        and mid-block attention).  Composes with `enable_vae_slicing` (per-frame tiled decode) and reaches the condition image's
+        encode."""
+        if getattr(self, "vae", None) is None:
+            raise ValueError("The pipeline must have a `vae` (AutoencoderKL) for using VAE tiling.")
+        self.vae.enable_tiling()
+
+    def disable_vae_tiling(self):
+        """pipe:149-153."""
+        if getattr(self, "vae", None) is None:
+            raise ValueError("The pipeline must have a `vae` (AutoencoderKL) for using VAE tiling.")
+        self.vae.disable_tiling()
+
     def enable_freeu(self, s1: float, s2: float, b1: float, b2: float):
         """pipe:155-176: FreeU (https://arxiv.org/abs/2309.11497) on the UNet's first two up blocks -- s1 / s2 attenuate the low
         frequencies of the skip features of stage 1 / 2, b1 / b2 amplify half of the backbone channels (SD-1.5: 0.9, 0.2, 1.2, 1.4).
@@ -479,6 +495,9 @@ def main(argv=None):
                         help="ddim (the reference's) or dpmsolver++ (DPM-Solver++(2M): 15-20 steps instead of 25-50)")
     parser.add_argument("--freeu", type=float, nargs=4, default=None, metavar=("S1", "S2", "B1", "B2"),
                         help="enable FreeU with these scales (SD-1.5: 0.9 0.2 1.2 1.4); off by default, as in the reference driver")
+    parser.add_argument("--vae_tiling", action="store_true",
+                        help="tile the VAE decode / condition-image encode above 512 px a side (pipe.enable_vae_tiling(); off by "
+                             "default, as in the reference driver)")
     args = parser.parse_args(argv)
     if args.task_name is None:
         logger.error("Checkpoint `task_name` must be specified.")
@@ -519,6 +538,8 @@ def main(argv=None):
     pipe.enable_vae_slicing()                                                                    # pipe:787
     if args.freeu is not None:
         pipe.enable_freeu(*args.freeu)
+    if args.vae_tiling:
+        pipe.enable_vae_tiling()
 
     sample_save_dir = os.path.join(args.samples_root, args.task_name, f"epoch_{args.checkpoint_epoch}")
     os.makedirs(sample_save_dir, exist_ok=True)

@@ -8,6 +8,10 @@ pipe:754) loads by key, and runs every op on the kernels of the UNet path: token
 3x3 implicit-GEMM convolutions with fused bias / shortcut / residual, nearest-2x folded into the conv gather, the
 encoder's stride-2 Downsample2D(padding=0) as the `asym_pad` gather.  The mid-block attention has ONE head of dim 512
 (> the flash kernel's 160): QK^T and PV run as GEMMs around the row-softmax kernel, per image.
+
+`enable_tiling` (the reference's `enable_vae_tiling`, pipe:139-153) is diffusers' tiled encode / decode: inputs above one tile are
+cut into overlapping tiles, each through the whole encoder / decoder, and stitched by one `i2v_vae_tile_blend` launch per tile
+(`tiled_decode`).
 """
 from typing import Optional, Tuple
 
@@ -227,6 +231,37 @@ class _Config(dict):
     __getattr__ = dict.get
 
 
+def plan_tiles(size: int, tile: int, overlap: int):
+    """[(start, length)] of the tiles diffusers' tiled_encode / tiled_decode cut along one axis of `size` elements:
+    `for i in range(0, size, overlap): x[i : i + tile]` -- full tiles every `overlap`, the last ones shorter.  Each tile keeps its
+    first min(length, overlap) elements after the blend (limit = overlap in output units), so the kept pieces cover range(size)
+    exactly once.  Pure Python: importable and testable without a GPU."""
+    if size <= 0 or tile <= 0 or overlap <= 0:
+        raise ValueError(f"plan_tiles: size {size}, tile {tile}, overlap {overlap} must be positive")
+    return [(s, min(tile, size - s)) for s in range(0, size, overlap)]
+
+
+def tile_geometry(tile_in: int, tile_out: int, overlap_factor: float):
+    """(overlap, blend_extent, limit) of diffusers 0.24's tiling for tiles of `tile_in` input elements that come out `tile_out` long
+    (decode: tile_latent_min_size -> tile_sample_min_size; encode: the other way round):
+        overlap = int(tile_in * (1 - f))   in input elements: the distance between tile starts
+        blend_extent = int(tile_out * f)   in output elements: the cross-fade E
+        limit = tile_out - blend_extent    in output elements: what is kept of each tile
+    The kernel evaluates diffusers' in-place raster-order blends in closed form from the raw tiles, which holds while a tile that has
+    a successor is at least 2 E long, i.e. f <= 1/3 (0.25 in diffusers); any other factor raises NotImplementedError rather than
+    blend differently."""
+    f = float(overlap_factor)
+    if f > 1.0 / 3.0:
+        raise NotImplementedError(f"tile_overlap_factor {f}: above 1/3 the blend zones of a tile overlap and the closed form of the "
+                                  "in-place blends (i2v_vae_tile_blend) does not hold")
+    overlap, extent = int(tile_in * (1 - f)), int(tile_out * f)
+    limit = tile_out - extent
+    if overlap <= 0 or extent <= 0 or limit < 2 * extent:
+        raise NotImplementedError(f"tile_overlap_factor {f} with tiles of {tile_in} -> {tile_out}: overlap {overlap}, blend extent "
+                                  f"{extent}, limit {limit} (needs overlap > 0, blend extent > 0, limit >= 2 blend extents)")
+    return overlap, extent, limit
+
+
 class AutoencoderKL(PretrainedMixin, HipModule):
     def __init__(self, in_channels=3, out_channels=3, block_out_channels: Tuple[int, ...] = (128, 256, 512, 512),
                  layers_per_block=2, latent_channels=4, norm_num_groups=32, sample_size=512,
@@ -240,6 +275,22 @@ class AutoencoderKL(PretrainedMixin, HipModule):
         self.decoder = Decoder(latent_channels, out_channels, block_out_channels, layers_per_block, norm_num_groups)
         self.quant_conv = nn.Conv2d(2 * latent_channels, 2 * latent_channels, 1)
         self.post_quant_conv = nn.Conv2d(latent_channels, latent_channels, 1)
+        # diffusers 0.24 AutoencoderKL.__init__: tiling is off; the geometry comes from the config (SD VAE: 512 / 64 / 0.25)
+        self.use_tiling = False
+        self.tile_sample_min_size = sample_size
+        self.tile_latent_min_size = int(sample_size / (2 ** (len(block_out_channels) - 1)))
+        self.tile_overlap_factor = 0.25
+
+    def enable_tiling(self, use_tiling: bool = True):
+        """diffusers `enable_tiling` (behind the reference's enable_vae_tiling, pipe:139-147): inputs larger than one tile
+        (tile_latent_min_size latents / tile_sample_min_size pixels on a side) are decoded / encoded tile by tile -- each tile through
+        the whole decoder / encoder on its own, GroupNorm statistics and mid-block attention included, so the result DIFFERS from the
+        untiled one -- and cross-faded over tile_overlap_factor of a tile.  Peak activation memory is that of one tile."""
+        self.use_tiling = bool(use_tiling)
+
+    def disable_tiling(self):
+        """diffusers `disable_tiling` (pipe:149-153)."""
+        self.enable_tiling(False)
 
     @property
     def device(self):
@@ -275,11 +326,8 @@ class AutoencoderKL(PretrainedMixin, HipModule):
             self._packed_key = key
         return self._packed
 
-    @torch.no_grad()
-    def encode(self, x: torch.Tensor):
-        """x (N, 3, H, W) in [-1, 1] -> `.latent_dist` (DiagonalGaussianDistribution over (N, 4, H / 8, W / 8))."""
-        if not x.is_cuda:
-            raise HipLibraryError(f"input is on {x.device}: the HIP path has no CPU fallback")
+    def _encode_tokens(self, x: torch.Tensor):
+        """x (N, 3, H, W) -> quant_conv(encoder(x)) as token-major fp16 [N, H / 8, W / 8, pad8(2 * latent)]"""
         p = self.packed()
         lc2 = 2 * self.config.latent_channels
         t = K.nchw_to_tokens(x.float() if x.dtype not in (torch.float32, f16) else x, self.encoder.packed()["cin_pad"])
@@ -290,18 +338,110 @@ class AutoencoderKL(PretrainedMixin, HipModule):
         if mp is not None:
             K.copy3d(a.view(1, -1, lc2), mp[:, :lc2].view(1, -1, lc2))
             a = mp
-        q = K.gemm(a, p["wq"], p["bq"]).view(n, hh, ww, -1)                    # quant_conv
-        return _Out(latent_dist=DiagonalGaussianDistribution(K.tokens_to_nchw(q, c=lc2, dtype=torch.float32)))
+        return K.gemm(a, p["wq"], p["bq"]).view(n, hh, ww, -1)                 # quant_conv
+
+    @torch.no_grad()
+    def encode(self, x: torch.Tensor):
+        """x (N, 3, H, W) in [-1, 1] -> `.latent_dist` (DiagonalGaussianDistribution over (N, 4, H / 8, W / 8)).  With tiling
+        enabled and a side above tile_sample_min_size pixels: `tiled_encode`."""
+        if not x.is_cuda:
+            raise HipLibraryError(f"input is on {x.device}: the HIP path has no CPU fallback")
+        if self.use_tiling and (x.shape[-1] > self.tile_sample_min_size or x.shape[-2] > self.tile_sample_min_size):
+            return self.tiled_encode(x)
+        q = self._encode_tokens(x)
+        return _Out(latent_dist=DiagonalGaussianDistribution(
+            K.tokens_to_nchw(q, c=2 * self.config.latent_channels, dtype=torch.float32)))
 
     @torch.no_grad()
     def decode(self, z: torch.Tensor):
-        """z (N, 4, h, w) -> `.sample` (N, 3, 8h, 8w) fp32."""
+        """z (N, 4, h, w) -> `.sample` (N, 3, 8h, 8w) fp32.  With tiling enabled and a side above tile_latent_min_size latents:
+        `tiled_decode`."""
         if not z.is_cuda:
             raise HipLibraryError(f"latents are on {z.device}: the HIP path has no CPU fallback")
+        if self.use_tiling and (z.shape[-1] > self.tile_latent_min_size or z.shape[-2] > self.tile_latent_min_size):
+            return self.tiled_decode(z)
+        y = self.decoder._fwd(self._post_quant_tokens(z))
+        return _Out(sample=K.tokens_to_nchw(y, dtype=torch.float32))
+
+    def _post_quant_tokens(self, z: torch.Tensor):
+        """z (N, 4, h, w) -> post_quant_conv(z) as token-major fp16 [N, h, w, pad8(latent)] (padded channels stay 0)"""
         p = self.packed()
         lcp = K.pad8(self.config.latent_channels)
         t = K.nchw_to_tokens(z.float() if z.dtype not in (torch.float32, f16) else z, lcp)
         n, hh, ww, _ = t.shape
-        t = K.gemm(t.view(-1, lcp), p["wp"], p["bp"]).view(n, hh, ww, lcp)     # post_quant_conv (padded channels stay 0)
-        y = self.decoder._fwd(t)
-        return _Out(sample=K.tokens_to_nchw(y, dtype=torch.float32))
+        return K.gemm(t.view(-1, lcp), p["wp"], p["bp"]).view(n, hh, ww, lcp)
+
+    def _stitch(self, rows, cols, run_tile, out_len, extent, limit, channels, n, device):
+        """the tile grid `rows` x `cols` ([(start, length)] per axis, in input elements) through `run_tile(i, th, j, tw)` (the raw
+        token-major output of one tile, out_len(th) x out_len(tw)) and i2v_vae_tile_blend: one launch per tile writes its crop
+        rectangle of the stitched image.  A tile needs the RAW tiles above, to the left and on the diagonal only, so two tile rows
+        of outputs are alive at any time, never the grid."""
+        height = sum(min(out_len(th), limit) for _, th in rows)
+        width = sum(min(out_len(tw), limit) for _, tw in cols)
+        out = torch.empty((n, channels, height, width), dtype=torch.float32, device=device)
+        above, oy = None, 0
+        for i, th in rows:
+            cur, ox = [], 0
+            for jx, (j, tw) in enumerate(cols):
+                y = run_tile(i, th, j, tw)
+                if tuple(y.shape[:3]) != (n, out_len(th), out_len(tw)):
+                    raise ValueError(f"a tile of {th} x {tw} came out {tuple(y.shape)}, expected {out_len(th)} x {out_len(tw)}")
+                up = above[jx] if above is not None else None
+                left = cur[jx - 1] if jx > 0 else None
+                K.vae_tile_blend(y, out, oy, ox, extent, limit, up=up, left=left,
+                                 upleft=above[jx - 1] if up is not None and left is not None else None, c=channels)
+                cur.append(y)
+                ox += min(out_len(tw), limit)
+            above = cur
+            oy += min(out_len(th), limit)
+        return out
+
+    @torch.no_grad()
+    def tiled_decode(self, z: torch.Tensor):
+        """diffusers 0.24 `AutoencoderKL.tiled_decode`: z (N, 4, h, w) -> `.sample` (N, 3, 8h, 8w) fp32.
+            overlap = int(tile_latent_min_size * (1 - f)); E = int(tile_sample_min_size * f); limit = tile_sample_min_size - E
+            for i in range(0, h, overlap), j in range(0, w, overlap):
+                tile = decoder(post_quant_conv(z[:, :, i : i + tile_latent_min_size, j : j + tile_latent_min_size]))
+            then in raster order, in place: tile = blend_v(tile above, tile, E); tile = blend_h(tile to the left, tile, E);
+            keep tile[:, :, :limit, :limit]; concatenate along W, then along H
+            blend_v(a, b, E): e = min(a.H, b.H, E); b[y] = a[a.H - e + y] (1 - y / e) + b[y] (y / e) for y < e; blend_h likewise
+        (SD VAE: tiles of 64 latents every 48, E = 128 px, limit = 384 px).  Every tile runs the whole decoder on its own -- its own
+        GroupNorm statistics and mid-block attention -- so the frames differ from the untiled decode, as in the reference.  The
+        in-place blends are evaluated in closed form from the raw tiles by one i2v_vae_tile_blend launch per tile (include/i2v_hip.h).
+        post_quant_conv is 1 x 1: it runs once on the whole latent and the tiles are cropped from its token-major output."""
+        tl, ts = self.tile_latent_min_size, self.tile_sample_min_size
+        overlap, extent, limit = tile_geometry(tl, ts, self.tile_overlap_factor)
+        if not z.is_cuda:
+            raise HipLibraryError(f"latents are on {z.device}: the HIP path has no CPU fallback")
+        scale = 2 ** (len(self.config.block_out_channels) - 1)
+        t = self._post_quant_tokens(z)
+        n, hh, ww, lcp = t.shape
+
+        def run_tile(i, th, j, tw):
+            crop = torch.empty((n, th, tw, lcp), dtype=f16, device=t.device)
+            # (a row of the crop is tw * lcp contiguous elements of the latent's row: one strided 3-D copy)
+            K.copy3d(t.as_strided((n, th, tw * lcp), (hh * ww * lcp, ww * lcp, 1), t.storage_offset() + (i * ww + j) * lcp),
+                     crop.view(n, th, tw * lcp))
+            return self.decoder._fwd(crop)
+
+        return _Out(sample=self._stitch(plan_tiles(hh, tl, overlap), plan_tiles(ww, tl, overlap), run_tile, lambda v: v * scale,
+                                        extent, limit, self.config.out_channels, n, z.device))
+
+    @torch.no_grad()
+    def tiled_encode(self, x: torch.Tensor):
+        """diffusers 0.24 `AutoencoderKL.tiled_encode`: the scheme of `tiled_decode` on pixels --
+            overlap = int(tile_sample_min_size * (1 - f)); E = int(tile_latent_min_size * f); limit = tile_latent_min_size - E
+        (SD VAE: tiles of 512 px every 384, E = 16 latents, limit = 48) -- each tile through the encoder and quant_conv, then blend,
+        crop and concatenate; the stitched moments feed DiagonalGaussianDistribution."""
+        tl, ts = self.tile_latent_min_size, self.tile_sample_min_size
+        overlap, extent, limit = tile_geometry(ts, tl, self.tile_overlap_factor)
+        if not x.is_cuda:
+            raise HipLibraryError(f"input is on {x.device}: the HIP path has no CPU fallback")
+        scale = 2 ** (len(self.config.block_out_channels) - 1)
+        n, _, hh, ww = x.shape
+        if hh % scale or ww % scale:
+            raise ValueError(f"tiled_encode: {hh} x {ww} pixels are not multiples of {scale}")
+        run_tile = lambda i, th, j, tw: self._encode_tokens(x[:, :, i: i + th, j: j + tw])
+        moments = self._stitch(plan_tiles(hh, ts, overlap), plan_tiles(ww, ts, overlap), run_tile, lambda v: v // scale, extent,
+                               limit, 2 * self.config.latent_channels, n, x.device)
+        return _Out(latent_dist=DiagonalGaussianDistribution(moments))

@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define I2V_ABI_VERSION 11
+#define I2V_ABI_VERSION 12
 
 #define I2V_OK 0
 #define I2V_ERR_INVALID_ARG (-1)
@@ -531,6 +531,27 @@ int i2v_dpm_cfg_step(float* latents, float* x0_prev, const void* noise_pred, int
  * four-frequency form does not hold --, h or w > 256, c1 or c2 not a multiple of 8. */
 int i2v_freeu_f16(const void* hidden, const void* hidden_lo, void* hidden_out, void* hidden_out_lo, const void* skip, void* skip_out,
                   int32_t n, int32_t h, int32_t w, int32_t c1, int32_t c2, float b, float s, i2v_stream_t stream);
+
+/* (ABI 12) Blend-and-stitch of the tiled VAE (pipe:139-153 enable_vae_tiling / disable_vae_tiling -> diffusers 0.24
+ * AutoencoderKL.tiled_decode / tiled_encode: tiles of tile_latent_min_size / tile_sample_min_size every `overlap`, each through the
+ * decoder / encoder on its own, then blend_v with the tile above, blend_h with the tile to the left, crop to `limit`, concatenate).
+ * One launch per tile writes exactly out[:, :, oy : oy + min(th, limit), ox : ox + min(tw, limit)] of the fp32 NCHW image
+ * [n, c, out_h, out_w] and nothing else; it fuses tokens_to_nchw, both blends, the crop and both concatenations.
+ *   tile [n, th, tw, ld], up [n, up_h, tw, ld] (the tile above), left [n, th, left_w, ld], upleft [n, up_h, left_w, ld] (the diagonal
+ *   one): the RAW outputs of the decoder (fp32, src_is_f32: conv_out with c_is_f32, its real leading dimension) or of quant_conv
+ *   (fp16), token-major, first c channels.  NULL = no such neighbour; upleft only together with both up and left.
+ * With ev = min(up_h, th, blend_extent), eh = min(left_w, tw, blend_extent), uy = up_h - ev + y, lx = left_w - eh + x and
+ * lerp(a, b, w) = a (1 - w) + b w in fp32:
+ *   FU  = x < eh ? lerp(upleft[uy, lx], up[uy, x], x / eh) : up[uy, x]        v   = y < ev ? lerp(FU, tile[y, x], y / ev) : tile[y, x]
+ *   FL  = y < ev ? lerp(upleft[uy, lx], left[y, lx], y / ev) : left[y, lx]    out = x < eh ? lerp(FL, v, x / eh) : v
+ * which equals diffusers' in-place raster-order blends whenever a tile that has a successor is >= 2 blend_extent long (overlap factor
+ * <= 1/3: the rows / columns a tile hands on lie outside its own blend zone); no source is modified and the launches of a grid are
+ * independent.  Outside the blend zones the source passes through bit for bit.  Sources are read with 16-byte loads along ld when
+ * ld is a multiple of 8 (fp16) / 4 (fp32) and the pointers are 16-byte aligned, 12-byte loads for fp32 with ld = c = 3.
+ * I2V_ERR_INVALID_ARG: c > ld, limit <= 0, blend_extent <= 0, a crop rectangle that leaves the destination, upleft without up and left. */
+int i2v_vae_tile_blend(const void* tile, const void* up, const void* left, const void* upleft, int32_t src_is_f32, int32_t n, int32_t th,
+                       int32_t tw, int64_t ld, int32_t c, int32_t up_h, int32_t left_w, int32_t blend_extent, int32_t limit, void* out,
+                       int32_t out_h, int32_t out_w, int32_t oy, int32_t ox, i2v_stream_t stream);
 
 /* First-frame-similarity prior and the initial add_noise of the sampling loop, pipe:647-656:
  *   prior   = mask * GaussianBlur3x3(cond) + (1 - mask) * cond, mask = (mask_uniform < strength), per frame (pipe:648-654)

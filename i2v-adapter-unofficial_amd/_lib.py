@@ -10,11 +10,12 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # I2V_LIB_PATH selects another build of the same ABI (same-box A/B of two kernels, tools/ab_bench.sh); the in-tree
 # library is never overwritten by tooling
 LIB_PATH = os.environ.get("I2V_LIB_PATH") or os.path.join(_HERE, "libi2v_hip.so")
-ABI_VERSION = 12
+ABI_VERSION = 13
 
 I2V_EPI_NONE, I2V_EPI_GELU, I2V_EPI_GEGLU = 0, 1, 2
 I2V_STORE_ROWMAJOR, I2V_STORE_ROWPERM, I2V_STORE_VT, I2V_STORE_VT_T = 0, 1, 2, 3
 I2V_A_PLAIN, I2V_A_CONV3X3 = 0, 1
+I2V_LORA_MAX_ADAPTERS, I2V_LORA_MAX_RANK = 8, 256
 
 
 class HipLibraryError(RuntimeError):
@@ -184,6 +185,10 @@ class GnParams(C.Structure):
     ]
 
 
+class LoraAdapter(C.Structure):
+    _fields_ = [("down", C.c_void_p), ("up", C.c_void_p), ("rank", C.c_int32), ("scale", C.c_float)]
+
+
 class LnParams(C.Structure):
     _fields_ = [
         ("x", C.c_void_p), ("ldx", C.c_int64),
@@ -273,6 +278,7 @@ SIGNATURES = {
     "i2v_freeu_f16": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, _P]),
     "i2v_vae_tile_blend": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
                                      C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),
+    "i2v_lora_merge": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.POINTER(LoraAdapter), C.c_int32, _P]),
     # the model handle: configuration, weight registry, plan, one captured step
     "i2v_unet_create": (C.c_int, [C.POINTER(UnetConfig), C.POINTER(_P)]),
     "i2v_unet_destroy": (C.c_int, [_P]),

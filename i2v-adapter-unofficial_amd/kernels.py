@@ -1178,6 +1178,40 @@ def vae_tile_blend(tile, out, oy, ox, blend_extent, limit, up=None, left=None, u
     return out
 
 
+def lora_merge(dst, base, adapters):
+    """dst = round(base + sum_j scale_j * up_j @ down_j) for one weight (i2v_lora_merge): base / dst contiguous, both fp16 or both
+    fp32, [out, in] or a conv weight [Cout, Cin, kh, kw] (in = Cin kh kw), not overlapping; `adapters` = [(down, up, scale), ...], at
+    most 8, down fp16 [rank, in] (or [rank, Cin, kh, kw]), up fp16 [out, rank] (or [out, rank, 1, 1]), contiguous, rank <= 256.  The
+    products are fp32 (MFMA), the scales multiply them in fp32 and the sum is rounded once; `base` is not modified.  `dst` may be a
+    Parameter: its version counter is bumped after the launch -- a write through a raw pointer does not do that, and the kernel-layout
+    packs (`HipModule.packed`) and the pipeline's graph key are keyed on it."""
+    lib = _lib.load()
+    _req(base, "base", dtype=None)
+    _req(dst, "dst", dtype=None)
+    if base.dtype not in (torch.float32, f16) or dst.dtype != base.dtype:
+        raise TypeError(f"base and dst must both be fp16 or both fp32, got {base.dtype} and {dst.dtype}")
+    if base.dim() < 2 or dst.shape != base.shape or not base.is_contiguous() or not dst.is_contiguous():
+        raise ValueError(f"base {tuple(base.shape)} and dst {tuple(dst.shape)} must be contiguous weights of one shape, [out, in, ...]")
+    out_f, in_f = base.shape[0], base.numel() // max(base.shape[0], 1)
+    if out_f < 1 or in_f < 1:
+        raise ValueError(f"empty weight {tuple(base.shape)}")
+    arr = (_lib.LoraAdapter * max(len(adapters), 1))()
+    for j, (down, up, scale) in enumerate(adapters):
+        _req(down, f"adapters[{j}].down")
+        _req(up, f"adapters[{j}].up")
+        if not down.is_contiguous() or not up.is_contiguous():
+            raise ValueError(f"adapters[{j}]: the factors must be contiguous")
+        rank = down.shape[0] if down.dim() >= 2 else 0
+        if rank < 1 or down.numel() != rank * in_f or up.dim() < 2 or up.shape[0] != out_f or up.numel() != out_f * rank:
+            raise ValueError(f"adapters[{j}]: down {tuple(down.shape)} / up {tuple(up.shape)} do not fit a weight [{out_f}, {in_f}] "
+                             "(down [rank, in], up [out, rank])")
+        arr[j] = _lib.LoraAdapter(down.data_ptr(), up.data_ptr(), rank, float(scale))
+    _lib.check(lib.i2v_lora_merge(_p(dst), _p(base), 1 if base.dtype == torch.float32 else 0, out_f, in_f, arr, len(adapters), _stream()),
+               "i2v_lora_merge")
+    torch.autograd.graph.increment_version(dst)
+    return dst
+
+
 # ---------------------------------------------------------------------------------------------- backward (SURVEY 8 f4)
 def transpose_tokens(x, batch_len, out=None):
     """[B * L, C] token-major -> [B, C, pad8(L)] channel-major (zero-filled pad): the K^T / Q^T / dO^T operands of the

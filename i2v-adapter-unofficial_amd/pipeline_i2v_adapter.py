@@ -170,6 +170,37 @@ class I2VAdapterPipeline:
         self.unet._load_ip_adapter_weights(
             load_ip_adapter_file(pretrained_model_name_or_path_or_dict, subfolder=subfolder, weight_name=weight_name))
 
+    # ------------------------------------------------------------------------------------------ LoRA (lora.py)
+    def load_lora_weights(self, pretrained_model_name_or_path_or_dict, adapter_name: Optional[str] = None,
+                          weight_name: Optional[str] = None, subfolder: Optional[str] = None):
+        """diffusers LoraLoaderMixin.load_lora_weights (pipe:57): a .safetensors / .bin file or a state dict in the diffusers, PEFT or
+        kohya key spelling; the UNet part is kept as a named adapter and MERGED into the UNet's weights at the next call (one
+        i2v_lora_merge launch per targeted weight, nothing per denoising step).  Text-encoder keys are skipped (CLIP is out of scope) and
+        counted in the returned report."""
+        return self.unet.load_lora(pretrained_model_name_or_path_or_dict, adapter_name=adapter_name, weight_name=weight_name,
+                                   subfolder=subfolder)
+
+    def set_adapters(self, adapter_names, adapter_weights=None):
+        self.unet.set_adapters(adapter_names, adapter_weights)
+
+    def get_active_adapters(self):
+        return self.unet.get_active_adapters()
+
+    def delete_adapters(self, adapter_names):
+        self.unet.delete_adapters(adapter_names)
+
+    def unload_lora_weights(self):
+        """the UNet's weights get their values from before the first load back, bit for bit"""
+        self.unet.unload_lora()
+
+    def fuse_lora(self, lora_scale: float = 1.0):
+        """merge the active adapters at `lora_scale` now and drop their factors (the per-call scale no longer applies)"""
+        self.unet.fuse_lora(lora_scale)
+
+    def unfuse_lora(self):
+        """the weights from before the LoRA, exactly (restored from the stash, not by subtracting the update as diffusers does)"""
+        self.unet.unfuse_lora()
+
     def load_motion_adapter(self, motion_adapter):
         self.unet.load_motion_modules(motion_adapter)
         self.motion_adapter = motion_adapter
@@ -320,6 +351,19 @@ class I2VAdapterPipeline:
                 return self.__call__(**kw)
             finally:
                 blocks.set_precise_stream(prev)
+        if cross_attention_kwargs and cross_attention_kwargs.get("scale") is not None:
+            # the LoRA scale of THIS call (diffusers: cross_attention_kwargs={"scale": s}); the previous one comes back afterwards.  A
+            # changed scale re-merges the weights and so re-captures the step once (_graph_key hashes the weights' versions)
+            kw = dict(locals())
+            for k in ("self", "precise_stream"):
+                kw.pop(k)
+            kw["cross_attention_kwargs"] = {k: v for k, v in cross_attention_kwargs.items() if k != "scale"}
+            prev = self.unet.set_lora_scale(cross_attention_kwargs["scale"])
+            try:
+                return self.__call__(**kw)
+            finally:
+                self.unet.set_lora_scale(prev)
+        self.unet._sync_lora()      # before anything reads a weight, a pack or the weights' versions (_graph_key)
         if prompt is not None or ip_adapter_image is not None:
             raise NotImplementedError(
                 "the CLIP text / image encoders are out of scope of this build (SURVEY section 2 row 3b): pass "
@@ -495,6 +539,10 @@ def main(argv=None):
                         help="ddim (the reference's) or dpmsolver++ (DPM-Solver++(2M): 15-20 steps instead of 25-50)")
     parser.add_argument("--freeu", type=float, nargs=4, default=None, metavar=("S1", "S2", "B1", "B2"),
                         help="enable FreeU with these scales (SD-1.5: 0.9 0.2 1.2 1.4); off by default, as in the reference driver")
+    parser.add_argument("--lora", action="append", default=[], metavar="PATH[:WEIGHT]",
+                        help="a LoRA file (.safetensors / .bin; diffusers, PEFT or kohya keys) merged into the UNet, with an optional "
+                             "adapter weight; repeatable")
+    parser.add_argument("--lora_scale", type=float, default=1.0, help="global LoRA scale (cross_attention_kwargs={'scale': S})")
     parser.add_argument("--vae_tiling", action="store_true",
                         help="tile the VAE decode / condition-image encode above 512 px a side (pipe.enable_vae_tiling(); off by "
                              "default, as in the reference driver)")
@@ -540,6 +588,16 @@ def main(argv=None):
         pipe.enable_freeu(*args.freeu)
     if args.vae_tiling:
         pipe.enable_vae_tiling()
+    if args.lora:
+        names, weights = [], []
+        for i, spec in enumerate(args.lora):
+            path, _, w = spec.rpartition(":") if ":" in spec and not os.path.exists(spec) else (spec, "", "")
+            rep = pipe.load_lora_weights(path, adapter_name=f"lora_{i}")
+            names.append(rep["adapter_name"])
+            weights.append(float(w) if w else 1.0)
+            logger.info(f"LoRA {path}: {rep['modules']} UNet modules, {rep['text_encoder_keys']} text-encoder keys skipped")
+        pipe.set_adapters(names, weights)
+        pipe.unet.set_lora_scale(args.lora_scale)
 
     sample_save_dir = os.path.join(args.samples_root, args.task_name, f"epoch_{args.checkpoint_epoch}")
     os.makedirs(sample_save_dir, exist_ok=True)

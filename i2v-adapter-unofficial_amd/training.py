@@ -492,6 +492,15 @@ class UpsampleTrainer:
 
 # ------------------------------------------------------------------------------------------------------------------------
 # The whole training step of the reference loop (src/train_image_to_video.py:839-884) for the adapter parameters.
+def _refuse_lora_on_trained(unet, update_motion_modules):
+    """the parameters the reference trains (unet:979-1026) must not carry LoRA state: the optimiser writes them in place, and the
+    next LoRA merge would rebuild them from the stash of their values from before (lora.py)"""
+    from .lora import check_not_trained
+    check_not_trained(unet, [n for n, _ in unet.named_parameters()
+                             if ".i2v_adapter.to_q." in n or ".i2v_adapter.to_out." in n
+                             or (update_motion_modules and ".motion_modules." in n)])
+
+
 class UNetAdapterTrainer:
     """forward(...) = UNetMotionCrossFrameAttnModel.forward with enable_cross_frame_attn=True (unet:1289-1451) in the un-fused
     training form, keeping every layer's input; backward(target, ...) = the loss without the first frame
@@ -505,6 +514,7 @@ class UNetAdapterTrainer:
         from .blocks import DownBlockMotion, UpBlockMotion  # noqa: F401  (attention-free blocks: resnet -> motion)
         self.unet = unet
         self.update_motion_modules = bool(update_motion_modules)
+        _refuse_lora_on_trained(unet, self.update_motion_modules)
         names = {m: n for n, m in unet.named_modules()}
         self.tape_layout = []          # (kind, trainer, extra) in forward order; built once, replayed per step
         self._mk = dict(resnet=ResnetTrainer, t2d=Transformer2DTrainer, motion=MotionModuleTrainer, down=DownsampleTrainer,
@@ -668,6 +678,7 @@ class AdapterOptimizer:
         min(ema_decay, (1 + t) / (10 + t)) with t = updates - 1, 0 on the first).  (The reference builds its EMA over a
         `UNet2DConditionModel`'s parameter list and steps it with the motion UNet's, :674-677 vs :889 -- lists that do not match;
         the EMA here covers the parameters that train, read back with `ema_state_dict()`.)"""
+        _refuse_lora_on_trained(unet, update_motion_modules)
         self.unet, self.group = unet, process_group
         self.accum_steps, self._micro = int(gradient_accumulation_steps), 0
         if self.accum_steps < 1:

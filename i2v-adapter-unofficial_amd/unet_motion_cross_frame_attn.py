@@ -21,6 +21,7 @@ from .blocks import (Attention, DownBlockMotion, Downsample2D, HipModule, ImageP
                      Upsample2D, _as_f16_matrix, _motion, from_tokens, pack_conv3x3, precise_stream, to_tokens, w16)
 from .checkpoint import PretrainedMixin
 from .i2v_adapter import I2VAdapterModule, I2VAdapterTransformer2DModel
+from .lora import UNetLoraMixin
 
 f16 = torch.float16
 
@@ -297,7 +298,7 @@ class AttnProcessorHIP:
         return isinstance(other, AttnProcessorHIP) and (self.num_tokens, self.scale) == (other.num_tokens, other.scale)
 
 
-class UNetMotionCrossFrameAttnModel(PretrainedMixin, HipModule):
+class UNetMotionCrossFrameAttnModel(UNetLoraMixin, PretrainedMixin, HipModule):
     """unet:696-1451."""
 
     def __init__(self, sample_size: Optional[int] = None, in_channels: int = 4, out_channels: int = 4,
@@ -599,6 +600,7 @@ class UNetMotionCrossFrameAttnModel(PretrainedMixin, HipModule):
                     w_out=pack_conv3x3(self.conv_out.weight), b_out=w16(self.conv_out.bias), cin_pad=cin_pad)
 
     def packed(self):
+        self._sync_lora()
         # only the UNet's own leaf parameters feed this pack (children pack themselves)
         leaves = [self.conv_in.weight, self.conv_in.bias, self.conv_norm_out.weight, self.conv_norm_out.bias,
                   self.conv_out.weight, self.conv_out.bias]
@@ -638,6 +640,7 @@ class UNetMotionCrossFrameAttnModel(PretrainedMixin, HipModule):
         """K / V^T of the text (+ image) context for every cross-attention layer, computed ONCE per sample instead of in
         every UNet call (they do not depend on the latents or the timestep).  `out`: a previous result whose buffers
         are overwritten in place (a captured hipGraph keeps reading the same memory for the next sample)."""
+        self._sync_lora()
         pc = out if out is not None else ProjectedContext(ctx_text, ctx_ip)
         if out is not None:
             pc.text, pc.ip = ctx_text, ctx_ip
@@ -648,6 +651,7 @@ class UNetMotionCrossFrameAttnModel(PretrainedMixin, HipModule):
 
     def _temb_pack(self):
         """time_emb_proj weights of all resnets concatenated ([sum Cout, 4 C0]) + the column slice of each resnet."""
+        self._sync_lora()
         resnets = [m for m in self.modules() if isinstance(m, ResnetBlock2D) and m.time_emb_proj is not None]
         key = tuple((r.time_emb_proj.weight.data_ptr(), r.time_emb_proj.weight._version, r.time_emb_proj.bias._version)
                     for r in resnets)
@@ -720,10 +724,12 @@ class UNetMotionCrossFrameAttnModel(PretrainedMixin, HipModule):
     def _embed_time(self, timesteps_f32, t_index=None):
         """Timesteps -> TimestepEmbedding (unet:1336-1343); one row per sample (the per-frame repeat of unet:1344
         is index arithmetic in the conv epilogue)."""
+        self._sync_lora()
         t_emb = K.timestep_embedding(timesteps_f32, self.config.block_out_channels[0], t_index=t_index)
         return self.time_embedding(t_emb)
 
     def _project_image_embeds(self, added_cond_kwargs):
+        self._sync_lora()
         if self.encoder_hid_proj is not None and self.config.encoder_hid_dim_type == "ip_image_proj":
             if added_cond_kwargs is None or "image_embeds" not in added_cond_kwargs:
                 raise ValueError(
@@ -738,9 +744,22 @@ class UNetMotionCrossFrameAttnModel(PretrainedMixin, HipModule):
                 down_block_additional_residuals=None, mid_block_additional_residual=None,
                 return_dict: bool = True):
         """unet:1289-1451.  sample (B, F, C, H, W) -> noise prediction (B, F, C, H, W) in sample's dtype.
+        `cross_attention_kwargs={"scale": s}`: the global LoRA scale of this call (lora.py).
         `cross_attention_kwargs={"cfg_shared_prefix": True}` (an addition; the reference ignores the dict on this path): the
         caller asserts that sample[B/2:] == sample[:B/2] and that all timesteps are equal -- the classifier-free-guidance
         batch of pipe:672-673 -- and the prompt-independent prefix of the network is computed once (see _fwd_tokens)."""
+        if cross_attention_kwargs and cross_attention_kwargs.get("scale") is not None:
+            # the LoRA scale of THIS call (diffusers' cross_attention_kwargs={"scale": s}): merged at s, the previous scale restored
+            rest = {k: v for k, v in cross_attention_kwargs.items() if k != "scale"}
+            prev = self.set_lora_scale(cross_attention_kwargs["scale"])
+            try:
+                return self.forward(sample, timestep, enable_cross_frame_attn, encoder_hidden_states, timestep_cond=timestep_cond,
+                                    attention_mask=attention_mask, cross_attention_kwargs=rest, added_cond_kwargs=added_cond_kwargs,
+                                    down_block_additional_residuals=down_block_additional_residuals,
+                                    mid_block_additional_residual=mid_block_additional_residual, return_dict=return_dict)
+            finally:
+                self.set_lora_scale(prev)
+        self._sync_lora()      # (a LoRA change since the last call: merge before any weight or pack is read)
         if attention_mask is not None:
             raise NotImplementedError("attention masks are never passed on the hot path (SURVEY 8b)")
         if down_block_additional_residuals is not None or mid_block_additional_residual is not None:

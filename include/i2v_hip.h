@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define I2V_ABI_VERSION 12
+#define I2V_ABI_VERSION 13
 
 #define I2V_OK 0
 #define I2V_ERR_INVALID_ARG (-1)
@@ -552,6 +552,33 @@ int i2v_freeu_f16(const void* hidden, const void* hidden_lo, void* hidden_out, v
 int i2v_vae_tile_blend(const void* tile, const void* up, const void* left, const void* upleft, int32_t src_is_f32, int32_t n, int32_t th,
                        int32_t tw, int64_t ld, int32_t c, int32_t up_h, int32_t left_w, int32_t blend_extent, int32_t limit, void* out,
                        int32_t out_h, int32_t out_w, int32_t oy, int32_t ox, i2v_stream_t stream);
+
+/* (ABI 13) LoRA merge (pipe:57 LoraLoaderMixin, unet:108 UNet2DConditionLoadersMixin: load_lora_weights / fuse_lora / the
+ * cross_attention_kwargs "scale"): the low-rank updates of up to I2V_LORA_MAX_ADAPTERS adapters folded into ONE weight matrix, one launch,
+ *   dst[o, i] = round( base[o, i] + sum_j scale_j * sum_r up_j[o, r] * down_j[r, i] ),   j < n_adapters, r < rank_j.
+ * base, dst [out, in] row-major and dense, both fp16 or both fp32 (is_f32); a conv weight [Cout, Cin, kh, kw] is the same problem with
+ * in = Cin kh kw (kohya and diffusers store conv LoRAs as down [r, Cin, kh, kw], up [Cout, r, 1, 1]).  dst must not overlap base or a
+ * factor; base is not modified.  Every adapter: down fp16 [rank, in], up fp16 [out, rank], dense, 1 <= rank <= I2V_LORA_MAX_RANK.
+ * The adapter list is read on the host and travels BY VALUE in the kernel arguments: no device-side table, no allocation, no
+ * synchronisation, like every other entry point.
+ *   The products run on the MFMA (fp16 in, fp32 accumulate; a rank that is no multiple of the MFMA's k is zero-padded in LDS, not in
+ *   memory); scale_j multiplies adapter j's fp32 product (never an fp16 factor); the result is rounded ONCE from the fp32 sum of base and
+ *   all adapters, so it does not depend on the order of the adapters beyond fp32 summation.  An element whose low-rank sum is exactly
+ *   zero -- n_adapters = 0, all scales 0 -- takes base's bits: -0, subnormals, infinities and NaN payloads come through unchanged.
+ * 16-byte loads / stores of base / dst when in is a multiple of 8 (fp16) / 4 (fp32) and both pointers are 16-byte aligned, an
+ * element-wise form otherwise (conv_in: 320 x 36); the factors likewise per adapter (rank % 8, in % 8, alignment).
+ * I2V_ERR_INVALID_ARG: null pointers, out or in < 1, n_adapters > I2V_LORA_MAX_ADAPTERS, a rank outside 1 .. I2V_LORA_MAX_RANK, dst
+ * overlapping base or a factor. */
+#define I2V_LORA_MAX_ADAPTERS 8
+#define I2V_LORA_MAX_RANK 256
+typedef struct i2v_lora_adapter {
+  const void* down; /* fp16 [rank, in]  */
+  const void* up;   /* fp16 [out, rank] */
+  int32_t rank;
+  float scale;
+} i2v_lora_adapter;
+int i2v_lora_merge(void* dst, const void* base, int32_t is_f32, int32_t out, int32_t in, const i2v_lora_adapter* adapters,
+                   int32_t n_adapters, i2v_stream_t stream);
 
 /* First-frame-similarity prior and the initial add_noise of the sampling loop, pipe:647-656:
  *   prior   = mask * GaussianBlur3x3(cond) + (1 - mask) * cond, mask = (mask_uniform < strength), per frame (pipe:648-654)

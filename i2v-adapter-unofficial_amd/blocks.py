@@ -1334,3 +1334,146 @@ class DPMSolverMultistepScheduler:
         while sa.dim() < original_samples.dim():
             sa, sb = sa.unsqueeze(-1), sb.unsqueeze(-1)
         return sa * original_samples + sb * noise
+
+
+class LCMScheduler:
+    """Latent-consistency sampling (LCM-LoRA, AnimateLCM: 4 - 8 steps) for the captured step: the host side of `i2v_lcm_cfg_step`.  A
+    restatement of diffusers 0.24's LCMScheduler for epsilon prediction without clipping or thresholding; keys and defaults are
+    diffusers' (`timestep_spacing`, `steps_offset` and `set_alpha_to_one` are carried in the config and, as there, do not enter the
+    arithmetic).  Any other value of an unsupported key raises NotImplementedError; keys it does not know are ignored, so
+    `LCMScheduler.from_config(pipe.scheduler.config)` works from a DDIM, DPM-Solver++ or PNDM config.
+
+    The update is stochastic: every step but the last re-noises the predicted clean latents with a fresh Gaussian draw.  The draws of a
+    whole sample are made before its first step (`step_noise`) and read on the device by the step counter, so the step stays one
+    captured hipGraph.  `scale_model_input` is the identity and `add_noise` is DDIM's."""
+
+    order = 1
+    init_noise_sigma = 1.0
+    sigma_data = 0.5
+    _SUPPORTED = {"prediction_type": ("epsilon",), "clip_sample": (False,), "thresholding": (False,), "rescale_betas_zero_snr": (False,),
+                  "beta_schedule": ("scaled_linear", "linear")}
+
+    def __init__(self, num_train_timesteps=1000, beta_start=0.00085, beta_end=0.012, beta_schedule="scaled_linear", trained_betas=None,
+                 original_inference_steps=50, clip_sample=False, set_alpha_to_one=True, steps_offset=0, prediction_type="epsilon",
+                 thresholding=False, timestep_spacing="leading", timestep_scaling=10.0, rescale_betas_zero_snr=False, **_unused):
+        self.config = dict(num_train_timesteps=num_train_timesteps, beta_start=beta_start, beta_end=beta_end, beta_schedule=beta_schedule,
+                           trained_betas=trained_betas, original_inference_steps=original_inference_steps, clip_sample=clip_sample,
+                           set_alpha_to_one=set_alpha_to_one, steps_offset=steps_offset, prediction_type=prediction_type,
+                           thresholding=thresholding, timestep_spacing=timestep_spacing, timestep_scaling=timestep_scaling,
+                           rescale_betas_zero_snr=rescale_betas_zero_snr)
+        for key, allowed in self._SUPPORTED.items():
+            v = self.config[key]
+            if not any(v == a and isinstance(v, bool) == isinstance(a, bool) for a in allowed):
+                raise NotImplementedError(f"LCMScheduler: {key}={v!r} is not supported (supported: "
+                                          f"{', '.join(repr(a) for a in allowed)})")
+        if trained_betas is not None:
+            raise NotImplementedError("LCMScheduler: trained_betas is not supported")
+        if beta_schedule == "scaled_linear":
+            self.betas = torch.linspace(beta_start ** 0.5, beta_end ** 0.5, num_train_timesteps, dtype=torch.float32) ** 2
+        else:
+            self.betas = torch.linspace(beta_start, beta_end, num_train_timesteps, dtype=torch.float32)
+        self.num_train_timesteps = num_train_timesteps
+        self.original_inference_steps = original_inference_steps
+        self.timestep_scaling = timestep_scaling
+        self.alphas_cumprod = torch.cumprod(1.0 - self.betas, dim=0)
+        self.final_alpha_cumprod = torch.tensor(1.0) if set_alpha_to_one else self.alphas_cumprod[0]
+        self.num_inference_steps = None
+        self.timesteps = torch.arange(num_train_timesteps - 1, -1, -1, dtype=torch.int64)
+
+    @classmethod
+    def from_config(cls, config: dict, **overrides):
+        """diffusers' `SchedulerMixin.from_config` (`LCMScheduler.from_config(pipe.scheduler.config)`): keys starting with `_` and
+        unknown keys are ignored."""
+        cfg = {k: v for k, v in dict(config).items() if not k.startswith("_")}
+        cfg.update(overrides)
+        return cls(**cfg)
+
+    @classmethod
+    def from_pretrained(cls, pretrained_model_path: str, subfolder: Optional[str] = None, **overrides):
+        """scheduler_config.json (of any scheduler class: an SD-1.5 checkpoint ships PNDM's) + keyword overrides."""
+        import json
+        import os
+        path = os.path.join(pretrained_model_path, subfolder) if subfolder else pretrained_model_path
+        with open(os.path.join(path, "scheduler_config.json")) as f:
+            return cls.from_config(json.load(f), **overrides)
+
+    def save_pretrained(self, save_directory: str):
+        import json
+        import os
+        os.makedirs(save_directory, exist_ok=True)
+        with open(os.path.join(save_directory, "scheduler_config.json"), "w") as f:
+            json.dump({"_class_name": "LCMScheduler", **self.config}, f, indent=2, sort_keys=True)
+
+    def set_timesteps(self, num_inference_steps: int, device=None):
+        """N of the `original_inference_steps` timesteps the consistency model was distilled on (k i - 1, k = T // original steps, from
+        T - 1 down), evenly skipped: origin[floor(linspace(0, len(origin), N, endpoint=False))]."""
+        import numpy as np
+        T, N, orig = self.num_train_timesteps, num_inference_steps, self.original_inference_steps
+        if orig > T:
+            raise ValueError(f"original_inference_steps {orig} cannot be larger than num_train_timesteps {T}")
+        if N > T:
+            raise ValueError(f"num_inference_steps {N} cannot be larger than num_train_timesteps {T}")
+        if N > orig:
+            raise ValueError(f"num_inference_steps {N} cannot be larger than original_inference_steps {orig}")
+        if N < 1:
+            raise ValueError(f"num_inference_steps {N} must be at least 1")
+        origin = (np.arange(1, orig + 1) * (T // orig) - 1)[::-1].copy()
+        idx = np.floor(np.linspace(0, len(origin), num=N, endpoint=False)).astype(np.int64)
+        self.timesteps = torch.from_numpy(origin[idx].astype(np.int64))
+        self.num_inference_steps = N
+
+    def scale_model_input(self, sample, timestep=None):
+        return sample
+
+    def _start_index(self, timesteps):
+        full = [int(v) for v in self.timesteps]
+        sub = [int(v) for v in timesteps]
+        if not sub or sub[0] not in full or full[full.index(sub[0]):] != sub:
+            raise ValueError("timesteps must be a tail of the scheduler's timesteps (set_timesteps first)")
+        return full.index(sub[0])
+
+    def step_coefficients(self, timesteps, eta: float = 0.0) -> torch.Tensor:
+        """[len(timesteps), 6] fp32 rows {sa_t, sb_t, c_skip, c_out, sa_p, sb_p} of `i2v_lcm_cfg_step`, built in float64.  Row k is the
+        step from t = timesteps[k] to the next entry of the full list (`timesteps` is that list or a tail of it:
+        frame_similarity_sample_ratio < 1):
+            x0 = (x - sb_t eps) / sa_t,   den = c_out x0 + c_skip x,   x' = sa_p den + sb_p z,
+        sa = sqrt(a), sb = sqrt(1 - a) of alphas_cumprod at t and at the next timestep, and the boundary-condition scalings
+        c_skip = sigma_d^2 / (s^2 + sigma_d^2), c_out = s / sqrt(s^2 + sigma_d^2) with s = t timestep_scaling, sigma_d = 0.5.  The last
+        entry of the full list has sa_p = 1, sb_p = 0: the step returns `den`.  `eta` is ignored, as for DPM-Solver++."""
+        start = self._start_index(timesteps)
+        full = [int(v) for v in self.timesteps]
+        ac = self.alphas_cumprod.double()
+        sd2 = self.sigma_data ** 2
+        rows = []
+        for i in range(start, len(full)):
+            a_t = float(ac[full[i]])
+            s = full[i] * float(self.timestep_scaling)
+            if i + 1 < len(full):
+                a_p = float(ac[full[i + 1]])
+                sa_p, sb_p = math.sqrt(a_p), math.sqrt(1.0 - a_p)
+            else:
+                sa_p, sb_p = 1.0, 0.0
+            rows.append([math.sqrt(a_t), math.sqrt(1.0 - a_t), sd2 / (s * s + sd2), s / math.sqrt(s * s + sd2), sa_p, sb_p])
+        return torch.tensor(rows, dtype=torch.float64).to(torch.float32)
+
+    def step_noise(self, timesteps, shape, generator=None, device=None):
+        """The noise table of `i2v_lcm_cfg_step`: one randn draw of `shape` (the latents') per step of `timesteps` that re-noises
+        (sb_p != 0: every step but the last of the full list), in step order, from `generator` -- the stream diffusers' per-step
+        `randn_tensor(model_output.shape, generator=...)` draws, since nothing else draws from `generator` between steps.  A host
+        generator reproduces the CPU numbers bit for bit; a list of generators draws each sample's rows from its own generator.
+        fp32 [draws, *shape] on `device`, or None when no step draws (a single step)."""
+        from .pipeline_i2v_adapter import _draw
+        n_draws = len(self.timesteps) - 1 - self._start_index(timesteps)
+        if n_draws < 1:
+            return None
+        device = device if device is not None else torch.device("cpu")
+        return torch.stack([_draw(torch.randn, tuple(shape), generator, device) for _ in range(n_draws)]).to(torch.float32).contiguous()
+
+    def add_noise(self, original_samples, noise, timesteps):
+        ac = self.alphas_cumprod.to(device=original_samples.device, dtype=original_samples.dtype)
+        timesteps = timesteps.to(original_samples.device)
+        sa = (ac[timesteps] ** 0.5).flatten()
+        sb = ((1 - ac[timesteps]) ** 0.5).flatten()
+        while sa.dim() < original_samples.dim():
+            sa, sb = sa.unsqueeze(-1), sb.unsqueeze(-1)
+        return sa * original_samples + sb * noise

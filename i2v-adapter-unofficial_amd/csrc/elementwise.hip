@@ -237,6 +237,55 @@ __global__ __launch_bounds__(256) void dpm_step_kernel(float* __restrict__ laten
   }
 }
 
+// Latent-consistency (LCM) update with the same CFG combine and the same V-pixels-per-thread form as dpm_step_kernel.  Row
+// {sa_t, sb_t, c_skip, c_out, sa_p, sb_p}:
+//   x0 = (x - sb_t eps) / sa_t;  den = c_out x0 + c_skip x;  x' = sa_p den + sb_p z,  z = noise[min(step, n_noise - 1)].
+// noise fp32 [n_noise][b, f, c, hw]: the fresh Gaussian draw of every step but the last, selected by the device-side step counter.
+// A row with sb_p == 0 (the last step: sa_p = 1) never reads the table.
+template <typename NP, int V>
+__global__ __launch_bounds__(256) void lcm_step_kernel(float* __restrict__ latents, const float* __restrict__ noise, int n_noise,
+                                                       const NP* __restrict__ np, int64_t ld_np, const float* __restrict__ coef,
+                                                       int n_steps, const int32_t* __restrict__ step_index, float guidance,
+                                                       int b, int f, int c, int hw, int copies) {
+  const int hwv = hw / V;
+  const int64_t groups = (int64_t)b * f * c * hwv;
+  const int step = min(max(*step_index, 0), n_steps - 1);
+  const float* cf = coef + 6 * (int64_t)step;
+  const float sa_t = cf[0], sb_t = cf[1], c_skip = cf[2], c_out = cf[3], sa_p = cf[4], sb_p = cf[5];
+  const bool renoise = sb_p != 0.f && noise != nullptr && n_noise > 0;
+  const float* z = renoise ? noise + (int64_t)min(step, n_noise - 1) * (groups * V) : nullptr;
+  const int64_t bf = (int64_t)b * f;
+  for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < groups; g += (int64_t)gridDim.x * 256) {
+    const int p0 = (int)(g % hwv) * V;
+    const int64_t t = g / hwv;
+    const int ch = (int)(t % c);
+    const int64_t img = t / c;  // b * f + fr
+    float x[V], out[V];
+    load_f32v<V>(latents + g * V, x);
+#pragma unroll
+    for (int j = 0; j < V; ++j) {
+      float eps;
+      if (copies == 2) {
+        const float u = (float)np[(img * hw + p0 + j) * ld_np + ch];
+        const float cnd = (float)np[((bf + img) * hw + p0 + j) * ld_np + ch];
+        eps = u + guidance * (cnd - u);
+      } else {
+        eps = (float)np[(img * hw + p0 + j) * ld_np + ch];
+      }
+      const float x0 = (x[j] - sb_t * eps) / sa_t;
+      const float den = c_out * x0 + c_skip * x[j];
+      out[j] = sa_p * den;
+    }
+    if (renoise) {
+      float zz[V];
+      load_f32v<V>(z + g * V, zz);
+#pragma unroll
+      for (int j = 0; j < V; ++j) out[j] += sb_p * zz[j];
+    }
+    store_f32v<V>(latents + g * V, out);
+  }
+}
+
 // First-frame-similarity prior + add_noise (pipe:647-656), one pass:
 //   prior = mask * blur3x3(cond) + (1 - mask) * cond,  mask = (u < strength)          (per frame, per element)
 //   latents = sqrt(a_t) * prior + sqrt(1 - a_t) * noise                                 (DDIMScheduler.add_noise)
@@ -481,6 +530,42 @@ extern "C" int i2v_dpm_cfg_step(float* latents, float* x0_prev, const void* nois
                        cfg_copies, s);
   hipLaunchKernelGGL(bump_step_kernel, dim3(1), dim3(64), 0, s, step_index, n_steps);
   return i2v_check_launch("i2v_dpm_cfg_step");
+}
+
+template <int V>
+static void launch_lcm_step(float* latents, const float* noise, int32_t n_noise, const void* noise_pred, int32_t np_is_f32,
+                            int64_t ld_np, const float* coef, int32_t n_steps, int32_t* step_index, float guidance_scale, int32_t b,
+                            int32_t f, int32_t c, int32_t hw, int32_t cfg_copies, hipStream_t s) {
+  const dim3 grid(ew_blocks((int64_t)b * f * c * (hw / V))), block(256);
+  if (np_is_f32)
+    hipLaunchKernelGGL((lcm_step_kernel<float, V>), grid, block, 0, s, latents, noise, n_noise, reinterpret_cast<const float*>(noise_pred),
+                       ld_np, coef, n_steps, step_index, guidance_scale, b, f, c, hw, cfg_copies);
+  else
+    hipLaunchKernelGGL((lcm_step_kernel<f16, V>), grid, block, 0, s, latents, noise, n_noise, reinterpret_cast<const f16*>(noise_pred),
+                       ld_np, coef, n_steps, step_index, guidance_scale, b, f, c, hw, cfg_copies);
+}
+
+extern "C" int i2v_lcm_cfg_step(float* latents, const float* noise, int32_t n_noise, const void* noise_pred, int32_t np_is_f32,
+                                int64_t ld_np, const float* coef, int32_t n_steps, int32_t* step_index, float guidance_scale,
+                                int32_t b, int32_t f, int32_t c, int32_t hw, int32_t cfg_copies, i2v_stream_t stream) {
+  I2V_CHECK_ARG(latents && noise_pred && coef && step_index, "i2v_lcm_cfg_step: null pointer");
+  I2V_CHECK_ARG(b > 0 && f > 0 && c > 0 && hw > 0, "i2v_lcm_cfg_step: b %d f %d c %d hw %d must be positive", b, f, c, hw);
+  I2V_CHECK_ARG(n_steps >= 1, "i2v_lcm_cfg_step: n_steps %d must be at least 1", n_steps);
+  I2V_CHECK_ARG(ld_np >= c, "i2v_lcm_cfg_step: ld_np %lld < c %d", (long long)ld_np, c);
+  I2V_CHECK_ARG(cfg_copies == 1 || cfg_copies == 2, "i2v_lcm_cfg_step: cfg_copies must be 1 or 2");
+  // a single-step schedule is its own last step (sb_p = 0) and draws no noise: only then may the table be absent
+  I2V_CHECK_ARG(noise != nullptr || n_steps == 1, "i2v_lcm_cfg_step: the noise table is NULL and the schedule has %d steps", n_steps);
+  I2V_CHECK_ARG(noise == nullptr || n_noise >= 1, "i2v_lcm_cfg_step: n_noise %d must be at least 1", n_noise);
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const bool vec4 = hw % 4 == 0 && (reinterpret_cast<uintptr_t>(latents) & 15) == 0 && (reinterpret_cast<uintptr_t>(noise) & 15) == 0;
+  if (vec4)
+    launch_lcm_step<4>(latents, noise, n_noise, noise_pred, np_is_f32, ld_np, coef, n_steps, step_index, guidance_scale, b, f, c, hw,
+                       cfg_copies, s);
+  else
+    launch_lcm_step<1>(latents, noise, n_noise, noise_pred, np_is_f32, ld_np, coef, n_steps, step_index, guidance_scale, b, f, c, hw,
+                       cfg_copies, s);
+  hipLaunchKernelGGL(bump_step_kernel, dim3(1), dim3(64), 0, s, step_index, n_steps);
+  return i2v_check_launch("i2v_lcm_cfg_step");
 }
 
 extern "C" int i2v_first_frame_prior_f32(const float* cond, const float* mask_uniform, const float* noise, float* latents,

@@ -32,15 +32,23 @@ ENTRY_IDS = {name: i for i, name in enumerate((
     "i2v_timestep_embedding", "i2v_silu_f16", "i2v_repeat_rows_f16", "i2v_copy3d_f16", "i2v_select_row_f16",
     "i2v_pack_ctx_fragments_f16", "i2v_ddim_prep", "i2v_ddim_cfg_step", "i2v_dpm_cfg_step"))}
 # ENTRY_IDS is the table as it stood at ABI 10 and stays that table (tests/test_dpm_solver.py pins i2v_dpm_cfg_step as its last id).
-# Entry points added since continue the numbering of `enum Entry` here; `entry_id` / `ENTRY_NAMES` cover both.
+# Entry points added since continue the numbering of `enum Entry` here; `entry_id` / `entry_name` cover both.
 LATER_ENTRY_IDS = {name: len(ENTRY_IDS) + i for i, name in enumerate((
-    "i2v_freeu_f16",))}                                             # ABI 11
-ENTRY_NAMES = {i: n for n, i in {**ENTRY_IDS, **LATER_ENTRY_IDS}.items()}
+    "i2v_freeu_f16",                                                # ABI 11
+    "i2v_lcm_cfg_step"))}                                           # ABI 14
+# ENTRY_NAMES is the id -> name table as it stood at ABI 11 and stays that table (tests/test_freeu.py pins its 22 ids); `entry_name`
+# covers every id.
+ENTRY_NAMES = {i: n for n, i in {**ENTRY_IDS, "i2v_freeu_f16": LATER_ENTRY_IDS["i2v_freeu_f16"]}.items()}
 
 
 def entry_id(name):
     """id of a launch entry point in csrc/handle.hip `enum Entry`, or None when a plan cannot carry it"""
     return ENTRY_IDS.get(name, LATER_ENTRY_IDS.get(name))
+
+
+def entry_name(i):
+    """name of launch entry point `i` of csrc/handle.hip `enum Entry`, or None"""
+    return next((n for n, j in {**ENTRY_IDS, **LATER_ENTRY_IDS}.items() if j == i), None)
 
 
 IO_SAMPLE, IO_TIMESTEPS, IO_CONTEXT, IO_IMAGE_EMBEDS, IO_OUT = range(5)
@@ -302,6 +310,7 @@ def record_forward_plan(unet, sample, timesteps, encoder_hidden_states, image_em
 # ---- the whole denoising loop (pipe:663-700) for a host without Python: a per-sample preparation plan and a per-step plan whose
 #      per-sample buffers are named like weights
 STEP_LATENTS, STEP_COND, STEP_INDEX, STEP_COEF, STEP_HISTORY = range(5)   # io slots of a step plan (STEP_HISTORY: DPM-Solver++ only)
+STEP_NOISE = STEP_HISTORY          # LCM only: the noise table (LCM has no history, DPM-Solver++ no noise: I2V_IO_SLOTS stays 5)
 PREP_CONTEXT, PREP_TIMESTEPS, PREP_IMAGE_EMBEDS = range(3)         # io slots of a preparation plan
 
 
@@ -332,7 +341,23 @@ def record_step_plan(pipe, st):
     io: STEP_LATENTS fp32 [B, F, C, H, W] (in / out), STEP_COND fp32 [B, C, H, W], STEP_INDEX int32 [1] (in / out: advanced by the
     step), STEP_COEF fp32 [T, 4]; the per-sample buffers are weights named `sample#...` (`sample_buffers`).
     With a DPMSolverMultistepScheduler the step ends in i2v_dpm_cfg_step: STEP_COEF is fp32 [T, 6] and STEP_HISTORY fp32 [B, F, C, H, W]
-    (= st["x0_prev"], in / out: the previous step's data prediction; not read by the first step of a sample)."""
+    (= st["x0_prev"], in / out: the previous step's data prediction; not read by the first step of a sample).
+    With an LCMScheduler the step ends in i2v_lcm_cfg_step: STEP_COEF is fp32 [T, 6] and STEP_NOISE (the same slot) fp32
+    [T - 1, B, F, C, H, W] (= st["noise"], read only: `LCMScheduler.step_noise`; absent for a single-step schedule)."""
+    if pipe._scheduler_kind() == "lcm":
+        noise = st.get("noise")
+        keep_lcm = (st["latents"].clone(), st["step_idx"].clone())
+
+        def restore_lcm():
+            st["latents"].copy_(keep_lcm[0])
+            st["step_idx"].copy_(keep_lcm[1])
+        io = {STEP_LATENTS: st["latents"], STEP_COND: st["cond"], STEP_INDEX: st["step_idx"], STEP_COEF: st["coef"]}
+        if noise is not None:
+            io[STEP_NOISE] = noise
+        blob, weights = record_plan(lambda: pipe._step(st), unet=pipe.unet, restore=restore_lcm, problem=_step_problem(st), io=io,
+                                    extra_persistent=lambda: sample_buffers(pipe.unet, st))
+        restore_lcm()
+        return blob, weights
     hist = st.get("x0_prev")
     keep = (st["latents"].clone(), st["step_idx"].clone(), None if hist is None else hist.clone())
 
@@ -513,7 +538,7 @@ def export_denoiser(pipe, out_dir, *, num_frames, latent_height, latent_width, b
     sch = pipe.scheduler
     if pipe._scheduler_kind() != "ddim":
         raise NotImplementedError("export_denoiser writes the DDIM loop (manifest `ddim_coefficients`, four io slots per step); "
-                                  "a DPM-Solver++ step plan comes from record_step_plan")
+                                  "a DPM-Solver++ or LCM step plan comes from record_step_plan")
     sch.set_timesteps(num_inference_steps)
     ts = sch.timesteps
     B, F, hh, ww = batch, num_frames, latent_height, latent_width

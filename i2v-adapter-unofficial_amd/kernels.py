@@ -1113,6 +1113,37 @@ def dpm_cfg_step(latents, x0_prev, noise_pred, coef, step_index, guidance_scale,
     return latents
 
 
+def lcm_cfg_step(latents, noise, noise_pred, coef, step_index, guidance_scale, cfg_copies):
+    """In-place latent-consistency (LCM) update of latents fp32 [B, F, C, H, W] from noise_pred tokens (fp32, or fp16)
+    [cfg_copies * B * F, H, W, ld]; noise fp32 [n, B, F, C, H, W] (`LCMScheduler.step_noise`: row min(step, n - 1) re-noises every
+    step but the last; None for a single-step schedule); coef fp32 [steps, 6] (`LCMScheduler.step_coefficients`); step_index device
+    int32 scalar (advanced by one, wrapping to 0 at the end of the table)."""
+    lib = _lib.load()
+    _req(latents, "latents", dtype=torch.float32)
+    _req(noise_pred, "noise_pred", dtype=None)
+    if noise_pred.dtype not in (torch.float32, f16):
+        raise TypeError("noise_pred must be fp32 or fp16")
+    _req(coef, "coef", dtype=torch.float32)
+    _req(step_index, "step_index", dtype=torch.int32)
+    if latents.dim() != 5 or not latents.is_contiguous():
+        raise ValueError("latents must be contiguous [B, F, C, H, W]")
+    b, f, c, h, w = latents.shape
+    if noise is not None:
+        _req(noise, "noise", dtype=torch.float32)
+        if noise.dim() != 6 or tuple(noise.shape[1:]) != tuple(latents.shape) or noise.shape[0] < 1 or not noise.is_contiguous():
+            raise ValueError(f"noise must be contiguous [n >= 1, {', '.join(str(v) for v in latents.shape)}], got {tuple(noise.shape)}")
+    if noise_pred.dim() != 4 or not noise_pred.is_contiguous() or noise_pred.shape[0] != cfg_copies * b * f or \
+            noise_pred.shape[1] != h or noise_pred.shape[2] != w or noise_pred.shape[3] < c:
+        raise ValueError(f"noise_pred must be contiguous [{cfg_copies * b * f}, {h}, {w}, >={c}]")
+    if coef.dim() != 2 or coef.shape[1] != 6 or not coef.is_contiguous():
+        raise ValueError("coef must be contiguous [steps, 6]")
+    _lib.check(lib.i2v_lcm_cfg_step(_p(latents), _p(noise) if noise is not None else None, noise.shape[0] if noise is not None else 0,
+                                    _p(noise_pred), 1 if noise_pred.dtype == torch.float32 else 0, noise_pred.shape[3], _p(coef),
+                                    coef.shape[0], _p(step_index), float(guidance_scale), b, f, c, h * w, cfg_copies, _stream()),
+               "i2v_lcm_cfg_step")
+    return latents
+
+
 def freeu(hidden, skip, b, s):
     """FreeU on the operands of an up block's skip concatenation (i2v_freeu_f16; diffusers apply_freeu, unet:453-478): hidden
     [N, H, W, C1], skip [N, H, W, C2] fp16 token-major -> (hidden', skip'), new tensors.  hidden'[..., :C1 // 2] = hidden * b, the

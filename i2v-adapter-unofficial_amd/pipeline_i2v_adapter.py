@@ -4,7 +4,8 @@
 
 One DDIM step = frame-0 overwrite + CFG duplicate + layout edge (i2v_ddim_prep), timestep embedding, the UNet,
 CFG combine + DDIM update (i2v_ddim_cfg_step; with a DPMSolverMultistepScheduler the DPM-Solver++(2M) update,
-i2v_dpm_cfg_step, which also keeps the previous data prediction on the device).  The whole step is captured ONCE as a hipGraph (through
+i2v_dpm_cfg_step, which also keeps the previous data prediction on the device; with an LCMScheduler the latent-consistency update,
+i2v_lcm_cfg_step, which re-noises with this step's row of a noise table drawn once per sample).  The whole step is captured ONCE as a hipGraph (through
 torch.cuda.CUDAGraph on the stream the ctypes launches go to) and replayed for every timestep: the step's
 scalars (t, sqrt(a_t), ...) are read on the device from small tables indexed by a device-side step counter, so
 there is no per-step host<->device traffic and no per-step sync (the reference syncs once per step on
@@ -22,7 +23,7 @@ import torch
 
 from . import kernels as K
 from ._lib import HipLibraryError
-from .blocks import DDIMScheduler, DPMSolverMultistepScheduler
+from .blocks import DDIMScheduler, DPMSolverMultistepScheduler, LCMScheduler
 from .image_processor import VaeImageProcessor, tensor2vid
 from .unet_motion_cross_frame_attn import UNetMotionCrossFrameAttnModel
 
@@ -229,13 +230,19 @@ class I2VAdapterPipeline:
 
     # ------------------------------------------------------------------------------------------ one step
     def _scheduler_kind(self):
-        """"dpmsolver++" for a DPMSolverMultistepScheduler (the i2v_dpm_cfg_step update), "ddim" for any other scheduler object
-        (the DDIM update, as before); the reference's other schedulers by class name raise."""
+        """"dpmsolver++" for a DPMSolverMultistepScheduler (the i2v_dpm_cfg_step update), "lcm" for an LCMScheduler (the
+        i2v_lcm_cfg_step update), "ddim" for any other scheduler object (the DDIM update, as before); the reference's other schedulers
+        by class name raise."""
+        if isinstance(self.scheduler, LCMScheduler):
+            return "lcm"
+        if isinstance(self.scheduler, DPMSolverMultistepScheduler):
+            return "dpmsolver++"
         name = type(self.scheduler).__name__
         if name in UNSUPPORTED_SCHEDULERS:
             raise NotImplementedError(f"{name} is not supported by this build: use DDIMScheduler or DPMSolverMultistepScheduler "
-                                      "(e.g. DPMSolverMultistepScheduler.from_config(pipe.scheduler.config))")
-        return "dpmsolver++" if isinstance(self.scheduler, DPMSolverMultistepScheduler) else "ddim"
+                                      "(e.g. DPMSolverMultistepScheduler.from_config(pipe.scheduler.config)), or LCMScheduler with an "
+                                      "LCM-LoRA")
+        return "ddim"
 
     def _step(self, st):
         """One iteration of pipe:666-697 as kernel launches on the current stream (captured into a hipGraph)."""
@@ -248,7 +255,9 @@ class I2VAdapterPipeline:
         y = unet._fwd_tokens(x, None, True, st.get("ctx_proj") or st["ctx_text"], st["ctx_ip"],
                              st["num_frames"], cfg_shared=CFG_SHARED and st["copies"] == 2, temb_proj=temb_proj,
                              forward_upsample_size=any(s % (2 ** unet.num_upsamplers) for s in st["latents"].shape[-2:]))   # pipe:676-683, unet:1304-1311
-        if isinstance(self.scheduler, DPMSolverMultistepScheduler):
+        if isinstance(self.scheduler, LCMScheduler):
+            K.lcm_cfg_step(st["latents"], st["noise"], y, st["coef"], st["step_idx"], st["guidance"], st["copies"])
+        elif isinstance(self.scheduler, DPMSolverMultistepScheduler):
             K.dpm_cfg_step(st["latents"], st["x0_prev"], y, st["coef"], st["step_idx"], st["guidance"], st["copies"])
         else:
             K.ddim_cfg_step(st["latents"], y, st["coef"], st["step_idx"], st["guidance"], st["copies"])  # pipe:686-691
@@ -258,7 +267,8 @@ class I2VAdapterPipeline:
         scalars passed as launch arguments (guidance, IP scales), the identity / version of every weight (the packed
         kernel-layout copies are rebuilt when a parameter changes, and a graph captured before that reads the old ones) and the
         scheduler's update (a scheduler swapped between calls re-captures) and FreeU's four scales (launch arguments: enabling,
-        changing or disabling FreeU re-captures)"""
+        changing or disabling FreeU re-captures) and the LCM noise table's shape (its row count is a launch argument: another step
+        count re-captures)"""
         unet = self.unet
         wsig = hash(tuple((p.data_ptr(), p._version) for p in unet.parameters()))
         ips = tuple((a.ip_num_tokens, float(a.ip_scale)) for a in unet._cross_attention_layers())
@@ -266,7 +276,7 @@ class I2VAdapterPipeline:
         from .blocks import precise_stream      # (a captured step keeps the residual-stream mode it was captured in)
         return (tuple(st["latents"].shape), st["copies"], st["num_frames"], st["guidance"], shp(st["t_table"]),
                 shp(st["ctx_text"]), shp(st["ctx_ip"]), str(st["latents"].device), wsig, ips, precise_stream(),
-                self._scheduler_kind(), shp(st["coef"]), unet.freeu_signature())
+                self._scheduler_kind(), shp(st["coef"]), unet.freeu_signature(), shp(st.get("noise")))
 
     def _run_steps(self, st, n_steps, use_graph):
         if not use_graph:
@@ -283,8 +293,8 @@ class I2VAdapterPipeline:
         hit = cache.get(key)
         if hit is not None:
             graph, gst = hit
-            for name in ("latents", "cond", "t_table", "coef", "ctx_text", "ctx_ip"):
-                if st[name] is not None:
+            for name in ("latents", "cond", "t_table", "coef", "ctx_text", "ctx_ip", "noise"):      # (noise: this sample's LCM draws)
+                if st.get(name) is not None:
                     gst[name].copy_(st[name])
             gst["step_idx"].zero_()
             self.unet.project_context(gst["ctx_text"], gst["ctx_ip"], out=gst["ctx_proj"])
@@ -409,7 +419,8 @@ class I2VAdapterPipeline:
                     negative_image_embeds = torch.zeros_like(image_embeds)                      # pipe:343
                 image_embeds = torch.cat([negative_image_embeds, image_embeds])                 # pipe:621-622
 
-        dpm = self._scheduler_kind() == "dpmsolver++"
+        kind = self._scheduler_kind()
+        dpm, lcm = kind == "dpmsolver++", kind == "lcm"
         self.scheduler.set_timesteps(num_inference_steps)                                       # pipe:630-631
         timesteps, _ = self.get_timesteps(num_inference_steps, frame_similarity_sample_ratio)
 
@@ -440,26 +451,31 @@ class I2VAdapterPipeline:
         if dpm:
             # the previous step's data prediction: the first step of a sample is first order and does not read it
             st["x0_prev"] = torch.empty_like(latents)
+        if lcm:
+            # every step's fresh noise (diffusers draws it inside `step`, from `generator`, after prepare_latents' draw): one table per
+            # sample, drawn after the prior's draws, read on the device by the step counter -- the steps stay captured
+            st["noise"] = self.scheduler.step_noise(timesteps, tuple(latents.shape), generator, dev)
         # K / V^T of the prompt (+ image) context for all 16 cross-attention layers: once per sample, not once per step
         # (projected where it is consumed: a graph-cache hit projects straight into the graph's static buffers)
         # (DPM-Solver++ has no stochastic form here: the reference passes `eta` only to a scheduler whose step takes it,
-        # pipe:184-199, so it is ignored and the steps stay captured)
-        if callback is None and (eta == 0.0 or dpm):
+        # pipe:184-199, so it is ignored and the steps stay captured; LCM's step takes no eta either, and its noise is in the table)
+        fixed = dpm or lcm
+        if callback is None and (eta == 0.0 or fixed):
             st["latents"] = self._run_steps(st, len(timesteps), use_graph)
         else:
             # eager steps: a per-step host hook (pipe:693-697), and / or the stochastic DDIM update (eta > 0, pipe:550, 659-660:
             # sigma_t is out of the direction coefficient -- `step_coefficients(timesteps, eta)` -- and comes back as fresh noise,
             # one draw of the latents' shape per step from `generator` as diffusers' scheduler draws it)
-            if eta != 0.0 and use_graph and not dpm:
+            if eta != 0.0 and use_graph and not fixed:
                 import warnings
                 warnings.warn("eta > 0: the stochastic DDIM update draws fresh noise on the host every step, so the steps run as "
                               "eager launches instead of the captured hipGraph (about 2x the step time)", RuntimeWarning, stacklevel=2)
-            sigmas = None if dpm else self.scheduler.step_sigmas(timesteps, eta)
+            sigmas = None if fixed else self.scheduler.step_sigmas(timesteps, eta)
             st["ctx_proj"] = self.unet.project_context(st["ctx_text"], st["ctx_ip"])
             st["temb_table"] = self.unet.project_time_table(st["t_table"])
             for i, t in enumerate(timesteps):                                                   # pipe:666-697
                 self._step(st)
-                if eta > 0 and not dpm:
+                if eta > 0 and not fixed:
                     z = _draw(torch.randn, tuple(st["latents"].shape), generator, dev).to(torch.float32).contiguous()
                     K.axpby(st["latents"], z, 1.0, sigmas[i])
                 if callback is not None and i % callback_steps == 0:
@@ -478,46 +494,29 @@ class I2VAdapterPipeline:
 
 
 SCHEDULERS = ("ddim", "dpmsolver++")
+STOCHASTIC_SCHEDULERS = ("lcm",)       # samplers whose step draws noise (from a device table: still one captured step)
 
 
 def load_scheduler(model_path, kind="ddim"):
     """the evaluation driver's scheduler (`--scheduler`) from `<model_path>/scheduler/scheduler_config.json`: "ddim" as the
     reference builds it (pipe:755-757), "dpmsolver++" the same config as a DPMSolverMultistepScheduler (DPM-Solver++(2M),
-    linspace spacing, steps_offset=1)."""
+    linspace spacing, steps_offset=1), "lcm" the same config as an LCMScheduler (the checkpoint's betas, diffusers' LCM defaults for the
+    rest: for a UNet with an LCM-LoRA or AnimateLCM merged in)."""
     if kind == "ddim":
         return DDIMScheduler.from_pretrained(model_path, subfolder="scheduler", clip_sample=False,
                                              timestep_spacing="linspace", steps_offset=1)          # pipe:755-757
     if kind == "dpmsolver++":
         return DPMSolverMultistepScheduler.from_pretrained(model_path, subfolder="scheduler", timestep_spacing="linspace",
                                                            steps_offset=1)
-    raise ValueError(f"unknown scheduler {kind!r}: one of {', '.join(SCHEDULERS)}")
+    if kind == "lcm":
+        return LCMScheduler.from_pretrained(model_path, subfolder="scheduler", timestep_spacing="leading", steps_offset=0,
+                                            set_alpha_to_one=True, clip_sample=False)
+    raise ValueError(f"unknown scheduler {kind!r}: one of {', '.join(SCHEDULERS + STOCHASTIC_SCHEDULERS)}")
 
 
-def main(argv=None):
-    """The reference's evaluation driver (pipe:721-809, the README command
-    `python src/pipelines/pipeline_i2v_adapter.py --task_name ... --checkpoint_epoch ...`): load MotionAdapter /
-    I2VAdapterModule / SD-1.5 UNet + VAE / IP-Adapter from the reference's directory layout, read the CSV of
-    (image_path, name) pairs, sample 16 frames per pair and write one GIF per prompt.
-
-    The CLIP text / image encoders are out of scope of this build, so the per-row `prompt_embeds`,
-    `negative_prompt_embeds` (and `image_embeds`) come from a safetensors file (--embeds) written by
-    `src/tools/encode_text.py`-style tooling; everything else follows the reference driver."""
+def build_parser():
+    """the evaluation driver's command line (`main`)"""
     import argparse
-    import logging
-    import os
-
-    import pandas as pd
-    import PIL.Image
-    from safetensors.torch import load_file
-
-    from .blocks import MotionAdapter
-    from .i2v_adapter import I2VAdapterModule
-    from .image_processor import export_to_gif
-    from .unet_motion_cross_frame_attn import UNet2DConditionModel
-    from .vae import AutoencoderKL
-
-    logger = logging.getLogger("i2v_adapter_pipeline")
-    logging.basicConfig(level=logging.INFO)
     parser = argparse.ArgumentParser()
     parser.add_argument("--checkpoint_epoch", type=int, default=0)
     parser.add_argument("--eval_data_path", type=str, default="./data/WebVid-10M/I2VAdapter-eval.csv")
@@ -535,8 +534,10 @@ def main(argv=None):
     parser.add_argument("--height", type=int, default=None)
     parser.add_argument("--width", type=int, default=None)
     parser.add_argument("--seed", type=int, default=0)
-    parser.add_argument("--scheduler", choices=SCHEDULERS, default="ddim",
-                        help="ddim (the reference's) or dpmsolver++ (DPM-Solver++(2M): 15-20 steps instead of 25-50)")
+    parser.add_argument("--scheduler", choices=SCHEDULERS + STOCHASTIC_SCHEDULERS, default="ddim",
+                        help="ddim (the reference's), dpmsolver++ (DPM-Solver++(2M): 15-20 steps instead of 25-50) or lcm (latent-consistency "
+                             "sampling for a UNet with an LCM-LoRA / AnimateLCM merged in (--lora): 4-8 steps, --guidance_scale 1-2)")
+    parser.add_argument("--guidance_scale", type=float, default=7.5, help="classifier-free guidance scale (pipe:794); <= 1 runs one copy")
     parser.add_argument("--freeu", type=float, nargs=4, default=None, metavar=("S1", "S2", "B1", "B2"),
                         help="enable FreeU with these scales (SD-1.5: 0.9 0.2 1.2 1.4); off by default, as in the reference driver")
     parser.add_argument("--lora", action="append", default=[], metavar="PATH[:WEIGHT]",
@@ -546,7 +547,34 @@ def main(argv=None):
     parser.add_argument("--vae_tiling", action="store_true",
                         help="tile the VAE decode / condition-image encode above 512 px a side (pipe.enable_vae_tiling(); off by "
                              "default, as in the reference driver)")
-    args = parser.parse_args(argv)
+    return parser
+
+
+def main(argv=None):
+    """The reference's evaluation driver (pipe:721-809, the README command
+    `python src/pipelines/pipeline_i2v_adapter.py --task_name ... --checkpoint_epoch ...`): load MotionAdapter /
+    I2VAdapterModule / SD-1.5 UNet + VAE / IP-Adapter from the reference's directory layout, read the CSV of
+    (image_path, name) pairs, sample 16 frames per pair and write one GIF per prompt.
+
+    The CLIP text / image encoders are out of scope of this build, so the per-row `prompt_embeds`,
+    `negative_prompt_embeds` (and `image_embeds`) come from a safetensors file (--embeds) written by
+    `src/tools/encode_text.py`-style tooling; everything else follows the reference driver."""
+    import logging
+    import os
+
+    import pandas as pd
+    import PIL.Image
+    from safetensors.torch import load_file
+
+    from .blocks import MotionAdapter
+    from .i2v_adapter import I2VAdapterModule
+    from .image_processor import export_to_gif
+    from .unet_motion_cross_frame_attn import UNet2DConditionModel
+    from .vae import AutoencoderKL
+
+    logger = logging.getLogger("i2v_adapter_pipeline")
+    logging.basicConfig(level=logging.INFO)
+    args = build_parser().parse_args(argv)
     if args.task_name is None:
         logger.error("Checkpoint `task_name` must be specified.")
         return -1
@@ -607,7 +635,7 @@ def main(argv=None):
         out = pipe(prompt_embeds=emb["prompt_embeds"][ind: ind + 1],
                    negative_prompt_embeds=neg[ind: ind + 1] if neg.shape[0] == n else neg[:1],
                    image_embeds=emb["image_embeds"][ind: ind + 1] if "image_embeds" in emb else None,
-                   condition_image=condition_images[ind], num_frames=args.num_frames, guidance_scale=7.5,
+                   condition_image=condition_images[ind], num_frames=args.num_frames, guidance_scale=args.guidance_scale,
                    num_inference_steps=args.num_inference_steps, frame_similarity_sample_ratio=0.9,
                    height=args.height, width=args.width, output_type="pil", generator=g(0),
                    prior_mask_generator=g(1), prior_noise_generator=g(2))                        # pipe:790-799

@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define I2V_ABI_VERSION 13
+#define I2V_ABI_VERSION 14
 
 #define I2V_OK 0
 #define I2V_ERR_INVALID_ARG (-1)
@@ -516,6 +516,20 @@ int i2v_ddim_cfg_step(float* latents, const void* noise_pred, int32_t np_is_f32,
 int i2v_dpm_cfg_step(float* latents, float* x0_prev, const void* noise_pred, int32_t np_is_f32, int64_t ld_np, const float* coef,
                      int32_t n_steps, int32_t* step_index, float guidance_scale, int32_t b, int32_t f, int32_t c, int32_t hw,
                      int32_t cfg_copies, i2v_stream_t stream);
+
+/* (ABI 14) The latent-consistency (LCM) form of the step half, for LCMScheduler (diffusers 0.24 LCMScheduler.step, epsilon prediction):
+ * the same CFG combine and the same layouts as i2v_dpm_cfg_step, then
+ *   x0 = (x - sb_t eps) / sa_t;  den = c_out x0 + c_skip x;  x' = sa_p den + sb_p z,  z = noise[min(step, n_noise - 1)]
+ * and *step_index advances / wraps as in the DDIM step.
+ * coef fp32 [n_steps][6] = {sa_t, sb_t, c_skip, c_out, sa_p, sb_p}: sa = sqrt(a), sb = sqrt(1 - a) at this step's timestep (t) and at the
+ * next one (p); c_skip = 0.25 / (s^2 + 0.25), c_out = s / sqrt(s^2 + 0.25) with s = t * timestep_scaling.  The last row of a schedule
+ * has sa_p = 1, sb_p = 0 (the step returns `den`).
+ * noise fp32 [n_noise][b, f, c, hw]: the Gaussian draw each step but the last re-noises with, one row per step, read on the device by
+ * the step counter (a replayed hipGraph has no per-step host draw).  A row with sb_p == 0 does not read it; noise may be NULL only
+ * when n_steps == 1.  16-byte accesses when hw % 4 == 0 and latents and noise are 16-byte aligned, scalar ones otherwise. */
+int i2v_lcm_cfg_step(float* latents, const float* noise, int32_t n_noise, const void* noise_pred, int32_t np_is_f32, int64_t ld_np,
+                     const float* coef, int32_t n_steps, int32_t* step_index, float guidance_scale, int32_t b, int32_t f, int32_t c,
+                     int32_t hw, int32_t cfg_copies, i2v_stream_t stream);
 
 /* (ABI 11) FreeU (pipe:155-181 enable_freeu; unet:453-478, 1213-1227: diffusers 0.24 apply_freeu / fourier_filter with threshold 1) on the
  * two operands of an up block's skip concatenation, before `cat([hidden, skip], 1)` (unet:478); one launch, new tensors out (neither

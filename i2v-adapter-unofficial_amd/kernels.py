@@ -1169,6 +1169,42 @@ def freeu(hidden, skip, b, s):
     return h_out, s_out
 
 
+_freeinit_ws = {}
+
+
+def freeinit_mix(latents, init_noise, z_rand, lpf, sqrt_alpha, sqrt_one_minus_alpha):
+    """FreeInit's re-initialisation (i2v_freeinit_mix; diffusers FreeInitMixin._apply_free_init): latents / init_noise / z_rand fp32
+    contiguous [B, F, C, H, W], lpf fp32 contiguous [F, H, W] (the centred low-pass table, `free_init.free_init_filter`) -> a new
+    tensor: the low frequencies over (F, H, W) of sqrt_alpha * latents + sqrt_one_minus_alpha * init_noise and the high ones of
+    z_rand.  F <= 32, H, W <= 128, any length.  The complex workspace (8 bytes per value) is kept per (device, shape): the launches
+    are stream-ordered, so consecutive calls share it."""
+    lib = _lib.load()
+    for t, name in ((latents, "latents"), (init_noise, "init_noise"), (z_rand, "z_rand"), (lpf, "lpf")):
+        _req(t, name, dtype=torch.float32)
+        if not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous")
+    if latents.dim() != 5 or init_noise.shape != latents.shape or z_rand.shape != latents.shape:
+        raise ValueError(f"latents {tuple(latents.shape)} / init_noise {tuple(init_noise.shape)} / z_rand {tuple(z_rand.shape)} must be "
+                         "one shape [B, F, C, H, W]")
+    b, f, c, h, w = latents.shape
+    if tuple(lpf.shape) != (f, h, w):
+        raise ValueError(f"lpf must be {(f, h, w)}, got {tuple(lpf.shape)}")
+    if len({t.device for t in (latents, init_noise, z_rand, lpf)}) != 1:
+        raise ValueError("latents, init_noise, z_rand and lpf must be on one device")
+    need = lib.i2v_freeinit_workspace_bytes(b, f, c, h, w)
+    if need < 0:
+        _lib.check(int(need), "i2v_freeinit_workspace_bytes")
+    key = (str(latents.device), b, f, c, h, w)
+    ws = _freeinit_ws.get(key)
+    if ws is None or ws.numel() < need:
+        _freeinit_ws.clear()                  # one shape at a time, like the pipeline's captured step
+        ws = _freeinit_ws[key] = torch.empty(need, dtype=torch.uint8, device=latents.device)
+    out = torch.empty_like(latents)
+    _lib.check(lib.i2v_freeinit_mix(_p(latents), _p(init_noise), _p(z_rand), _p(lpf), _p(out), _p(ws), ws.numel(), b, f, c, h, w,
+                                    float(sqrt_alpha), float(sqrt_one_minus_alpha), _stream()), "i2v_freeinit_mix")
+    return out
+
+
 def vae_tile_blend(tile, out, oy, ox, blend_extent, limit, up=None, left=None, upleft=None, c=None):
     """One tile of the tiled VAE into the stitched image (i2v_vae_tile_blend; diffusers tiled_decode / tiled_encode): tile
     [N, th, tw, ld] token-major, fp32 (the decoder's conv_out) or fp16 (quant_conv), is blended over its first `blend_extent` rows

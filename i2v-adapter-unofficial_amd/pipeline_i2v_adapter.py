@@ -92,6 +92,7 @@ class I2VAdapterPipeline:
         self._vae_slicing = False
         self._graph = None
         self._graph_cache = {}
+        self._free_init = None
 
     def enable_vae_slicing(self):
         """pipe:122-128: decode the frames one at a time (peak activation memory / num_frames)."""
@@ -127,6 +128,30 @@ class I2VAdapterPipeline:
     def disable_freeu(self):
         """pipe:179-181."""
         self.unet.disable_freeu()
+
+    def enable_free_init(self, num_iters: int = 3, use_fast_sampling: bool = False, method: str = "butterworth", order: int = 4,
+                         spatial_stop_frequency: float = 0.25, temporal_stop_frequency: float = 0.25):
+        """diffusers FreeInitMixin.enable_free_init (FreeInit, https://arxiv.org/abs/2312.07537): every call samples the clip `num_iters`
+        times.  Between two rounds the clip as the call would return it is diffused back to the first step's noise level with the
+        round-0 noise, and one launch group of `i2v_freeinit_mix` keeps its low frequencies over (frames, height, width) -- a
+        "butterworth" (with `order`), "gaussian" or "ideal" low-pass at the two stop frequencies -- and takes the high ones from a fresh
+        draw of `generator`.  The rounds replay the ONE captured step a plain call uses (enabling this neither enters the graph key nor
+        captures); the mix runs as eager launches between the replays.  `use_fast_sampling` gives round i only
+        max(1, int(num_inference_steps / num_iters * (i + 1))) steps: the step tables then change shape from round to round, so every
+        round re-captures the step (accepted: the cache holds one shape at a time).  num_iters=1 is a plain call, bit for bit."""
+        from .free_init import check_free_init_args
+        check_free_init_args(num_iters, method, order, spatial_stop_frequency, temporal_stop_frequency)
+        self._free_init = dict(num_iters=int(num_iters), use_fast_sampling=bool(use_fast_sampling), method=method, order=int(order),
+                               spatial_stop_frequency=float(spatial_stop_frequency),
+                               temporal_stop_frequency=float(temporal_stop_frequency))
+
+    def disable_free_init(self):
+        """diffusers FreeInitMixin.disable_free_init: one sampling round per call again"""
+        self._free_init = None
+
+    @property
+    def free_init_enabled(self):
+        return self._free_init is not None
 
     def decode_latents(self, latents):
         """pipe:300-320: latents (B, F, 4, h, w) -> video (B, F, 3, 8h, 8w) float32 through the HIP VAE decoder."""
@@ -421,8 +446,17 @@ class I2VAdapterPipeline:
 
         kind = self._scheduler_kind()
         dpm, lcm = kind == "dpmsolver++", kind == "lcm"
-        self.scheduler.set_timesteps(num_inference_steps)                                       # pipe:630-631
-        timesteps, _ = self.get_timesteps(num_inference_steps, frame_similarity_sample_ratio)
+        # FreeInit (enable_free_init): `rounds` sampling passes; with fast sampling round i has its own, shorter schedule
+        fi = self._free_init
+        rounds = fi["num_iters"] if fi is not None else 1
+        fast = fi is not None and fi["use_fast_sampling"] and rounds > 1
+        if fast:
+            from .free_init import round_inference_steps
+            round_steps = [round_inference_steps(num_inference_steps, rounds, i) for i in range(rounds)]
+        else:
+            round_steps = [num_inference_steps] * rounds
+        self.scheduler.set_timesteps(round_steps[0])                                            # pipe:630-631
+        timesteps, _ = self.get_timesteps(round_steps[0], frame_similarity_sample_ratio)
 
         cond_dev = condition_image_latents.detach().to(dev, torch.float32).contiguous()
         latents = self.prepare_latents(batch_size, self.unet.config.in_channels, num_frames, height, width,
@@ -460,6 +494,52 @@ class I2VAdapterPipeline:
         # (DPM-Solver++ has no stochastic form here: the reference passes `eta` only to a scheduler whose step takes it,
         # pipe:184-199, so it is ignored and the steps stay captured; LCM's step takes no eta either, and its noise is in the table)
         fixed = dpm or lcm
+        for rnd in range(rounds):
+            if rnd > 0:
+                timesteps = self._free_init_round(st, rnd, round_steps, fast, noise, generator, frame_similarity_sample_ratio, eta, lcm)
+            self._sample_round(st, timesteps, use_graph, callback, callback_steps, eta, fixed, generator)
+            latents = st["latents"]
+            latents[:, 0] = st["cond"]                                                          # pipe:699-700
+        if output_type == "latent":                                                             # pipe:702-703
+            video = latents
+        else:
+            video_tensor = self.decode_latents(latents)                                         # pipe:706
+            video = video_tensor if output_type == "pt" else tensor2vid(video_tensor, self.image_processor,
+                                                                        output_type=output_type)  # pipe:708-711
+        if not return_dict:
+            return (video,)
+        return I2VAdapterPipelineOutput(frames=video)
+
+    def _free_init_round(self, st, rnd, round_steps, fast, init_noise, generator, ratio, eta, lcm):
+        """FreeInit between round rnd - 1 and round rnd >= 1 (diffusers `_apply_free_init`), in the order of the draws: the fresh noise
+        z_rand from the call's `generator` (after everything the previous round drew), this round's schedule under fast sampling, the
+        mix -- st["latents"], the clip as the call would return it, re-noised with the round-0 noise to the level of this round's first
+        timestep (the level the prior noises to, pipe:656, and the one the round's first step expects) and low-passed against z_rand
+        --, then an LCM round's noise table.  The state goes through `_run_steps`' copy-in path like a new sample's: same graph key
+        without fast sampling, so the rounds replay one captured step.  (DPM-Solver++: x0_prev needs no reset, a round's first step is
+        first order.)  Returns the round's timesteps."""
+        from .free_init import free_init_filter
+        fi, prev, dev = self._free_init, st["latents"], st["latents"].device
+        z_rand = _draw(torch.randn, tuple(prev.shape), generator, dev).to(torch.float32).contiguous()
+        if fast:
+            self.scheduler.set_timesteps(round_steps[rnd])
+            timesteps, _ = self.get_timesteps(round_steps[rnd], ratio)
+            st["t_table"] = timesteps.to(torch.float32).to(dev)
+            st["coef"] = self.scheduler.step_coefficients(timesteps, eta).to(dev)
+        else:
+            timesteps, _ = self.get_timesteps(round_steps[rnd], ratio)
+        b, f, c, h, w = prev.shape
+        lpf = free_init_filter((f, h, w), fi["method"], fi["order"], fi["spatial_stop_frequency"], fi["temporal_stop_frequency"], device=dev)
+        a_t = float(self.scheduler.alphas_cumprod[int(timesteps[0])])
+        st["latents"] = K.freeinit_mix(prev.contiguous(), init_noise.contiguous(), z_rand, lpf, a_t ** 0.5, (1.0 - a_t) ** 0.5)
+        if lcm:
+            st["noise"] = self.scheduler.step_noise(timesteps, tuple(prev.shape), generator, dev)
+        st["step_idx"] = torch.zeros(1, dtype=torch.int32, device=dev)
+        return timesteps
+
+    def _sample_round(self, st, timesteps, use_graph, callback, callback_steps, eta, fixed, generator):
+        """one sampling pass over `timesteps` (pipe:663-697): st["latents"] in, st["latents"] out"""
+        dev = st["latents"].device
         if callback is None and (eta == 0.0 or fixed):
             st["latents"] = self._run_steps(st, len(timesteps), use_graph)
         else:
@@ -469,7 +549,7 @@ class I2VAdapterPipeline:
             if eta != 0.0 and use_graph and not fixed:
                 import warnings
                 warnings.warn("eta > 0: the stochastic DDIM update draws fresh noise on the host every step, so the steps run as "
-                              "eager launches instead of the captured hipGraph (about 2x the step time)", RuntimeWarning, stacklevel=2)
+                              "eager launches instead of the captured hipGraph (about 2x the step time)", RuntimeWarning, stacklevel=3)
             sigmas = None if fixed else self.scheduler.step_sigmas(timesteps, eta)
             st["ctx_proj"] = self.unet.project_context(st["ctx_text"], st["ctx_ip"])
             st["temb_table"] = self.unet.project_time_table(st["t_table"])
@@ -480,17 +560,6 @@ class I2VAdapterPipeline:
                     K.axpby(st["latents"], z, 1.0, sigmas[i])
                 if callback is not None and i % callback_steps == 0:
                     callback(i, t, st["latents"])
-        latents = st["latents"]
-        latents[:, 0] = st["cond"]                                                              # pipe:699-700
-        if output_type == "latent":                                                             # pipe:702-703
-            video = latents
-        else:
-            video_tensor = self.decode_latents(latents)                                         # pipe:706
-            video = video_tensor if output_type == "pt" else tensor2vid(video_tensor, self.image_processor,
-                                                                        output_type=output_type)  # pipe:708-711
-        if not return_dict:
-            return (video,)
-        return I2VAdapterPipelineOutput(frames=video)
 
 
 SCHEDULERS = ("ddim", "dpmsolver++")
@@ -547,6 +616,13 @@ def build_parser():
     parser.add_argument("--vae_tiling", action="store_true",
                         help="tile the VAE decode / condition-image encode above 512 px a side (pipe.enable_vae_tiling(); off by "
                              "default, as in the reference driver)")
+    parser.add_argument("--free_init", type=int, nargs="?", const=3, default=None, metavar="N",
+                        help="FreeInit (pipe.enable_free_init): sample every clip N times (3 when given without a value), re-initialising "
+                             "the noise's low frequencies from the previous round; off by default")
+    parser.add_argument("--free_init_method", choices=("butterworth", "gaussian", "ideal"), default="butterworth",
+                        help="FreeInit's low-pass filter")
+    parser.add_argument("--free_init_fast", action="store_true",
+                        help="FreeInit's use_fast_sampling: earlier rounds take fewer steps (every round re-captures the step)")
     return parser
 
 
@@ -616,6 +692,8 @@ def main(argv=None):
         pipe.enable_freeu(*args.freeu)
     if args.vae_tiling:
         pipe.enable_vae_tiling()
+    if args.free_init is not None:
+        pipe.enable_free_init(num_iters=args.free_init, use_fast_sampling=args.free_init_fast, method=args.free_init_method)
     if args.lora:
         names, weights = [], []
         for i, spec in enumerate(args.lora):

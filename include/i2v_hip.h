@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define I2V_ABI_VERSION 14
+#define I2V_ABI_VERSION 15
 
 #define I2V_OK 0
 #define I2V_ERR_INVALID_ARG (-1)
@@ -593,6 +593,27 @@ typedef struct i2v_lora_adapter {
 } i2v_lora_adapter;
 int i2v_lora_merge(void* dst, const void* base, int32_t is_f32, int32_t out, int32_t in, const i2v_lora_adapter* adapters,
                    int32_t n_adapters, i2v_stream_t stream);
+
+/* (ABI 15) FreeInit (https://arxiv.org/abs/2312.07537; diffusers 0.24 FreeInitMixin, `enable_free_init`): the re-initialisation between two
+ * sampling rounds of one clip.  All tensors fp32, dense, in the pipeline's latent layout [b, f, c, h, w]; per (b, c) volume over (f, h, w):
+ *   z_t = sqrt_alpha * latents + sqrt_one_minus_alpha * init_noise                          (scheduler.add_noise, fused into the load)
+ *   out = Re ifftn( ifftshift( fftshift(fftn(z_t)) * lpf + fftshift(fftn(z_rand)) * (1 - lpf) ) )
+ *       = z_rand + Re ifftn( ifftshift(lpf) * fftn(z_t - z_rand) )                          (what is computed: one transform pair)
+ * latents: the previous round's clean result; init_noise: the noise the first round started from; z_rand: a fresh draw; lpf fp32
+ * [f, h, w]: the low-pass table in diffusers' CENTRED layout -- index (t, y, x) multiplies frequency (t - f/2, y - h/2, x - w/2), i.e. the
+ * fftshift-ed spectrum.  The table is read as given (built on the host: an "ideal" filter's `<=` must not be re-evaluated in fp32).  At
+ * odd sizes the centred table is not symmetric about the zero frequency, so the inverse is a full complex one and its real part is taken
+ * last; nothing assumes a Hermitian spectrum.  An all-zero table returns z_rand bit for bit.
+ * Every axis is a direct DFT in fp32 FMAs (any length, no radix plan, no FFT library) with per-workgroup twiddle tables indexed by the
+ * integer (k n) mod N; five launches: rows forward (z_t - z_rand formed on load), columns forward, frames forward x lpf x frames
+ * inverse, columns inverse, rows inverse (+ z_rand).  The complex volume lives in `workspace` (caller-owned, 8-byte aligned, at least
+ * i2v_freeinit_workspace_bytes(b, f, c, h, w) = 8 b f c h w bytes, every byte of it written before it is read).
+ * I2V_ERR_INVALID_ARG: null pointers, f outside 1..32, h or w outside 1..128, b or c < 1, more than 2^30 values, a workspace that is too
+ * small or overlaps an operand, `out` overlapping an input (i2v_freeinit_workspace_bytes returns the same code for bad sizes). */
+int64_t i2v_freeinit_workspace_bytes(int32_t b, int32_t f, int32_t c, int32_t h, int32_t w);
+int i2v_freeinit_mix(const float* latents, const float* init_noise, const float* z_rand, const float* lpf, float* out, void* workspace,
+                     int64_t workspace_bytes, int32_t b, int32_t f, int32_t c, int32_t h, int32_t w, float sqrt_alpha,
+                     float sqrt_one_minus_alpha, i2v_stream_t stream);
 
 /* First-frame-similarity prior and the initial add_noise of the sampling loop, pipe:647-656:
  *   prior   = mask * GaussianBlur3x3(cond) + (1 - mask) * cond, mask = (mask_uniform < strength), per frame (pipe:648-654)

@@ -765,6 +765,7 @@ class TemporalTransformerBlock(HipModule):
         self.norm3 = nn.LayerNorm(dim, elementwise_affine=norm_elementwise_affine, eps=norm_eps)
         self.ff = FeedForward(dim, dropout=dropout, activation_fn=activation_fn)
         self._plan = LnFoldPlan()
+        self.free_noise = None        # FreeNoiseSettings while FreeNoise is enabled (TransformerTemporalModel.set_free_noise)
 
     def _pack(self):
         p = LazyPack(pe=w16(self.pos_embed.pe[0]))
@@ -794,8 +795,9 @@ class TemporalTransformerBlock(HipModule):
         p.lazy("b3_f32", lambda n3=self.norm3: n3.bias.detach().float().contiguous())
         return p
 
-    def _fold_ok(self, t, frames):
-        """(attention sites, feed-forward site): is the LayerNorm fold implemented for this problem's GEMMs?"""
+    def _fold_ok(self, t, frames, sites=("attn", "ff")):
+        """(attention sites, feed-forward site): is the LayerNorm fold implemented for this problem's GEMMs?  (a site not in `sites`
+        is not asked and answers False)"""
         def probe_attn():
             p = self.packed()
             if frames & (frames - 1):
@@ -810,17 +812,38 @@ class TemporalTransformerBlock(HipModule):
             return p["f_ff"] is not None and self.ff.folded_supported(t, self.eps, p["f_ff"])
 
         key = (t.shape[0], frames)
-        return self._plan.get(("attn",) + key, probe_attn), self._plan.get(("ff",) + key, probe_ff)
+        return (self._plan.get(("attn",) + key, probe_attn) if "attn" in sites else False,
+                self._plan.get(("ff",) + key, probe_ff) if "ff" in sites else False)
 
     def _fwd(self, t, n_pixels, frames, tail=None):
         """t [n_pixels * frames, C] in (b, pixel, frame) order.  With `tail` (FeedForward.tail_supported) returns
         (result, applied): applied = the module's proj_out (+ residual, rows back in (b, frame, pixel) order) ran inside the
         fused feed-forward launch and `result` is the module's output; otherwise the caller's proj_out GEMM does it."""
+        fn = self.free_noise
+        if fn is not None and frames > fn.context_length:
+            return self._fwd_windows(t, n_pixels, frames, fn, tail)
         if frames > self.max_len:
             raise ValueError(f"num_frames {frames} exceeds the positional table ({self.max_len})")
+        fold_attn, fold_ff = self._fold_ok(t, frames)
+        return self._fwd_ff(self._fwd_attn(t, n_pixels, frames, fold_attn), fold_ff, tail)
+
+    def _fwd_windows(self, t, n_pixels, frames, fn, tail):
+        """FreeNoise (`free_noise.py`; diffusers FreeNoiseTransformerBlock): the two attention sub-blocks on the sliding windows of
+        `fn.context_length` frames -- every window a clip of its own, n_pixels * windows "pixels", positions restarting in each --
+        then the weighted mean of the windows per frame, then the feed-forward once on all frames."""
+        from . import free_noise
+        length = fn.context_length
+        starts, idx, coef = free_noise.tables(frames, fn, t.device)
+        windows = starts.numel()
+        tw = K.freenoise_gather(t, starts, n_pixels=n_pixels, frames=frames, length=length)
+        tw = self._fwd_attn(tw, n_pixels * windows, length, self._fold_ok(tw, length, sites=("attn",))[0])
+        t = K.freenoise_blend(tw, idx, coef, n_pixels=n_pixels, windows=windows, length=length)
+        return self._fwd_ff(t, self._fold_ok(t, frames, sites=("ff",))[1], tail)
+
+    def _fwd_attn(self, t, n_pixels, frames, fold_attn):
+        """the two self-attention sub-blocks over `frames` consecutive rows per pixel (frames <= the positional table)"""
         p = self.packed()
         c = self.dim
-        fold_attn, fold_ff = self._fold_ok(t, frames)
         overlap = t.shape[0] <= streams.MAX_ROWS       # q|k beside V^T on two streams where neither fills the chip
         fused = FUSED_MOTION_ATTN and K.motion_attn_supported(t.shape[0], c, self.heads, self.dim_head, frames)
         for i in (1, 2):
@@ -852,6 +875,12 @@ class TemporalTransformerBlock(HipModule):
             o = K.temporal_attention(qk[:, :c], qk[:, c:], vt, n_pixels=n_pixels, frames=frames, heads=self.heads,
                                      head_dim=self.dim_head, scale=self.dim_head ** -0.5)
             t = K.gemm(o, p[f"wo{i}"], p[f"bo{i}"], residual=t)
+        return t
+
+    def _fwd_ff(self, t, fold_ff, tail):
+        """t + FF(LayerNorm3(t)) on all rows (any number of frames; the tail's row permutation needs a power of two)"""
+        p = self.packed()
+
         def ret(v, applied=False):
             return v if tail is None else (v, applied)
         if self.ff.fused_supported(t):
@@ -898,6 +927,18 @@ class TransformerTemporalModel(HipModule):
         # proj_out as the tail of the last block's fused feed-forward (the SD-1.5 64^2 width: a square 320 x 320 Linear)
         p.lazy("tail", lambda po=self.proj_out, ci=self.inner_dim, co=self.in_channels: ff_tail_operands(po.weight, po.bias, ci, co))
         return p
+
+    def set_free_noise(self, settings):
+        """FreeNoise on (a `free_noise.FreeNoiseSettings` whose context_length fits the positional table) or off (None) for every
+        transformer block of the module: clips longer than context_length then run the temporal attention on sliding windows.
+        Internal: `UNetMotionCrossFrameAttnModel.enable_free_noise` is the switch -- set here directly, the UNet's signature (and so
+        the pipeline's captured-step key) does not know about it."""
+        for blk in self.transformer_blocks:
+            if settings is not None and settings.context_length > blk.max_len:
+                raise ValueError(f"`context_length` {settings.context_length} exceeds the motion module's num_positional_embeddings "
+                                 f"({blk.max_len})")
+        for blk in self.transformer_blocks:
+            blk.free_noise = settings
 
     def _fwd(self, x, num_frames):
         p = self.packed()

@@ -36,7 +36,8 @@ enum { RELOC_ARENA = 0, RELOC_WEIGHT = 1, RELOC_IO = 2 };
 enum Entry {
   E_GEMM = 0, E_ATTN, E_TATTN, E_MOTION_ATTN, E_CROSS_ATTN_FUSED, E_LN_QKV, E_FF_FUSED, E_GROUPNORM, E_LAYERNORM,      // struct + stream
   E_GROUPNORM_FOLD, E_NCHW_TO_TOKENS, E_TOKENS_TO_NCHW, E_TIMESTEP_EMBEDDING, E_SILU, E_REPEAT_ROWS, E_COPY3D, E_SELECT_ROW,
-  E_PACK_CTX_FRAGMENTS, E_DDIM_PREP, E_DDIM_CFG_STEP, E_DPM_CFG_STEP, E_FREEU, E_LCM_CFG_STEP, E_COUNT
+  E_PACK_CTX_FRAGMENTS, E_DDIM_PREP, E_DDIM_CFG_STEP, E_DPM_CFG_STEP, E_FREEU, E_LCM_CFG_STEP, E_FREENOISE_GATHER,
+  E_FREENOISE_BLEND, E_COUNT
 };
 struct EntryInfo {
   const char* name;
@@ -67,6 +68,8 @@ const EntryInfo ENTRIES[E_COUNT] = {
     {"i2v_dpm_cfg_step", 0, 14},
     {"i2v_freeu_f16", 0, 13},
     {"i2v_lcm_cfg_step", 0, 15},
+    {"i2v_freenoise_gather_f16", 0, 10},
+    {"i2v_freenoise_blend_f16", 0, 12},
 };
 inline uint32_t pad8(uint32_t n) { return (n + 7u) & ~7u; }
 
@@ -413,6 +416,14 @@ extern "C" int i2v_unet_run(i2v_unet* h, const void* const* io_args, int32_t n_i
         rc = i2v_lcm_cfg_step(reinterpret_cast<float*>(P(0)), reinterpret_cast<const float*>(P(1)), (int32_t)I(2), P(3), (int32_t)I(4), I(5),
                               reinterpret_cast<const float*>(P(6)), (int32_t)I(7), reinterpret_cast<int32_t*>(P(8)), F(9), (int32_t)I(10),
                               (int32_t)I(11), (int32_t)I(12), (int32_t)I(13), (int32_t)I(14), stream);
+        break;
+      case E_FREENOISE_GATHER:
+        rc = i2v_freenoise_gather_f16(P(0), I(1), P(2), I(3), reinterpret_cast<const int32_t*>(P(4)), I(5), (int32_t)I(6), (int32_t)I(7),
+                                      (int32_t)I(8), (int32_t)I(9), stream);
+        break;
+      case E_FREENOISE_BLEND:
+        rc = i2v_freenoise_blend_f16(P(0), I(1), P(2), I(3), reinterpret_cast<const int32_t*>(P(4)), reinterpret_cast<const float*>(P(5)), I(6),
+                                     (int32_t)I(7), (int32_t)I(8), (int32_t)I(9), (int32_t)I(10), (int32_t)I(11), stream);
         break;
       default: I2V_FAIL(I2V_ERR_UNSUPPORTED, "i2v_unet_forward: launch %u names entry point %u", i, op.entry);
     }

@@ -8,6 +8,10 @@ METHODS = ("butterworth", "gaussian", "ideal")
 _tables = {}
 
 
+# the largest clip `i2v_freeinit_mix` takes: frames, latent height and width (csrc/freeinit.hip FI_MAX_F / FI_MAX_HW)
+MAX_FRAMES, MAX_HW = 32, 128
+
+
 def free_init_filter(shape, method="butterworth", order=4, spatial_stop_frequency=0.25, temporal_stop_frequency=0.25, device=None):
     """diffusers `_get_free_init_freq_filter` for the (F, H, W) axes: fp32 [F, H, W] in the CENTRED layout (index (t, h, w) is frequency
     (t - F // 2, h - H // 2, w - W // 2), what multiplies the fftshift-ed spectrum), vectorised.  With d_s / d_t the spatial / temporal

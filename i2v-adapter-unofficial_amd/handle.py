@@ -35,7 +35,8 @@ ENTRY_IDS = {name: i for i, name in enumerate((
 # Entry points added since continue the numbering of `enum Entry` here; `entry_id` / `entry_name` cover both.
 LATER_ENTRY_IDS = {name: len(ENTRY_IDS) + i for i, name in enumerate((
     "i2v_freeu_f16",                                                # ABI 11
-    "i2v_lcm_cfg_step"))}                                           # ABI 14
+    "i2v_lcm_cfg_step",                                             # ABI 14
+    "i2v_freenoise_gather_f16", "i2v_freenoise_blend_f16"))}       # ABI 16
 # ENTRY_NAMES is the id -> name table as it stood at ABI 11 and stays that table (tests/test_freeu.py pins its 22 ids); `entry_name`
 # covers every id.
 ENTRY_NAMES = {i: n for n, i in {**ENTRY_IDS, "i2v_freeu_f16": LATER_ENTRY_IDS["i2v_freeu_f16"]}.items()}
@@ -137,6 +138,9 @@ def persistent_tensors(unet):
                 add(f"{mname}#{k}", v)
         for (site, frames), tab in getattr(m, "_ma_tables", {}).items():
             add(f"{mname}#ma_table{site}_{frames}", tab)
+    from .free_noise import persistent_tables
+    for k, v in persistent_tables(next(unet.parameters()).device).items():     # FreeNoise's window / coefficient tables (cached)
+        add(k, v)
     tp = getattr(unet, "_temb_packed", None)
     if tp is not None:
         add("#temb_proj", tp[:2])

@@ -1172,6 +1172,47 @@ def freeu(hidden, skip, b, s):
 _freeinit_ws = {}
 
 
+def _freenoise_rows(t, name, rows):
+    t, ld = _mat(t, name)
+    if t.shape[0] != rows or t.shape[1] % 8 != 0:
+        raise ValueError(f"{name} is {tuple(t.shape)}, expected [{rows}, C] with C a multiple of 8")
+    return t, ld
+
+
+def freenoise_gather(t, starts, *, n_pixels, frames, length):
+    """FreeNoise's window expansion (i2v_freenoise_gather_f16): t [n_pixels * frames, C] fp16 rows in (b, pixel, frame) order (any row
+    stride) -> [n_pixels * windows * length, C], row (p, w, j) = row (p, starts[w] + j) bit for bit.  starts: device int32 [windows]
+    (`free_noise.tables`)."""
+    lib = _lib.load()
+    t, ld = _freenoise_rows(t, "t", n_pixels * frames)
+    _req(starts, "starts", dtype=torch.int32)
+    if starts.dim() != 1 or not starts.is_contiguous() or starts.numel() < 1:
+        raise ValueError("starts must be a contiguous int32 vector")
+    windows, c = starts.numel(), t.shape[1]
+    out = torch.empty((n_pixels * windows * length, c), dtype=f16, device=t.device)
+    _lib.check(lib.i2v_freenoise_gather_f16(_p(t), ld, _p(out), c, _p(starts), n_pixels, frames, windows, length, c, _stream()),
+               "i2v_freenoise_gather_f16")
+    return out
+
+
+def freenoise_blend(tw, idx, coef, *, n_pixels, windows, length):
+    """FreeNoise's weighted mean of the windows (i2v_freenoise_blend_f16): tw [n_pixels * windows * length, C] fp16 ->
+    [n_pixels * frames, C], row (p, f) = sum_k coef[f, k] * row (p, idx[f, k]) in fp32, rounded once.  idx int32 / coef fp32 device
+    tables [frames, pairs] (`free_noise.tables`); pairs with coefficient 0 behind the first are padding."""
+    lib = _lib.load()
+    tw, ld = _freenoise_rows(tw, "tw", n_pixels * windows * length)
+    _req(idx, "idx", dtype=torch.int32)
+    _req(coef, "coef", dtype=torch.float32)
+    if idx.dim() != 2 or idx.shape != coef.shape or not idx.is_contiguous() or not coef.is_contiguous():
+        raise ValueError("idx / coef must be contiguous [frames, pairs] tables of one shape")
+    frames, pairs = idx.shape
+    c = tw.shape[1]
+    out = torch.empty((n_pixels * frames, c), dtype=f16, device=tw.device)
+    _lib.check(lib.i2v_freenoise_blend_f16(_p(tw), ld, _p(out), c, _p(idx), _p(coef), n_pixels, frames, windows, length, pairs, c,
+                                           _stream()), "i2v_freenoise_blend_f16")
+    return out
+
+
 def freeinit_mix(latents, init_noise, z_rand, lpf, sqrt_alpha, sqrt_one_minus_alpha):
     """FreeInit's re-initialisation (i2v_freeinit_mix; diffusers FreeInitMixin._apply_free_init): latents / init_noise / z_rand fp32
     contiguous [B, F, C, H, W], lpf fp32 contiguous [F, H, W] (the centred low-pass table, `free_init.free_init_filter`) -> a new

@@ -153,6 +153,35 @@ class I2VAdapterPipeline:
     def free_init_enabled(self):
         return self._free_init is not None
 
+    def enable_free_noise(self, context_length: int = 16, context_stride: int = 4, weighting_scheme: str = "pyramid",
+                          noise_type: str = "shuffle_context"):
+        """diffusers AnimateDiffFreeNoiseMixin.enable_free_noise (FreeNoise, https://arxiv.org/abs/2310.15169): clips longer than the
+        motion modules' positional table (`num_frames` 32, 64, 128 from a 16-frame motion adapter).  The motion modules attend inside
+        sliding windows of `context_length` frames, `context_stride` apart, and average the windows per frame (`weighting_scheme`:
+        "flat", "pyramid", "delayed_reverse_sawtooth"); the initial noise of the frames behind the first window is a reshuffle of
+        the first window's (`noise_type`: "shuffle_context", "repeat_context", "random").  The step stays one captured hipGraph,
+        re-captured once when the settings change."""
+        if getattr(self, "unet", None) is None:
+            raise ValueError("The pipeline must have `unet` for using FreeNoise.")
+        self.unet.enable_free_noise(context_length=context_length, context_stride=context_stride, weighting_scheme=weighting_scheme,
+                                    noise_type=noise_type)
+
+    def disable_free_noise(self):
+        """diffusers disable_free_noise"""
+        self.unet.disable_free_noise()
+
+    def _free_noise_settings(self):
+        """the UNet's `free_noise.FreeNoiseSettings`, or None while FreeNoise is off"""
+        sig = self.unet.free_noise_signature()
+        if sig is None:
+            return None
+        from .free_noise import FreeNoiseSettings
+        return FreeNoiseSettings(*sig)
+
+    @property
+    def free_noise_enabled(self):
+        return self.unet.free_noise_signature() is not None
+
     def decode_latents(self, latents):
         """pipe:300-320: latents (B, F, 4, h, w) -> video (B, F, 3, 8h, 8w) float32 through the HIP VAE decoder."""
         if self.vae is None:
@@ -293,7 +322,8 @@ class I2VAdapterPipeline:
         kernel-layout copies are rebuilt when a parameter changes, and a graph captured before that reads the old ones) and the
         scheduler's update (a scheduler swapped between calls re-captures) and FreeU's four scales (launch arguments: enabling,
         changing or disabling FreeU re-captures) and the LCM noise table's shape (its row count is a launch argument: another step
-        count re-captures)"""
+        count re-captures) and FreeNoise's window settings (they decide the launches of every motion module: enabling, changing or
+        disabling FreeNoise re-captures; its noise_type only shapes the initial noise and does not)"""
         unet = self.unet
         wsig = hash(tuple((p.data_ptr(), p._version) for p in unet.parameters()))
         ips = tuple((a.ip_num_tokens, float(a.ip_scale)) for a in unet._cross_attention_layers())
@@ -301,7 +331,7 @@ class I2VAdapterPipeline:
         from .blocks import precise_stream      # (a captured step keeps the residual-stream mode it was captured in)
         return (tuple(st["latents"].shape), st["copies"], st["num_frames"], st["guidance"], shp(st["t_table"]),
                 shp(st["ctx_text"]), shp(st["ctx_ip"]), str(st["latents"].device), wsig, ips, precise_stream(),
-                self._scheduler_kind(), shp(st["coef"]), unet.freeu_signature(), shp(st.get("noise")))
+                self._scheduler_kind(), shp(st["coef"]), unet.freeu_signature(), shp(st.get("noise")), unet.free_noise_launch_signature())
 
     def _run_steps(self, st, n_steps, use_graph):
         if not use_graph:
@@ -398,6 +428,15 @@ class I2VAdapterPipeline:
                 return self.__call__(**kw)
             finally:
                 self.unet.set_lora_scale(prev)
+        # FreeNoise (enable_free_noise): the settings against this call's num_frames, before anything is launched or encoded
+        fnz = self._free_noise_settings()
+        if fnz is not None:
+            from .free_init import MAX_FRAMES, MAX_HW
+            from .free_noise import check_num_frames
+            check_num_frames(num_frames, fnz)
+            if self._free_init is not None and num_frames > MAX_FRAMES:
+                raise ValueError(f"FreeNoise with FreeInit: num_frames {num_frames} exceeds FreeInit's {MAX_FRAMES} x {MAX_HW} x {MAX_HW} "
+                                 "limit (frames x latent height x width of i2v_freeinit_mix) -- disable_free_init() for longer clips")
         self.unet._sync_lora()      # before anything reads a weight, a pack or the weights' versions (_graph_key)
         if prompt is not None or ip_adapter_image is not None:
             raise NotImplementedError(
@@ -469,7 +508,12 @@ class I2VAdapterPipeline:
                                          else prior_mask_generator)
         shape = (batch_size, num_frames) + tuple(cond_dev.shape[1:])
         mask_u = _draw(torch.rand, shape, prior_mask_generator, dev)                            # pipe:652
-        noise = _draw(torch.randn, shape, prior_noise_generator, dev)                           # pipe:655
+        if fnz is not None and num_frames > fnz.context_length:
+            # FreeNoise: the frames behind the first window re-use its noise (repeated or shuffled: `free_noise.reschedule_noise`)
+            from .free_noise import reschedule_noise
+            noise = reschedule_noise(lambda shp, g: _draw(torch.randn, shp, g, dev), shape, fnz, prior_noise_generator)
+        else:
+            noise = _draw(torch.randn, shape, prior_noise_generator, dev)                       # pipe:655
         a_t = float(self.scheduler.alphas_cumprod[int(timesteps[0])])
         latents = K.first_frame_prior(cond_dev, mask_u.contiguous(), noise.contiguous(), blur_sigma,
                                       frame_similarity_blurred_strength, a_t ** 0.5, (1.0 - a_t) ** 0.5)
@@ -621,6 +665,14 @@ def build_parser():
                              "the noise's low frequencies from the previous round; off by default")
     parser.add_argument("--free_init_method", choices=("butterworth", "gaussian", "ideal"), default="butterworth",
                         help="FreeInit's low-pass filter")
+    parser.add_argument("--free_noise", type=int, nargs="?", const=16, default=None, metavar="L",
+                        help="FreeNoise (pipe.enable_free_noise): clips longer than the motion modules' 32 positions -- temporal attention "
+                             "on sliding windows of L frames (16 when given without a value); off by default")
+    parser.add_argument("--free_noise_stride", type=int, default=4, metavar="S", help="frames between two FreeNoise windows (4)")
+    parser.add_argument("--free_noise_weighting", choices=("flat", "pyramid", "delayed_reverse_sawtooth"), default="pyramid",
+                        help="FreeNoise's weights over the position in a window (diffusers' default: pyramid)")
+    parser.add_argument("--free_noise_noise", choices=("shuffle_context", "repeat_context", "random"), default="shuffle_context",
+                        help="FreeNoise's initial noise behind the first window (diffusers' default: shuffle_context)")
     parser.add_argument("--free_init_fast", action="store_true",
                         help="FreeInit's use_fast_sampling: earlier rounds take fewer steps (every round re-captures the step)")
     return parser
@@ -692,6 +744,9 @@ def main(argv=None):
         pipe.enable_freeu(*args.freeu)
     if args.vae_tiling:
         pipe.enable_vae_tiling()
+    if args.free_noise is not None:
+        pipe.enable_free_noise(context_length=args.free_noise, context_stride=args.free_noise_stride,
+                               weighting_scheme=args.free_noise_weighting, noise_type=args.free_noise_noise)
     if args.free_init is not None:
         pipe.enable_free_init(num_iters=args.free_init, use_fast_sampling=args.free_init_fast, method=args.free_init_method)
     if args.lora:

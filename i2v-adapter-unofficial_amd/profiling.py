@@ -122,7 +122,8 @@ _WRAPPED = {
     "copy3d": _work_misc("elementwise"), "timestep_embedding": _work_misc("elementwise"),
     "ddim_prep": _work_misc("elementwise"), "ddim_cfg_step": _work_misc("elementwise"),
     "nchw_to_tokens": _work_misc("elementwise"), "tokens_to_nchw": _work_misc("elementwise"),
-    "lcm_cfg_step": _work_misc("elementwise"),
+    "lcm_cfg_step": _work_misc("elementwise"), "freenoise_gather": _work_misc("elementwise"),
+    "freenoise_blend": _work_misc("elementwise"),
 }
 
 

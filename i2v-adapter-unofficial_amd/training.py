@@ -538,6 +538,9 @@ class UNetAdapterTrainer:
         if any(fs is not None for fs in u.freeu_signature()):
             raise NotImplementedError("FreeU (enable_freeu) is a sampling-time switch: the training step has no backward of "
                                       "i2v_freeu_f16 -- call unet.disable_freeu() before training")
+        if u.free_noise_signature() is not None:
+            raise NotImplementedError("FreeNoise (enable_free_noise) is a sampling-time switch: the training step has no backward of "
+                                      "the window gather / blend -- call unet.disable_free_noise() before training")
         b, F, c, hh, ww = sample.shape
         p = u.packed()
         t = timestep if torch.is_tensor(timestep) else torch.tensor([timestep])

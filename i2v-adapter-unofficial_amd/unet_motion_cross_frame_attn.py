@@ -630,6 +630,46 @@ class UNetMotionCrossFrameAttnModel(UNetLoraMixin, PretrainedMixin, HipModule):
         """what FreeU bakes into the launches of a forward: (b, s) of every up block that applies it (None where it does not)"""
         return tuple(freeu_scales(blk) for blk in self.up_blocks)
 
+    def _motion_modules(self):
+        from .blocks import TransformerTemporalModel
+        return [m for m in self.modules() if isinstance(m, TransformerTemporalModel)]
+
+    def enable_free_noise(self, context_length: int = 16, context_stride: int = 4, weighting_scheme: str = "pyramid",
+                          noise_type: str = "shuffle_context") -> None:
+        """diffusers AnimateDiffFreeNoiseMixin.enable_free_noise (FreeNoise, https://arxiv.org/abs/2310.15169): clips longer than
+        `context_length` frames.  Every motion module then runs its temporal attention on sliding windows of `context_length` frames,
+        `context_stride` apart (positions restart in each), and takes per frame the mean of the windows that cover it, weighted over
+        the position in the window by `weighting_scheme` ("flat", "pyramid", "delayed_reverse_sawtooth"); everything else -- entry
+        GroupNorm, projections, feed-forward, the spatial path -- runs on all frames as before.  `noise_type` ("shuffle_context",
+        "repeat_context", "random") is the pipeline's rescheduling of the initial noise.  A forward of at most `context_length`
+        frames is unchanged; the settings are checked here and against num_frames in the forward."""
+        from . import free_noise
+        settings = free_noise.check_free_noise_args(context_length, context_stride, weighting_scheme, noise_type,
+                                                    self.config["motion_max_seq_length"])
+        for m in self._motion_modules():
+            m.set_free_noise(settings)
+        self._free_noise = settings
+
+    def disable_free_noise(self) -> None:
+        """diffusers disable_free_noise: the motion modules attend over the whole clip again (at most motion_max_seq_length frames)"""
+        for m in self._motion_modules():
+            m.set_free_noise(None)
+        self._free_noise = None
+
+    _free_noise = None      # FreeNoiseSettings while enabled (class default: modules built before the switch existed read None)
+
+    def free_noise_signature(self):
+        """the FreeNoise settings: None when disabled, else (context_length, context_stride, weighting_scheme, noise_type).  The
+        first three decide the launches of a forward (`free_noise_launch_signature`); noise_type only the pipeline's initial noise."""
+        fn = self._free_noise
+        return None if fn is None else tuple(fn)
+
+    def free_noise_launch_signature(self):
+        """what FreeNoise bakes into the launches of a forward (the captured step's key): None, or (context_length, context_stride,
+        weighting_scheme)"""
+        sig = self.free_noise_signature()
+        return None if sig is None else sig[:3]
+
     def _cross_attention_layers(self):
         """the spatial blocks' attn2 modules, in attn_processors order."""
         modules = dict(self.named_modules())
@@ -680,6 +720,9 @@ class UNetMotionCrossFrameAttnModel(UNetLoraMixin, PretrainedMixin, HipModule):
         """x: model-input tokens [B*F, H, W, cin_pad] fp16; temb [B, 4*C0] fp16 (pre-SiLU) -- or temb_proj [B or 1, sum Cout]:
         the resnets' time-embedding projections already computed (project_time_table); ctx_text [B, Lt, D]
         (+ ctx_ip [B, 4, D]) or a ProjectedContext; returns noise-prediction tokens [B*F, H, W, out_channels]."""
+        if self._free_noise is not None:
+            from .free_noise import check_num_frames
+            check_num_frames(num_frames, self._free_noise)
         p = self.packed()
         wt, bt, slices = self._temb_pack()
         # ResnetBlock2D: time_emb_proj(nonlinearity(temb)) of all 22 resnets in one GEMM

@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define I2V_ABI_VERSION 15
+#define I2V_ABI_VERSION 16
 
 #define I2V_OK 0
 #define I2V_ERR_INVALID_ARG (-1)
@@ -614,6 +614,31 @@ int64_t i2v_freeinit_workspace_bytes(int32_t b, int32_t f, int32_t c, int32_t h,
 int i2v_freeinit_mix(const float* latents, const float* init_noise, const float* z_rand, const float* lpf, float* out, void* workspace,
                      int64_t workspace_bytes, int32_t b, int32_t f, int32_t c, int32_t h, int32_t w, float sqrt_alpha,
                      float sqrt_one_minus_alpha, i2v_stream_t stream);
+
+/* (ABI 16) FreeNoise (https://arxiv.org/abs/2310.15169; diffusers AnimateDiffFreeNoiseMixin.enable_free_noise / FreeNoiseTransformerBlock):
+ * clips longer than the motion modules' positional table.  The temporal attention of a motion module runs on sliding windows of `length`
+ * frames -- positions restart in every window -- and a frame's result is the weighted mean of the windows that cover it.  A window is a
+ * `length`-frame clip of the (b, pixel, frame) row layout, so the existing attention entry points run it unchanged on n_pixels * windows
+ * "pixels"; these two entry points move the rows into windows and back.  fp16 rows of c values (c a multiple of 8), unit stride along c,
+ * row strides ld_* in elements (multiples of 8, >= c), 16-byte aligned pointers, dst never overlapping src.
+ *   i2v_freenoise_gather_f16   src [n_pixels, frames, c] -> dst [n_pixels, windows, length, c]:
+ *       dst[p, w, j, :] = src[p, starts[w] + j, :], bit for bit.  starts: DEVICE int32 [windows] (the trailing window is one more entry;
+ *       a captured step holds no host value).
+ *   i2v_freenoise_blend_f16    src [n_pixels, windows, length, c] -> dst [n_pixels, frames, c]:
+ *       dst[p, f, :] = sum_k coef[f, k] * src[p, idx[f, k], :],  idx in [0, windows * length) = w * length + j.
+ *       idx DEVICE int32 [frames, pairs], coef DEVICE fp32 [frames, pairs], pairs in 1..33 (ceil(length / stride) + 1); the normalised
+ *       coefficients are the host's (fp64, rounded to fp32).  Pair 0 is always read; a later pair with coefficient 0 is padding and is
+ *       not read (give it index 0).  fp32 accumulation -- pair 0 as a product, the others as fmas --, one rounding to fp16: a frame whose
+ *       only coefficient is 1.0 leaves as the bits of its source row.
+ * Both are gathers with one owner per output row (no atomics, no LDS, deterministic) that stream 16 bytes per lane; table entries are
+ * clamped to the operand on the device, so a corrupt table cannot cause an access outside it.
+ * I2V_ERR_INVALID_ARG: null pointers, n_pixels / windows < 1, length outside 1..frames, windows > frames, c not a multiple of 8, a bad row
+ * stride or alignment, 2^31 rows or more, overlapping operands, pairs outside 1..33. */
+int i2v_freenoise_gather_f16(const void* src, int64_t ld_src, void* dst, int64_t ld_dst, const int32_t* starts, int64_t n_pixels,
+                             int32_t frames, int32_t windows, int32_t length, int32_t c, i2v_stream_t stream);
+int i2v_freenoise_blend_f16(const void* src, int64_t ld_src, void* dst, int64_t ld_dst, const int32_t* idx, const float* coef,
+                            int64_t n_pixels, int32_t frames, int32_t windows, int32_t length, int32_t pairs, int32_t c,
+                            i2v_stream_t stream);
 
 /* First-frame-similarity prior and the initial add_noise of the sampling loop, pipe:647-656:
  *   prior   = mask * GaussianBlur3x3(cond) + (1 - mask) * cond, mask = (mask_uniform < strength), per frame (pipe:648-654)

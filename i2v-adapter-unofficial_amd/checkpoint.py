@@ -42,6 +42,14 @@ class PretrainedMixin:
     in `self.config` (a dict)."""
 
     config_name = CONFIG_NAME
+    # diffusers' file names; a transformers-layout folder (`text_encoder/`: model.safetensors / pytorch_model.bin) overrides them
+    weights_name = WEIGHTS_NAME
+    safetensors_weights_name = SAFETENSORS_WEIGHTS_NAME
+
+    @classmethod
+    def _convert_state_dict(cls, state: dict, target: dict) -> dict:
+        """hook: a file's state dict -> the module's keys (`target` is the module's state dict)"""
+        return convert_deprecated_attention_keys(state, target)
 
     def save_pretrained(self, save_directory: str, is_main_process: bool = True, safe_serialization: bool = True,
                         variant: Optional[str] = None, push_to_hub: bool = False, **_unused):
@@ -59,10 +67,10 @@ class PretrainedMixin:
         state = {k: v.detach().to("cpu").contiguous() for k, v in self.state_dict().items()}
         if safe_serialization:
             from safetensors.torch import save_file
-            save_file(state, os.path.join(save_directory, _add_variant(SAFETENSORS_WEIGHTS_NAME, variant)),
+            save_file(state, os.path.join(save_directory, _add_variant(self.safetensors_weights_name, variant)),
                       metadata={"format": "pt"})
         else:
-            torch.save(state, os.path.join(save_directory, _add_variant(WEIGHTS_NAME, variant)))
+            torch.save(state, os.path.join(save_directory, _add_variant(self.weights_name, variant)))
 
     @classmethod
     def load_config(cls, pretrained_model_path: str, subfolder: Optional[str] = None) -> dict:
@@ -85,17 +93,17 @@ class PretrainedMixin:
         path = os.path.join(pretrained_model_path, subfolder) if subfolder else pretrained_model_path
         config = cls.load_config(path)
         model = cls.from_config(config)
-        st_file = os.path.join(path, _add_variant(SAFETENSORS_WEIGHTS_NAME, variant))
-        bin_file = os.path.join(path, _add_variant(WEIGHTS_NAME, variant))
+        st_file = os.path.join(path, _add_variant(cls.safetensors_weights_name, variant))
+        bin_file = os.path.join(path, _add_variant(cls.weights_name, variant))
         if use_safetensors is not False and os.path.isfile(st_file):
             from safetensors.torch import load_file
             state = load_file(st_file)
         elif use_safetensors is not True and os.path.isfile(bin_file):
             state = torch.load(bin_file, map_location="cpu", weights_only=True)
         else:
-            raise EnvironmentError(f"Error no file named {_add_variant(SAFETENSORS_WEIGHTS_NAME, variant)} or "
-                                   f"{_add_variant(WEIGHTS_NAME, variant)} found in directory {path}.")
-        state = convert_deprecated_attention_keys(state, model.state_dict())
+            raise EnvironmentError(f"Error no file named {_add_variant(cls.safetensors_weights_name, variant)} or "
+                                   f"{_add_variant(cls.weights_name, variant)} found in directory {path}.")
+        state = cls._convert_state_dict(state, model.state_dict())
         missing, unexpected = model.load_state_dict(state, strict=False)
         # recomputable buffers (the sinusoidal table) may be absent from third-party files; anything else is an error
         missing = [k for k in missing if not k.endswith("pos_embed.pe")]

@@ -956,6 +956,66 @@ def silu(x):
     return y
 
 
+# ---------------------------------------------------------------------------------------------- CLIP text tower (clip_text.py)
+def clip_embed(token_embedding, position_embedding, input_ids):
+    """token + position embedding lookup (i2v_clip_embed_f16): tables fp16 [vocab, hidden] / [max_positions, hidden] on the device,
+    input_ids an integer [B, L] tensor on either side -> fp16 [B * L, hidden].  The ids are validated on the HOST (an id outside the
+    vocabulary raises before anything is launched), so ids that live on the device are copied back once."""
+    lib = _lib.load()
+    tok, pos = _req(token_embedding, "token_embedding"), _req(position_embedding, "position_embedding")
+    if tok.dim() != 2 or pos.dim() != 2 or tok.shape[1] != pos.shape[1] or not tok.is_contiguous() or not pos.is_contiguous():
+        raise ValueError(f"embedding tables must be contiguous [rows, hidden] of one width, got {tuple(tok.shape)} / {tuple(pos.shape)}")
+    if not isinstance(input_ids, torch.Tensor) or input_ids.dim() != 2 or input_ids.dtype not in (torch.int32, torch.int64):
+        raise TypeError("input_ids must be an int32 / int64 [B, L] tensor")
+    host = input_ids.detach().to("cpu", torch.int32).contiguous()
+    dev = host.to(tok.device)
+    b, l = host.shape
+    out = torch.empty((b * l, tok.shape[1]), dtype=f16, device=tok.device)
+    _lib.check(lib.i2v_clip_embed_f16(_p(tok), _p(pos), _p(dev), C.c_void_p(host.data_ptr()), _p(out), b, l, tok.shape[0], pos.shape[0],
+                                      tok.shape[1], _stream()), "i2v_clip_embed_f16")
+    return out
+
+
+def clip_attention(qkv, *, batch, length, heads, head_dim, q_off=None, k_off=None, v_off=None, scale=None, out=None):
+    """causal self-attention of `batch` sequences of `length` tokens (i2v_clip_attention_f16), q / k / v read in place from the packed
+    result of one QKV GEMM: qkv fp16 [batch * length, >= 3 * hidden], head h of q / k / v in columns q_off / k_off / v_off + h * head_dim
+    (default 0, hidden, 2 * hidden) -> fp16 [batch * length, hidden].  head_dim 64 and length <= 128 only (anything else raises)."""
+    lib = _lib.load()
+    qkv, ld = _mat(qkv, "qkv")
+    hidden = heads * head_dim
+    q_off = 0 if q_off is None else q_off
+    k_off = hidden if k_off is None else k_off
+    v_off = 2 * hidden if v_off is None else v_off
+    if qkv.shape[0] != batch * length or max(q_off, k_off, v_off) + hidden > qkv.shape[1]:
+        raise ValueError(f"qkv is {tuple(qkv.shape)}: expected [{batch * length}, >= offset + {hidden}]")
+    if out is None:
+        out = torch.empty((batch * length, hidden), dtype=f16, device=qkv.device)
+    out, ldo = _mat(out, "out")
+    if out.shape != (batch * length, hidden):
+        raise ValueError(f"out must be {(batch * length, hidden)}, got {tuple(out.shape)}")
+    scale = float(head_dim) ** -0.5 if scale is None else float(scale)
+    _lib.check(lib.i2v_clip_attention_f16(_p(qkv), ld, q_off, k_off, v_off, _p(out), ldo, batch, length, heads, head_dim, scale, _stream()),
+               "i2v_clip_attention_f16")
+    return out
+
+
+def quick_gelu(x, out=None):
+    """x * sigmoid(1.702 x) in fp32, rounded to fp16 (i2v_quick_gelu_f16); `out` may be x itself (in place)."""
+    lib = _lib.load()
+    _req(x, "x")
+    if not x.is_contiguous():
+        raise ValueError("x must be contiguous")
+    if out is None:
+        out = torch.empty_like(x)
+    _req(out, "out")
+    if out.shape != x.shape or not out.is_contiguous():
+        raise ValueError("out must be contiguous with x's shape")
+    if x.numel() == 0:
+        return out
+    _lib.check(lib.i2v_quick_gelu_f16(_p(x), _p(out), x.numel(), _stream()), "i2v_quick_gelu_f16")
+    return out
+
+
 def select_row(table, row_index, out=None):
     """[1, cols] = table[clamp(*row_index)] for a device int32 scalar `row_index` (a replayed step's row of a per-timestep
     table)."""

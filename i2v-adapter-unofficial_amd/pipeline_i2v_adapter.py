@@ -13,9 +13,11 @@ there is no per-step host<->device traffic and no per-step sync (the reference s
 
 Either side of the loop: the condition image is encoded and the final latents are decoded by the HIP
 AutoencoderKL (vae.py: pipe:300-320, 626-627) when a `vae` is given; pre / post-processing, `tensor2vid` and GIF
-export are host-side plumbing (image_processor.py).  Out of scope: the CLIP text / image
-encoders -- pass `prompt_embeds`, `negative_prompt_embeds` and optional `image_embeds`.
+export are host-side plumbing (image_processor.py).  A `prompt` is encoded by the HIP CLIP text encoder (clip_text.py, `encode_prompt`
+pipe:348-527) when the pipeline holds a `text_encoder` and a `tokenizer`; `prompt_embeds` / `negative_prompt_embeds` are taken as given.
+Out of scope: the CLIP image encoder -- pass `image_embeds`, not `ip_adapter_image`.
 """
+import logging
 import os
 from typing import Optional
 
@@ -33,6 +35,7 @@ from .unet_motion_cross_frame_attn import UNetMotionCrossFrameAttnModel
 CFG_SHARED = os.environ.get("I2V_CFG_SHARED", "1") != "0"
 
 f16 = torch.float16
+logger = logging.getLogger(__name__)
 
 # diffusers schedulers the reference's pipeline accepts (pipe:25-32, 83-90) that this build does not: each needs what the
 # captured step has no room for (sigma-scaled inputs and prior, per-step host noise, 3-4 history tensors)
@@ -206,7 +209,7 @@ class I2VAdapterPipeline:
 
     def to(self, device=None, dtype=None):
         """move the models the pipeline holds (pipe:784); fp16 is the storage dtype of the HIP path."""
-        for name in ("unet", "vae"):
+        for name in ("unet", "vae", "text_encoder"):
             m = getattr(self, name)
             if m is not None:
                 setattr(self, name, m.to(device=device, dtype=dtype))
@@ -390,6 +393,85 @@ class I2VAdapterPipeline:
             use_graph = False
         return output_type, use_graph
 
+    # ------------------------------------------------------------------------------------------ encode_prompt
+    def encode_prompt(self, prompt, device, num_images_per_prompt, do_classifier_free_guidance, negative_prompt=None,
+                      prompt_embeds=None, negative_prompt_embeds=None, lora_scale=None, clip_skip=None):
+        """pipe:348-527, line for line: tokenise (padding to `model_max_length`, truncation with the reference's warning), the text
+        encoder (clip_text.CLIPTextModel on the HIP kernels), `clip_skip` (`hidden_states[-(clip_skip + 1)]` through
+        `final_layer_norm`), the per-prompt repeat, and the negative prompt ("" when none is given) under classifier-free guidance.
+        Returns (prompt_embeds, negative_prompt_embeds).  `lora_scale` is accepted and ignored (text-encoder LoRA keys are skipped and
+        reported by `load_lora_weights`); there is no textual inversion.  `self.tokenizer` is used as given: any object with
+        CLIPTokenizer's call interface and `model_max_length`."""
+        if prompt is not None and isinstance(prompt, str):
+            batch_size = 1
+        elif prompt is not None and isinstance(prompt, list):
+            batch_size = len(prompt)
+        else:
+            batch_size = prompt_embeds.shape[0]
+        needs_encoder = prompt_embeds is None or (do_classifier_free_guidance and negative_prompt_embeds is None)
+        if needs_encoder and (self.text_encoder is None or self.tokenizer is None):
+            raise ValueError("encoding a `prompt` needs both a `text_encoder` and a `tokenizer`: build the pipeline with them, or pass "
+                             "`prompt_embeds` (and `negative_prompt_embeds`)")
+        if needs_encoder and getattr(self.text_encoder.config, "use_attention_mask", None):
+            raise NotImplementedError("text_encoder.config.use_attention_mask: padding attention masks are not implemented")
+
+        if prompt_embeds is None:
+            text_inputs = self.tokenizer(prompt, padding="max_length", max_length=self.tokenizer.model_max_length, truncation=True,
+                                         return_tensors="pt")
+            text_input_ids = text_inputs.input_ids
+            untruncated_ids = self.tokenizer(prompt, padding="longest", return_tensors="pt").input_ids
+            if untruncated_ids.shape[-1] >= text_input_ids.shape[-1] and not torch.equal(text_input_ids, untruncated_ids):
+                removed_text = self.tokenizer.batch_decode(untruncated_ids[:, self.tokenizer.model_max_length - 1: -1])
+                logger.warning("The following part of your input was truncated because CLIP can only handle sequences up to"
+                               f" {self.tokenizer.model_max_length} tokens: {removed_text}")
+            if clip_skip is None:
+                prompt_embeds = self.text_encoder(text_input_ids, attention_mask=None)
+                prompt_embeds = prompt_embeds[0]
+            else:
+                prompt_embeds = self.text_encoder(text_input_ids, attention_mask=None, output_hidden_states=True)
+                # the tuple of all hidden states, then the desired layer's; the final LayerNorm is applied here, as to the
+                # `last_hidden_state` the default path takes (pipe:445-453)
+                prompt_embeds = prompt_embeds[-1][-(clip_skip + 1)]
+                prompt_embeds = self.text_encoder.text_model.final_layer_norm(prompt_embeds)
+
+        if self.text_encoder is not None:
+            prompt_embeds_dtype = self.text_encoder.dtype
+        elif self.unet is not None:
+            prompt_embeds_dtype = self.unet.dtype
+        else:
+            prompt_embeds_dtype = prompt_embeds.dtype
+        prompt_embeds = prompt_embeds.to(dtype=prompt_embeds_dtype, device=device)
+        bs_embed, seq_len, _ = prompt_embeds.shape
+        prompt_embeds = prompt_embeds.repeat(1, num_images_per_prompt, 1)
+        prompt_embeds = prompt_embeds.view(bs_embed * num_images_per_prompt, seq_len, -1)
+
+        if do_classifier_free_guidance and negative_prompt_embeds is None:
+            if negative_prompt is None:
+                uncond_tokens = [""] * batch_size
+            elif prompt is not None and type(prompt) is not type(negative_prompt):
+                raise TypeError(f"`negative_prompt` should be the same type to `prompt`, but got {type(negative_prompt)} !="
+                                f" {type(prompt)}.")
+            elif isinstance(negative_prompt, str):
+                uncond_tokens = [negative_prompt]
+            elif batch_size != len(negative_prompt):
+                raise ValueError(f"`negative_prompt`: {negative_prompt} has batch size {len(negative_prompt)}, but `prompt`:"
+                                 f" {prompt} has batch size {batch_size}. Please make sure that passed `negative_prompt` matches"
+                                 " the batch size of `prompt`.")
+            else:
+                uncond_tokens = negative_prompt
+            max_length = prompt_embeds.shape[1]
+            uncond_input = self.tokenizer(uncond_tokens, padding="max_length", max_length=max_length, truncation=True,
+                                          return_tensors="pt")
+            negative_prompt_embeds = self.text_encoder(uncond_input.input_ids, attention_mask=None)
+            negative_prompt_embeds = negative_prompt_embeds[0]
+
+        if do_classifier_free_guidance:
+            seq_len = negative_prompt_embeds.shape[1]
+            negative_prompt_embeds = negative_prompt_embeds.to(dtype=prompt_embeds_dtype, device=device)
+            negative_prompt_embeds = negative_prompt_embeds.repeat(1, num_images_per_prompt, 1)
+            negative_prompt_embeds = negative_prompt_embeds.view(batch_size * num_images_per_prompt, seq_len, -1)
+        return prompt_embeds, negative_prompt_embeds
+
     # ------------------------------------------------------------------------------------------ __call__
     @torch.no_grad()
     def __call__(self, prompt=None, condition_image=None, num_frames: Optional[int] = 16,
@@ -438,13 +520,27 @@ class I2VAdapterPipeline:
                 raise ValueError(f"FreeNoise with FreeInit: num_frames {num_frames} exceeds FreeInit's {MAX_FRAMES} x {MAX_HW} x {MAX_HW} "
                                  "limit (frames x latent height x width of i2v_freeinit_mix) -- disable_free_init() for longer clips")
         self.unet._sync_lora()      # before anything reads a weight, a pack or the weights' versions (_graph_key)
-        if prompt is not None or ip_adapter_image is not None:
+        if ip_adapter_image is not None:
             raise NotImplementedError(
-                "the CLIP text / image encoders are out of scope of this build (SURVEY section 2 row 3b): pass "
-                "`prompt_embeds`, `negative_prompt_embeds` (and `image_embeds`)")
-        if prompt_embeds is None:
+                "the CLIP image encoder is out of scope of this build (SURVEY section 2 row 3b): pass `image_embeds` "
+                "(and `negative_image_embeds`) instead of `ip_adapter_image`")
+        if prompt is not None and prompt_embeds is not None:                                    # pipe:222-226
+            raise ValueError(f"Cannot forward both `prompt`: {prompt} and `prompt_embeds`: {prompt_embeds}. Please make sure to"
+                             " only forward one of the two.")
+        if prompt is None and prompt_embeds is None:
             raise ValueError("Provide either `prompt` or `prompt_embeds`. Cannot leave both `prompt` and "
                              "`prompt_embeds` undefined.")
+        if prompt is not None:                                                                  # pipe:595-609
+            if not isinstance(prompt, (str, list)):
+                raise ValueError(f"`prompt` has to be of type `str` or `list` but is {type(prompt)}")
+            if self.text_encoder is None or self.tokenizer is None:
+                raise ValueError("a `prompt` needs both a `text_encoder` and a `tokenizer`: build the pipeline with them, or pass "
+                                 "`prompt_embeds` and `negative_prompt_embeds`")
+            prompt_embeds, negative_prompt_embeds = self.encode_prompt(
+                prompt, self.unet.device, num_videos_per_prompt, guidance_scale > 1.0, negative_prompt,
+                prompt_embeds=None, negative_prompt_embeds=negative_prompt_embeds,
+                lora_scale=cross_attention_kwargs.get("scale", None) if cross_attention_kwargs is not None else None,
+                clip_skip=clip_skip)
         if condition_image is not None and condition_image_latents is None:                     # pipe:624-627
             if height is None or width is None:
                 height = height or self.unet.config.sample_size * self.vae_scale_factor         # pipe:568-569
@@ -627,6 +723,19 @@ def load_scheduler(model_path, kind="ddim"):
     raise ValueError(f"unknown scheduler {kind!r}: one of {', '.join(SCHEDULERS + STOCHASTIC_SCHEDULERS)}")
 
 
+def load_text_encoder(model_path):
+    """(text_encoder, tokenizer) of an SD-1.5 folder (pipe:752-753): `<model_path>/text_encoder` as the HIP `CLIPTextModel`,
+    `<model_path>/tokenizer` as transformers' `CLIPTokenizer` (there is no tokenizer of our own; nothing is downloaded)."""
+    from .clip_text import CLIPTextModel
+    try:
+        from transformers import CLIPTokenizer
+    except ImportError as e:
+        raise ImportError("encoding prompts needs the `transformers` package for CLIPTokenizer (the tokenizer is not part of this "
+                          "build): install it, or pass --embeds with precomputed embeddings") from e
+    tokenizer = CLIPTokenizer.from_pretrained(os.path.join(model_path, "tokenizer"), local_files_only=True)
+    return CLIPTextModel.from_pretrained(os.path.join(model_path, "text_encoder")), tokenizer
+
+
 def build_parser():
     """the evaluation driver's command line (`main`)"""
     import argparse
@@ -634,9 +743,12 @@ def build_parser():
     parser.add_argument("--checkpoint_epoch", type=int, default=0)
     parser.add_argument("--eval_data_path", type=str, default="./data/WebVid-10M/I2VAdapter-eval.csv")
     parser.add_argument("--task_name", type=str)
-    parser.add_argument("--embeds", type=str, required=True,
+    parser.add_argument("--embeds", type=str, default=None,
                         help="safetensors with prompt_embeds [N,77,768], negative_prompt_embeds [N or 1,77,768], "
-                             "optional image_embeds [N,1024] (row i = CSV row i)")
+                             "optional image_embeds [N,1024] (row i = CSV row i); without it the CSV's prompts are encoded by "
+                             "<model_path>/text_encoder with <model_path>/tokenizer")
+    parser.add_argument("--negative_prompt", type=str, default="",
+                        help="the negative prompt of every row when the prompts are encoded here (no --embeds)")
     parser.add_argument("--model_path", type=str, default="./SG161222_Realistic_Vision_V5.1_noVAE/")
     parser.add_argument("--motion_adapter_path", type=str, default="./animatediff-motion-adapter-v1-5-2")
     parser.add_argument("--ip_adapter_path", type=str, default="./IP-Adapter/")
@@ -684,9 +796,10 @@ def main(argv=None):
     I2VAdapterModule / SD-1.5 UNet + VAE / IP-Adapter from the reference's directory layout, read the CSV of
     (image_path, name) pairs, sample 16 frames per pair and write one GIF per prompt.
 
-    The CLIP text / image encoders are out of scope of this build, so the per-row `prompt_embeds`,
-    `negative_prompt_embeds` (and `image_embeds`) come from a safetensors file (--embeds) written by
-    `src/tools/encode_text.py`-style tooling; everything else follows the reference driver."""
+    The CSV's prompts are encoded by the HIP CLIP text encoder (`<model_path>/text_encoder`, clip_text.py) with transformers'
+    `CLIPTokenizer` (`<model_path>/tokenizer`), as the reference does (pipe:752-753).  With --embeds the per-row `prompt_embeds`,
+    `negative_prompt_embeds` (and `image_embeds`: the CLIP image encoder is out of scope) come from a safetensors file instead and
+    neither is loaded; everything else follows the reference driver."""
     import logging
     import os
 
@@ -730,12 +843,17 @@ def main(argv=None):
     eval_data_df = pd.read_csv(args.eval_data_path)
     condition_images = [PIL.Image.open(os.path.join(eval_data_dir, p)) for p in eval_data_df["image_path"]]
     eval_prompts = eval_data_df["name"].tolist()
-    emb = load_file(args.embeds)
     n = len(eval_prompts)
-    if emb["prompt_embeds"].shape[0] != n:
-        raise ValueError(f"{args.embeds} holds {emb['prompt_embeds'].shape[0]} prompt embeddings for {n} CSV rows")
+    text_encoder = tokenizer = None
+    if args.embeds is not None:
+        emb = load_file(args.embeds)
+        if emb["prompt_embeds"].shape[0] != n:
+            raise ValueError(f"{args.embeds} holds {emb['prompt_embeds'].shape[0]} prompt embeddings for {n} CSV rows")
+    else:
+        emb = {}
+        text_encoder, tokenizer = load_text_encoder(args.model_path)                             # pipe:752-753
 
-    pipe = I2VAdapterPipeline(vae, None, None, unet2d.to(device).half(), motion_adapter, i2v_adapter, scheduler)
+    pipe = I2VAdapterPipeline(vae, text_encoder, tokenizer, unet2d.to(device).half(), motion_adapter, i2v_adapter, scheduler)
     if "image_embeds" in emb:                                                                    # pipe:783
         pipe.load_ip_adapter(args.ip_adapter_path, subfolder="models", weight_name="ip-adapter_sd15.bin")
     pipe.to(device, torch.float16)
@@ -762,11 +880,15 @@ def main(argv=None):
 
     sample_save_dir = os.path.join(args.samples_root, args.task_name, f"epoch_{args.checkpoint_epoch}")
     os.makedirs(sample_save_dir, exist_ok=True)
-    neg = emb["negative_prompt_embeds"]
+    neg = emb.get("negative_prompt_embeds")
     for ind in range(n):                                         # one sample per call: every sample replays the graph
         g = lambda k: torch.Generator().manual_seed(args.seed * 1000 + 10 * ind + k)
-        out = pipe(prompt_embeds=emb["prompt_embeds"][ind: ind + 1],
-                   negative_prompt_embeds=neg[ind: ind + 1] if neg.shape[0] == n else neg[:1],
+        if args.embeds is not None:
+            text = dict(prompt_embeds=emb["prompt_embeds"][ind: ind + 1],
+                        negative_prompt_embeds=neg[ind: ind + 1] if neg.shape[0] == n else neg[:1])
+        else:
+            text = dict(prompt=str(eval_prompts[ind]), negative_prompt=args.negative_prompt)
+        out = pipe(**text,
                    image_embeds=emb["image_embeds"][ind: ind + 1] if "image_embeds" in emb else None,
                    condition_image=condition_images[ind], num_frames=args.num_frames, guidance_scale=args.guidance_scale,
                    num_inference_steps=args.num_inference_steps, frame_similarity_sample_ratio=0.9,

@@ -109,6 +109,12 @@ def _work_ln(args, kw, out):
     return "layernorm", 0.0, 2 * _numel_bytes(out), "x".join(map(str, out.shape))
 
 
+def _work_clip_attn(args, kw, out):
+    b, l, h, d = kw["batch"], kw["length"], kw["heads"], kw["head_dim"]
+    # causal: half of the L x L tile pairs, Q K^T and P V; q / k / v read once, out written once
+    return "clip_text", 2.0 * 2 * b * h * d * l * (l + 1) / 2, 4 * _numel_bytes(out), f"causal b{b} h{h} L{l} d{d}"
+
+
 def _work_misc(name):
     def f(args, kw, out):
         return name, 0.0, 2 * _numel_bytes(out), ""
@@ -124,6 +130,9 @@ _WRAPPED = {
     "nchw_to_tokens": _work_misc("elementwise"), "tokens_to_nchw": _work_misc("elementwise"),
     "lcm_cfg_step": _work_misc("elementwise"), "freenoise_gather": _work_misc("elementwise"),
     "freenoise_blend": _work_misc("elementwise"),
+    # the CLIP text tower's own kernels (once per prompt, not per step): one class, so that a profile of `pipe(prompt=...)` shows what
+    # the prompt cost beside the step's classes; its GEMMs and LayerNorms are counted with theirs
+    "clip_embed": _work_misc("clip_text"), "clip_attention": _work_clip_attn, "quick_gelu": _work_misc("clip_text"),
 }
 
 

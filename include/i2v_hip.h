@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define I2V_ABI_VERSION 16
+#define I2V_ABI_VERSION 17
 
 #define I2V_OK 0
 #define I2V_ERR_INVALID_ARG (-1)
@@ -639,6 +639,31 @@ int i2v_freenoise_gather_f16(const void* src, int64_t ld_src, void* dst, int64_t
 int i2v_freenoise_blend_f16(const void* src, int64_t ld_src, void* dst, int64_t ld_dst, const int32_t* idx, const float* coef,
                             int64_t n_pixels, int32_t frames, int32_t windows, int32_t length, int32_t pairs, int32_t c,
                             i2v_stream_t stream);
+
+/* (ABI 17) The CLIP text tower (transformers CLIPTextModel as the pipeline's encode_prompt calls it, pipe:412-453; SD-1.5: 12 pre-LN layers,
+ * width 768, 12 heads of 64, 77 tokens).  Its projections and LayerNorms are i2v_gemm_f16 / i2v_layernorm_f16; these are the three kernels the
+ * UNet has no use for.  Not per-step work: a prompt is encoded once per sample.
+ *   i2v_clip_embed_f16      out[b * len + l, :] = fp16(float(tok[ids[b, l], :]) + float(pos[l, :])).  tok fp16 [vocab, hidden], pos fp16
+ *       [max_positions, hidden], out fp16 [batch * len, hidden], all dense.  ids: DEVICE int32 [batch, len]; ids_host: the HOST copy of the same
+ *       table, which is what is validated -- an id outside [0, vocab) is rejected before anything is launched (the kernel also clamps what it
+ *       reads on the device, so a device table that differs from its host copy gives wrong numbers, never an access outside tok).
+ *       I2V_ERR_INVALID_ARG: null pointers, an id out of range, len > max_positions, hidden % 8 != 0, misaligned or overlapping operands.
+ *   i2v_clip_attention_f16  causal multi-head self-attention of one short sequence per batch entry:
+ *           out[b * len + i, h * 64 + :] = softmax_j<=i( scale * q[b, i, h, :] . k[b, j, h, :] ) v[b, j, h, :]
+ *       q, k and v are read in place from the packed result of one QKV GEMM: qkv fp16 [batch * len, ld_qkv], head h of q / k / v of a row in
+ *       columns q_off / k_off / v_off + h * 64 (offsets multiples of 8); out fp16 [batch * len, ld_out].  No transposed V, no mask tensor: key j
+ *       is visible to query i iff j <= i (and j < len), by index compare, so no row is ever fully masked.  One workgroup per (batch, head), the
+ *       head's q / k / v staged in LDS once, rows padded to the MFMA tile in LDS only (nothing at or beyond row batch * len is read or written).
+ *       Numerics: Q K^T and P V on MFMA with fp32 accumulation, softmax in fp32 in base 2 with the logits scaled by scale * log2(e) in fp32, P
+ *       rounded to fp16 for P V, the row sum taken over the unrounded P.
+ *       I2V_ERR_UNSUPPORTED: head_dim != 64, len > 128.  I2V_ERR_INVALID_ARG: null / misaligned / overlapping operands, bad strides or offsets.
+ *   i2v_quick_gelu_f16      y = fp16(x * sigmoid(1.702 x)) evaluated in fp32 (CLIP's "quick_gelu").  Any n >= 1; y may be x (in place), and may not
+ *       overlap it otherwise; 16-byte aligned operands take 16 bytes per lane, the tail and unaligned operands one value per lane. */
+int i2v_clip_embed_f16(const void* tok, const void* pos, const int32_t* ids, const int32_t* ids_host, void* out, int32_t batch, int32_t len,
+                       int32_t vocab, int32_t max_positions, int32_t hidden, i2v_stream_t stream);
+int i2v_clip_attention_f16(const void* qkv, int64_t ld_qkv, int32_t q_off, int32_t k_off, int32_t v_off, void* out, int64_t ld_out,
+                           int32_t batch, int32_t len, int32_t heads, int32_t head_dim, float scale, i2v_stream_t stream);
+int i2v_quick_gelu_f16(const void* x, void* y, int64_t n, i2v_stream_t stream);
 
 /* First-frame-similarity prior and the initial add_noise of the sampling loop, pipe:647-656:
  *   prior   = mask * GaussianBlur3x3(cond) + (1 - mask) * cond, mask = (mask_uniform < strength), per frame (pipe:648-654)

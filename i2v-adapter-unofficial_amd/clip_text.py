@@ -14,7 +14,7 @@ after the embedding lookup (i2v_clip_embed_f16) and before the final LayerNorm: 
 LayerNorm is folded where the library says it folds this problem (`gemm(..., query_ln_support=True)`) and materialised otherwise.  The
 1 / sqrt(d) of the attention is applied to the logits in fp32 inside the kernel.  Not per-step work: a prompt is encoded once per sample
 (DESIGN 4.11).  Out of scope: padding attention masks (`use_attention_mask`; SD-1.5 does not use them, pipe:433-436), `pooler_output`, text
-projection, the CLIP vision tower.
+projection (the CLIP vision tower is clip_vision.py, on the same layer modules and helpers).
 """
 from typing import Optional
 
@@ -89,6 +89,47 @@ class CLIPEncoder(nn.Module):
         self.layers = nn.ModuleList([CLIPEncoderLayer(hidden, inter, eps) for _ in range(n)])
 
 
+def pack_layers(layers):
+    """kernel-layout operands of CLIPEncoderLayers (shared by the text and the vision tower): q | k | v as one GEMM, both LayerNorms in
+    their plain and their folded form"""
+    out = []
+    for lyr in layers:
+        a, m = lyr.self_attn, lyr.mlp
+        wqkv = torch.cat([a.q_proj.weight, a.k_proj.weight, a.v_proj.weight], dim=0)
+        bqkv = torch.cat([a.q_proj.bias, a.k_proj.bias, a.v_proj.bias], dim=0)
+        out.append(dict(
+            ln1=(w16(lyr.layer_norm1.weight), w16(lyr.layer_norm1.bias)), qkv=(w16(wqkv), w16(bqkv)),
+            qkv_fold=fold_layernorm(wqkv, bqkv, lyr.layer_norm1.weight, lyr.layer_norm1.bias),
+            out=(w16(a.out_proj.weight), w16(a.out_proj.bias)),
+            ln2=(w16(lyr.layer_norm2.weight), w16(lyr.layer_norm2.bias)), fc1=(w16(m.fc1.weight), w16(m.fc1.bias)),
+            fc1_fold=fold_layernorm(m.fc1.weight, m.fc1.bias, lyr.layer_norm2.weight, lyr.layer_norm2.bias),
+            fc2=(w16(m.fc2.weight), w16(m.fc2.bias))))
+    return out
+
+
+def ln_gemm(p, x, plain, folded, ln, epilogue):
+    """LayerNorm + Linear: folded into the GEMM where the library folds this problem, LayerNorm kernel + GEMM otherwise.  p: the pack
+    (`eps`, and `fold`, the cache of the library's answers)"""
+    wf, wsum, bf = folded
+    key = (x.shape[0], wf.shape, epilogue)
+    if key not in p["fold"]:
+        p["fold"][key] = K.gemm(x, wf, bf, ln=(wsum, p["eps"]), epilogue=epilogue, query_ln_support=True)
+    if p["fold"][key]:
+        return K.gemm(x, wf, bf, ln=(wsum, p["eps"]), epilogue=epilogue)
+    return K.gemm(K.layernorm(x, ln[0], ln[1], p["eps"]), plain[0], plain[1], epilogue=epilogue)
+
+
+def encoder_layer(p, lp, x, attention, quick_gelu):
+    """one pre-LN CLIP layer on the [B * L, hidden] stream: LN1 | q|k|v GEMM -> `attention(qkv)` -> out_proj + residual -> LN2 | fc1
+    (erf-GELU epilogue, or quick-GELU after it) -> fc2 + residual"""
+    qkv = ln_gemm(p, x, lp["qkv"], lp["qkv_fold"], lp["ln1"], I2V_EPI_NONE)
+    x = K.gemm(attention(qkv), lp["out"][0], lp["out"][1], residual=x)
+    h = ln_gemm(p, x, lp["fc1"], lp["fc1_fold"], lp["ln2"], I2V_EPI_NONE if quick_gelu else I2V_EPI_GELU)
+    if quick_gelu:
+        K.quick_gelu(h, out=h)
+    return K.gemm(h, lp["fc2"][0], lp["fc2"][1], residual=x)
+
+
 class CLIPTextEmbeddings(nn.Module):
     def __init__(self, vocab, positions, hidden):
         super().__init__()
@@ -154,31 +195,9 @@ class CLIPTextModel(PretrainedMixin, HipModule):
 
     # ------------------------------------------------------------------------------------------ kernel-layout weights
     def _pack(self):
-        tm, eps = self.text_model, self.config.layer_norm_eps
-        layers = []
-        for lyr in tm.encoder.layers:
-            a, m = lyr.self_attn, lyr.mlp
-            wqkv = torch.cat([a.q_proj.weight, a.k_proj.weight, a.v_proj.weight], dim=0)
-            bqkv = torch.cat([a.q_proj.bias, a.k_proj.bias, a.v_proj.bias], dim=0)
-            layers.append(dict(
-                ln1=(w16(lyr.layer_norm1.weight), w16(lyr.layer_norm1.bias)), qkv=(w16(wqkv), w16(bqkv)),
-                qkv_fold=fold_layernorm(wqkv, bqkv, lyr.layer_norm1.weight, lyr.layer_norm1.bias),
-                out=(w16(a.out_proj.weight), w16(a.out_proj.bias)),
-                ln2=(w16(lyr.layer_norm2.weight), w16(lyr.layer_norm2.bias)), fc1=(w16(m.fc1.weight), w16(m.fc1.bias)),
-                fc1_fold=fold_layernorm(m.fc1.weight, m.fc1.bias, lyr.layer_norm2.weight, lyr.layer_norm2.bias),
-                fc2=(w16(m.fc2.weight), w16(m.fc2.bias))))
-        return dict(tok=w16(tm.embeddings.token_embedding.weight), pos=w16(tm.embeddings.position_embedding.weight), layers=layers,
-                    eps=eps, fold={})
-
-    def _ln_gemm(self, p, x, plain, folded, ln, epilogue):
-        """LayerNorm + Linear: folded into the GEMM where the library folds this problem, LayerNorm kernel + GEMM otherwise"""
-        wf, wsum, bf = folded
-        key = (x.shape[0], wf.shape, epilogue)
-        if key not in p["fold"]:
-            p["fold"][key] = K.gemm(x, wf, bf, ln=(wsum, p["eps"]), epilogue=epilogue, query_ln_support=True)
-        if p["fold"][key]:
-            return K.gemm(x, wf, bf, ln=(wsum, p["eps"]), epilogue=epilogue)
-        return K.gemm(K.layernorm(x, ln[0], ln[1], p["eps"]), plain[0], plain[1], epilogue=epilogue)
+        tm = self.text_model
+        return dict(tok=w16(tm.embeddings.token_embedding.weight), pos=w16(tm.embeddings.position_embedding.weight),
+                    layers=pack_layers(tm.encoder.layers), eps=self.config.layer_norm_eps, fold={})
 
     @torch.no_grad()
     def forward(self, input_ids, attention_mask=None, output_hidden_states: Optional[bool] = False, **_unused):
@@ -193,17 +212,11 @@ class CLIPTextModel(PretrainedMixin, HipModule):
             raise ValueError(f"{l} tokens for a position table of {cfg.max_position_embeddings} rows")
         p = self.packed()
         heads, hid = cfg.num_attention_heads, cfg.hidden_size
-        act_epi = I2V_EPI_GELU if cfg.hidden_act == "gelu" else I2V_EPI_NONE
         x = K.clip_embed(p["tok"], p["pos"], input_ids)
         hidden = [x]
+        attention = lambda qkv: K.clip_attention(qkv, batch=b, length=l, heads=heads, head_dim=HEAD_DIM)
         for lp in p["layers"]:
-            qkv = self._ln_gemm(p, x, lp["qkv"], lp["qkv_fold"], lp["ln1"], I2V_EPI_NONE)
-            a = K.clip_attention(qkv, batch=b, length=l, heads=heads, head_dim=HEAD_DIM)
-            x = K.gemm(a, lp["out"][0], lp["out"][1], residual=x)
-            h = self._ln_gemm(p, x, lp["fc1"], lp["fc1_fold"], lp["ln2"], act_epi)
-            if cfg.hidden_act == "quick_gelu":
-                K.quick_gelu(h, out=h)
-            x = K.gemm(h, lp["fc2"][0], lp["fc2"][1], residual=x)
+            x = encoder_layer(p, lp, x, attention, cfg.hidden_act == "quick_gelu")
             hidden.append(x)
         last = self.text_model.final_layer_norm(x).view(b, l, hid)
         return CLIPTextModelOutput(last_hidden_state=last, pooler_output=None,

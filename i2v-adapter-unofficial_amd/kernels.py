@@ -1016,6 +1016,69 @@ def quick_gelu(x, out=None):
     return out
 
 
+# ---------------------------------------------------------------------------------------------- CLIP vision tower (clip_vision.py)
+def clip_patchify(pixel_values, patch, ld=None, out=None):
+    """im2col of the patch embedding (i2v_clip_patchify_f16): pixel_values fp16 [B, C, S, S] contiguous -> fp16 [B * (S / patch)^2, ld],
+    row b * P + py * (S / patch) + px = patch (py, px) in column order (c, dy, dx), columns C * patch^2 .. ld - 1 zero.  ld defaults to
+    pad8(C * patch^2); S % patch != 0 raises (nothing is launched)."""
+    lib = _lib.load()
+    _req(pixel_values, "pixel_values")
+    if pixel_values.dim() != 4 or pixel_values.shape[2] != pixel_values.shape[3] or not pixel_values.is_contiguous():
+        raise ValueError(f"pixel_values must be contiguous [B, C, S, S], got {tuple(pixel_values.shape)}")
+    b, c, s, _ = pixel_values.shape
+    ld = pad8(c * patch * patch) if ld is None else ld
+    rows = b * (s // patch) ** 2
+    if out is None:
+        out = torch.empty((rows, ld), dtype=f16, device=pixel_values.device)
+    _req(out, "out")
+    if out.shape != (rows, ld) or not out.is_contiguous():
+        raise ValueError(f"out must be contiguous {(rows, ld)}, got {tuple(out.shape)}")
+    _lib.check(lib.i2v_clip_patchify_f16(_p(pixel_values), _p(out), ld, b, c, s, patch, _stream()), "i2v_clip_patchify_f16")
+    return out
+
+
+def clip_vision_embed(class_embedding, patch_embeds, position_embedding, *, batch):
+    """class token + patch embeddings + positions (i2v_clip_vision_embed_f16): class_embedding fp16 [hidden], patch_embeds fp16
+    [batch * P, hidden] (the patch GEMM's result), position_embedding fp16 [P + 1, hidden] -> fp16 [batch * (P + 1), hidden]."""
+    lib = _lib.load()
+    cls, pos = _req(class_embedding, "class_embedding"), _req(position_embedding, "position_embedding")
+    patch_embeds, ldp = _mat(patch_embeds, "patch_embeds")
+    hidden = patch_embeds.shape[1]
+    if patch_embeds.shape[0] % batch != 0:
+        raise ValueError(f"{patch_embeds.shape[0]} patch rows for a batch of {batch}")
+    patches = patch_embeds.shape[0] // batch
+    if cls.shape != (hidden,) or pos.shape != (patches + 1, hidden) or not cls.is_contiguous() or not pos.is_contiguous():
+        raise ValueError(f"class_embedding must be [{hidden}] and position_embedding [{patches + 1}, {hidden}], contiguous; got "
+                         f"{tuple(cls.shape)} / {tuple(pos.shape)}")
+    out = torch.empty((batch * (patches + 1), hidden), dtype=f16, device=patch_embeds.device)
+    _lib.check(lib.i2v_clip_vision_embed_f16(_p(cls), _p(patch_embeds), ldp, _p(pos), _p(out), batch, patches, hidden, _stream()),
+               "i2v_clip_vision_embed_f16")
+    return out
+
+
+def clip_vision_attention(qkv, *, batch, length, heads, head_dim, q_off=None, k_off=None, v_off=None, scale=None, out=None):
+    """NON-causal self-attention of `batch` sequences of `length` tokens (i2v_clip_vision_attention_f16), q / k / v read in place from the
+    packed result of one QKV GEMM, as `clip_attention` takes them -> fp16 [batch * length, hidden].  head_dim 64 or 80 and length <= 288
+    only (anything else raises)."""
+    lib = _lib.load()
+    qkv, ld = _mat(qkv, "qkv")
+    hidden = heads * head_dim
+    q_off = 0 if q_off is None else q_off
+    k_off = hidden if k_off is None else k_off
+    v_off = 2 * hidden if v_off is None else v_off
+    if qkv.shape[0] != batch * length or max(q_off, k_off, v_off) + hidden > qkv.shape[1]:
+        raise ValueError(f"qkv is {tuple(qkv.shape)}: expected [{batch * length}, >= offset + {hidden}]")
+    if out is None:
+        out = torch.empty((batch * length, hidden), dtype=f16, device=qkv.device)
+    out, ldo = _mat(out, "out")
+    if out.shape != (batch * length, hidden):
+        raise ValueError(f"out must be {(batch * length, hidden)}, got {tuple(out.shape)}")
+    scale = float(head_dim) ** -0.5 if scale is None else float(scale)
+    _lib.check(lib.i2v_clip_vision_attention_f16(_p(qkv), ld, q_off, k_off, v_off, _p(out), ldo, batch, length, heads, head_dim, scale,
+                                                 _stream()), "i2v_clip_vision_attention_f16")
+    return out
+
+
 def select_row(table, row_index, out=None):
     """[1, cols] = table[clamp(*row_index)] for a device int32 scalar `row_index` (a replayed step's row of a per-timestep
     table)."""

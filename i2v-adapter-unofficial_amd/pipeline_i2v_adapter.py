@@ -15,7 +15,9 @@ Either side of the loop: the condition image is encoded and the fina
 AutoencoderKL (vae.py: pipe:300-320, 626-627) when a `vae` is given; pre / post-processing, `tensor2vid` and GIF
 export are host-side plumbing (image_processor.py).  A `prompt` is encoded by the HIP CLIP text encoder (clip_text.py, `encode_prompt`
 pipe:348-527) when the pipeline holds a `text_encoder` and a `tokenizer`; `prompt_embeds` / `negative_prompt_embeds` are taken as given.
-Out of scope: the CLIP image encoder -- pass `image_embeds`, not `ip_adapter_image`.
+`ip_adapter_image` is encoded by `encode_image` (same as pipe:323-345) when the pipeline holds an `image_encoder`
+(clip_vision.CLIPVisionModelWithProjection; `load_ip_adapter` loads it from `<path>/<subfolder>/image_encoder`) and the UNet an
+IP-Adapter; `image_embeds` / `negative_image_embeds` are taken as given.
 """
 import logging
 import os
@@ -209,7 +211,7 @@ class I2VAdapterPipeline:
 
     def to(self, device=None, dtype=None):
         """move the models the pipeline holds (pipe:784); fp16 is the storage dtype of the HIP path."""
-        for name in ("unet", "vae", "text_encoder"):
+        for name in ("unet", "vae", "text_encoder", "image_encoder"):
             m = getattr(self, name)
             if m is not None:
                 setattr(self, name, m.to(device=device, dtype=dtype))
@@ -222,11 +224,27 @@ class I2VAdapterPipeline:
     def load_ip_adapter(self, pretrained_model_name_or_path_or_dict, subfolder: Optional[str] = None,
                         weight_name: Optional[str] = None, **_unused):
         """diffusers IPAdapterMixin.load_ip_adapter as called at pipe:783: reads ip-adapter_sd15.{bin,safetensors} and
-        installs the decoupled cross-attention branch + ImageProjection (unet:1230-1287).  (The CLIP image encoder it
-        also loads upstream is out of scope: pass `image_embeds`.)"""
+        installs the decoupled cross-attention branch + ImageProjection (unet:1230-1287).  As diffusers does, a pipeline without an
+        `image_encoder` takes it from `<path>/<subfolder>/image_encoder` when the argument is a path and that folder exists (the HIP
+        `CLIPVisionModelWithProjection`, moved to the UNet's device and dtype; no folder: `image_encoder` stays None and only
+        `image_embeds` can be passed), and a pipeline without a `feature_extractor` gets transformers' `CLIPImageProcessor()` when
+        transformers is importable (any object with that call interface works)."""
         from .checkpoint import load_ip_adapter_file
         self.unet._load_ip_adapter_weights(
             load_ip_adapter_file(pretrained_model_name_or_path_or_dict, subfolder=subfolder, weight_name=weight_name))
+        if self.image_encoder is None and not isinstance(pretrained_model_name_or_path_or_dict, dict):
+            folder = os.path.join(pretrained_model_name_or_path_or_dict, subfolder or "", "image_encoder")
+            if os.path.isdir(folder):
+                from .clip_vision import CLIPVisionModelWithProjection
+                logger.info(f"loading image_encoder from {folder}")
+                enc = CLIPVisionModelWithProjection.from_pretrained(folder)
+                self.image_encoder = enc.to(device=self.unet.device, dtype=self.unet.dtype)
+        if self.feature_extractor is None:
+            try:
+                from transformers import CLIPImageProcessor
+                self.feature_extractor = CLIPImageProcessor()
+            except ImportError:
+                pass
 
     # ------------------------------------------------------------------------------------------ LoRA (lora.py, DESIGN 4.10)
     def load_lora_weights(self, pretrained_model_name_or_path_or_dict, adapter_name: Optional[str] = None,
@@ -393,6 +411,33 @@ class I2VAdapterPipeline:
             use_graph = False
         return output_type, use_graph
 
+    # ------------------------------------------------------------------------------------------ encode_image
+    def encode_image(self, image, device, num_images_per_prompt, output_hidden_states=None):
+        """pipe:323-345, both branches: a non-tensor image goes through `self.feature_extractor` (resize, crop and normalisation stay
+        on the host, as tokenisation does), the image encoder (clip_vision.CLIPVisionModelWithProjection on the HIP kernels), the
+        per-prompt repeat.  Returns (image_embeds, zeros_like) -- or, with `output_hidden_states`, the penultimate hidden states of the
+        image and of a zero image."""
+        if self.image_encoder is None:
+            raise ValueError("encoding an image needs an `image_encoder`: build the pipeline with one, or `load_ip_adapter` from a "
+                             "folder that holds `image_encoder/`")
+        dtype = next(self.image_encoder.parameters()).dtype
+        if not isinstance(image, torch.Tensor):
+            if self.feature_extractor is None:
+                raise ValueError("an `ip_adapter_image` that is not a pixel_values tensor needs a `feature_extractor` (transformers' "
+                                 "CLIPImageProcessor, or any object with its call interface)")
+            image = self.feature_extractor(image, return_tensors="pt").pixel_values
+        image = image.to(device=device, dtype=dtype)
+        if output_hidden_states:
+            image_enc_hidden_states = self.image_encoder(image, output_hidden_states=True).hidden_states[-2]
+            image_enc_hidden_states = image_enc_hidden_states.repeat_interleave(num_images_per_prompt, dim=0)
+            uncond_image_enc_hidden_states = self.image_encoder(torch.zeros_like(image), output_hidden_states=True).hidden_states[-2]
+            uncond_image_enc_hidden_states = uncond_image_enc_hidden_states.repeat_interleave(num_images_per_prompt, dim=0)
+            return image_enc_hidden_states, uncond_image_enc_hidden_states
+        image_embeds = self.image_encoder(image).image_embeds
+        image_embeds = image_embeds.repeat_interleave(num_images_per_prompt, dim=0)
+        uncond_image_embeds = torch.zeros_like(image_embeds)
+        return image_embeds, uncond_image_embeds
+
     # ------------------------------------------------------------------------------------------ encode_prompt
     def encode_prompt(self, prompt, device, num_images_per_prompt, do_classifier_free_guidance, negative_prompt=None,
                       prompt_embeds=None, negative_prompt_embeds=None, lora_scale=None, clip_skip=None):
@@ -521,9 +566,18 @@ class I2VAdapterPipeline:
                                  "limit (frames x latent height x width of i2v_freeinit_mix) -- disable_free_init() for longer clips")
         self.unet._sync_lora()      # before anything reads a weight, a pack or the weights' versions (_graph_key)
         if ip_adapter_image is not None:
-            raise NotImplementedError(
-                "the CLIP image encoder is out of scope of this build (SURVEY section 2 row 3b): pass `image_embeds` "
-                "(and `negative_image_embeds`) instead of `ip_adapter_image`")
+            if image_embeds is not None:
+                raise ValueError("Cannot forward both `ip_adapter_image` and `image_embeds`. Please make sure to only forward one of "
+                                 "the two.")
+            if self.image_encoder is None:
+                raise NotImplementedError(
+                    "`ip_adapter_image` needs an image encoder and this pipeline has none: `load_ip_adapter(path, subfolder=...)` loads "
+                    "`<path>/<subfolder>/image_encoder` (IP-Adapter's `models/image_encoder`), or build the pipeline with "
+                    "`image_encoder=CLIPVisionModelWithProjection.from_pretrained(...)`, or pass `image_embeds` (and "
+                    "`negative_image_embeds`) instead")
+            if self.unet.encoder_hid_proj is None:
+                # (the reference encodes the image and the UNet then ignores it silently, unet:1351)
+                raise ValueError("`ip_adapter_image` was passed but the UNet has no IP-Adapter: call `load_ip_adapter` first")
         if prompt is not None and prompt_embeds is not None:                                    # pipe:222-226
             raise ValueError(f"Cannot forward both `prompt`: {prompt} and `prompt_embeds`: {prompt_embeds}. Please make sure to"
                              " only forward one of the two.")
@@ -541,6 +595,10 @@ class I2VAdapterPipeline:
                 prompt_embeds=None, negative_prompt_embeds=negative_prompt_embeds,
                 lora_scale=cross_attention_kwargs.get("scale", None) if cross_attention_kwargs is not None else None,
                 clip_skip=clip_skip)
+        if ip_adapter_image is not None:                                                        # pipe:616-622
+            # once per sample, before the step is captured; the ImageProjection is the only `encoder_hid_proj` there is
+            # (`_load_ip_adapter_weights` refuses IP-Adapter Plus), so it is the plain branch: no negative half is ever encoded
+            image_embeds, negative_image_embeds = self.encode_image(ip_adapter_image, self.unet.device, num_videos_per_prompt, False)
         if condition_image is not None and condition_image_latents is None:                     # pipe:624-627
             if height is None or width is None:
                 height = height or self.unet.config.sample_size * self.vae_scale_factor         # pipe:568-569
@@ -752,6 +810,9 @@ def build_parser():
     parser.add_argument("--model_path", type=str, default="./SG161222_Realistic_Vision_V5.1_noVAE/")
     parser.add_argument("--motion_adapter_path", type=str, default="./animatediff-motion-adapter-v1-5-2")
     parser.add_argument("--ip_adapter_path", type=str, default="./IP-Adapter/")
+    parser.add_argument("--ip_adapter", action="store_true",
+                        help="load IP-Adapter and its CLIP image encoder from <ip_adapter_path>/models (pipe:783) and pass every row's "
+                             "condition image as `ip_adapter_image` (pipe:796) unless --embeds holds image_embeds; off by default")
     parser.add_argument("--checkpoint_root", type=str, default="./checkpoint")
     parser.add_argument("--samples_root", type=str, default="./samples")
     parser.add_argument("--num_frames", type=int, default=16)
@@ -798,8 +859,9 @@ def main(argv=None):
 
     The CSV's prompts are encoded by the HIP CLIP text encoder (`<model_path>/text_encoder`, clip_text.py) with transformers'
     `CLIPTokenizer` (`<model_path>/tokenizer`), as the reference does (pipe:752-753).  With --embeds the per-row `prompt_embeds`,
-    `negative_prompt_embeds` (and `image_embeds`: the CLIP image encoder is out of scope) come from a safetensors file instead and
-    neither is loaded; everything else follows the reference driver."""
+    `negative_prompt_embeds` (and `image_embeds`) come from a safetensors file instead and neither is loaded.  With --ip_adapter the
+    IP-Adapter and its CLIP image encoder (`<ip_adapter_path>/models/image_encoder`, clip_vision.py) are loaded and the condition
+    image is the image prompt, as in the reference (pipe:783, 796); everything else follows the reference driver."""
     import logging
     import os
 
@@ -854,7 +916,7 @@ def main(argv=None):
         text_encoder, tokenizer = load_text_encoder(args.model_path)                             # pipe:752-753
 
     pipe = I2VAdapterPipeline(vae, text_encoder, tokenizer, unet2d.to(device).half(), motion_adapter, i2v_adapter, scheduler)
-    if "image_embeds" in emb:                                                                    # pipe:783
+    if "image_embeds" in emb or args.ip_adapter:                                                 # pipe:783
         pipe.load_ip_adapter(args.ip_adapter_path, subfolder="models", weight_name="ip-adapter_sd15.bin")
     pipe.to(device, torch.float16)
     pipe.enable_vae_slicing()                                                                    # pipe:787
@@ -888,8 +950,11 @@ def main(argv=None):
                         negative_prompt_embeds=neg[ind: ind + 1] if neg.shape[0] == n else neg[:1])
         else:
             text = dict(prompt=str(eval_prompts[ind]), negative_prompt=args.negative_prompt)
-        out = pipe(**text,
-                   image_embeds=emb["image_embeds"][ind: ind + 1] if "image_embeds" in emb else None,
+        if "image_embeds" in emb:
+            image = dict(image_embeds=emb["image_embeds"][ind: ind + 1])
+        else:
+            image = dict(ip_adapter_image=condition_images[ind]) if args.ip_adapter else {}      # pipe:796
+        out = pipe(**text, **image,
                    condition_image=condition_images[ind], num_frames=args.num_frames, guidance_scale=args.guidance_scale,
                    num_inference_steps=args.num_inference_steps, frame_similarity_sample_ratio=0.9,
                    height=args.height, width=args.width, output_type="pil", generator=g(0),

@@ -115,6 +115,12 @@ def _work_clip_attn(args, kw, out):
     return "clip_text", 2.0 * 2 * b * h * d * l * (l + 1) / 2, 4 * _numel_bytes(out), f"causal b{b} h{h} L{l} d{d}"
 
 
+def _work_clip_vision_attn(args, kw, out):
+    b, l, h, d = kw["batch"], kw["length"], kw["heads"], kw["head_dim"]
+    # every L x L tile pair, Q K^T and P V; q / k / v read once, out written once
+    return "clip_vision", 2.0 * 2 * b * h * d * l * l, 4 * _numel_bytes(out), f"bidirectional b{b} h{h} L{l} d{d}"
+
+
 def _work_misc(name):
     def f(args, kw, out):
         return name, 0.0, 2 * _numel_bytes(out), ""
@@ -133,6 +139,9 @@ _WRAPPED = {
     # the CLIP text tower's own kernels (once per prompt, not per step): one class, so that a profile of `pipe(prompt=...)` shows what
     # the prompt cost beside the step's classes; its GEMMs and LayerNorms are counted with theirs
     "clip_embed": _work_misc("clip_text"), "clip_attention": _work_clip_attn, "quick_gelu": _work_misc("clip_text"),
+    # the CLIP vision tower's own kernels (once per image prompt): a class of their own, for `pipe(ip_adapter_image=...)`
+    "clip_patchify": _work_misc("clip_vision"), "clip_vision_embed": _work_misc("clip_vision"),
+    "clip_vision_attention": _work_clip_vision_attn,
 }
 
 

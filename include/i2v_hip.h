@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define I2V_ABI_VERSION 17
+#define I2V_ABI_VERSION 18
 
 #define I2V_OK 0
 #define I2V_ERR_INVALID_ARG (-1)
@@ -664,6 +664,37 @@ int i2v_clip_embed_f16(const void* tok, const void* pos, const int32_t* ids, con
 int i2v_clip_attention_f16(const void* qkv, int64_t ld_qkv, int32_t q_off, int32_t k_off, int32_t v_off, void* out, int64_t ld_out,
                            int32_t batch, int32_t len, int32_t heads, int32_t head_dim, float scale, i2v_stream_t stream);
 int i2v_quick_gelu_f16(const void* x, void* y, int64_t n, i2v_stream_t stream);
+
+/* (ABI 18) The CLIP vision tower (transformers CLIPVisionModelWithProjection as the pipeline's encode_image calls it, pipe:323-345; IP-Adapter's
+ * image encoder, OpenCLIP ViT-H/14: 32 pre-LN layers, width 1280, 16 heads of 80, 256 patches of 14 px + the class token = 257 tokens).  Its
+ * projections and LayerNorms are i2v_gemm_f16 / i2v_layernorm_f16, its quick-GELU (ViT-L/14) i2v_quick_gelu_f16; these are the three kernels
+ * nothing else has a use for.  Not per-step work: an image is encoded once per sample.
+ *   i2v_clip_patchify_f16   the im2col of the patch embedding (a bias-free convolution of kernel = stride = patch): pixel_values fp16
+ *       [batch, channels, size, size] dense -> out fp16 [batch * (size / patch)^2, ld_out].  Row b * P + py * (size / patch) + px holds patch
+ *       (py, px) in column order (c, dy, dx) -- the order of patch_embedding.weight.flatten(1) -- and columns channels * patch^2 .. ld_out - 1
+ *       are written as ZERO, so the embedding is i2v_gemm_f16 against the weight zero-padded to the same row length (ViT-H/14: 588 -> 592, the
+ *       GEMM's K % 8 == 0).  ld_out a multiple of 8, >= channels * patch^2.
+ *       I2V_ERR_INVALID_ARG: size % patch != 0, null / misaligned / overlapping operands, a bad ld_out; nothing is launched.
+ *   i2v_clip_vision_embed_f16   out[b, 0, :] = fp16(float(cls) + float(pos[0])), out[b, 1 + t, :] = fp16(float(patch[b * patches + t]) +
+ *       float(pos[1 + t])): cls fp16 [hidden], patch fp16 [batch * patches, ld_patch] (the GEMM's result), pos fp16 [patches + 1, hidden] dense,
+ *       out fp16 [batch * (patches + 1), hidden] dense.  hidden % 8 == 0 (one 16-byte chunk per lane).
+ *   i2v_clip_vision_attention_f16   NON-causal multi-head self-attention of one sequence per batch entry:
+ *           out[b * len + i, h * d + :] = softmax_j<len( scale * q[b, i, h, :] . k[b, j, h, :] ) v[b, j, h, :]
+ *       The argument list is i2v_clip_attention_f16's: q, k, v read in place from the packed result of one QKV GEMM (qkv fp16 [batch * len,
+ *       ld_qkv], head h of q / k / v in columns q_off / k_off / v_off + h * head_dim, offsets multiples of 8), out fp16 [batch * len, ld_out].
+ *       Grid (batch * heads, ceil(len / 64)): a workgroup of 4 waves owns 64 queries and stages the head's whole K (head_dim padded with zeros to
+ *       the MFMA K-step, 80 -> 96) and V^T (keys padded with zeros to a multiple of 32) in LDS, 114 KB.  Key j is visible iff j < len, by index
+ *       compare (P of a pad key is exactly 0; key 0 is always visible, so no row is fully masked); rows at or beyond batch * len are never
+ *       read, only queries < len are stored.  Numerics as i2v_clip_attention_f16: MFMA 16x16x32 with fp32 accumulation, softmax in fp32 in
+ *       base 2 with the logits scaled by scale * log2(e) in fp32, P rounded to fp16 for P V, the row sum taken over the unrounded P.
+ *       I2V_ERR_UNSUPPORTED (nothing launched): head_dim not 64 or 80, len > 288 (L_max: 18 key tiles; ViT-H/14 at 224 px is 257).
+ *       I2V_ERR_INVALID_ARG: null / misaligned / overlapping operands, bad strides or offsets. */
+int i2v_clip_patchify_f16(const void* pixel_values, void* out, int64_t ld_out, int32_t batch, int32_t channels, int32_t size, int32_t patch,
+                          i2v_stream_t stream);
+int i2v_clip_vision_embed_f16(const void* cls, const void* patch, int64_t ld_patch, const void* pos, void* out, int32_t batch, int32_t patches,
+                              int32_t hidden, i2v_stream_t stream);
+int i2v_clip_vision_attention_f16(const void* qkv, int64_t ld_qkv, int32_t q_off, int32_t k_off, int32_t v_off, void* out, int64_t ld_out,
+                                  int32_t batch, int32_t len, int32_t heads, int32_t head_dim, float scale, i2v_stream_t stream);
 
 /* First-frame-similarity prior and the initial add_noise of the sampling loop, pipe:647-656:
  *   prior   = mask * GaussianBlur3x3(cond) + (1 - mask) * cond, mask = (mask_uniform < strength), per frame (pipe:648-654)

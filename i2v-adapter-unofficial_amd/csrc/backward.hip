@@ -1210,8 +1210,6 @@ int launch_bwd(const i2v_attn_bwd_params& p, hipStream_t s) {
   return rc;
 }
 
-inline bool al16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
-
 }  // namespace
 
 extern "C" int i2v_attention_lse_f32(const i2v_attn_params* pp, float* lse, i2v_stream_t stream) {
@@ -1223,7 +1221,7 @@ extern "C" int i2v_attention_lse_f32(const i2v_attn_params* pp, float* lse, i2v_
   I2V_CHECK_ARG(p.head_dim > 0 && p.head_dim % 8 == 0 && p.head_dim <= 160, "i2v_attention_lse_f32: head_dim (%d) must be a "
                 "multiple of 8 and <= 160", p.head_dim);
   I2V_CHECK_ARG(p.q_row_stride % 8 == 0 && p.k_row_stride % 8 == 0 && p.q_batch_stride % 8 == 0 && p.k_batch_stride % 8 == 0 &&
-                    al16(p.q) && al16(p.k), "i2v_attention_lse_f32: q / k strides must be multiples of 8 elements, 16-byte aligned");
+                    i2v_al16(p.q) && i2v_al16(p.k), "i2v_attention_lse_f32: q / k strides must be multiples of 8 elements, 16-byte aligned");
   I2V_CHECK_ARG(p.heads <= 65535 && p.batch_q <= 65535, "i2v_attention_lse_f32: heads / batch_q exceed the grid limits");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const float c = p.scale * LOG2E;
@@ -1262,11 +1260,11 @@ extern "C" int i2v_attention_bwd_f16(const i2v_attn_bwd_params* pp, i2v_stream_t
                              p.v_batch_stride, p.kt_batch_stride, p.do_row_stride, p.do_batch_stride, p.dq_row_stride,
                              p.dq_batch_stride};
   for (int64_t st : strides) I2V_CHECK_ARG(st % 8 == 0, "i2v_attention_bwd_f16: strides must be multiples of 8 elements");
-  I2V_CHECK_ARG(al16(p.q) && al16(p.k) && al16(p.v) && al16(p.kt) && al16(p.dout) && al16(p.dq) && al16(p.lse) && al16(p.delta),
+  I2V_CHECK_ARG(i2v_al16(p.q) && i2v_al16(p.k) && i2v_al16(p.v) && i2v_al16(p.kt) && i2v_al16(p.dout) && i2v_al16(p.dq) && i2v_al16(p.lse) && i2v_al16(p.delta),
                 "i2v_attention_bwd_f16: pointers must be 16-byte aligned");
   I2V_CHECK_ARG(p.kv_partitions >= 0, "i2v_attention_bwd_f16: kv_partitions must be >= 0");
   if (p.dk != nullptr && p.kv_partitions > 1)
-    I2V_CHECK_ARG(p.dkv_partial != nullptr && al16(p.dkv_partial) && p.kv_group % p.kv_partitions == 0 &&
+    I2V_CHECK_ARG(p.dkv_partial != nullptr && i2v_al16(p.dkv_partial) && p.kv_group % p.kv_partitions == 0 &&
                       (p.heads * p.head_dim) % 4 == 0,
                   "i2v_attention_bwd_f16: kv_partitions (%d) needs the dkv_partial scratch and must divide kv_group (%d)",
                   p.kv_partitions, p.kv_group);
@@ -1275,8 +1273,8 @@ extern "C" int i2v_attention_bwd_f16(const i2v_attn_bwd_params* pp, i2v_stream_t
     const int lq8 = (p.lq + 7) & ~7;
     I2V_CHECK_ARG(p.qt_row_stride >= lq8 && p.qt_row_stride % 8 == 0 && p.dot_row_stride >= lq8 && p.dot_row_stride % 8 == 0 &&
                       p.qt_batch_stride % 8 == 0 && p.dot_batch_stride % 8 == 0 && p.dk_row_stride % 8 == 0 &&
-                      p.dk_batch_stride % 8 == 0 && p.dv_row_stride % 8 == 0 && p.dv_batch_stride % 8 == 0 && al16(p.qt) &&
-                      al16(p.doutt) && al16(p.dk) && al16(p.dv),
+                      p.dk_batch_stride % 8 == 0 && p.dv_row_stride % 8 == 0 && p.dv_batch_stride % 8 == 0 && i2v_al16(p.qt) &&
+                      i2v_al16(p.doutt) && i2v_al16(p.dk) && i2v_al16(p.dv),
                   "i2v_attention_bwd_f16: Q^T / dO^T / dK / dV strides and alignment");
   }
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
@@ -1305,7 +1303,7 @@ extern "C" int i2v_transpose_f16(const void* src, int64_t src_batch_stride, int6
 extern "C" int i2v_rowdot_heads_f32(const void* a, int64_t lda, const void* b, int64_t ldb, float* out, int64_t rows,
                                     int32_t rows_per_batch, int32_t heads, int32_t head_dim, i2v_stream_t stream) {
   I2V_CHECK_ARG(a && b && out && rows > 0 && rows_per_batch > 0 && rows % rows_per_batch == 0 && heads > 0 && head_dim > 0 &&
-                    head_dim % 8 == 0 && lda % 8 == 0 && ldb % 8 == 0 && al16(a) && al16(b),
+                    head_dim % 8 == 0 && lda % 8 == 0 && ldb % 8 == 0 && i2v_al16(a) && i2v_al16(b),
                 "i2v_rowdot_heads_f32: bad arguments");
   hipLaunchKernelGGL(rowdot_kernel, dim3((unsigned)i2v_cdiv(rows * heads, 256)), dim3(256), 0,
                      reinterpret_cast<hipStream_t>(stream), reinterpret_cast<const f16*>(a), lda,
@@ -1317,7 +1315,7 @@ extern "C" int i2v_layernorm_bwd_f16(const void* x, int64_t ldx, const void* dn,
                                      const void* add, int64_t ldadd, void* dx, int64_t lddx, int32_t rows, int32_t C, float eps,
                                      i2v_stream_t stream) {
   I2V_CHECK_ARG(x && dn && gamma && dx && rows > 0 && C > 0 && C % 8 == 0 && ldx % 8 == 0 && lddn % 8 == 0 && lddx % 8 == 0 &&
-                    (!add || ldadd % 8 == 0) && al16(x) && al16(dn) && al16(gamma) && al16(dx) && (!add || al16(add)),
+                    (!add || ldadd % 8 == 0) && i2v_al16(x) && i2v_al16(dn) && i2v_al16(gamma) && i2v_al16(dx) && (!add || i2v_al16(add)),
                 "i2v_layernorm_bwd_f16: bad arguments (C and the strides must be multiples of 8, pointers 16-byte aligned)");
   hipLaunchKernelGGL(ln_bwd_kernel, dim3((unsigned)i2v_cdiv(rows, 4)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
                      reinterpret_cast<const f16*>(x), ldx, reinterpret_cast<const f16*>(dn), lddn,
@@ -1329,7 +1327,7 @@ extern "C" int i2v_layernorm_bwd_f16(const void* x, int64_t ldx, const void* dn,
 extern "C" int i2v_geglu_bwd_f16(const void* h, int64_t ldh, const void* dy, int64_t lddy, void* dh, int64_t lddh, int64_t rows,
                                  int32_t inner, i2v_stream_t stream) {
   I2V_CHECK_ARG(h && dy && dh && rows > 0 && inner > 0 && inner % 4 == 0 && ldh % 8 == 0 && lddh % 8 == 0 && lddy % 4 == 0 &&
-                    al16(h) && al16(dh) && (reinterpret_cast<uintptr_t>(dy) & 7) == 0,
+                    i2v_al16(h) && i2v_al16(dh) && (reinterpret_cast<uintptr_t>(dy) & 7) == 0,
                 "i2v_geglu_bwd_f16: bad arguments");
   hipLaunchKernelGGL(geglu_bwd_kernel, dim3(ew_grid(rows * (inner / 4))), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
                      reinterpret_cast<const f16*>(h), ldh, reinterpret_cast<const f16*>(dy), lddy, reinterpret_cast<f16*>(dh),
@@ -1339,7 +1337,7 @@ extern "C" int i2v_geglu_bwd_f16(const void* h, int64_t ldh, const void* dy, int
 
 extern "C" int i2v_geglu_f16(const void* h, int64_t ldh, void* y, int64_t ldy, int64_t rows, int32_t inner, i2v_stream_t stream) {
   I2V_CHECK_ARG(h && y && rows > 0 && inner > 0 && inner % 8 == 0 && ldh % 8 == 0 && ldy % 8 == 0 && ldh >= 2 * inner &&
-                    ldy >= inner && al16(h) && al16(y),
+                    ldy >= inner && i2v_al16(h) && i2v_al16(y),
                 "i2v_geglu_f16: bad arguments");
   hipLaunchKernelGGL(geglu_fwd_kernel, dim3(ew_grid(rows * (inner / 8))), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
                      reinterpret_cast<const f16*>(h), ldh, reinterpret_cast<f16*>(y), ldy, rows, inner);
@@ -1385,7 +1383,7 @@ extern "C" int i2v_colsum_det_f32(const void* a, int64_t lda, const void* b, int
 extern "C" int i2v_masked_mse_grad_f16(const void* y, const void* target, void* grad, int64_t n_img, int32_t tokens,
                                        int32_t channels, int32_t frames, float coef, i2v_stream_t stream) {
   I2V_CHECK_ARG(y && target && grad && n_img > 0 && tokens > 0 && channels > 0 && channels % 8 == 0 && frames > 0 &&
-                    n_img % frames == 0 && al16(y) && al16(target) && al16(grad),
+                    n_img % frames == 0 && i2v_al16(y) && i2v_al16(target) && i2v_al16(grad),
                 "i2v_masked_mse_grad_f16: bad arguments");
   hipLaunchKernelGGL(mse_grad_kernel, dim3(ew_grid(n_img * tokens * (channels / 8))), dim3(256), 0,
                      reinterpret_cast<hipStream_t>(stream), reinterpret_cast<const f16*>(y),
@@ -1396,7 +1394,7 @@ extern "C" int i2v_masked_mse_grad_f16(const void* y, const void* target, void* 
 extern "C" int i2v_masked_mse_grad_f32(const float* y, const float* target, void* grad, float* rowsq, int64_t n_img, int32_t tokens,
                                        int32_t channels, int32_t frames, float coef, i2v_stream_t stream) {
   I2V_CHECK_ARG(y && target && grad && rowsq && n_img > 0 && tokens > 0 && channels > 0 && channels % 8 == 0 && frames > 0 &&
-                    n_img % frames == 0 && al16(y) && al16(target) && al16(grad),
+                    n_img % frames == 0 && i2v_al16(y) && i2v_al16(target) && i2v_al16(grad),
                 "i2v_masked_mse_grad_f32: bad arguments");
   hipLaunchKernelGGL(mse_grad_f32_kernel, dim3(ew_grid(n_img * tokens)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), y, target,
                      reinterpret_cast<f16*>(grad), rowsq, n_img, tokens, channels, frames, coef);
@@ -1404,7 +1402,7 @@ extern "C" int i2v_masked_mse_grad_f32(const float* y, const float* target, void
 }
 
 extern "C" int i2v_add_f16(const void* a, const void* b, void* out, int64_t n, i2v_stream_t stream) {
-  I2V_CHECK_ARG(a && b && out && n > 0 && n % 8 == 0 && al16(a) && al16(b) && al16(out), "i2v_add_f16: bad arguments");
+  I2V_CHECK_ARG(a && b && out && n > 0 && n % 8 == 0 && i2v_al16(a) && i2v_al16(b) && i2v_al16(out), "i2v_add_f16: bad arguments");
   hipLaunchKernelGGL(add_kernel, dim3(ew_grid(n / 8)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
                      reinterpret_cast<const f16*>(a), reinterpret_cast<const f16*>(b), reinterpret_cast<f16*>(out), n / 8);
   return i2v_check_launch("i2v_add_f16");
@@ -1413,7 +1411,7 @@ extern "C" int i2v_add_f16(const void* a, const void* b, void* out, int64_t n, i
 extern "C" int i2v_permute_rows_f16(const void* src, void* dst, int64_t batches, int32_t frames, int32_t hw, int32_t channels,
                                     int32_t to_pixel_major, i2v_stream_t stream) {
   I2V_CHECK_ARG(src && dst && src != dst && batches > 0 && frames > 0 && hw > 0 && channels > 0 && channels % 8 == 0 &&
-                    al16(src) && al16(dst), "i2v_permute_rows_f16: bad arguments");
+                    i2v_al16(src) && i2v_al16(dst), "i2v_permute_rows_f16: bad arguments");
   hipLaunchKernelGGL(permute_rows_kernel, dim3(ew_grid(batches * frames * hw * (channels / 8))), dim3(256), 0,
                      reinterpret_cast<hipStream_t>(stream), reinterpret_cast<const f16*>(src), reinterpret_cast<f16*>(dst),
                      batches, frames, hw, channels, to_pixel_major);
@@ -1422,7 +1420,7 @@ extern "C" int i2v_permute_rows_f16(const void* src, void* dst, int64_t batches,
 
 extern "C" int i2v_zero_insert2x_f16(const void* src, void* dst, int64_t n_img, int32_t h, int32_t w, int32_t channels,
                                      i2v_stream_t stream) {
-  I2V_CHECK_ARG(src && dst && n_img > 0 && h > 0 && w > 0 && channels > 0 && channels % 8 == 0 && al16(src) && al16(dst),
+  I2V_CHECK_ARG(src && dst && n_img > 0 && h > 0 && w > 0 && channels > 0 && channels % 8 == 0 && i2v_al16(src) && i2v_al16(dst),
                 "i2v_zero_insert2x_f16: bad arguments");
   hipLaunchKernelGGL(zero_insert_kernel, dim3(ew_grid(n_img * 4 * h * w * (channels / 8))), dim3(256), 0,
                      reinterpret_cast<hipStream_t>(stream), reinterpret_cast<const f16*>(src), reinterpret_cast<f16*>(dst), n_img, h,
@@ -1432,7 +1430,7 @@ extern "C" int i2v_zero_insert2x_f16(const void* src, void* dst, int64_t n_img, 
 
 extern "C" int i2v_sum_pool2x_f16(const void* src, void* dst, int64_t n_img, int32_t h, int32_t w, int32_t channels,
                                   i2v_stream_t stream) {
-  I2V_CHECK_ARG(src && dst && n_img > 0 && h > 0 && w > 0 && channels > 0 && channels % 8 == 0 && al16(src) && al16(dst),
+  I2V_CHECK_ARG(src && dst && n_img > 0 && h > 0 && w > 0 && channels > 0 && channels % 8 == 0 && i2v_al16(src) && i2v_al16(dst),
                 "i2v_sum_pool2x_f16: bad arguments");
   hipLaunchKernelGGL(sum_pool_kernel, dim3(ew_grid(n_img * h * w * (channels / 8))), dim3(256), 0,
                      reinterpret_cast<hipStream_t>(stream), reinterpret_cast<const f16*>(src), reinterpret_cast<f16*>(dst), n_img, h,

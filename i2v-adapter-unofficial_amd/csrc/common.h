@@ -41,6 +41,17 @@ int i2v_big_lds_kernel_cus(const void* func, size_t lds_bytes);
 int i2v_persistent_grid(int ntiles, int cus);
 
 static inline int64_t i2v_cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
+// host-side argument checks: a pointer the 16-byte loads / stores may take; byte ranges [a, a + na) and [b, b + nb) that intersect
+static inline bool i2v_al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+static inline bool i2v_overlap(const void* a, int64_t na, const void* b, int64_t nb) {
+  const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
+  return x < y + (uintptr_t)nb && y < x + (uintptr_t)na;
+}
+// grid of a grid-stride elementwise kernel: one lane per item, at least one block, at most max_blocks
+static inline unsigned i2v_ew_grid(int64_t items, int threads, int max_blocks) {
+  const int64_t g = i2v_cdiv(items, threads);
+  return (unsigned)(g < 1 ? 1 : (g < max_blocks ? g : max_blocks));
+}
 
 // D(16x16, f32) += A(16x32, f16) * B(32x16, f16)
 //   A fragment: lane l holds A[row = l & 15][k = 8 * (l >> 4) + j], j = 0..7

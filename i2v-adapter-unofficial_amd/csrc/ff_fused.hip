@@ -521,8 +521,6 @@ __global__ __launch_bounds__(64 * H) void ff_fused_kernel(const i2v_ff_fused_par
 #endif
 }
 
-inline bool al16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
-
 constexpr size_t FF_LDS = 2 * (size_t)FF_PIX * 16 * 320 * sizeof(f16);      // panel + (chunk buffers | raw rows): 160 KB
 
 template <bool PROJ, bool HILO = false>
@@ -553,20 +551,20 @@ extern "C" int i2v_ff_fused_f16(const i2v_ff_fused_params* pp, i2v_stream_t stre
                 "i2v_ff_fused_f16: rows %lld channels %d inner %d is not a fused shape (i2v_ff_fused_supported)", (long long)p.rows,
                 p.channels, p.inner);
   I2V_CHECK_ARG(p.ldx >= p.channels && p.ldx % 8 == 0 && p.ldo >= p.channels && p.ldo % 8 == 0, "i2v_ff_fused_f16: row strides");
-  I2V_CHECK_ARG(al16(p.x) && al16(p.gamma) && al16(p.beta) && al16(p.w1) && al16(p.b1) && al16(p.w2) && al16(p.b2) && al16(p.out),
+  I2V_CHECK_ARG(i2v_al16(p.x) && i2v_al16(p.gamma) && i2v_al16(p.beta) && i2v_al16(p.w1) && i2v_al16(p.b1) && i2v_al16(p.w2) && i2v_al16(p.b2) && i2v_al16(p.out),
                 "i2v_ff_fused_f16: pointers must be 16-byte aligned");
   // one workgroup reads a tile's rows through a 32-bit buffer descriptor
   I2V_CHECK_ARG(p.ldx < (1 << 24), "i2v_ff_fused_f16: ldx");
   if (tail) {
     I2V_CHECK_ARG(p.b3 && p.res2, "i2v_ff_fused_f16: the tail needs w3, b3 and res2");
-    I2V_CHECK_ARG(al16(p.w3) && al16(p.b3) && al16(p.res2) && p.ld_res2 >= p.channels && p.ld_res2 % 8 == 0,
+    I2V_CHECK_ARG(i2v_al16(p.w3) && i2v_al16(p.b3) && i2v_al16(p.res2) && p.ld_res2 >= p.channels && p.ld_res2 % 8 == 0,
                   "i2v_ff_fused_f16: tail operands must be 16-byte aligned, ld_res2 a multiple of 8");
     I2V_CHECK_ARG(i2v_ff_fused_tail_supported(p.rows, p.channels, p.inner, p.perm_frames, p.perm_hw) ||
                       ff_cus<true>() == 0,
                   "i2v_ff_fused_f16: perm_frames %d / perm_hw %d do not describe rows %lld (i2v_ff_fused_tail_supported)", p.perm_frames,
                   p.perm_hw, (long long)p.rows);
     I2V_CHECK_ARG(!(p.perm_frames > 0 && p.out == p.x), "i2v_ff_fused_f16: out must not alias x when the tail permutes the rows");
-    I2V_CHECK_ARG((p.res2_lo == nullptr) == (p.out_lo == nullptr) && al16(p.res2_lo) && al16(p.out_lo) && (p.out_lo == nullptr || p.out_lo != p.out),
+    I2V_CHECK_ARG((p.res2_lo == nullptr) == (p.out_lo == nullptr) && i2v_al16(p.res2_lo) && i2v_al16(p.out_lo) && (p.out_lo == nullptr || p.out_lo != p.out),
                   "i2v_ff_fused_f16: res2_lo and out_lo come together, 16-byte aligned");
   } else {
     I2V_CHECK_ARG(p.b3 == nullptr && p.res2 == nullptr && p.perm_frames == 0 && p.perm_hw == 0 && p.res2_lo == nullptr && p.out_lo == nullptr,

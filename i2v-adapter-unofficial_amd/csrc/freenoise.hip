@@ -74,16 +74,6 @@ __global__ __launch_bounds__(FN_THREADS) void freenoise_blend_kernel(const f16* 
   }
 }
 
-inline bool fn_al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-inline bool fn_overlap(const void* a, int64_t na, const void* b, int64_t nb) {
-  const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
-  return x < y + (uintptr_t)nb && y < x + (uintptr_t)na;
-}
-inline unsigned fn_grid(int64_t total) {
-  const int64_t g = i2v_cdiv(total, FN_THREADS);
-  return (unsigned)(g < FN_MAX_BLOCKS ? g : FN_MAX_BLOCKS);
-}
-
 // the checks the two entry points share; `what` names the entry point
 int fn_check(const char* what, const void* src, int64_t ld_src, const void* dst, int64_t ld_dst, int64_t n_pixels, int32_t frames,
              int32_t windows, int32_t length, int32_t c, int64_t src_rows, int64_t dst_rows) {
@@ -94,10 +84,10 @@ int fn_check(const char* what, const void* src, int64_t ld_src, const void* dst,
   I2V_CHECK_ARG(c > 0 && c % 8 == 0, "%s: c %d must be a positive multiple of 8", what, c);
   I2V_CHECK_ARG(ld_src >= c && ld_dst >= c && ld_src % 8 == 0 && ld_dst % 8 == 0 && ld_src < (1 << 20) && ld_dst < (1 << 20),
                 "%s: row strides %lld / %lld must be multiples of 8, at least c %d", what, (long long)ld_src, (long long)ld_dst, c);
-  I2V_CHECK_ARG(fn_al16(src) && fn_al16(dst), "%s: pointers must be 16-byte aligned", what);
+  I2V_CHECK_ARG(i2v_al16(src) && i2v_al16(dst), "%s: pointers must be 16-byte aligned", what);
   I2V_CHECK_ARG(src_rows < ((int64_t)1 << 31) && dst_rows < ((int64_t)1 << 31), "%s: problem too large (%lld / %lld rows)", what,
                 (long long)src_rows, (long long)dst_rows);
-  I2V_CHECK_ARG(!fn_overlap(src, ((src_rows - 1) * ld_src + c) * 2, dst, ((dst_rows - 1) * ld_dst + c) * 2),
+  I2V_CHECK_ARG(!i2v_overlap(src, ((src_rows - 1) * ld_src + c) * 2, dst, ((dst_rows - 1) * ld_dst + c) * 2),
                 "%s: dst is a new tensor (it must not overlap src)", what);
   return I2V_OK;
 }
@@ -112,7 +102,8 @@ extern "C" int i2v_freenoise_gather_f16(const void* src, int64_t ld_src, void* d
   I2V_CHECK_ARG(starts != nullptr, "i2v_freenoise_gather_f16: null window table");
   const int chunks = c / 8;
   const int64_t total = dst_rows * chunks;
-  hipLaunchKernelGGL(freenoise_gather_kernel, dim3(fn_grid(total)), dim3(FN_THREADS), 0, reinterpret_cast<hipStream_t>(stream),
+  hipLaunchKernelGGL(freenoise_gather_kernel, dim3(i2v_ew_grid(total, FN_THREADS, FN_MAX_BLOCKS)), dim3(FN_THREADS), 0,
+                     reinterpret_cast<hipStream_t>(stream),
                      reinterpret_cast<const f16*>(src), ld_src, reinterpret_cast<f16*>(dst), ld_dst, starts, frames, windows, length, chunks,
                      total);
   return i2v_check_launch("i2v_freenoise_gather_f16");
@@ -128,7 +119,8 @@ extern "C" int i2v_freenoise_blend_f16(const void* src, int64_t ld_src, void* ds
   I2V_CHECK_ARG(pairs >= 1 && pairs <= FN_MAX_PAIRS, "i2v_freenoise_blend_f16: pairs %d must be in [1, %d]", pairs, FN_MAX_PAIRS);
   const int chunks = c / 8;
   const int64_t total = dst_rows * chunks;
-  hipLaunchKernelGGL(freenoise_blend_kernel, dim3(fn_grid(total)), dim3(FN_THREADS), 0, reinterpret_cast<hipStream_t>(stream),
+  hipLaunchKernelGGL(freenoise_blend_kernel, dim3(i2v_ew_grid(total, FN_THREADS, FN_MAX_BLOCKS)), dim3(FN_THREADS), 0,
+                     reinterpret_cast<hipStream_t>(stream),
                      reinterpret_cast<const f16*>(src), ld_src, reinterpret_cast<f16*>(dst), ld_dst, idx, coef, frames, windows * length, pairs,
                      chunks, total);
   return i2v_check_launch("i2v_freenoise_blend_f16");

@@ -155,8 +155,6 @@ __global__ __launch_bounds__(FU_THREADS) void freeu_kernel(const f16* __restrict
   }
 }
 
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 }  // namespace
 
 extern "C" int i2v_freeu_f16(const void* hidden, const void* hidden_lo, void* hidden_out, void* hidden_out_lo, const void* skip,
@@ -172,8 +170,8 @@ extern "C" int i2v_freeu_f16(const void* hidden, const void* hidden_lo, void* hi
   I2V_CHECK_ARG(c1 % 8 == 0 && c2 % 8 == 0, "i2v_freeu_f16: not implemented for this problem (c1 %d, c2 %d: multiples of 8)", c1, c2);
   I2V_CHECK_ARG(hidden != hidden_out && skip != skip_out && (hidden_lo == nullptr || hidden_lo != hidden_out_lo),
                 "i2v_freeu_f16: the outputs are new tensors (not in place)");
-  I2V_CHECK_ARG(aligned16(hidden) && aligned16(hidden_out) && aligned16(skip) && aligned16(skip_out) && aligned16(hidden_lo) &&
-                    aligned16(hidden_out_lo),
+  I2V_CHECK_ARG(i2v_al16(hidden) && i2v_al16(hidden_out) && i2v_al16(skip) && i2v_al16(skip_out) && i2v_al16(hidden_lo) &&
+                    i2v_al16(hidden_out_lo),
                 "i2v_freeu_f16: operands must be 16-byte aligned");
   I2V_CHECK_ARG((int64_t)n * h * w * (int64_t)(c1 > c2 ? c1 : c2) < (int64_t)1 << 40, "i2v_freeu_f16: problem too large");
   const int chunks = (int)i2v_cdiv(c2, FU_CH);

@@ -268,8 +268,6 @@ __global__ __launch_bounds__(64 * H) void ln_qkv_kernel(const i2v_ln_qkv_params 
   }
 }
 
-inline bool al16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
-
 constexpr size_t LQ_LDS = 2 * (size_t)LQ_PIX * 16 * 320 * sizeof(f16);
 int lq_cus() { return i2v_big_lds_kernel_cus(reinterpret_cast<const void*>(ln_qkv_kernel<320, 8>), LQ_LDS); }
 
@@ -293,7 +291,7 @@ extern "C" int i2v_ln_qkv_f16(const i2v_ln_qkv_params* pp, i2v_stream_t stream) 
                     p.vt_batch_stride >= (int64_t)p.channels * p.vt_row_stride && p.vt_batch_stride % 8 == 0 &&
                     (p.x_image_stride == 0 || (p.x_image_stride >= p.rows_per_image * p.ldx && p.x_image_stride % 8 == 0)),
                 "i2v_ln_qkv_f16: strides");
-  I2V_CHECK_ARG(al16(p.x) && al16(p.gamma) && al16(p.beta) && al16(p.w) && al16(p.qk) && al16(p.vt),
+  I2V_CHECK_ARG(i2v_al16(p.x) && i2v_al16(p.gamma) && i2v_al16(p.beta) && i2v_al16(p.w) && i2v_al16(p.qk) && i2v_al16(p.vt),
                 "i2v_ln_qkv_f16: pointers must be 16-byte aligned");
   const int cus = lq_cus();
   if (cus <= 0) I2V_FAIL(I2V_ERR_UNSUPPORTED, "i2v_ln_qkv_f16: %zu bytes of LDS refused by this device", LQ_LDS);

@@ -173,12 +173,6 @@ __global__ __launch_bounds__(LM_THREADS) void lora_merge_kernel(void* __restrict
   }
 }
 
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-inline bool overlaps(const void* a, int64_t abytes, const void* b, int64_t bbytes) {
-  const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
-  return a0 < b0 + (uintptr_t)bbytes && b0 < a0 + (uintptr_t)abytes;
-}
-
 }  // namespace
 
 extern "C" int i2v_lora_merge(void* dst, const void* base, int32_t is_f32, int32_t out, int32_t in, const i2v_lora_adapter* adapters,
@@ -191,18 +185,18 @@ extern "C" int i2v_lora_merge(void* dst, const void* base, int32_t is_f32, int32
   I2V_CHECK_ARG((int64_t)out * in < (int64_t)1 << 40, "i2v_lora_merge: problem too large");
   I2V_CHECK_ARG(i2v_cdiv(out, LM_ROWS) <= 65535, "i2v_lora_merge: out %d exceeds the grid", out);
   const int64_t wbytes = (int64_t)out * in * (is_f32 ? 4 : 2);
-  I2V_CHECK_ARG(!overlaps(dst, wbytes, base, wbytes), "i2v_lora_merge: dst and base must not alias (base is not modified)");
+  I2V_CHECK_ARG(!i2v_overlap(dst, wbytes, base, wbytes), "i2v_lora_merge: dst and base must not alias (base is not modified)");
   LoraAdapters ad = {};
   for (int j = 0; j < n_adapters; ++j) {
     const i2v_lora_adapter& a = adapters[j];
     I2V_CHECK_ARG(a.down && a.up, "i2v_lora_merge: adapter %d: null pointer", j);
     I2V_CHECK_ARG(a.rank >= 1 && a.rank <= I2V_LORA_MAX_RANK, "i2v_lora_merge: adapter %d: rank %d (1 .. %d)", j, a.rank,
                   I2V_LORA_MAX_RANK);
-    I2V_CHECK_ARG(!overlaps(dst, wbytes, a.down, (int64_t)a.rank * in * 2) && !overlaps(dst, wbytes, a.up, (int64_t)out * a.rank * 2),
+    I2V_CHECK_ARG(!i2v_overlap(dst, wbytes, a.down, (int64_t)a.rank * in * 2) && !i2v_overlap(dst, wbytes, a.up, (int64_t)out * a.rank * 2),
                   "i2v_lora_merge: adapter %d: dst must not alias a factor", j);
     ad.a[j] = a;
   }
-  const bool vec = in % (is_f32 ? 4 : 8) == 0 && aligned16(dst) && aligned16(base);
+  const bool vec = in % (is_f32 ? 4 : 8) == 0 && i2v_al16(dst) && i2v_al16(base);
   const dim3 grid((unsigned)i2v_cdiv(in, LM_COLS), (unsigned)i2v_cdiv(out, LM_ROWS));
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
 #define LM_LAUNCH(F32, VEC) \

@@ -565,8 +565,6 @@ int launch_ma(const ma_args& p, int64_t rows, float scale, hipStream_t s, const 
   return i2v_check_launch(what);
 }
 
-inline bool al16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
-
 }  // namespace
 
 extern "C" int32_t i2v_motion_attn_supported(int64_t rows, int32_t channels, int32_t heads, int32_t head_dim, int32_t frames) {
@@ -587,14 +585,14 @@ extern "C" int i2v_motion_attn_f16(const i2v_motion_attn_params* pp, i2v_stream_
                 "(i2v_motion_attn_supported)", (long long)p.rows, p.channels, p.heads, p.head_dim, p.frames);
   I2V_CHECK_ARG(p.ldx >= p.channels && p.ldx % 8 == 0 && p.ldo >= p.channels && p.ldo % 8 == 0 && p.ld_shift >= p.channels &&
                 p.ld_shift % 4 == 0, "i2v_motion_attn_f16: row strides");
-  I2V_CHECK_ARG(al16(p.x) && al16(p.gamma) && al16(p.shift) && al16(p.w_qkv) && al16(p.out),
+  I2V_CHECK_ARG(i2v_al16(p.x) && i2v_al16(p.gamma) && i2v_al16(p.shift) && i2v_al16(p.w_qkv) && i2v_al16(p.out),
                 "i2v_motion_attn_f16: pointers must be 16-byte aligned");
   ma_args a = {};
   a.x = p.x; a.ldx = p.ldx; a.gamma = p.gamma; a.shift = p.shift; a.ld_shift = p.ld_shift; a.w = p.w_qkv; a.out = p.out;
   a.ldo = p.ldo; a.eps = p.eps;
   // (OUTP: the residual rows go through a buffer descriptor and per-lane offsets of 32 bits)
   I2V_CHECK_ARG(p.w_o == nullptr || p.ldx < (1 << 23), "i2v_motion_attn_f16: ldx (%lld) must be below 2^23 with the out-projection", (long long)p.ldx);
-  I2V_CHECK_ARG((p.w_o == nullptr) == (p.b_o == nullptr) && al16(p.w_o) && al16(p.b_o),
+  I2V_CHECK_ARG((p.w_o == nullptr) == (p.b_o == nullptr) && i2v_al16(p.w_o) && i2v_al16(p.b_o),
                 "i2v_motion_attn_f16: w_o and b_o come together, 16-byte aligned");
   a.w_o = p.w_o; a.b_o = p.b_o;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
@@ -630,7 +628,7 @@ extern "C" int i2v_cross_attn_fused_f16(const i2v_cross_attn_fused_params* pp, i
                 "(i2v_cross_attn_fused_supported)", (long long)p.rows, p.channels, p.heads, p.head_dim, p.ctx_len,
                 (long long)p.rows_per_ctx);
   I2V_CHECK_ARG(p.ldx >= p.channels && p.ldx % 8 == 0 && p.ldo >= p.channels && p.ldo % 8 == 0, "i2v_cross_attn_fused_f16: row strides");
-  I2V_CHECK_ARG(al16(p.x) && al16(p.gamma) && al16(p.beta) && al16(p.w_q) && al16(p.out) && al16(p.ctx_frag) && al16(p.ip_frag),
+  I2V_CHECK_ARG(i2v_al16(p.x) && i2v_al16(p.gamma) && i2v_al16(p.beta) && i2v_al16(p.w_q) && i2v_al16(p.out) && i2v_al16(p.ctx_frag) && i2v_al16(p.ip_frag),
                 "i2v_cross_attn_fused_f16: pointers must be 16-byte aligned");
   I2V_CHECK_ARG(p.ip_frag == nullptr || (p.ip_len >= 1 && p.ip_len <= 16), "i2v_cross_attn_fused_f16: ip_len (%d) must be in [1, 16]",
                 p.ip_len);
@@ -642,7 +640,7 @@ extern "C" int i2v_cross_attn_fused_f16(const i2v_cross_attn_fused_params* pp, i
   a.tiles_per_ctx = (int32_t)(p.rows_per_ctx / (MA_PIX * MA_F));
   // (OUTP: the residual rows go through a buffer descriptor and per-lane offsets of 32 bits)
   I2V_CHECK_ARG(p.w_o == nullptr || p.ldx < (1 << 23), "i2v_cross_attn_fused_f16: ldx (%lld) must be below 2^23 with the out-projection", (long long)p.ldx);
-  I2V_CHECK_ARG((p.w_o == nullptr) == (p.b_o == nullptr) && al16(p.w_o) && al16(p.b_o),
+  I2V_CHECK_ARG((p.w_o == nullptr) == (p.b_o == nullptr) && i2v_al16(p.w_o) && i2v_al16(p.b_o),
                 "i2v_cross_attn_fused_f16: w_o and b_o come together, 16-byte aligned");
   a.w_o = p.w_o; a.b_o = p.b_o;
   if (p.w_o != nullptr)

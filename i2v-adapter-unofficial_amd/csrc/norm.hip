@@ -790,8 +790,6 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(const f16* __restrict
   for (int c = nvec * 8 + lane; c < cols; c += 64) yr[c] = (f16)(__builtin_amdgcn_exp2f((float)xr[c] * scale_log2 - mb) * inv);
 }
 
-inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 }  // namespace
 
 extern "C" int64_t i2v_groupnorm_workspace_bytes(int32_t n_img, int32_t hw, int32_t channels) {
@@ -815,7 +813,7 @@ extern "C" int i2v_groupnorm_fold_f16(const i2v_gn_params* pp, const void* w, in
                 p.groups);
   I2V_CHECK_ARG(p.frames_per_stat > 0 && p.n_img % p.frames_per_stat == 0,
                 "i2v_groupnorm_fold_f16: n_img %d not divisible by frames_per_stat %d", p.n_img, p.frames_per_stat);
-  I2V_CHECK_ARG(al16(p.x) && (!p.x2 || al16(p.x2)) && al16(p.workspace) && al16(p.gamma) && al16(p.beta),
+  I2V_CHECK_ARG(i2v_al16(p.x) && (!p.x2 || i2v_al16(p.x2)) && i2v_al16(p.workspace) && i2v_al16(p.gamma) && i2v_al16(p.beta),
                 "i2v_groupnorm_fold_f16: pointers must be 16-byte aligned");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const int rpc = gn_rows_per_chunk(p.n_img, p.hw);
@@ -857,7 +855,7 @@ extern "C" int i2v_groupnorm_f16(const i2v_gn_params* pp, i2v_stream_t stream) {
   I2V_CHECK_ARG(p.frames_per_stat > 0 && p.n_img % p.frames_per_stat == 0,
                 "i2v_groupnorm_f16: n_img %d not divisible by frames_per_stat %d", p.n_img, p.frames_per_stat);
   if (p.out_perm) I2V_CHECK_ARG(p.frames > 0 && p.n_img % p.frames == 0, "i2v_groupnorm_f16: bad frames for out_perm");
-  I2V_CHECK_ARG(al16(p.x) && al16(p.y) && (!p.x2 || al16(p.x2)) && al16(p.workspace) && al16(p.gamma) && al16(p.beta),
+  I2V_CHECK_ARG(i2v_al16(p.x) && i2v_al16(p.y) && (!p.x2 || i2v_al16(p.x2)) && i2v_al16(p.workspace) && i2v_al16(p.gamma) && i2v_al16(p.beta),
                 "i2v_groupnorm_f16: pointers must be 16-byte aligned");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   if (p.gpartial_in != nullptr) {
@@ -947,8 +945,8 @@ extern "C" int i2v_groupnorm_bwd_f16(const i2v_gn_params* pp, const void* dy, vo
   I2V_CHECK_ARG(p.c1 % 8 == 0 && p.c2 % 8 == 0 && p.groups > 0 && C % p.groups == 0, "i2v_groupnorm_bwd_f16: channel counts");
   I2V_CHECK_ARG(p.frames_per_stat > 0 && p.n_img % p.frames_per_stat == 0 && !p.out_perm,
                 "i2v_groupnorm_bwd_f16: frames_per_stat must divide n_img; out_perm is not supported");
-  I2V_CHECK_ARG(al16(p.x) && (!p.x2 || al16(p.x2)) && al16(dy) && al16(dx) && (!dx2 || al16(dx2)) && al16(p.workspace) &&
-                    al16(p.gamma) && al16(p.beta), "i2v_groupnorm_bwd_f16: pointers must be 16-byte aligned");
+  I2V_CHECK_ARG(i2v_al16(p.x) && (!p.x2 || i2v_al16(p.x2)) && i2v_al16(dy) && i2v_al16(dx) && (!dx2 || i2v_al16(dx2)) && i2v_al16(p.workspace) &&
+                    i2v_al16(p.gamma) && i2v_al16(p.beta), "i2v_groupnorm_bwd_f16: pointers must be 16-byte aligned");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const int rpc = gn_rows_per_chunk(p.n_img, p.hw);
   const int nchunk = (int)i2v_cdiv(p.hw, rpc);
@@ -981,8 +979,8 @@ extern "C" int i2v_layernorm_f16(const i2v_ln_params* pp, i2v_stream_t stream) {
   I2V_CHECK_ARG(p.rows > 0 && p.C > 0 && p.C % 8 == 0 && p.C <= 4096,
                 "i2v_layernorm_f16: C (%d) must be a multiple of 8 and <= 4096", p.C);
   I2V_CHECK_ARG(p.ldx % 8 == 0 && p.ldy % 8 == 0 && p.ldx >= p.C && p.ldy >= p.C, "i2v_layernorm_f16: bad ldx / ldy");
-  I2V_CHECK_ARG(al16(p.x) && al16(p.y) && al16(p.gamma) && al16(p.beta), "i2v_layernorm_f16: 16-byte alignment");
-  if (p.pe) I2V_CHECK_ARG(p.pe_period > 0 && p.ld_pe % 8 == 0 && al16(p.pe), "i2v_layernorm_f16: bad pe arguments");
+  I2V_CHECK_ARG(i2v_al16(p.x) && i2v_al16(p.y) && i2v_al16(p.gamma) && i2v_al16(p.beta), "i2v_layernorm_f16: 16-byte alignment");
+  if (p.pe) I2V_CHECK_ARG(p.pe_period > 0 && p.ld_pe % 8 == 0 && i2v_al16(p.pe), "i2v_layernorm_f16: bad pe arguments");
   I2V_CHECK_ARG(p.x_rows_per_batch >= 0 && (p.x_rows_per_batch == 0 || (p.x_batch_stride % 8 == 0 && p.x_batch_stride > 0)),
                 "i2v_layernorm_f16: x_batch_stride must be a positive multiple of 8 elements");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
@@ -1006,7 +1004,7 @@ extern "C" int i2v_softmax_rows_f16(const void* x, int64_t ldx, void* y, int64_t
                                     float scale, i2v_stream_t stream) {
   I2V_CHECK_ARG(x && y && rows > 0 && cols > 0 && ldx >= cols && ldy >= cols, "i2v_softmax_rows_f16: bad arguments");
   I2V_CHECK_ARG(scale > 0.f, "i2v_softmax_rows_f16: scale must be positive");
-  I2V_CHECK_ARG(ldx % 8 == 0 && ldy % 8 == 0 && al16(x) && al16(y), "i2v_softmax_rows_f16: rows must be 16-byte aligned");
+  I2V_CHECK_ARG(ldx % 8 == 0 && ldy % 8 == 0 && i2v_al16(x) && i2v_al16(y), "i2v_softmax_rows_f16: rows must be 16-byte aligned");
   hipLaunchKernelGGL(softmax_rows_kernel, dim3((unsigned)i2v_cdiv(rows, 4)), dim3(256), 0,
                      reinterpret_cast<hipStream_t>(stream), reinterpret_cast<const f16*>(x), ldx,
                      reinterpret_cast<f16*>(y), ldy, rows, cols, scale * 1.4426950408889634f);

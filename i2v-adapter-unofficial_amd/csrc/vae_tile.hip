@@ -110,8 +110,6 @@ __global__ __launch_bounds__(VT_BX* VT_BY) void vae_tile_blend_kernel(const void
     if (cb + j < c) dst[j * plane] = v[j];
 }
 
-inline bool vt_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 template <bool F32, int VEC>
 void vt_launch(dim3 grid, hipStream_t st, const void* tile, const void* up, const void* left, const void* upleft, int th, int tw, int ld,
                int c, int up_h, int left_w, int ev, int eh, int crop_h, int crop_w, float* out, int out_h, int out_w, int oy, int ox,
@@ -150,7 +148,7 @@ extern "C" int i2v_vae_tile_blend(const void* tile, const void* up, const void* 
   int vec = VT_SCALAR;
   if (f32 && ld == 3 && c == 3)
     vec = VT_F32X3;
-  else if (ld % w == 0 && vt_aligned16(tile) && vt_aligned16(up) && vt_aligned16(left) && vt_aligned16(upleft))
+  else if (ld % w == 0 && i2v_al16(tile) && i2v_al16(up) && i2v_al16(left) && i2v_al16(upleft))
     vec = VT_VECTOR;
   const int chunks = vec == VT_F32X3 ? 1 : (int)i2v_cdiv(c, w);
   const int64_t gy = i2v_cdiv(crop_h, VT_BY), gz = (int64_t)n * chunks;

@@ -976,10 +976,10 @@ def clip_embed(token_embedding, position_embedding, input_ids):
     return out
 
 
-def clip_attention(qkv, *, batch, length, heads, head_dim, q_off=None, k_off=None, v_off=None, scale=None, out=None):
-    """causal self-attention of `batch` sequences of `length` tokens (i2v_clip_attention_f16), q / k / v read in place from the packed
-    result of one QKV GEMM: qkv fp16 [batch * length, >= 3 * hidden], head h of q / k / v in columns q_off / k_off / v_off + h * head_dim
-    (default 0, hidden, 2 * hidden) -> fp16 [batch * length, hidden].  head_dim 64 and length <= 128 only (anything else raises)."""
+def _clip_attention(entry_name, qkv, *, batch, length, heads, head_dim, q_off=None, k_off=None, v_off=None, scale=None, out=None):
+    """what `clip_attention` and `clip_vision_attention` share (csrc/clip_attention.hip: one kernel, one set of argument checks): qkv
+    fp16 [batch * length, >= 3 * hidden], head h of q / k / v in columns q_off / k_off / v_off + h * head_dim (default 0, hidden,
+    2 * hidden) -> fp16 [batch * length, hidden]; `entry_name` is the C entry point, which holds the envelope."""
     lib = _lib.load()
     qkv, ld = _mat(qkv, "qkv")
     hidden = heads * head_dim
@@ -994,9 +994,16 @@ def clip_attention(qkv, *, batch, length, heads, head_dim, q_off=None, k_off=Non
     if out.shape != (batch * length, hidden):
         raise ValueError(f"out must be {(batch * length, hidden)}, got {tuple(out.shape)}")
     scale = float(head_dim) ** -0.5 if scale is None else float(scale)
-    _lib.check(lib.i2v_clip_attention_f16(_p(qkv), ld, q_off, k_off, v_off, _p(out), ldo, batch, length, heads, head_dim, scale, _stream()),
-               "i2v_clip_attention_f16")
+    _lib.check(getattr(lib, entry_name)(_p(qkv), ld, q_off, k_off, v_off, _p(out), ldo, batch, length, heads, head_dim, scale, _stream()),
+               entry_name)
     return out
+
+
+def clip_attention(qkv, **kw):
+    """causal self-attention of `batch` sequences of `length` tokens (i2v_clip_attention_f16), q / k / v read in place from the packed
+    result of one QKV GEMM: qkv fp16 [batch * length, >= 3 * hidden], head h of q / k / v in columns q_off / k_off / v_off + h * head_dim
+    (default 0, hidden, 2 * hidden) -> fp16 [batch * length, hidden].  head_dim 64 and length <= 128 only (anything else raises)."""
+    return _clip_attention("i2v_clip_attention_f16", qkv, **kw)
 
 
 def quick_gelu(x, out=None):
@@ -1056,27 +1063,11 @@ def clip_vision_embed(class_embedding, patch_embeds, position_embedding, *, batc
     return out
 
 
-def clip_vision_attention(qkv, *, batch, length, heads, head_dim, q_off=None, k_off=None, v_off=None, scale=None, out=None):
+def clip_vision_attention(qkv, **kw):
     """NON-causal self-attention of `batch` sequences of `length` tokens (i2v_clip_vision_attention_f16), q / k / v read in place from the
     packed result of one QKV GEMM, as `clip_attention` takes them -> fp16 [batch * length, hidden].  head_dim 64 or 80 and length <= 288
     only (anything else raises)."""
-    lib = _lib.load()
-    qkv, ld = _mat(qkv, "qkv")
-    hidden = heads * head_dim
-    q_off = 0 if q_off is None else q_off
-    k_off = hidden if k_off is None else k_off
-    v_off = 2 * hidden if v_off is None else v_off
-    if qkv.shape[0] != batch * length or max(q_off, k_off, v_off) + hidden > qkv.shape[1]:
-        raise ValueError(f"qkv is {tuple(qkv.shape)}: expected [{batch * length}, >= offset + {hidden}]")
-    if out is None:
-        out = torch.empty((batch * length, hidden), dtype=f16, device=qkv.device)
-    out, ldo = _mat(out, "out")
-    if out.shape != (batch * length, hidden):
-        raise ValueError(f"out must be {(batch * length, hidden)}, got {tuple(out.shape)}")
-    scale = float(head_dim) ** -0.5 if scale is None else float(scale)
-    _lib.check(lib.i2v_clip_vision_attention_f16(_p(qkv), ld, q_off, k_off, v_off, _p(out), ldo, batch, length, heads, head_dim, scale,
-                                                 _stream()), "i2v_clip_vision_attention_f16")
-    return out
+    return _clip_attention("i2v_clip_vision_attention_f16", qkv, **kw)
 
 
 def select_row(table, row_index, out=None):

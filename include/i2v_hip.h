@@ -652,8 +652,9 @@ int i2v_freenoise_blend_f16(const void* src, int64_t ld_src, void* dst, int64_t 
  *           out[b * len + i, h * 64 + :] = softmax_j<=i( scale * q[b, i, h, :] . k[b, j, h, :] ) v[b, j, h, :]
  *       q, k and v are read in place from the packed result of one QKV GEMM: qkv fp16 [batch * len, ld_qkv], head h of q / k / v of a row in
  *       columns q_off / k_off / v_off + h * 64 (offsets multiples of 8); out fp16 [batch * len, ld_out].  No transposed V, no mask tensor: key j
- *       is visible to query i iff j <= i (and j < len), by index compare, so no row is ever fully masked.  One workgroup per (batch, head), the
- *       head's q / k / v staged in LDS once, rows padded to the MFMA tile in LDS only (nothing at or beyond row batch * len is read or written).
+ *       is visible to query i iff j <= i (and j < len), by index compare, so no row is ever fully masked.  The kernel is
+ *       i2v_clip_vision_attention_f16's with the causal mask (csrc/clip_attention.hip): grid (batch * heads, ceil(len / 64)), the head's whole K
+ *       and V^T staged in LDS, padded to the MFMA tile there only (nothing at or beyond row batch * len is read or written).
  *       Numerics: Q K^T and P V on MFMA with fp32 accumulation, softmax in fp32 in base 2 with the logits scaled by scale * log2(e) in fp32, P
  *       rounded to fp16 for P V, the row sum taken over the unrounded P.
  *       I2V_ERR_UNSUPPORTED: head_dim != 64, len > 128.  I2V_ERR_INVALID_ARG: null / misaligned / overlapping operands, bad strides or offsets.
@@ -685,8 +686,9 @@ int i2v_quick_gelu_f16(const void* x, void* y, int64_t n, i2v_stream_t stream);
  *       Grid (batch * heads, ceil(len / 64)): a workgroup of 4 waves owns 64 queries and stages the head's whole K (head_dim padded with zeros to
  *       the MFMA K-step, 80 -> 96) and V^T (keys padded with zeros to a multiple of 32) in LDS, 114 KB.  Key j is visible iff j < len, by index
  *       compare (P of a pad key is exactly 0; key 0 is always visible, so no row is fully masked); rows at or beyond batch * len are never
- *       read, only queries < len are stored.  Numerics as i2v_clip_attention_f16: MFMA 16x16x32 with fp32 accumulation, softmax in fp32 in
- *       base 2 with the logits scaled by scale * log2(e) in fp32, P rounded to fp16 for P V, the row sum taken over the unrounded P.
+ *       read, only queries < len are stored.  Numerics as i2v_clip_attention_f16 (the same kernel without the causal mask): MFMA 16x16x32
+ *       with fp32 accumulation, softmax in fp32 in base 2 with the logits scaled by scale * log2(e) in fp32, P rounded to fp16 for P V, the
+ *       row sum taken over the unrounded P.
  *       I2V_ERR_UNSUPPORTED (nothing launched): head_dim not 64 or 80, len > 288 (L_max: 18 key tiles; ViT-H/14 at 224 px is 257).
  *       I2V_ERR_INVALID_ARG: null / misaligned / overlapping operands, bad strides or offsets. */
 int i2v_clip_patchify_f16(const void* pixel_values, void* out, int64_t ld_out, int32_t batch, int32_t channels, int32_t size, int32_t patch,

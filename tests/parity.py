@@ -82,6 +82,25 @@ def compare(got, ref, rel=REL_TOL_MODULE, name="", abs_tol=None):
     return err, scale
 
 
+def fp16_gate(name, got, half, ref, factor, log_env, **extra):
+    """max|got - ref| <= factor * max|half - ref|: `half` is torch's own fp16 evaluation of the problem `ref` is the yardstick of.  The
+    measured pair is printed and appended to the file $`log_env` names (JSON lines: the CLIP towers' profiles/clip_*_errors.jsonl)."""
+    import json
+    ref = ref.double().cpu()
+    assert got.shape == ref.shape and torch.isfinite(got).all(), name
+    err = (got.double().cpu() - ref).abs().max().item()
+    base = (half.double().cpu() - ref).abs().max().item()
+    scale = ref.abs().max().item()
+    rec = dict(name=name, err=err, torch_fp16_err=base, max_ref=scale, ratio=(err / base if base > 0 else (0.0 if err == 0 else float("inf"))),
+               **extra)
+    print(json.dumps(rec))
+    path = os.environ.get(log_env)
+    if path:
+        with open(path, "a") as f:
+            f.write(json.dumps(rec) + "\n")
+    assert err <= factor * base, f"{name}: err {err:.4e} > {factor} x torch-fp16 err {base:.4e} (max|ref| {scale:.3e})"
+
+
 def oracle_small_unet(seed=1234, ip=False):
     from oracle.unet_motion_cross_frame_attn import UNetMotionCrossFrameAttnModel
     torch.manual_seed(seed)

@@ -6,14 +6,13 @@ The accuracy gates are relative to what fp16 torch itself loses on the same prob
 error over max|ref| may be at most TWICE that of torch's fp16 CPU evaluation against the same float64 (fp32) yardstick.  Every
 measured pair goes to $I2V_CLIP_TEXT_LOG as JSON lines (profiles/clip_text_errors.jsonl is one such run)."""
 import ctypes as C
-import json
 import os
 
 import pytest
 import torch
 
 from tests.clip_text_reference import PREFIX, ClipTextReference, StubTokenizer, causal_attention, prompt_like_ids, seeded_state
-from tests.parity import SMALL_UNET, hip_model_random
+from tests.parity import SMALL_UNET, fp16_gate, hip_model_random
 
 pytestmark = pytest.mark.gpu
 f16 = torch.float16
@@ -28,25 +27,8 @@ def pkg():
     return p
 
 
-def _log(name, err, base, scale, **extra):
-    rec = dict(name=name, err=err, torch_fp16_err=base, max_ref=scale, ratio=(err / base if base > 0 else (0.0 if err == 0 else float("inf"))),
-               **extra)
-    print(json.dumps(rec))
-    path = os.environ.get("I2V_CLIP_TEXT_LOG")
-    if path:
-        with open(path, "a") as f:
-            f.write(json.dumps(rec) + "\n")
-    return rec
-
-
 def _gate(name, got, half, ref, **extra):
-    """max|got - ref| <= FACTOR * max|half - ref|: `half` is torch's own fp16 evaluation of the problem `ref` is the yardstick of"""
-    ref = ref.double().cpu()
-    assert torch.isfinite(got).all(), name
-    err = (got.double().cpu() - ref).abs().max().item()
-    base = (half.double().cpu() - ref).abs().max().item()
-    _log(name, err, base, ref.abs().max().item(), **extra)
-    assert err <= FACTOR * base, f"{name}: err {err:.4e} > {FACTOR} x torch-fp16 err {base:.4e} (max|ref| {ref.abs().max().item():.3e})"
+    fp16_gate(name, got, half, ref, FACTOR, "I2V_CLIP_TEXT_LOG", **extra)
 
 
 # ------------------------------------------------------------------------------------------------------------ embedding

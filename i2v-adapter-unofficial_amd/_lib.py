@@ -10,12 +10,14 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # I2V_LIB_PATH selects another build of the same ABI (same-box A/B of two kernels, tools/ab_bench.sh); the in-tree
 # library is never overwritten by tooling
 LIB_PATH = os.environ.get("I2V_LIB_PATH") or os.path.join(_HERE, "libi2v_hip.so")
-ABI_VERSION = 18
+ABI_VERSION = 19
 
 I2V_EPI_NONE, I2V_EPI_GELU, I2V_EPI_GEGLU = 0, 1, 2
 I2V_STORE_ROWMAJOR, I2V_STORE_ROWPERM, I2V_STORE_VT, I2V_STORE_VT_T = 0, 1, 2, 3
 I2V_A_PLAIN, I2V_A_CONV3X3 = 0, 1
 I2V_LORA_MAX_ADAPTERS, I2V_LORA_MAX_RANK = 8, 256
+I2V_ROUTE_GENERIC, I2V_ROUTE_CONV_THIN, I2V_ROUTE_BIG_TILE, I2V_ROUTE_BIG_DEEP, I2V_ROUTE_BIG_SPLITK = 0, 1, 2, 3, 4
+I2V_EXTRA_NONE, I2V_EXTRA_LNF, I2V_EXTRA_HILO, I2V_EXTRA_GNS, I2V_EXTRA_UPF = 0, 1, 2, 4, 8
 
 
 class HipLibraryError(RuntimeError):
@@ -48,6 +50,21 @@ class GemmParams(C.Structure):
         ("gn_partial", C.c_void_p), ("gn_groups", C.c_int32),
         ("residual_lo", C.c_void_p), ("c_lo", C.c_void_p),
     ]
+
+
+class GemmRoute(C.Structure):
+    """struct i2v_gemm_route: the kernel instantiation a GEMM / conv problem takes"""
+    _fields_ = [
+        ("family", C.c_int32), ("a_mode", C.c_int32),
+        ("rows", C.c_int32), ("cols", C.c_int32), ("stages", C.c_int32),
+        ("splits", C.c_int32), ("kps", C.c_int32),
+        ("extra", C.c_int32), ("persistent", C.c_int32),
+        ("generic_tile", C.c_int32), ("vec4", C.c_int32),
+        ("epilogue", C.c_int32), ("store_mode", C.c_int32),
+    ]
+
+    def as_dict(self):
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
 
 
 class AttnParams(C.Structure):
@@ -212,6 +229,9 @@ SIGNATURES = {
     "i2v_gemm_upconv_fold_supported": (C.c_int, [C.POINTER(GemmParams)]),
     "i2v_gemm_workspace_bytes": (C.c_int64, [C.POINTER(GemmParams)]),
     "i2v_gemm_gn_partial_rows": (C.c_int32, [C.POINTER(GemmParams)]),
+    "i2v_gemm_route": (C.c_int, [C.POINTER(GemmParams), C.POINTER(GemmRoute)]),
+    "i2v_gemm_last_route": (C.c_int, [C.POINTER(GemmRoute)]),
+    "i2v_gemm_kernel_exists": (C.c_int, [C.POINTER(GemmRoute)]),
     "i2v_attention_f16": (C.c_int, [C.POINTER(AttnParams), _P]),
     "i2v_temporal_attention_f16": (C.c_int, [C.POINTER(TAttnParams), _P]),
     "i2v_motion_attn_supported": (C.c_int32, [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),

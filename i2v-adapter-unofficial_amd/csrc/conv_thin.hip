@@ -1,5 +1,5 @@
 // 3x3 / pad 1 / stride 1 convolution with a NARROW output (Cout <= 16): the UNet's conv_out (320 -> 4 channels, unet:879-881, 1443) and
-// the VAE decoder's (128 -> 3).  Reached through i2v_gemm_f16's I2V_A_CONV3X3 mode (i2v_conv_thin_try): no entry point of its own.
+// the VAE decoder's (128 -> 3).  Reached through i2v_gemm_f16's I2V_A_CONV3X3 mode (i2v_conv_thin_ok / i2v_conv_thin_launch): no entry point of its own.
 //
 // As an implicit GEMM with N = 4 the tile kernels gather every input pixel nine times through LDS for four useful columns: 755 MB
 // through the gather path for a 3-GFLOP problem at the 64^2 level -- 97 us, 0.9 TB/s of the input actually read (r5_step_shapes).
@@ -24,6 +24,7 @@ constexpr int CT_PS = CT_CB * 2 + 16;                // bytes per staged pixel: 
 constexpr int CT_PIECES = CT_HH * CT_HW * (CT_CB / 8);   // 16-byte pieces of a halo tile: 1440
 constexpr int CT_NLD = (CT_PIECES + 255) / 256;          // per thread: 6
 constexpr int CT_MAXCOUT = 16;
+constexpr size_t CT_MAXLDS = 80 * 1024;             // (two workgroups per CU)
 
 __global__ __launch_bounds__(256, 2) void conv_thin_kernel(const i2v_gemm_params p, const int tiles_x, const int tiles_y) {
   extern __shared__ __attribute__((aligned(16))) char smem[];     // [2][CT_HH * CT_HW * CT_PS] halo tiles, then W [cout][9 cin] fp16
@@ -134,24 +135,28 @@ __global__ __launch_bounds__(256, 2) void conv_thin_kernel(const i2v_gemm_params
 
 }  // namespace
 
-// 0: not a problem of this kernel (the caller goes on to the tile kernels); 1: launched; < 0: error
-int i2v_conv_thin_try(const i2v_gemm_params& p, hipStream_t s) {
+// whether p is a problem of this kernel: pure host arithmetic (the route of i2v_gemm_f16 reads it, gemm.hip)
+bool i2v_conv_thin_ok(const i2v_gemm_params& p) {
   static const int off = getenv("I2V_CONV_THIN") ? (atoi(getenv("I2V_CONV_THIN")) == 0) : 0;
-  if (off || p.a_mode != I2V_A_CONV3X3 || p.N > CT_MAXCOUT || p.stride != 1 || p.upsample || p.asym_pad) return 0;
-  if (p.cin % CT_CB != 0 || (p.conv_kblock != 0 && p.conv_kblock != 64) || p.in_h % CT_TH != 0 || p.in_w % CT_TW != 0) return 0;
+  if (off || p.a_mode != I2V_A_CONV3X3 || p.N > CT_MAXCOUT || p.stride != 1 || p.upsample || p.asym_pad) return false;
+  if (p.cin % CT_CB != 0 || (p.conv_kblock != 0 && p.conv_kblock != 64) || p.in_h % CT_TH != 0 || p.in_w % CT_TW != 0) return false;
   if (p.epilogue != I2V_EPI_NONE || p.store_mode != I2V_STORE_ROWMAJOR || p.residual || p.rowvec || p.ln_wsum || p.rows_per_w > 0 ||
       p.a_perm_frames > 0 || p.a2 || p.residual_lo || p.c_lo)
-    return 0;
-  if ((int64_t)p.in_h * p.in_w * p.lda >= (1ll << 31) || (reinterpret_cast<uintptr_t>(p.c) & (p.c_is_f32 ? 15 : 7)) != 0) return 0;
+    return false;
+  if ((int64_t)p.in_h * p.in_w * p.lda >= (1ll << 31) || (reinterpret_cast<uintptr_t>(p.c) & (p.c_is_f32 ? 15 : 7)) != 0) return false;
+  if (2 * (size_t)CT_HH * CT_HW * CT_PS + (size_t)p.N * 9 * p.cin * sizeof(f16) > CT_MAXLDS) return false;
+  return (int64_t)p.n_img * (p.in_w / CT_TW) * (p.in_h / CT_TH) < (1ll << 31);
+}
+
+// launches a problem i2v_conv_thin_ok accepted.  1: launched; 0: the device refuses the kernel its LDS (the caller goes on to the
+// tile kernels); < 0: error
+int i2v_conv_thin_launch(const i2v_gemm_params& p, hipStream_t s) {
   const size_t lds = 2 * (size_t)CT_HH * CT_HW * CT_PS + (size_t)p.N * 9 * p.cin * sizeof(f16);
-  constexpr size_t CT_MAXLDS = 80 * 1024;        // (two workgroups per CU)
-  if (lds > CT_MAXLDS) return 0;
   // (the opt-in is cached per kernel and device: asked once, for the most any problem of this kernel may use)
   const int cus = i2v_big_lds_kernel_cus(reinterpret_cast<const void*>(conv_thin_kernel), CT_MAXLDS);
   if (cus <= 0) return 0;
   const int tiles_x = p.in_w / CT_TW, tiles_y = p.in_h / CT_TH;
   const int64_t grid = (int64_t)p.n_img * tiles_x * tiles_y;
-  if (grid >= (1ll << 31)) return 0;
   hipLaunchKernelGGL(conv_thin_kernel, dim3((unsigned)grid), dim3(256), lds, s, p, tiles_x, tiles_y);
   const int rc = i2v_check_launch("i2v_gemm_f16(thin conv)");
   return rc < 0 ? rc : 1;

@@ -12,6 +12,7 @@
 // A-operand loaders: plain row-major (optionally two K-ranges = skip-connection concat without a cat copy),
 // or im2col-on-the-fly over an NHWC image for 3x3 / stride 1|2 / nearest-2x-upsample convolutions.
 #include <cstdlib>
+#include <utility>
 
 #include "gemm_common.h"
 
@@ -320,13 +321,14 @@ __global__ __launch_bounds__(256) void gemm_kernel(const i2v_gemm_params p, cons
   }
 }
 
-struct TileCfg {
-  int bm, bn, blocks_per_cu;
-  float eff;  // relative MFMA efficiency of the tile shape (operand reuse)
-};
+// The launch table of this kernel: tile shapes (rows x columns) by index, each instantiated for both A sources.  The launch
+// and the existence query (i2v_gemm_kernel_exists) read this array.
+constexpr int GENERIC_TILES[4][2] = {{128, 128}, {128, 64}, {64, 128}, {64, 64}};
+constexpr int N_GENERIC_TILES = sizeof(GENERIC_TILES) / sizeof(GENERIC_TILES[0]);
 
-template <int BM, int BN>
+template <int T>
 int launch(const i2v_gemm_params& p, int vec4, hipStream_t s) {
+  constexpr int BM = GENERIC_TILES[T][0], BN = GENERIC_TILES[T][1];
   const int tiles_m = (int)i2v_cdiv(p.M, BM), tiles_n = (int)i2v_cdiv(p.N, BN);
   const dim3 grid(tiles_m * tiles_n), block(256);
   if (p.a_mode == I2V_A_CONV3X3)
@@ -334,6 +336,19 @@ int launch(const i2v_gemm_params& p, int vec4, hipStream_t s) {
   else
     hipLaunchKernelGGL((gemm_kernel<BM, BN, I2V_A_PLAIN>), grid, block, 0, s, p, tiles_n, vec4);
   return i2v_check_launch("i2v_gemm_f16");
+}
+template <int... Ts>
+int launch_tile(int tile, const i2v_gemm_params& p, int vec4, hipStream_t s, std::integer_sequence<int, Ts...>) {
+  int rc = I2V_ERR_UNSUPPORTED;
+  ((tile == Ts ? (rc = launch<Ts>(p, vec4, s), 0) : 0), ...);
+  return rc;
+}
+// (epilogue, store and vec4 are run-time arguments of this kernel: one instantiation per tile and A source)
+bool generic_kernel_exists(const GemmRoute& r) {
+  if (r.generic_tile < 0 || r.generic_tile >= N_GENERIC_TILES || (r.a_mode != I2V_A_PLAIN && r.a_mode != I2V_A_CONV3X3)) return false;
+  return r.rows == GENERIC_TILES[r.generic_tile][0] && r.cols == GENERIC_TILES[r.generic_tile][1] && r.stages == 0 && r.extra == 0 &&
+         r.persistent == 0 && r.epilogue >= I2V_EPI_NONE && r.epilogue <= I2V_EPI_GEGLU && r.store_mode >= I2V_STORE_ROWMAJOR &&
+         r.store_mode <= I2V_STORE_VT_T;
 }
 
 inline bool aligned_to(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0; }
@@ -360,7 +375,101 @@ int vector_epilogue_ok(const i2v_gemm_params& p) {
   return vec4;
 }
 
+// tile of the generic kernel: modelled time = waves of tiles over 256 CUs x tile area / shape efficiency
+// `eff` is measured relative throughput per tile area on MI355X at the UNet's shapes (tools/kernel_bench.py sweep,
+// profiles/r1_tile_sweep.txt): the loop is latency-bound, so the smaller tiles with 3 blocks / CU win except
+// for very long K; the im2col loader favours a short M tile (fewer gathered rows per block).
+int generic_tile(const i2v_gemm_params& p) {
+  struct TileCfg {
+    int blocks_per_cu;
+    float eff;  // relative MFMA efficiency of the tile shape (operand reuse)
+  };
+  const bool conv = p.a_mode == I2V_A_CONV3X3;
+  const bool long_k = p.K >= 2048;
+  const TileCfg cfgs[N_GENERIC_TILES] = {{2, long_k ? 1.15f : 1.00f}, {3, conv ? 1.00f : 1.30f}, {3, conv ? 1.25f : 1.25f}, {5, 1.10f}};
+  int best = 0;
+  double best_t = 1e300;
+  for (int i = 0; i < N_GENERIC_TILES; ++i) {
+    const int bm = GENERIC_TILES[i][0], bn = GENERIC_TILES[i][1];
+    const double tiles = (double)i2v_cdiv(p.M, bm) * (double)i2v_cdiv(p.N, bn);
+    const double slots = 256.0 * cfgs[i].blocks_per_cu;
+    const double rounds = tiles <= slots ? 1.0 : tiles / slots;  // partial last round amortised when large
+    const double conc = tiles < slots ? tiles : slots;
+    // per-round time ~ tile area / eff, divided by how busy the CUs are (at most blocks_per_cu blocks share a CU)
+    const double per_cu = (conc / 256.0 < 1.0) ? 1.0 : conc / 256.0;
+    const double t = rounds * per_cu * bm * bn / cfgs[i].eff;
+    if (t < best_t) {
+      best_t = t;
+      best = i;
+    }
+  }
+  static const int tile_env = getenv("I2V_GEMM_TILE") ? atoi(getenv("I2V_GEMM_TILE")) : -1;  // tuning override
+  if (tile_env >= 0 && tile_env < N_GENERIC_TILES) best = tile_env;
+  return best;
+}
+
+// THE dispatch rule: which kernel runs p.  i2v_gemm_f16 launches what this answers and i2v_gemm_route reports it; pure host
+// arithmetic.  thin_allowed = false: the answer for a device that refuses the thin convolution its LDS.
+struct Dispatch {
+  GemmRoute route;
+  GemmBigPlan plan;   // of the 8-wave kernel (the four host queries read it, too)
+  int vec4;           // vector-epilogue flag as the chosen kernel takes it
+};
+Dispatch dispatch(const i2v_gemm_params& p, bool thin_allowed = true) {
+  Dispatch d;
+  d.vec4 = vector_epilogue_ok(p);
+  d.plan = i2v_gemm_big_plan(p, d.vec4);   // which form of the 8-wave kernel (gemm_big.hip) runs this, if any
+  GemmRoute& r = d.route;
+  r = GemmRoute{};
+  r.a_mode = p.a_mode, r.epilogue = p.epilogue, r.store_mode = p.store_mode;
+  r.generic_tile = r.vec4 = -1;
+  if (thin_allowed && i2v_conv_thin_ok(p)) {
+    // narrow-output 3x3 convolutions (conv_out: 4 channels): a halo-tile kernel of their own (conv_thin.hip)
+    r.family = I2V_ROUTE_CONV_THIN;
+  } else if (d.plan.form != GemmBigForm::None) {
+    // large problems whose N is a multiple of 320 (and what else the planner takes) go to the 8-wave LDS-DMA kernel (gemm_big.hip)
+    i2v_gemm_big_route(p, d.plan, r);
+  } else {
+    if (p.store_mode == I2V_STORE_VT_T) d.vec4 = 0;   // the generic kernel stores this mode element by element
+    r.family = I2V_ROUTE_GENERIC;
+    r.generic_tile = generic_tile(p);
+    r.rows = GENERIC_TILES[r.generic_tile][0], r.cols = GENERIC_TILES[r.generic_tile][1];
+    r.vec4 = d.vec4;
+  }
+  return d;
+}
+
+thread_local GemmRoute last_route;
+thread_local bool have_last_route = false;
+
 }  // namespace
+
+extern "C" int i2v_gemm_route(const i2v_gemm_params* pp, GemmRoute* route) {
+  I2V_CHECK_ARG(pp != nullptr && route != nullptr, "i2v_gemm_route: null argument");
+  I2V_CHECK_ARG(pp->M > 0 && pp->N > 0 && pp->K > 0, "i2v_gemm_route: M, N, K must be positive");
+  *route = dispatch(*pp).route;
+  return I2V_OK;
+}
+
+extern "C" int i2v_gemm_last_route(GemmRoute* route) {
+  I2V_CHECK_ARG(route != nullptr, "i2v_gemm_last_route: null argument");
+  I2V_CHECK_ARG(have_last_route, "i2v_gemm_last_route: this thread has launched no i2v_gemm_f16 yet");
+  *route = last_route;
+  return I2V_OK;
+}
+
+extern "C" int i2v_gemm_kernel_exists(const GemmRoute* route) {
+  if (route == nullptr) return 0;
+  switch (route->family) {
+    case I2V_ROUTE_GENERIC: return generic_kernel_exists(*route) ? 1 : 0;
+    case I2V_ROUTE_CONV_THIN:   // one kernel: a plain convolution (i2v_conv_thin_ok refuses everything else)
+      return route->a_mode == I2V_A_CONV3X3 && route->epilogue == I2V_EPI_NONE && route->store_mode == I2V_STORE_ROWMAJOR &&
+                     route->rows == 0 && route->cols == 0 && route->stages == 0 && route->extra == 0 && route->persistent == 0 &&
+                     route->generic_tile == -1
+                 ? 1 : 0;
+    default: return route->generic_tile == -1 && i2v_gemm_big_exists(*route) ? 1 : 0;
+  }
+}
 
 extern "C" int64_t i2v_gemm_workspace_bytes(const i2v_gemm_params* pp) {
   if (pp == nullptr || pp->M <= 0 || pp->N <= 0 || pp->K <= 0) return 0;
@@ -463,8 +572,8 @@ extern "C" int i2v_gemm_f16(const i2v_gemm_params* pp, i2v_stream_t stream) {
     I2V_CHECK_ARG(p.residual == nullptr && p.rowvec == nullptr, "i2v_gemm_f16: VT store takes no residual/rowvec");
   }
 
-  int vec4 = vector_epilogue_ok(p);
-  const GemmBigPlan big_plan = i2v_gemm_big_plan(p, vec4);   // which form of the 8-wave kernel (gemm_big.hip) runs this, if any
+  Dispatch d = dispatch(p);   // the kernel this problem takes; everything below follows it
+  const GemmBigPlan& big_plan = d.plan;
   if (p.rowvec && p.rowvec_period > 0)
     I2V_CHECK_ARG(p.store_mode != I2V_STORE_ROWPERM && p.store_mode != I2V_STORE_VT &&
                       (p.rowvec_period & (p.rowvec_period - 1)) == 0,
@@ -502,49 +611,19 @@ extern "C" int i2v_gemm_f16(const i2v_gemm_params* pp, i2v_stream_t stream) {
     if (ws != 0) return ws < 0 ? ws : I2V_OK;
   }
 #endif
-  // narrow-output 3x3 convolutions (conv_out: 4 channels): a halo-tile kernel of their own (conv_thin.hip)
-  {
-    const int thin = i2v_conv_thin_try(p, reinterpret_cast<hipStream_t>(stream));
-    if (thin != 0) return thin < 0 ? thin : I2V_OK;
-  }
-  // large problems whose N is a multiple of 320 go to the 8-wave LDS-DMA kernel (gemm_big.hip)
-  {
-    const int big = i2v_gemm_big_launch(p, vec4, big_plan, reinterpret_cast<hipStream_t>(stream));
-    if (big != 0) return big < 0 ? big : I2V_OK;
-  }
-  if (p.store_mode == I2V_STORE_VT_T) vec4 = 0;   // the generic kernel stores this mode element by element
-  // tile selection: modelled time = waves of tiles over 256 CUs x tile area / shape efficiency
-  // `eff` is measured relative throughput per tile area on MI355X at the UNet's shapes (tools/kernel_bench.py sweep,
-  // profiles/r1_tile_sweep.txt): the loop is latency-bound, so the smaller tiles with 3 blocks / CU win except
-  // for very long K; the im2col loader favours a short M tile (fewer gathered rows per block).
-  const bool conv = p.a_mode == I2V_A_CONV3X3;
-  const bool long_k = p.K >= 2048;
-  const TileCfg cfgs[4] = {{128, 128, 2, long_k ? 1.15f : 1.00f},
-                           {128, 64, 3, conv ? 1.00f : 1.30f},
-                           {64, 128, 3, conv ? 1.25f : 1.25f},
-                           {64, 64, 5, 1.10f}};
-  int best = 0;
-  double best_t = 1e300;
-  for (int i = 0; i < 4; ++i) {
-    const double tiles = (double)i2v_cdiv(p.M, cfgs[i].bm) * (double)i2v_cdiv(p.N, cfgs[i].bn);
-    const double slots = 256.0 * cfgs[i].blocks_per_cu;
-    const double rounds = tiles <= slots ? 1.0 : tiles / slots;  // partial last round amortised when large
-    const double conc = tiles < slots ? tiles : slots;
-    // per-round time ~ tile area / eff, divided by how busy the CUs are (at most blocks_per_cu blocks share a CU)
-    const double per_cu = (conc / 256.0 < 1.0) ? 1.0 : conc / 256.0;
-    const double t = rounds * per_cu * cfgs[i].bm * cfgs[i].bn / cfgs[i].eff;
-    if (t < best_t) {
-      best_t = t;
-      best = i;
-    }
-  }
-  static const int tile_env = getenv("I2V_GEMM_TILE") ? atoi(getenv("I2V_GEMM_TILE")) : -1;  // tuning override
-  if (tile_env >= 0 && tile_env < 4) best = tile_env;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  switch (best) {
-    case 0: return launch<128, 128>(p, vec4, s);
-    case 1: return launch<128, 64>(p, vec4, s);
-    case 2: return launch<64, 128>(p, vec4, s);
-    default: return launch<64, 64>(p, vec4, s);
+  if (d.route.family == I2V_ROUTE_CONV_THIN) {
+    const int thin = i2v_conv_thin_launch(p, s);
+    if (thin < 0) return thin;
+    if (thin == 0) d = dispatch(p, false);   // the device refuses the kernel its LDS: the route without it
   }
+  int rc = I2V_OK;
+  if (d.route.family == I2V_ROUTE_GENERIC) {
+    rc = launch_tile(d.route.generic_tile, p, d.vec4, s, std::make_integer_sequence<int, N_GENERIC_TILES>{});
+  } else if (d.route.family != I2V_ROUTE_CONV_THIN) {
+    const int big = i2v_gemm_big_launch(p, d.vec4, d.plan, d.route, s);
+    rc = big < 0 ? big : I2V_OK;
+  }
+  if (rc == I2V_OK) last_route = d.route, have_last_route = true;   // (a thread_local: free under capture and replay)
+  return rc;
 }

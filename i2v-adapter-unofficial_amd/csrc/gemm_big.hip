@@ -1336,7 +1336,13 @@ bool want_4wave(const i2v_gemm_params& p, const GemmBigPlan& plan) {
 
 // ---- the launch table
 // what a kernel adds to the plain epilogue; at most one of them per problem
-enum BigExtra { EXTRA_NONE = 0, EXTRA_LNF = 1, EXTRA_HILO = 2, EXTRA_GNS = 4, EXTRA_UPF = 8 };
+enum BigExtra { EXTRA_NONE = I2V_EXTRA_NONE, EXTRA_LNF = I2V_EXTRA_LNF, EXTRA_HILO = I2V_EXTRA_HILO, EXTRA_GNS = I2V_EXTRA_GNS,
+                EXTRA_UPF = I2V_EXTRA_UPF };
+// (split-K: the kernel writes fp32 partials; the reduce pass adds residual_lo and writes c_lo)
+int big_extra(const i2v_gemm_params& p, bool split) {
+  return (p.ln_wsum ? EXTRA_LNF : 0) | (lo_stream(p) && !split ? EXTRA_HILO : 0) | (p.gn_partial ? EXTRA_GNS : 0) |
+         (upconv_fold(p) ? EXTRA_UPF : 0);
+}
 
 // The instantiations of gemm_big_kernel that exist, per tile geometry: everything else is refused by the planner (or, for
 // ln_wsum / gn_partial, by i2v_gemm_f16 through the plan's ln_fold / gn_rows).
@@ -1371,9 +1377,7 @@ int launch_form(const i2v_gemm_params& p, const GemmBigPlan& plan, hipStream_t s
   constexpr int BK = NW == 8 ? 64 : 32;
   const int tiles_n = p.N / BN, ntiles = (int)i2v_cdiv(p.M, BM) * tiles_n;
   const dim3 grid(FAST ? persistent_grid(ntiles) : ntiles, SPLIT ? plan.splits : 1), block(NW * 64);
-  // (split-K: the kernel writes fp32 partials; the reduce pass adds residual_lo and writes c_lo)
-  const int extra = (p.ln_wsum ? EXTRA_LNF : 0) | (lo_stream(p) && !SPLIT ? EXTRA_HILO : 0) | (p.gn_partial ? EXTRA_GNS : 0) |
-                    (upconv_fold(p) ? EXTRA_UPF : 0);
+  const int extra = big_extra(p, SPLIT);
   bool launched = false;
   with_constant<I2V_EPI_NONE, I2V_EPI_GEGLU>(p.epilogue, [&](auto epi) {
     with_constant<I2V_STORE_ROWMAJOR, I2V_STORE_ROWPERM, I2V_STORE_VT, I2V_STORE_VT_T>(p.store_mode, [&](auto store) {
@@ -1395,11 +1399,48 @@ int launch_form(const i2v_gemm_params& p, const GemmBigPlan& plan, hipStream_t s
   return rc < 0 ? rc : 1;
 }
 
-// the plan's tile height as a template argument
-template <int BN, int NS, int AMODE, bool SPLIT = false, bool FAST = false>
-int launch_rows(const i2v_gemm_params& p, const GemmBigPlan& plan, hipStream_t s, const char* what) {
-  return plan.rows == 256 ? launch_form<256, BN, NS, AMODE, SPLIT, FAST>(p, plan, s, what)
-                          : launch_form<128, BN, NS, AMODE, SPLIT, FAST>(p, plan, s, what);
+// The tile geometries of the launch table: every (tile height, column tile, LDS stages, A source, split-K, persistent walk) that a
+// route can name.  The launch and the existence query (i2v_gemm_kernel_exists) both walk THIS list: a geometry added here is
+// launched and reported, one that is not here is neither.
+template <int BM_, int BN_, int NS_, int AMODE_, bool SPLIT_ = false, bool FAST_ = false>
+struct Geo {
+  static constexpr int BM = BM_, BN = BN_, NS = NS_, AMODE = AMODE_;
+  static constexpr bool SPLIT = SPLIT_, FAST = FAST_;
+  static bool is(const GemmRoute& r) {
+    const int family = NS > 2 ? I2V_ROUTE_BIG_DEEP : SPLIT ? I2V_ROUTE_BIG_SPLITK : I2V_ROUTE_BIG_TILE;
+    return r.family == family && r.rows == BM && r.cols == BN && r.stages == NS && r.a_mode == AMODE && (r.persistent != 0) == FAST;
+  }
+};
+// f(Geo<...>{}) for each geometry until one returns true; false if none does
+template <class F>
+bool for_each_geometry(F&& f) {
+  constexpr int PLAIN = I2V_A_PLAIN, CONV = I2V_A_CONV3X3;
+  return
+      // the tile form: 320 columns, plain (one tile per workgroup, or the persistent walk) or 3x3 convolution
+      f(Geo<256, BIG_BN, 2, PLAIN>{}) || f(Geo<128, BIG_BN, 2, PLAIN>{}) ||
+      f(Geo<256, BIG_BN, 2, PLAIN, false, true>{}) || f(Geo<128, BIG_BN, 2, PLAIN, false, true>{}) ||
+      f(Geo<256, BIG_BN, 2, CONV>{}) || f(Geo<128, BIG_BN, 2, CONV>{}) ||
+      // 3x3 convolutions whose channel count is not a multiple of 320 (the VAE: 128 / 256 / 512): column tiles of 256 or 128
+      f(Geo<256, 256, 2, CONV>{}) || f(Geo<128, 256, 2, CONV>{}) || f(Geo<256, 128, 2, CONV>{}) || f(Geo<128, 128, 2, CONV>{}) ||
+      // the deep-pipeline form
+      f(Geo<128, 256, 3, PLAIN>{}) || f(Geo<128, 128, 4, PLAIN>{}) ||
+      // split-K
+      f(Geo<256, BIG_BN, 2, PLAIN, true>{}) || f(Geo<128, BIG_BN, 2, PLAIN, true>{}) ||
+      f(Geo<256, BIG_BN, 2, CONV, true>{}) || f(Geo<128, BIG_BN, 2, CONV, true>{});
+}
+
+int launch_route(const i2v_gemm_params& p, const GemmBigPlan& plan, const GemmRoute& route, hipStream_t s, const char* what) {
+  int rc = 0;
+  const bool found = for_each_geometry([&](auto g) {
+    using G = decltype(g);
+    if (!G::is(route)) return false;
+    rc = launch_form<G::BM, G::BN, G::NS, G::AMODE, G::SPLIT, G::FAST>(p, plan, s, what);
+    return true;
+  });
+  if (!found)
+    I2V_FAIL(I2V_ERR_UNSUPPORTED, "%s: no %d x %d tile with %d stages (a_mode %d, family %d, persistent %d) in the launch table", what,
+             route.rows, route.cols, route.stages, route.a_mode, route.family, route.persistent);
+  return rc;
 }
 
 }  // namespace
@@ -1422,30 +1463,42 @@ GemmBigPlan i2v_gemm_big_plan(const i2v_gemm_params& p, int vec4) {
 int i2v_gemm_alt_try(const i2v_gemm_params& p, hipStream_t s);   // variants/gemm_alt.hip: short-K problems, alternating wave groups
 #endif
 
-int i2v_gemm_big_launch(const i2v_gemm_params& p, int vec4, const GemmBigPlan& plan, hipStream_t s) {
-  constexpr int PLAIN = I2V_A_PLAIN, CONV = I2V_A_CONV3X3;
-  const bool conv = p.a_mode == I2V_A_CONV3X3;
+void i2v_gemm_big_route(const i2v_gemm_params& p, const GemmBigPlan& plan, GemmRoute& route) {
+  route.family = plan.form == GemmBigForm::Deep ? I2V_ROUTE_BIG_DEEP : plan.form == GemmBigForm::SplitK ? I2V_ROUTE_BIG_SPLITK : I2V_ROUTE_BIG_TILE;
+  route.rows = plan.rows, route.cols = plan.cols, route.stages = plan.stages;
+  route.splits = plan.splits, route.kps = plan.kps;
+  route.extra = big_extra(p, plan.form == GemmBigForm::SplitK);
+  route.persistent = plan.persistent ? 1 : 0;
+}
+
+bool i2v_gemm_big_exists(const GemmRoute& route) {
+  bool exists = false;
+  for_each_geometry([&](auto g) {
+    using G = decltype(g);
+    if (!G::is(route)) return false;
+    exists = big_kernel_exists<G::BN, G::NS, G::AMODE, G::SPLIT, G::FAST, 8>(route.epilogue, route.store_mode, route.extra);
+    return true;
+  });
+  return exists;
+}
+
+int i2v_gemm_big_launch(const i2v_gemm_params& p, int vec4, const GemmBigPlan& plan, GemmRoute& route, hipStream_t s) {
   switch (plan.form) {
     case GemmBigForm::None:
       return 0;
     case GemmBigForm::Tile:
-      // 3x3 convolutions whose channel count is not a multiple of 320 (the VAE: 128 / 256 / 512): column tiles of 256 or 128
-      if (plan.cols == 256) return launch_rows<256, 2, CONV>(p, plan, s, "i2v_gemm_f16(big conv)");
-      if (plan.cols == 128) return launch_rows<128, 2, CONV>(p, plan, s, "i2v_gemm_f16(big conv)");
 #ifdef I2V_VARIANTS
-      if (const int rc = i2v_gemm_alt_try(p, s); rc != 0) return rc;
-      if (plan.four_wave) return launch_form<128, BIG_BN, 2, PLAIN, false, false, 4>(p, plan, s, "i2v_gemm_f16(big, 4-wave)");
+      if (plan.cols == BIG_BN) {
+        if (const int rc = i2v_gemm_alt_try(p, s); rc != 0) return rc;
+        if (plan.four_wave) return launch_form<128, BIG_BN, 2, I2V_A_PLAIN, false, false, 4>(p, plan, s, "i2v_gemm_f16(big, 4-wave)");
+      }
 #endif
-      if (conv) return launch_rows<BIG_BN, 2, CONV>(p, plan, s, "i2v_gemm_f16(big)");
-      if (plan.persistent && persistent_grid(1 << 20) != (1 << 20))   // (the CU count is known)
-        return launch_rows<BIG_BN, 2, PLAIN, false, true>(p, plan, s, "i2v_gemm_f16(big, persistent)");
-      return launch_rows<BIG_BN, 2, PLAIN>(p, plan, s, "i2v_gemm_f16(big)");
+      if (route.persistent && persistent_grid(1 << 20) == (1 << 20)) route.persistent = 0;   // (the CU count is not known)
+      return launch_route(p, plan, route, s, route.persistent ? "i2v_gemm_f16(big, persistent)" : "i2v_gemm_f16(big)");
     case GemmBigForm::Deep:
-      return plan.cols == 256 ? launch_form<128, 256, 3, PLAIN>(p, plan, s, "i2v_gemm_f16(big, deep pipeline)")
-                              : launch_form<128, 128, 4, PLAIN>(p, plan, s, "i2v_gemm_f16(big, deep pipeline)");
+      return launch_route(p, plan, route, s, "i2v_gemm_f16(big, deep pipeline)");
     case GemmBigForm::SplitK: {
-      const int rc = conv ? launch_rows<BIG_BN, 2, CONV, true>(p, plan, s, "i2v_gemm_f16(split-K)")
-                          : launch_rows<BIG_BN, 2, PLAIN, true>(p, plan, s, "i2v_gemm_f16(split-K)");
+      const int rc = launch_route(p, plan, route, s, "i2v_gemm_f16(split-K)");
       if (rc < 0) return rc;
       const int64_t groups = (int64_t)p.M * (p.N / 4);
       const int blocks = (int)(i2v_cdiv(groups, 256) < 2048 ? i2v_cdiv(groups, 256) : 2048);

@@ -146,10 +146,19 @@ struct GemmBigPlan {
 };
 // Pure host arithmetic (no device call).  The form depends on whether p.workspace is attached; workspace_bytes does not.
 GemmBigPlan i2v_gemm_big_plan(const i2v_gemm_params& p, int vec4);
-// returns 1 if it launched, 0 if plan.form is None (the caller uses the generic kernel), < 0 on error
-int i2v_gemm_big_launch(const i2v_gemm_params& p, int vec4, const GemmBigPlan& plan, hipStream_t s);
-// conv_thin.hip: 3x3 convolutions with <= 16 output channels (same return convention)
-int i2v_conv_thin_try(const i2v_gemm_params& p, hipStream_t s);
+using GemmRoute = struct i2v_gemm_route;   // (include/i2v_hip.h; the bare name is the query function)
+// The plan as the fields of a route (include/i2v_hip.h, i2v_gemm_route): family, tile, stages, split plan, extra, persistent.
+// plan.form must not be None.
+void i2v_gemm_big_route(const i2v_gemm_params& p, const GemmBigPlan& plan, GemmRoute& route);
+// Launches the instantiation `route` names (filled by i2v_gemm_big_route from `plan`): 1 if it launched, < 0 on error.  A
+// persistent route whose walk cannot be sized (the device's CU count is unknown) runs un-walked and is corrected in place.
+int i2v_gemm_big_launch(const i2v_gemm_params& p, int vec4, const GemmBigPlan& plan, GemmRoute& route, hipStream_t s);
+// whether the launch table of the 8-wave kernel holds the instantiation `route` names (read from the table itself)
+bool i2v_gemm_big_exists(const GemmRoute& route);
+// conv_thin.hip: 3x3 convolutions with <= 16 output channels.  _ok: whether p is its problem (pure host arithmetic);
+// _launch: 1 launched, 0 the device refuses its LDS (the caller goes on to the tile kernels), < 0 error
+bool i2v_conv_thin_ok(const i2v_gemm_params& p);
+int i2v_conv_thin_launch(const i2v_gemm_params& p, hipStream_t s);
 // implemented in gemm_ws.hip: the weight-stationary kernel for K = 320 row-major projections with >= 16384 rows (W slices in
 // registers, A streamed through three LDS stages); same return convention as i2v_gemm_big_launch
 int i2v_gemm_ws_try(const i2v_gemm_params& p, hipStream_t s);

@@ -203,6 +203,14 @@ def _attach_splitk_workspace(lib, p, device):
     return ws
 
 
+def last_gemm_route() -> dict:
+    """the kernel instantiation that this thread's most recent `gemm` / `conv3x3` / `project_vt` launch took, as the fields of
+    i2v_gemm_route (family, a_mode, rows, cols, stages, splits, kps, extra, persistent, generic_tile, vec4, epilogue, store_mode)"""
+    r = _lib.GemmRoute()
+    _lib.check(_lib.load().i2v_gemm_last_route(C.byref(r)), "i2v_gemm_last_route")
+    return r.as_dict()
+
+
 def conv_k_block(cin: int) -> int:
     """contraction order of the 3x3 convolution for this (padded) channel count: 64 = channel-block-major (the 9 taps
     of a 64-channel block are consecutive, i2v_gemm_params.conv_kblock), 0 = tap-major.  `blocks.pack_conv3x3` lays the

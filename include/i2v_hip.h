@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define I2V_ABI_VERSION 18
+#define I2V_ABI_VERSION 19
 
 #define I2V_OK 0
 #define I2V_ERR_INVALID_ARG (-1)
@@ -180,6 +180,43 @@ int64_t i2v_gemm_workspace_bytes(const i2v_gemm_params* p);
 /* rows per block of the GroupNorm partials i2v_gemm_f16 would write for this problem with gn_partial set (gn_groups must be set;
    pointers are not dereferenced); 0: not implemented for it. */
 int32_t i2v_gemm_gn_partial_rows(const i2v_gemm_params* p);
+
+/* (ABI 19) Which kernel a problem takes.  i2v_gemm_f16 dispatches to one of several dozen kernel instantiations; the route names
+   the one a problem gets, decided by the same function the launch follows (there is no second copy of the rules). */
+enum {
+  I2V_ROUTE_GENERIC = 0,   /* the 4-wave register-staged kernel (csrc/gemm.hip): `generic_tile`, `vec4`              */
+  I2V_ROUTE_CONV_THIN = 1, /* the halo-tile kernel of narrow 3x3 convolutions (csrc/conv_thin.hip)                    */
+  I2V_ROUTE_BIG_TILE = 2,  /* the 8-wave LDS-DMA kernel (csrc/gemm_big.hip), one output tile per workgroup / walk     */
+  I2V_ROUTE_BIG_DEEP = 3,  /* ... its deep-pipeline form (three / four LDS stages)                                     */
+  I2V_ROUTE_BIG_SPLITK = 4 /* ... with K split over workgroups and the reduce pass                                     */
+};
+enum { I2V_EXTRA_NONE = 0, I2V_EXTRA_LNF = 1, I2V_EXTRA_HILO = 2, I2V_EXTRA_GNS = 4, I2V_EXTRA_UPF = 8 };
+
+/* (a struct tag only: the query below carries the same name) */
+struct i2v_gemm_route {
+  int32_t family;       /* I2V_ROUTE_*                                                                                */
+  int32_t a_mode;       /* I2V_A_* (echoed: the kernels are instantiated per A source)                                */
+  int32_t rows, cols;   /* tile: 8-wave kernel 256 / 128 x 320 / 256 / 128; generic 128 / 64 x 128 / 64; thin 0, 0    */
+  int32_t stages;       /* LDS stages of the 8-wave kernel (2; deep: 3 / 4), else 0                                   */
+  int32_t splits, kps;  /* split-K: K ranges and 64-deep K tiles per range, else 0                                    */
+  int32_t extra;        /* I2V_EXTRA_*: what the 8-wave kernel adds to the plain epilogue (LayerNorm fold, hi + lo
+                           stores, GroupNorm partials, folded up-sampling); 0 for the other families                 */
+  int32_t persistent;   /* 1: the persistent tile walk (I2V_GEMM_PERSIST)                                             */
+  int32_t generic_tile; /* generic kernel: 0 = 128x128, 1 = 128x64, 2 = 64x128, 3 = 64x64; else -1                    */
+  int32_t vec4;         /* generic kernel: 1 = 8-byte vector epilogue, 0 = element by element; else -1                */
+  int32_t epilogue;     /* I2V_EPI_* (echoed)                                                                         */
+  int32_t store_mode;   /* I2V_STORE_* (echoed)                                                                       */
+};
+
+/* The route i2v_gemm_f16 would take for p (its workspace and pointers as attached; pointers are only tested for null and
+   alignment): pure host arithmetic, no device call.  The problem's arguments are NOT validated here; < 0 on null arguments. */
+int i2v_gemm_route(const i2v_gemm_params* p, struct i2v_gemm_route* route);
+/* The route of the calling thread's most recent i2v_gemm_f16 that reached a launch (< 0: none yet). */
+int i2v_gemm_last_route(struct i2v_gemm_route* route);
+/* 1 if the kernel instantiation that `route` names (family, a_mode, rows, cols, stages, extra, persistent, generic_tile,
+   epilogue, store_mode; splits / kps / vec4 are run-time arguments and are not read) is in the launch table, else 0.  Read from
+   the launch table itself. */
+int i2v_gemm_kernel_exists(const struct i2v_gemm_route* route);
 
 /* ------------------------------------------------------------------------------------------------
  * Flash-style attention forward (MFMA QK^T / PV, wavefront-shuffle online softmax).

@@ -43,7 +43,8 @@ def test_every_declared_symbol_is_exported_and_bound(lib):
 def test_ctypes_structs_match_header(lib):
     names = {"i2v_gemm_params": lib.GemmParams, "i2v_attn_params": lib.AttnParams, "i2v_tattn_params": lib.TAttnParams,
              "i2v_gn_params": lib.GnParams, "i2v_ln_params": lib.LnParams, "i2v_motion_attn_params": lib.MotionAttnParams,
-             "i2v_cross_attn_fused_params": lib.CrossAttnFusedParams, "i2v_ff_fused_params": lib.FfFusedParams}
+             "i2v_cross_attn_fused_params": lib.CrossAttnFusedParams, "i2v_ff_fused_params": lib.FfFusedParams,
+             "struct i2v_gemm_route": lib.GemmRoute}
     prog = ['#include <stdio.h>', '#include <stddef.h>', f'#include "{HEADER}"', "int main(void){"]
     for cname, cls in names.items():
         prog.append(f'printf("{cname} %zu\\n", sizeof({cname}));')
@@ -55,7 +56,7 @@ def test_ctypes_structs_match_header(lib):
         open(src, "w").write("\n".join(prog))
         subprocess.run(["gcc", "-std=c99", "-o", exe, src], check=True)
         out = subprocess.run([exe], check=True, capture_output=True, text=True).stdout
-    got = dict(line.split() for line in out.strip().splitlines())
+    got = dict(line.rsplit(" ", 1) for line in out.strip().splitlines())
     for cname, cls in names.items():
         assert int(got[cname]) == C.sizeof(cls), cname
         for fname, _ in cls._fields_:

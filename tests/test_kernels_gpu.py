@@ -52,13 +52,14 @@ def test_gemm_plain(dev, M, N, K_):
 
 
 @pytest.mark.parametrize("M,N,K_,kind", [
-    (49152, 320, 320, "plain"), (49152, 640, 136, "plain"), (16384, 320, 640, "plain"), (16500, 320, 200, "plain"),
-    (49152, 640, 64, "geglu"), (16384, 320, 64, "rowperm"), (49152, 320, 128, "dual"), (320, 40960, 64, "vt"),
-    # M tails through the LDS-staged row-contiguous epilogue (K % 64 == 0 keeps them on the 8-wave kernel)
+    (49152, 320, 320, "plain"), (49152, 640, 192, "plain"), (16384, 320, 640, "plain"), (16500, 320, 256, "plain"),
+    (49152, 640, 128, "geglu"), (16384, 320, 128, "rowperm"), (49152, 320, 128, "dual"), (320, 40960, 128, "vt"),
+    # M tails through the LDS-staged row-contiguous epilogue (K % 64 == 0, K >= 128 keeps them on the 8-wave kernel)
     (16500, 320, 192, "plain"), (33000, 640, 128, "geglu"), (16416, 320, 128, "rowperm"), (40000, 960, 320, "plain")])
 def test_gemm_big_tiles(dev, M, N, K_, kind):
-    """shapes that take the 8-wave LDS-DMA kernel (N % 320 == 0, >= 128 tiles): 256- and 128-row tiles, M / K tails,
-    every epilogue / store mode."""
+    """shapes that take the 8-wave LDS-DMA kernel (N % 320 == 0, >= 125 tiles, K a multiple of 64 from 128 on): 256- and 128-row
+    tiles, M tails, odd K-tile counts, every epilogue / store mode.  The route is asserted: a planner threshold that moves must not
+    move these cases to another kernel unnoticed."""
     k = K()
     g = torch.Generator().manual_seed(M + N + K_)
     a = h(torch.randn(M, K_, generator=g))
@@ -85,6 +86,7 @@ def test_gemm_big_tiles(dev, M, N, K_, kind):
         vt = k.project_vt(wd, ad, 4096)       # tokens = w (N rows), weight = a (M = 320 channels)
         ref = (w @ a.T).reshape(N // 4096, 4096, M).permute(0, 2, 1)
         close(vt[:, :, :4096], ref, name="big vt")
+    assert k.last_gemm_route()["family"] == k._lib.I2V_ROUTE_BIG_TILE
 
 
 def test_gemm_and_conv_split_k(dev):
@@ -96,6 +98,7 @@ def test_gemm_and_conv_split_k(dev):
     b, r = h(torch.randn(N, generator=g)), h(torch.randn(M, N, generator=g))
     out = k.gemm(a.half().to(dev), w.half().to(dev), b.half().to(dev), residual=r.half().to(dev))
     close(out, a @ w.T + b + r, name="split-K gemm")
+    assert k.last_gemm_route()["family"] == k._lib.I2V_ROUTE_BIG_SPLITK and k.last_gemm_route()["rows"] == 256
     n, hh, ww, cin, cout = 32, 8, 8, 320, 1280
     x = h(torch.randn(n, cin, hh, ww, generator=g))
     wc = h(torch.randn(cout, cin, 3, 3, generator=g) / math.sqrt(9 * cin))
@@ -106,6 +109,7 @@ def test_gemm_and_conv_split_k(dev):
     wp = _pack_conv(wc).to(dev)
     out = k.conv3x3(xt, wp, bc.half().to(dev), rowvec=rv.half().to(dev), rows_per_vec=hh * ww)
     close(out.permute(0, 3, 1, 2), ref, name="split-K conv")
+    assert k.last_gemm_route()["family"] == k._lib.I2V_ROUTE_BIG_SPLITK and k.last_gemm_route()["rows"] == 128
 
 
 @pytest.mark.parametrize("M,N,K_,kind", [
@@ -143,6 +147,7 @@ def test_gemm_deep_pipeline_small_levels(dev, M, N, K_, kind):
         vt = k.project_vt(wd, ad, 64)
         ref = (w @ a.T).reshape(N // 64, 64, M).permute(0, 2, 1)
         close(vt[:, :, :64], ref, name="deep vt")
+    assert k.last_gemm_route()["family"] == k._lib.I2V_ROUTE_BIG_DEEP
 
 
 @pytest.mark.parametrize("batches,L,C,Kd", [(4, 6, 24, 16), (2, 64, 320, 64), (3, 4096, 640, 64), (5, 16, 320, 320)])

@@ -10,7 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # I2V_LIB_PATH selects another build of the same ABI (same-box A/B of two kernels, tools/ab_bench.sh); the in-tree
 # library is never overwritten by tooling
 LIB_PATH = os.environ.get("I2V_LIB_PATH") or os.path.join(_HERE, "libi2v_hip.so")
-ABI_VERSION = 19
+ABI_VERSION = 20
 
 I2V_EPI_NONE, I2V_EPI_GELU, I2V_EPI_GEGLU = 0, 1, 2
 I2V_STORE_ROWMAJOR, I2V_STORE_ROWPERM, I2V_STORE_VT, I2V_STORE_VT_T = 0, 1, 2, 3
@@ -18,6 +18,7 @@ I2V_A_PLAIN, I2V_A_CONV3X3 = 0, 1
 I2V_LORA_MAX_ADAPTERS, I2V_LORA_MAX_RANK = 8, 256
 I2V_ROUTE_GENERIC, I2V_ROUTE_CONV_THIN, I2V_ROUTE_BIG_TILE, I2V_ROUTE_BIG_DEEP, I2V_ROUTE_BIG_SPLITK = 0, 1, 2, 3, 4
 I2V_EXTRA_NONE, I2V_EXTRA_LNF, I2V_EXTRA_HILO, I2V_EXTRA_GNS, I2V_EXTRA_UPF = 0, 1, 2, 4, 8
+I2V_TATTN_LDS_FORM, I2V_TATTN_REG_FORM = 0, 1
 
 
 class HipLibraryError(RuntimeError):
@@ -108,6 +109,17 @@ class TAttnParams(C.Structure):
         ("n_pixels", C.c_int32), ("frames", C.c_int32), ("heads", C.c_int32), ("head_dim", C.c_int32),
         ("scale", C.c_float),
     ]
+
+
+class TAttnRoute(C.Structure):
+    """struct i2v_tattn_route: the kernel instantiation a temporal-attention problem takes"""
+    _fields_ = [
+        ("form", C.c_int32), ("dqk", C.c_int32), ("dpv", C.c_int32),
+        ("pf", C.c_int32), ("nqt", C.c_int32), ("blocks", C.c_int32),
+    ]
+
+    def as_dict(self):
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
 
 
 class MotionAttnParams(C.Structure):
@@ -234,6 +246,9 @@ SIGNATURES = {
     "i2v_gemm_kernel_exists": (C.c_int, [C.POINTER(GemmRoute)]),
     "i2v_attention_f16": (C.c_int, [C.POINTER(AttnParams), _P]),
     "i2v_temporal_attention_f16": (C.c_int, [C.POINTER(TAttnParams), _P]),
+    "i2v_temporal_attention_route": (C.c_int, [C.POINTER(TAttnParams), C.POINTER(TAttnRoute)]),
+    "i2v_temporal_attention_last_route": (C.c_int, [C.POINTER(TAttnRoute)]),
+    "i2v_tattn_kernel_exists": (C.c_int, [C.POINTER(TAttnRoute)]),
     "i2v_motion_attn_supported": (C.c_int32, [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "i2v_motion_attn_pack_rows": (C.c_int32, [C.c_int32, C.c_int32]),
     "i2v_motion_attn_f16": (C.c_int, [C.POINTER(MotionAttnParams), _P]),

@@ -260,64 +260,132 @@ __global__ __launch_bounds__(256) void tattn_lds_kernel(const i2v_tattn_params p
   }
 }
 
-template <int DQK, int DPV>
-int launch_t(const i2v_tattn_params& p, hipStream_t s) {
-  const float scale_log2 = p.scale * 1.4426950408889634f;
-  const int C = p.heads * p.head_dim;
-  static const int lds_off = getenv("I2V_TATTN_LDS") ? (atoi(getenv("I2V_TATTN_LDS")) == 0) : 0;
-  // 64 KiB = the dynamic-LDS size a kernel may request without hipFuncSetAttribute, and two workgroups per CU
-  const size_t lds = (size_t)(3 * 16 * (C + 8) + C * (p.vt_ld + 8)) * sizeof(f16);
-  if (!lds_off && p.frames <= 16 && lds <= 64 * 1024 && p.o_row_stride % 8 == 0 &&
-      (reinterpret_cast<uintptr_t>(p.o) & 15) == 0) {
-    int64_t blocks = p.n_pixels < 256 * 8 ? p.n_pixels : 256 * 8;
-    const int chunks = (C / 8) * (p.frames > p.vt_ld ? p.frames : p.vt_ld);   // max(F * C / 8, C * vt_ld / 8)
-    if (chunks <= 256)
-      hipLaunchKernelGGL((tattn_lds_kernel<DQK, DPV, 1>), dim3((unsigned)blocks), dim3(256), lds, s, p, scale_log2);
-    else if (chunks <= 512)
-      hipLaunchKernelGGL((tattn_lds_kernel<DQK, DPV, 2>), dim3((unsigned)blocks), dim3(256), lds, s, p, scale_log2);
-    else if (chunks <= 768)
-      hipLaunchKernelGGL((tattn_lds_kernel<DQK, DPV, 3>), dim3((unsigned)blocks), dim3(256), lds, s, p, scale_log2);
-    else
-      hipLaunchKernelGGL((tattn_lds_kernel<DQK, DPV, 4>), dim3((unsigned)blocks), dim3(256), lds, s, p, scale_log2);
-    return i2v_check_launch("i2v_temporal_attention_f16");
-  }
-  const int64_t items64 = (int64_t)p.n_pixels * p.heads;
-  const int n_items = (int)items64;
-  int64_t blocks = i2v_cdiv(items64, 4);
-  if (blocks > 256 * 8) blocks = 256 * 8;
-  if (p.frames <= 16)
-    hipLaunchKernelGGL((tattn_kernel<DQK, DPV, 1>), dim3((unsigned)blocks), dim3(256), 0, s, p, scale_log2, n_items);
-  else
-    hipLaunchKernelGGL((tattn_kernel<DQK, DPV, 2>), dim3((unsigned)blocks), dim3(256), 0, s, p, scale_log2, n_items);
-  return i2v_check_launch("i2v_temporal_attention_f16");
+using TattnRoute = struct i2v_tattn_route;   // (include/i2v_hip.h)
+
+// ---- THE launch table: every instantiation the library holds.  The launch (i2v_temporal_attention_f16) and the existence query
+// (i2v_tattn_kernel_exists) both walk this array; a class or a form added here is launchable and visible at once.
+using LaunchFn = void (*)(const i2v_tattn_params& p, float scale_log2, unsigned blocks, size_t lds, int n_items, hipStream_t s);
+
+template <int DQK, int DPV, int PF>
+void run_lds(const i2v_tattn_params& p, float scale_log2, unsigned blocks, size_t lds, int, hipStream_t s) {
+  hipLaunchKernelGGL((tattn_lds_kernel<DQK, DPV, PF>), dim3(blocks), dim3(256), lds, s, p, scale_log2);
+}
+template <int DQK, int DPV, int NQT>
+void run_reg(const i2v_tattn_params& p, float scale_log2, unsigned blocks, size_t, int n_items, hipStream_t s) {
+  hipLaunchKernelGGL((tattn_kernel<DQK, DPV, NQT>), dim3(blocks), dim3(256), 0, s, p, scale_log2, n_items);
+}
+
+struct TattnEntry {
+  int form, dqk, dpv, pf, nqt;
+  LaunchFn fn;
+};
+constexpr int MAX_PF = 4;   // the largest chunk count per thread and operand the LDS form is instantiated with
+#define TATTN_CLASS(DQK, DPV)                                                                                        \
+  {I2V_TATTN_LDS_FORM, DQK, DPV, 1, 0, run_lds<DQK, DPV, 1>}, {I2V_TATTN_LDS_FORM, DQK, DPV, 2, 0, run_lds<DQK, DPV, 2>}, \
+  {I2V_TATTN_LDS_FORM, DQK, DPV, 3, 0, run_lds<DQK, DPV, 3>}, {I2V_TATTN_LDS_FORM, DQK, DPV, 4, 0, run_lds<DQK, DPV, 4>}, \
+  {I2V_TATTN_REG_FORM, DQK, DPV, 0, 1, run_reg<DQK, DPV, 1>}, {I2V_TATTN_REG_FORM, DQK, DPV, 0, 2, run_reg<DQK, DPV, 2>}
+// head-dim classes in ascending order of DPV: a head_dim takes the first class whose DPV holds it
+const TattnEntry TATTN_TABLE[] = {TATTN_CLASS(32, 16),  TATTN_CLASS(32, 32),  TATTN_CLASS(64, 48),   TATTN_CLASS(64, 64),
+                                  TATTN_CLASS(96, 80),  TATTN_CLASS(96, 96),  TATTN_CLASS(128, 128), TATTN_CLASS(160, 160)};
+#undef TATTN_CLASS
+constexpr int MAX_HEAD_DIM = 160;
+
+const TattnEntry* find_entry(const TattnRoute& r) {
+  for (const TattnEntry& e : TATTN_TABLE)
+    if (e.form == r.form && e.dqk == r.dqk && e.dpv == r.dpv && e.pf == r.pf && e.nqt == r.nqt) return &e;
+  return nullptr;
 }
 
 inline bool al(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0; }
 
+// what the kernels assume of a problem (pointers: null and alignment only)
+int check_args(const i2v_tattn_params& p, const char* who) {
+  I2V_CHECK_ARG(p.q && p.k && p.vt && p.o, "%s: null pointer", who);
+  I2V_CHECK_ARG(p.n_pixels > 0 && p.heads > 0, "%s: n_pixels / heads must be positive", who);
+  I2V_CHECK_ARG((int64_t)p.n_pixels * p.heads < (1ll << 31), "%s: too many items", who);
+  I2V_CHECK_ARG(p.frames >= 1 && p.frames <= 32, "%s: frames (%d) must be in [1, 32]", who, p.frames);
+  I2V_CHECK_ARG(p.head_dim > 0 && p.head_dim % 8 == 0 && p.head_dim <= MAX_HEAD_DIM,
+                "%s: head_dim (%d) must be a multiple of 8 and <= %d", who, p.head_dim, MAX_HEAD_DIM);
+  I2V_CHECK_ARG((int64_t)p.heads * p.head_dim < (1ll << 31), "%s: heads * head_dim does not fit 31 bits", who);
+  I2V_CHECK_ARG(p.q_row_stride % 8 == 0 && p.k_row_stride % 8 == 0 && p.o_row_stride % 4 == 0,
+                "%s: row strides must be multiples of 8 (q, k) / 4 (o)", who);
+  I2V_CHECK_ARG(p.vt_ld % 8 == 0 && p.vt_ld >= ((p.frames + 7) / 8) * 8,
+                "%s: vt_ld must be a multiple of 8 and >= frames rounded up to 8", who);
+  I2V_CHECK_ARG(al(p.q, 16) && al(p.k, 16) && al(p.vt, 16) && al(p.o, 8), "%s: pointer alignment", who);
+  return I2V_OK;
+}
+
+// THE dispatch rule: which instantiation runs a problem that passed check_args.  i2v_temporal_attention_f16 launches what this
+// answers and i2v_temporal_attention_route reports it; pure host arithmetic.
+struct TattnDispatch {
+  TattnRoute route;
+  size_t lds;   // dynamic LDS bytes of the LDS form, else 0
+};
+TattnDispatch dispatch(const i2v_tattn_params& p) {
+  TattnDispatch d{};
+  TattnRoute& r = d.route;
+  for (const TattnEntry& e : TATTN_TABLE)
+    if (p.head_dim <= e.dpv) {
+      r.dqk = e.dqk, r.dpv = e.dpv;
+      break;
+    }
+  static const int lds_off = getenv("I2V_TATTN_LDS") ? (atoi(getenv("I2V_TATTN_LDS")) == 0) : 0;
+  const int64_t C = (int64_t)p.heads * p.head_dim;
+  // 64 KiB = the dynamic-LDS size a kernel may request without hipFuncSetAttribute, and two workgroups per CU
+  const int64_t lds = (3 * 16 * (C + 8) + C * ((int64_t)p.vt_ld + 8)) * (int64_t)sizeof(f16);
+  // 16-byte chunks of the larger operand of one pixel: max(F * C / 8, C * vt_ld / 8) = C * vt_ld / 8 (vt_ld >= frames); a thread of
+  // the LDS form moves PF of them, so more than 256 * MAX_PF cannot be staged (a vt_ld wider than pad8(frames) reaches that inside
+  // the 64 KiB) and go to the register form, which reads V^T rows in place
+  const int64_t chunks = (C / 8) * p.vt_ld;
+  if (!lds_off && p.frames <= 16 && lds <= 64 * 1024 && chunks <= 256 * MAX_PF && p.o_row_stride % 8 == 0 && al(p.o, 16)) {
+    r.form = I2V_TATTN_LDS_FORM;
+    r.pf = (int)i2v_cdiv(chunks, 256);
+    r.blocks = p.n_pixels < 256 * 8 ? p.n_pixels : 256 * 8;
+    d.lds = (size_t)lds;
+  } else {
+    r.form = I2V_TATTN_REG_FORM;
+    r.nqt = p.frames <= 16 ? 1 : 2;
+    const int64_t blocks = i2v_cdiv((int64_t)p.n_pixels * p.heads, 4);
+    r.blocks = (int32_t)(blocks < 256 * 8 ? blocks : 256 * 8);
+  }
+  return d;
+}
+
+thread_local TattnRoute last_route;
+thread_local bool have_last_route = false;
+
 }  // namespace
+
+extern "C" int i2v_temporal_attention_route(const i2v_tattn_params* pp, TattnRoute* route) {
+  I2V_CHECK_ARG(pp != nullptr && route != nullptr, "i2v_temporal_attention_route: null argument");
+  if (const int rc = check_args(*pp, "i2v_temporal_attention_route")) return rc;
+  *route = dispatch(*pp).route;
+  return I2V_OK;
+}
+
+extern "C" int i2v_temporal_attention_last_route(TattnRoute* route) {
+  I2V_CHECK_ARG(route != nullptr, "i2v_temporal_attention_last_route: null argument");
+  I2V_CHECK_ARG(have_last_route, "i2v_temporal_attention_last_route: this thread has launched no i2v_temporal_attention_f16 yet");
+  *route = last_route;
+  return I2V_OK;
+}
+
+extern "C" int i2v_tattn_kernel_exists(const TattnRoute* route) {
+  return route != nullptr && find_entry(*route) != nullptr ? 1 : 0;
+}
 
 extern "C" int i2v_temporal_attention_f16(const i2v_tattn_params* pp, i2v_stream_t stream) {
   I2V_CHECK_ARG(pp != nullptr, "i2v_temporal_attention_f16: null params");
   const i2v_tattn_params& p = *pp;
-  I2V_CHECK_ARG(p.q && p.k && p.vt && p.o, "i2v_temporal_attention_f16: null pointer");
-  I2V_CHECK_ARG(p.n_pixels > 0 && p.heads > 0, "i2v_temporal_attention_f16: n_pixels / heads must be positive");
-  I2V_CHECK_ARG((int64_t)p.n_pixels * p.heads < (1ll << 31), "i2v_temporal_attention_f16: too many items");
-  I2V_CHECK_ARG(p.frames >= 1 && p.frames <= 32, "i2v_temporal_attention_f16: frames (%d) must be in [1, 32]", p.frames);
-  I2V_CHECK_ARG(p.head_dim > 0 && p.head_dim % 8 == 0 && p.head_dim <= 160,
-                "i2v_temporal_attention_f16: head_dim (%d) must be a multiple of 8 and <= 160", p.head_dim);
-  I2V_CHECK_ARG(p.q_row_stride % 8 == 0 && p.k_row_stride % 8 == 0 && p.o_row_stride % 4 == 0,
-                "i2v_temporal_attention_f16: row strides must be multiples of 8 (q, k) / 4 (o)");
-  I2V_CHECK_ARG(p.vt_ld % 8 == 0 && p.vt_ld >= ((p.frames + 7) / 8) * 8,
-                "i2v_temporal_attention_f16: vt_ld must be a multiple of 8 and >= frames rounded up to 8");
-  I2V_CHECK_ARG(al(p.q, 16) && al(p.k, 16) && al(p.vt, 16) && al(p.o, 8), "i2v_temporal_attention_f16: pointer alignment");
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const int d = p.head_dim;
-  if (d <= 16) return launch_t<32, 16>(p, s);
-  if (d <= 32) return launch_t<32, 32>(p, s);
-  if (d <= 48) return launch_t<64, 48>(p, s);
-  if (d <= 64) return launch_t<64, 64>(p, s);
-  if (d <= 80) return launch_t<96, 80>(p, s);
-  if (d <= 96) return launch_t<96, 96>(p, s);
-  if (d <= 128) return launch_t<128, 128>(p, s);
-  return launch_t<160, 160>(p, s);
+  if (const int rc = check_args(p, "i2v_temporal_attention_f16")) return rc;
+  const TattnDispatch d = dispatch(p);
+  const TattnEntry* e = find_entry(d.route);
+  if (e == nullptr)
+    I2V_FAIL(I2V_ERR_UNSUPPORTED, "i2v_temporal_attention_f16: no kernel for form %d, class <%d, %d>, PF %d, NQT %d", d.route.form,
+             d.route.dqk, d.route.dpv, d.route.pf, d.route.nqt);
+  const float scale_log2 = p.scale * 1.4426950408889634f;
+  e->fn(p, scale_log2, (unsigned)d.route.blocks, d.lds, (int)((int64_t)p.n_pixels * p.heads), reinterpret_cast<hipStream_t>(stream));
+  last_route = d.route;
+  have_last_route = true;
+  return i2v_check_launch("i2v_temporal_attention_f16");
 }

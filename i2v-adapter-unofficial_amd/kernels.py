@@ -444,9 +444,11 @@ def attention(q, k, vt, *, batch_q, lq, lk, heads, head_dim, kv_group=1, scale=N
     return (out, lse) if return_lse else out
 
 
-def temporal_attention(q, k, vt, *, n_pixels, frames, heads, head_dim, scale=None):
+def temporal_attention(q, k, vt, *, n_pixels, frames, heads, head_dim, scale=None, out=None):
     """Motion-module attention over the frame axis; tokens in (b, pixel, frame) order.
-    q, k [n_pixels * frames, >= C]; vt [n_pixels, C, >= pad8(frames)]."""
+    q, k [n_pixels * frames, >= C]; vt [n_pixels, C, >= pad8(frames)].
+    out: optional 2-D fp16 view [n_pixels * frames, >= C] to write into (columns [0, C); row stride a multiple of 4, base 8-byte
+    aligned); by default a new [n_pixels * frames, C] tensor."""
     lib = _lib.load()
     q, ldq = _mat(q, "q")
     k, ldk = _mat(k, "k")
@@ -457,16 +459,30 @@ def temporal_attention(q, k, vt, *, n_pixels, frames, heads, head_dim, scale=Non
     if vt.dim() != 3 or not vt.is_contiguous() or vt.shape[0] != n_pixels or vt.shape[1] != Cc or \
             vt.shape[2] < pad8(frames):
         raise ValueError(f"vt is {tuple(vt.shape)}, expected contiguous [{n_pixels}, {Cc}, >={pad8(frames)}]")
-    out = torch.empty((n_pixels * frames, Cc), dtype=f16, device=q.device)
+    if out is None:
+        out, ldo = torch.empty((n_pixels * frames, Cc), dtype=f16, device=q.device), Cc
+    else:
+        out, ldo = _mat(out, "out")
+        if out.shape[0] != n_pixels * frames or out.shape[1] < Cc or ldo % 4 != 0 or out.device != q.device:
+            raise ValueError(f"out is {tuple(out.shape)} with row stride {ldo}, expected [{n_pixels * frames}, >={Cc}] on {q.device} "
+                             "with a row stride that is a multiple of 4")
     p = TAttnParams()
     p.q, p.q_row_stride = _p(q), ldq
     p.k, p.k_row_stride = _p(k), ldk
     p.vt, p.vt_ld = _p(vt), vt.shape[2]
-    p.o, p.o_row_stride = _p(out), Cc
+    p.o, p.o_row_stride = _p(out), ldo
     p.n_pixels, p.frames, p.heads, p.head_dim = n_pixels, frames, heads, head_dim
     p.scale = float(head_dim) ** -0.5 if scale is None else scale
     _lib.check(lib.i2v_temporal_attention_f16(C.byref(p), _stream()), "i2v_temporal_attention_f16")
     return out
+
+
+def last_tattn_route() -> dict:
+    """the kernel instantiation that this thread's most recent `temporal_attention` launch took, as the fields of i2v_tattn_route
+    (form, dqk, dpv, pf, nqt, blocks)"""
+    r = _lib.TAttnRoute()
+    _lib.check(_lib.load().i2v_temporal_attention_last_route(C.byref(r)), "i2v_temporal_attention_last_route")
+    return r.as_dict()
 
 
 def motion_attn_supported(rows, channels, heads, head_dim, frames):

@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define I2V_ABI_VERSION 19
+#define I2V_ABI_VERSION 20
 
 #define I2V_OK 0
 #define I2V_ERR_INVALID_ARG (-1)
@@ -267,6 +267,32 @@ typedef struct i2v_tattn_params {
 } i2v_tattn_params;
 
 int i2v_temporal_attention_f16(const i2v_tattn_params* p, i2v_stream_t stream);
+
+/* (ABI 20) Which kernel a temporal-attention problem takes.  i2v_temporal_attention_f16 dispatches to 48 kernel instantiations:
+   8 head-dim classes <dqk, dpv> (<32,16> <32,32> <64,48> <64,64> <96,80> <96,96> <128,128> <160,160>: head_dim takes the first
+   whose dpv holds it), each in an LDS-staged form (frames <= 16, one pixel's operands within 64 KiB of LDS and within 256 * 4
+   16-byte chunks per operand, o 16-byte aligned with a row stride that is a multiple of 8; I2V_TATTN_LDS=0 turns the form off)
+   with pf = 1..4 chunks per thread, and in a register form with nqt = 1 (frames <= 16) or 2 query tiles.  The route is decided
+   by the same function the launch follows (there is no second copy of the rules). */
+enum { I2V_TATTN_LDS_FORM = 0, I2V_TATTN_REG_FORM = 1 };
+
+/* (a struct tag only, as i2v_gemm_route) */
+struct i2v_tattn_route {
+  int32_t form;     /* I2V_TATTN_*_FORM                                                                      */
+  int32_t dqk, dpv; /* the head-dim class: head_dim padded to the QK^T contraction (32) and to the PV tile (16) */
+  int32_t pf;       /* LDS form: 16-byte chunks per thread and operand, 1..4; register form 0                */
+  int32_t nqt;      /* register form: 16-query tiles per wave, 1 | 2; LDS form 0                             */
+  int32_t blocks;   /* workgroups of the launch                                                              */
+};
+
+/* The route i2v_temporal_attention_f16 would take for p: pure host arithmetic, no device call.  p is validated as the launch
+   validates it (< 0: the launch would refuse it, or a null argument); pointers are only tested for null and alignment. */
+int i2v_temporal_attention_route(const i2v_tattn_params* p, struct i2v_tattn_route* route);
+/* The route of the calling thread's most recent i2v_temporal_attention_f16 that reached a launch (< 0: none yet). */
+int i2v_temporal_attention_last_route(struct i2v_tattn_route* route);
+/* 1 if the kernel instantiation that `route` names (form, dqk, dpv, pf, nqt; blocks is a run-time argument and is not read) is
+   in the launch table, else 0.  Read from the launch table itself. */
+int i2v_tattn_kernel_exists(const struct i2v_tattn_route* route);
 
 /* ------------------------------------------------------------------------------------------------
  * The whole attention sub-block of a motion module's temporal transformer block in one launch:

@@ -44,7 +44,7 @@ def test_ctypes_structs_match_header(lib):
     names = {"i2v_gemm_params": lib.GemmParams, "i2v_attn_params": lib.AttnParams, "i2v_tattn_params": lib.TAttnParams,
              "i2v_gn_params": lib.GnParams, "i2v_ln_params": lib.LnParams, "i2v_motion_attn_params": lib.MotionAttnParams,
              "i2v_cross_attn_fused_params": lib.CrossAttnFusedParams, "i2v_ff_fused_params": lib.FfFusedParams,
-             "struct i2v_gemm_route": lib.GemmRoute}
+             "struct i2v_gemm_route": lib.GemmRoute, "struct i2v_tattn_route": lib.TAttnRoute}
     prog = ['#include <stdio.h>', '#include <stddef.h>', f'#include "{HEADER}"', "int main(void){"]
     for cname, cls in names.items():
         prog.append(f'printf("{cname} %zu\\n", sizeof({cname}));')

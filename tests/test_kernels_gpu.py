@@ -581,6 +581,29 @@ def test_attention_strided_qk_and_spike(dev):
     close(out.view(bq, lq, c), ref, name="attention strided+spike")
 
 
+def _tattn_route(form, dqk, dpv, variant, blocks):
+    """i2v_tattn_route as kernels.last_tattn_route() reports it: form 0 = LDS-staged (variant = pf), 1 = register (variant = nqt)"""
+    return dict(form=form, dqk=dqk, dpv=dpv, pf=variant if form == 0 else 0, nqt=variant if form == 1 else 0, blocks=blocks)
+
+
+def _tattn_check(k, q, kk, v, heads, out, route, rel, name):
+    """the launch took the kernel the test is about, and every element obeys the derived bound of tests/tattn_bounds.py against fp64,
+    which is nowhere wider than the  rel * |ref| + rel * max|ref|  this test allowed before"""
+    from tests import tattn_bounds as B
+    assert k.last_tattn_route() == route, f"{name}: another kernel ran than the test is about"
+    ref, W, tol0 = B.evaluate(q.half(), kk.half(), v.half(), heads)
+    assert bool((tol0 + B.SOFTMAX_ERR * W <= rel * ref.abs() + rel * ref.abs().max()).all()), f"{name}: the derived bound is wider than the old one"
+    msg = B.check_against(out.view(ref.shape), ref, W, tol0)
+    assert msg is None, f"{name}: {msg}"
+
+
+# (n_pixels, frames, heads, head_dim) -> the kernel instantiation the shape is there for: (form, dqk, dpv, pf | nqt, workgroups)
+TATTN_ROUTES = {(10, 16, 8, 40): (0, 64, 48, 3, 10), (7, 8, 4, 8): (0, 32, 16, 1, 7), (5, 4, 2, 16): (0, 32, 16, 1, 5),
+                (33, 32, 8, 80): (1, 96, 80, 2, 66), (3, 24, 2, 160): (1, 160, 160, 2, 2), (64, 16, 8, 160): (1, 160, 160, 1, 128),
+                (9, 5, 3, 24): (0, 32, 32, 1, 9), (64, 16, 8, 40): (0, 64, 48, 3, 64), (8192, 16, 8, 40): (0, 64, 48, 3, 2048),
+                (16, 24, 2, 160): (1, 160, 160, 2, 8)}
+
+
 @pytest.mark.parametrize("npix,frames,heads,d", [(10, 16, 8, 40), (7, 8, 4, 8), (5, 4, 2, 16), (33, 32, 8, 80),
                                                  (3, 24, 2, 160), (64, 16, 8, 160), (9, 5, 3, 24)])
 def test_temporal_attention(dev, npix, frames, heads, d):
@@ -590,13 +613,12 @@ def test_temporal_attention(dev, npix, frames, heads, d):
     q = h(torch.randn(npix, frames, c, generator=g))
     kk = h(torch.randn(npix, frames, c, generator=g))
     v = h(torch.randn(npix, frames, c, generator=g))
-    ref = _attn_ref(q, kk, v, heads, 1)
     ld = k.pad8(frames)
     vt = torch.full((npix, c, ld), float("nan"))
     vt[:, :, :frames] = v.permute(0, 2, 1)
     out = k.temporal_attention(q.reshape(-1, c).half().to(dev), kk.reshape(-1, c).half().to(dev), vt.half().to(dev),
                                n_pixels=npix, frames=frames, heads=heads, head_dim=d)
-    close(out.view(npix, frames, c), ref, name="temporal attention")
+    _tattn_check(k, q, kk, v, heads, out, _tattn_route(*TATTN_ROUTES[npix, frames, heads, d]), 3e-3, "temporal attention")
 
 
 @pytest.mark.parametrize("npix,frames,heads,d,amp", [(64, 16, 8, 40, 3.0), (33, 32, 8, 80, 4.0), (8192, 16, 8, 40, 4.0),
@@ -609,12 +631,11 @@ def test_temporal_attention_large_logits(dev, npix, frames, heads, d, amp):
     q = h(torch.randn(npix, frames, c, generator=g) * amp)
     kk = h(torch.randn(npix, frames, c, generator=g) * amp)
     v = h(torch.randn(npix, frames, c, generator=g))
-    ref = _attn_ref(q, kk, v, heads, 1)
     vt = torch.zeros((npix, c, k.pad8(frames)))
     vt[:, :, :frames] = v.permute(0, 2, 1)
     out = k.temporal_attention(q.reshape(-1, c).half().to(dev), kk.reshape(-1, c).half().to(dev), vt.half().to(dev),
                                n_pixels=npix, frames=frames, heads=heads, head_dim=d)
-    close(out.view(npix, frames, c), ref, rel=6e-4 * amp * amp, name="temporal attention, large logits")
+    _tattn_check(k, q, kk, v, heads, out, _tattn_route(*TATTN_ROUTES[npix, frames, heads, d]), 6e-4 * amp * amp, "temporal attention, large logits")
 
 
 @pytest.mark.parametrize("npix,amp,strided,frames", [(8, 1.0, False, 16), (1000, 1.0, True, 16), (256, 3.0, False, 16),

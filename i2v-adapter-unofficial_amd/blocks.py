@@ -986,6 +986,107 @@ class ImageProjection(HipModule):
         return y.view(x.shape[0], self.num_image_text_embeds, self.cross_attention_dim)
 
 
+class _ResamplerAttention(nn.Module):
+    """the parameters of a Resampler layer's attention under diffusers' names (`to_q`, `to_k`, `to_v`, `to_out.0`, no biases).  Not an
+    `Attention`: it has no processor, and the UNet's `attn_processor_names` must not list it."""
+
+    def __init__(self, dim, inner):
+        super().__init__()
+        self.to_q, self.to_k, self.to_v = (nn.Linear(dim, inner, bias=False) for _ in range(3))
+        self.to_out = nn.ModuleList([nn.Linear(inner, dim, bias=False), nn.Dropout(0.0)])
+
+
+class _ResamplerFeedForward(nn.Module):
+    """diffusers' FeedForward(activation_fn="gelu", bias=False) by its keys: `net.0.proj`, `net.2`"""
+
+    def __init__(self, dim, inner):
+        super().__init__()
+        self.net = nn.ModuleList([GELU(dim, inner, bias=False), nn.Dropout(0.0), nn.Linear(inner, dim, bias=False)])
+
+
+class Resampler(HipModule):
+    """IP-Adapter Plus's image projection (diffusers' Resampler, the reference's pipe:21 / unet:1234-1239): `num_queries` learned latents
+    attend, `depth` times, to the image encoder's penultimate hidden states and to themselves.
+
+        latents = self.latents repeated over B;  x = proj_in(x)
+        per layer:  kv_in   = cat([ln0(x), ln1(latents)], dim=-2)
+                    latents = to_out(softmax(to_q(ln1(latents)) to_k(kv_in)^T / sqrt(dim_head)) to_v(kv_in)) + latents
+                    latents = ff(latents) + latents
+        return norm_out(proj_out(latents))                                     # [B, num_queries, output_dims]
+
+    Library launches only, 9 per layer: ln0 -> [Wk;Wv] GEMM | ln1 -> [Wq;Wk;Wv] GEMM | i2v_perceiver_attention_f16 (the concatenation is
+    never made: the kernel reads both packed GEMM results in place) | to_out + residual | LayerNorm -> FF up + erf-GELU -> FF down +
+    residual.  The attention kernel's envelope is the module's: dim_head 64, num_queries <= 64, T + num_queries <= 288."""
+
+    DIM_HEAD, MAX_QUERIES, MAX_KEYS = 64, 64, 288           # i2v_perceiver_attention_f16
+
+    def __init__(self, embed_dims=768, output_dims=1024, hidden_dims=1280, depth=4, dim_head=64, heads=16, num_queries=8, ffn_ratio=4):
+        super().__init__()
+        if dim_head != self.DIM_HEAD:
+            raise NotImplementedError(f"dim_head {dim_head}: the attention kernel (i2v_perceiver_attention_f16) implements head_dim "
+                                      f"{self.DIM_HEAD} only")
+        if not 1 <= num_queries <= self.MAX_QUERIES:
+            raise NotImplementedError(f"num_queries {num_queries}: the attention kernel (i2v_perceiver_attention_f16) takes 1 to "
+                                      f"{self.MAX_QUERIES} queries")
+        inner_ff = int(hidden_dims * ffn_ratio)
+        if embed_dims % 8 or output_dims % 8 or hidden_dims % 8 or inner_ff % 8 or inner_ff != hidden_dims * ffn_ratio:
+            raise NotImplementedError(f"embed_dims {embed_dims}, output_dims {output_dims}, hidden_dims {hidden_dims} and hidden_dims * "
+                                      f"ffn_ratio {hidden_dims * ffn_ratio} must be multiples of 8 (i2v_gemm_f16)")
+        self.embed_dims, self.output_dims, self.hidden_dims = embed_dims, output_dims, hidden_dims
+        self.depth, self.dim_head, self.heads, self.num_queries, self.ffn_ratio = depth, dim_head, heads, num_queries, ffn_ratio
+        self.latents = nn.Parameter(torch.randn(1, num_queries, hidden_dims) / hidden_dims ** 0.5)
+        self.proj_in = nn.Linear(embed_dims, hidden_dims)
+        self.proj_out = nn.Linear(hidden_dims, output_dims)
+        self.norm_out = nn.LayerNorm(output_dims)
+        self.layers = nn.ModuleList([
+            nn.ModuleList([nn.LayerNorm(hidden_dims), nn.LayerNorm(hidden_dims), _ResamplerAttention(hidden_dims, dim_head * heads),
+                           nn.Sequential(nn.LayerNorm(hidden_dims), _ResamplerFeedForward(hidden_dims, inner_ff))])
+            for _ in range(depth)])
+
+    def check_tokens(self, tokens: int):
+        """the limit on the image tokens T, for callers that know T before the first forward (the loader)"""
+        if tokens < 1 or tokens + self.num_queries > self.MAX_KEYS:
+            raise NotImplementedError(f"{tokens} image tokens + {self.num_queries} queries: the attention kernel "
+                                      f"(i2v_perceiver_attention_f16) takes at most {self.MAX_KEYS} keys")
+
+    def _pack(self):
+        ln = lambda m: (w16(m.weight), w16(m.bias), m.eps)
+        layers = []
+        for ln0, ln1, attn, ff in self.layers:
+            layers.append(dict(
+                ln0=ln(ln0), ln1=ln(ln1), wkv=w16(torch.cat([attn.to_k.weight, attn.to_v.weight], dim=0)),
+                wqkv=w16(torch.cat([attn.to_q.weight, attn.to_k.weight, attn.to_v.weight], dim=0)), wo=w16(attn.to_out[0].weight),
+                ln2=ln(ff[0]), w1=w16(ff[1].net[0].proj.weight), w2=w16(ff[1].net[2].weight)))
+        # the latents repeated over the batch are an operand made once per batch size (`rep`), not a copy in every forward
+        return dict(lat=w16(self.latents[0]), rep={}, w_in=w16(self.proj_in.weight), b_in=w16(self.proj_in.bias),
+                    w_out=w16(self.proj_out.weight), b_out=w16(self.proj_out.bias), norm=ln(self.norm_out), layers=layers)
+
+    @torch.no_grad()
+    def forward(self, x):
+        if not isinstance(x, torch.Tensor) or x.dim() != 3 or x.shape[2] != self.embed_dims:
+            raise ValueError(f"Resampler takes image hidden states [batch, tokens, {self.embed_dims}], got "
+                             f"{tuple(x.shape) if isinstance(x, torch.Tensor) else type(x).__name__}")
+        p = self.packed()
+        x = _as_f16_matrix(x)
+        b, t, _ = x.shape
+        self.check_tokens(t)
+        nq, heads, inner = self.num_queries, self.heads, self.heads * self.dim_head
+        if b not in p["rep"]:
+            p["rep"][b] = p["lat"].repeat(b, 1)
+        lat = p["rep"][b]                                                        # [b * nq, hidden]; never written (every GEMM makes its `out`)
+        x = K.gemm(x.view(b * t, -1), p["w_in"], p["b_in"])
+        for lp in p["layers"]:
+            kv = K.gemm(K.layernorm(x, *lp["ln0"]), lp["wkv"])                   # [b * t, k | v]
+            qkv = K.gemm(K.layernorm(lat, *lp["ln1"]), lp["wqkv"])               # [b * nq, q | k | v]
+            att = K.perceiver_attention(qkv, kv, qkv, batch=b, n_q=nq, len_a=t, len_b=nq, heads=heads, head_dim=self.dim_head,
+                                        q_off=0, ka_off=0, va_off=inner, kb_off=inner, vb_off=2 * inner)
+            lat = K.gemm(att, lp["wo"], residual=lat)
+            up = K.gemm(K.layernorm(lat, *lp["ln2"]), lp["w1"], epilogue=I2V_EPI_GELU)
+            lat = K.gemm(up, lp["w2"], residual=lat)
+        y = K.layernorm(K.gemm(lat, p["w_out"], p["b_out"]), *p["norm"])
+        return y.view(b, nq, self.output_dims)
+
+
 # ---------------------------------------------------------------------------------------------------------- A11
 def _motion(out_channels, heads, groups, cross_dim, max_seq):
     return TransformerTemporalModel(num_attention_heads=heads, in_channels=out_channels, norm_num_groups=groups,

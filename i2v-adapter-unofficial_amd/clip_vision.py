@@ -15,8 +15,8 @@ library launches only, no torch ops on the data:
     -> post_layernorm on the class rows, read in place -> visual_projection GEMM
 
 Not per-step work: an image is encoded once per sample.  Resize, crop and normalisation stay in transformers'
-`CLIPImageProcessor` on the host, as tokenisation does.  Out of scope: `CLIPVisionModel` without projection, 336-px towers (577 tokens),
-IP-Adapter Plus / Resampler, training through the tower.
+`CLIPImageProcessor` on the host, as tokenisation does.  IP-Adapter Plus reads `hidden_states[-2]` of this tower (blocks.Resampler, DESIGN
+4.13).  Out of scope: `CLIPVisionModel` without projection, 336-px towers (577 tokens), training through the tower.
 """
 from typing import Optional
 

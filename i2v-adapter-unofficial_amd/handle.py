@@ -543,6 +543,10 @@ def export_denoiser(pipe, out_dir, *, num_frames, latent_height, latent_width, b
     if pipe._scheduler_kind() != "ddim":
         raise NotImplementedError("export_denoiser writes the DDIM loop (manifest `ddim_coefficients`, four io slots per step); "
                                   "a DPM-Solver++ or LCM step plan comes from record_step_plan")
+    from .blocks import Resampler
+    if clip_dim and isinstance(unet.encoder_hid_proj, Resampler):
+        raise NotImplementedError("export_denoiser with IP-Adapter Plus loaded is not implemented: the C host's inputs file holds 2-D "
+                                  "image embeds, a Resampler takes [batch, tokens, embed_dims] hidden states")
     sch.set_timesteps(num_inference_steps)
     ts = sch.timesteps
     B, F, hh, ww = batch, num_frames, latent_height, latent_width
@@ -569,7 +573,7 @@ def export_denoiser(pipe, out_dir, *, num_frames, latent_height, latent_width, b
         "abi_version": _lib.ABI_VERSION,
         "unet_config": {k: (list(v) if isinstance(v, (tuple, list)) else v) for k, v in dict(cfg).items()
                         if isinstance(v, (int, float, str, bool, tuple, list)) or v is None},
-        "ip_num_tokens": 4 if ie is not None else 0,
+        "ip_num_tokens": max((a.ip_num_tokens for a in unet._cross_attention_layers()), default=0) if ie is not None else 0,
         "problem": dict(zip(("batch", "frames", "height", "width", "ctx_len", "has_ip"), _step_problem(st))),
         "samples": B, "cfg_copies": 2, "guidance_scale": float(guidance_scale), "num_inference_steps": int(num_inference_steps),
         "prepare": {"plan": "prepare.plan", "launches": int.from_bytes(prep_blob[12:16], "little"),

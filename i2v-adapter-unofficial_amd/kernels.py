@@ -1094,6 +1094,45 @@ def clip_vision_attention(qkv, **kw):
     return _clip_attention("i2v_clip_vision_attention_f16", qkv, **kw)
 
 
+def perceiver_attention(q, kv_a, kv_b=None, *, batch, n_q, len_a, len_b=0, heads, head_dim=64, q_off=0, ka_off=0, va_off=None, kb_off=None,
+                        vb_off=None, scale=None, out=None):
+    """attention of `n_q` queries per batch entry over the concatenation of two key / value row sources (i2v_perceiver_attention_f16,
+    the Resampler's attention): q fp16 [batch * n_q, >= q_off + hidden]; kv_a fp16 [batch * len_a, ...] with head h of k / v in columns
+    ka_off / va_off + h * head_dim (default 0, hidden); kv_b the same for len_b rows per entry (default offsets hidden, 2 * hidden: a
+    packed q | k | v buffer, which may be `q` itself) -> fp16 [batch * n_q, hidden].  head_dim 64, n_q <= 64, len_a >= 1 and
+    len_a + len_b <= 288 only (anything else raises)."""
+    lib = _lib.load()
+    hidden = heads * head_dim
+    q, ldq = _mat(q, "q")
+    kv_a, lda = _mat(kv_a, "kv_a")
+    va_off = hidden if va_off is None else va_off
+    kb_off = hidden if kb_off is None else kb_off
+    vb_off = 2 * hidden if vb_off is None else vb_off
+    if q.shape[0] != batch * n_q or q_off + hidden > q.shape[1]:
+        raise ValueError(f"q is {tuple(q.shape)}: expected [{batch * n_q}, >= {q_off} + {hidden}]")
+    if kv_a.shape[0] != batch * len_a or max(ka_off, va_off) + hidden > kv_a.shape[1]:
+        raise ValueError(f"kv_a is {tuple(kv_a.shape)}: expected [{batch * len_a}, >= offset + {hidden}]")
+    if len_b > 0:
+        if kv_b is None:
+            raise ValueError(f"len_b = {len_b} needs kv_b")
+        kv_b, ldb = _mat(kv_b, "kv_b")
+        if kv_b.shape[0] != batch * len_b or max(kb_off, vb_off) + hidden > kv_b.shape[1]:
+            raise ValueError(f"kv_b is {tuple(kv_b.shape)}: expected [{batch * len_b}, >= offset + {hidden}]")
+        pb = _p(kv_b)
+    else:
+        pb, ldb, kb_off, vb_off = None, 0, 0, 0
+    if out is None:
+        out = torch.empty((batch * n_q, hidden), dtype=f16, device=q.device)
+    out, ldo = _mat(out, "out")
+    if out.shape != (batch * n_q, hidden):
+        raise ValueError(f"out must be {(batch * n_q, hidden)}, got {tuple(out.shape)}")
+    scale = float(head_dim) ** -0.5 if scale is None else float(scale)
+    _lib.check(lib.i2v_perceiver_attention_f16(_p(q), ldq, q_off, _p(kv_a), lda, ka_off, va_off, len_a, pb, ldb, kb_off, vb_off, len_b,
+                                               _p(out), ldo, batch, n_q, heads, head_dim, scale, _stream()),
+               "i2v_perceiver_attention_f16")
+    return out
+
+
 def select_row(table, row_index, out=None):
     """[1, cols] = table[clamp(*row_index)] for a device int32 scalar `row_index` (a replayed step's row of a per-timestep
     table)."""

@@ -27,7 +27,7 @@ import torch
 
 from . import kernels as K
 from ._lib import HipLibraryError
-from .blocks import DDIMScheduler, DPMSolverMultistepScheduler, LCMScheduler
+from .blocks import DDIMScheduler, DPMSolverMultistepScheduler, ImageProjection, LCMScheduler, Resampler
 from .image_processor import VaeImageProcessor, tensor2vid
 from .unet_motion_cross_frame_attn import UNetMotionCrossFrameAttnModel
 
@@ -223,15 +223,17 @@ class I2VAdapterPipeline:
 
     def load_ip_adapter(self, pretrained_model_name_or_path_or_dict, subfolder: Optional[str] = None,
                         weight_name: Optional[str] = None, **_unused):
-        """diffusers IPAdapterMixin.load_ip_adapter as called at pipe:783: reads ip-adapter_sd15.{bin,safetensors} and
-        installs the decoupled cross-attention branch + ImageProjection (unet:1230-1287).  As diffusers does, a pipeline without an
+        """diffusers IPAdapterMixin.load_ip_adapter as called at pipe:783: reads ip-adapter_sd15.{bin,safetensors} or an IP-Adapter Plus
+        file (ip-adapter-plus_sd15, ip-adapter-plus-face_sd15) and installs the decoupled cross-attention branch + ImageProjection, or
+        + Resampler for Plus (unet:1230-1287; Full Face raises).  As diffusers does, a pipeline without an
         `image_encoder` takes it from `<path>/<subfolder>/image_encoder` when the argument is a path and that folder exists (the HIP
         `CLIPVisionModelWithProjection`, moved to the UNet's device and dtype; no folder: `image_encoder` stays None and only
         `image_embeds` can be passed), and a pipeline without a `feature_extractor` gets transformers' `CLIPImageProcessor()` when
         transformers is importable (any object with that call interface works)."""
         from .checkpoint import load_ip_adapter_file
         self.unet._load_ip_adapter_weights(
-            load_ip_adapter_file(pretrained_model_name_or_path_or_dict, subfolder=subfolder, weight_name=weight_name))
+            load_ip_adapter_file(pretrained_model_name_or_path_or_dict, subfolder=subfolder, weight_name=weight_name),
+            num_image_tokens=self._image_encoder_tokens())
         if self.image_encoder is None and not isinstance(pretrained_model_name_or_path_or_dict, dict):
             folder = os.path.join(pretrained_model_name_or_path_or_dict, subfolder or "", "image_encoder")
             if os.path.isdir(folder):
@@ -239,12 +241,28 @@ class I2VAdapterPipeline:
                 logger.info(f"loading image_encoder from {folder}")
                 enc = CLIPVisionModelWithProjection.from_pretrained(folder)
                 self.image_encoder = enc.to(device=self.unet.device, dtype=self.unet.dtype)
+                if isinstance(self.unet.encoder_hid_proj, Resampler):
+                    self.unet.encoder_hid_proj.check_tokens(self._image_encoder_tokens())
         if self.feature_extractor is None:
             try:
                 from transformers import CLIPImageProcessor
                 self.feature_extractor = CLIPImageProcessor()
             except ImportError:
                 pass
+
+    def _image_encoder_tokens(self):
+        """tokens per image of `image_encoder`'s hidden states (what a Resampler attends to), None without an encoder"""
+        cfg = getattr(self.image_encoder, "config", None)
+        if cfg is None or getattr(cfg, "image_size", None) is None or getattr(cfg, "patch_size", None) is None:
+            return None
+        return (cfg.image_size // cfg.patch_size) ** 2 + 1
+
+    def set_ip_adapter_scale(self, scale: float):
+        """diffusers IPAdapterMixin.set_ip_adapter_scale: the weight of the image-prompt branch in every cross-attention that carries
+        one.  The scale is a launch argument of the captured step, so the next call re-captures once (`_graph_key` holds it)."""
+        for attn in self.unet._cross_attention_layers():
+            if attn.ip_num_tokens:
+                attn.ip_scale = float(scale)
 
     # ------------------------------------------------------------------------------------------ LoRA (lora.py, DESIGN 4.10)
     def load_lora_weights(self, pretrained_model_name_or_path_or_dict, adapter_name: Optional[str] = None,
@@ -596,9 +614,20 @@ class I2VAdapterPipeline:
                 lora_scale=cross_attention_kwargs.get("scale", None) if cross_attention_kwargs is not None else None,
                 clip_skip=clip_skip)
         if ip_adapter_image is not None:                                                        # pipe:616-622
-            # once per sample, before the step is captured; the ImageProjection is the only `encoder_hid_proj` there is
-            # (`_load_ip_adapter_weights` refuses IP-Adapter Plus), so it is the plain branch: no negative half is ever encoded
-            image_embeds, negative_image_embeds = self.encode_image(ip_adapter_image, self.unet.device, num_videos_per_prompt, False)
+            # once per sample, before the step is captured.  ImageProjection (plain IP-Adapter) takes the pooled embeds and a zero
+            # negative; a Resampler (IP-Adapter Plus) the penultimate hidden states of the image and of a zero image
+            output_hidden_state = not isinstance(self.unet.encoder_hid_proj, ImageProjection)
+            image_embeds, negative_image_embeds = self.encode_image(ip_adapter_image, self.unet.device, num_videos_per_prompt,
+                                                                    output_hidden_state)
+        elif image_embeds is not None and self.unet.encoder_hid_proj is not None:
+            plus = isinstance(self.unet.encoder_hid_proj, Resampler)
+            for name, t in (("image_embeds", image_embeds), ("negative_image_embeds", negative_image_embeds)):
+                if t is not None and t.dim() != (3 if plus else 2):
+                    raise ValueError(
+                        f"`{name}` has shape {tuple(t.shape)}: " +
+                        (f"IP-Adapter Plus is loaded (Resampler), which takes the image encoder's penultimate hidden states "
+                         f"[batch, tokens, {self.unet.encoder_hid_proj.embed_dims}]" if plus else
+                         "the plain IP-Adapter is loaded (ImageProjection), which takes the pooled image embeds [batch, embed_dim]"))
         if condition_image is not None and condition_image_latents is None:                     # pipe:624-627
             if height is None or width is None:
                 height = height or self.unet.config.sample_size * self.vae_scale_factor         # pipe:568-569
@@ -813,6 +842,11 @@ def build_parser():
     parser.add_argument("--ip_adapter", action="store_true",
                         help="load IP-Adapter and its CLIP image encoder from <ip_adapter_path>/models (pipe:783) and pass every row's "
                              "condition image as `ip_adapter_image` (pipe:796) unless --embeds holds image_embeds; off by default")
+    parser.add_argument("--ip_adapter_weight_name", type=str, default="ip-adapter_sd15.bin",
+                        help="the IP-Adapter file under <ip_adapter_path>/models: the plain adapter (4 image tokens) or an IP-Adapter "
+                             "Plus file such as ip-adapter-plus_sd15.bin (16 image tokens through the Resampler)")
+    parser.add_argument("--ip_adapter_scale", type=float, default=None,
+                        help="weight of the image-prompt branch (pipe.set_ip_adapter_scale); default: the adapter's 1.0")
     parser.add_argument("--checkpoint_root", type=str, default="./checkpoint")
     parser.add_argument("--samples_root", type=str, default="./samples")
     parser.add_argument("--num_frames", type=int, default=16)
@@ -917,7 +951,9 @@ def main(argv=None):
 
     pipe = I2VAdapterPipeline(vae, text_encoder, tokenizer, unet2d.to(device).half(), motion_adapter, i2v_adapter, scheduler)
     if "image_embeds" in emb or args.ip_adapter:                                                 # pipe:783
-        pipe.load_ip_adapter(args.ip_adapter_path, subfolder="models", weight_name="ip-adapter_sd15.bin")
+        pipe.load_ip_adapter(args.ip_adapter_path, subfolder="models", weight_name=args.ip_adapter_weight_name)
+        if args.ip_adapter_scale is not None:
+            pipe.set_ip_adapter_scale(args.ip_adapter_scale)
     pipe.to(device, torch.float16)
     pipe.enable_vae_slicing()                                                                    # pipe:787
     if args.freeu is not None:

@@ -127,6 +127,12 @@ def _work_misc(name):
     return f
 
 
+def _work_perceiver_attn(args, kw, out):
+    b, nq, h, d, l = kw["batch"], kw["n_q"], kw["heads"], kw.get("head_dim", 64), kw["len_a"] + kw.get("len_b", 0)
+    # Q K^T and P V over the concatenated keys; k / v of both sources read once, q read and out written once
+    return "perceiver", 2.0 * 2 * b * h * d * nq * l, 2 * _numel_bytes(out) + 4 * b * h * d * l, f"b{b} h{h} q{nq} keys{l} d{d}"
+
+
 _WRAPPED = {
     "gemm": _work_gemm, "conv3x3": _work_conv, "attention": _work_attn, "temporal_attention": _work_tattn,
     "motion_attn": _work_mattn, "cross_attn_fused": _work_cattn, "ff_fused": _work_ff, "ln_qkv": _work_lnqkv,
@@ -141,7 +147,7 @@ _WRAPPED = {
     "clip_embed": _work_misc("clip_text"), "clip_attention": _work_clip_attn, "quick_gelu": _work_misc("clip_text"),
     # the CLIP vision tower's own kernels (once per image prompt): a class of their own, for `pipe(ip_adapter_image=...)`
     "clip_patchify": _work_misc("clip_vision"), "clip_vision_embed": _work_misc("clip_vision"),
-    "clip_vision_attention": _work_clip_vision_attn,
+    "clip_vision_attention": _work_clip_vision_attn, "perceiver_attention": _work_perceiver_attn,
 }
 
 

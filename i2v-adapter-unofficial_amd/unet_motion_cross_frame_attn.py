@@ -16,7 +16,7 @@ from torch import nn
 
 from . import kernels as K
 from ._lib import HipLibraryError
-from .blocks import (Attention, DownBlockMotion, Downsample2D, HipModule, ImageProjection, MotionAdapter,
+from .blocks import (Attention, DownBlockMotion, Downsample2D, HipModule, ImageProjection, MotionAdapter, Resampler,
                      ProjectedContext, ProjectedTemb, ResnetBlock2D, TimestepEmbedding, Timesteps, UpBlockMotion, freeu_scales,
                      Upsample2D, _as_f16_matrix, _motion, from_tokens, pack_conv3x3, precise_stream, to_tokens, w16)
 from .checkpoint import PretrainedMixin
@@ -298,6 +298,68 @@ class AttnProcessorHIP:
         return isinstance(other, AttnProcessorHIP) and (self.num_tokens, self.scale) == (other.num_tokens, other.scale)
 
 
+def convert_ip_adapter_plus_image_proj(image_proj):
+    """the `image_proj` part of an IP-Adapter Plus file (the original repository's Resampler: `to_kv` fused, `norm1` / `norm2`) ->
+    (constructor arguments of `blocks.Resampler`, its state dict).  The geometry is read off the file's shapes; every key the Resampler
+    has must be there with its shape and no other may be: ValueError names the first that is not.  Nothing is built or modified."""
+    sd = dict(image_proj)
+
+    def need(key, dims):
+        if key not in sd:
+            raise ValueError(f"image_proj: missing key {key}")
+        if sd[key].dim() != dims:
+            raise ValueError(f"image_proj: {key} has shape {tuple(sd[key].shape)}, expected {dims} dimensions")
+        return sd[key]
+
+    latents = need("latents", 3)
+    w_in, w_out = need("proj_in.weight", 2), need("proj_out.weight", 2)
+    depth = 1 + max((int(k.split(".")[1]) for k in sd if k.startswith("layers.") and k.split(".")[1].isdigit()), default=-1)
+    if depth < 1:
+        raise ValueError("image_proj: missing key layers.0.0.to_q.weight")
+    wq, w1 = need("layers.0.0.to_q.weight", 2), need("layers.0.1.1.weight", 2)
+    hidden = latents.shape[2]
+    if wq.shape[0] % 64 != 0 or wq.shape[0] == 0:
+        raise ValueError(f"image_proj: layers.0.0.to_q.weight has {wq.shape[0]} rows, not a multiple of the head dimension 64")
+    if w1.shape[0] % hidden != 0:
+        raise ValueError(f"image_proj: layers.0.1.1.weight has {w1.shape[0]} rows, not a multiple of the latents' width {hidden}")
+    kwargs = dict(embed_dims=w_in.shape[1], output_dims=w_out.shape[0], hidden_dims=hidden, depth=depth, dim_head=64,
+                  heads=wq.shape[0] // 64, num_queries=latents.shape[1], ffn_ratio=w1.shape[0] // hidden)
+    inner, ff = wq.shape[0], w1.shape[0]
+    out, used = {}, set()
+
+    def take(src, dst, shape):
+        if src not in sd:
+            raise ValueError(f"image_proj: missing key {src}")
+        if tuple(sd[src].shape) != tuple(shape):
+            raise ValueError(f"image_proj: {src} has shape {tuple(sd[src].shape)}, expected {tuple(shape)}")
+        used.add(src)
+        if dst is not None:
+            out[dst] = sd[src]
+        return sd[src]
+
+    take("latents", "latents", (1, kwargs["num_queries"], hidden))
+    for name, shape in (("proj_in", (hidden, kwargs["embed_dims"])), ("proj_out", (kwargs["output_dims"], hidden))):
+        take(f"{name}.weight", f"{name}.weight", shape)
+        take(f"{name}.bias", f"{name}.bias", shape[:1])
+    for sfx in ("weight", "bias"):
+        take(f"norm_out.{sfx}", f"norm_out.{sfx}", (kwargs["output_dims"],))
+    for i in range(depth):
+        for sfx in ("weight", "bias"):
+            take(f"layers.{i}.0.norm1.{sfx}", f"layers.{i}.0.{sfx}", (hidden,))
+            take(f"layers.{i}.0.norm2.{sfx}", f"layers.{i}.1.{sfx}", (hidden,))
+            take(f"layers.{i}.1.0.{sfx}", f"layers.{i}.3.0.{sfx}", (hidden,))
+        take(f"layers.{i}.0.to_q.weight", f"layers.{i}.2.to_q.weight", (inner, hidden))
+        kv = take(f"layers.{i}.0.to_kv.weight", None, (2 * inner, hidden))
+        out[f"layers.{i}.2.to_k.weight"], out[f"layers.{i}.2.to_v.weight"] = kv.chunk(2, dim=0)
+        take(f"layers.{i}.0.to_out.weight", f"layers.{i}.2.to_out.0.weight", (hidden, inner))
+        take(f"layers.{i}.1.1.weight", f"layers.{i}.3.1.net.0.proj.weight", (ff, hidden))
+        take(f"layers.{i}.1.3.weight", f"layers.{i}.3.1.net.2.weight", (hidden, ff))
+    for k in sd:
+        if k not in used:
+            raise ValueError(f"image_proj: unexpected key {k}")
+    return kwargs, out
+
+
 class UNetMotionCrossFrameAttnModel(UNetLoraMixin, PretrainedMixin, HipModule):
     """unet:696-1451."""
 
@@ -566,29 +628,47 @@ class UNetMotionCrossFrameAttnModel(UNetLoraMixin, PretrainedMixin, HipModule):
             rec(name, module)
         return names
 
-    def _load_ip_adapter_weights(self, state_dict):
-        """unet:1230-1287 (plain IP-Adapter: 4 image tokens through ImageProjection)."""
-        if "proj.weight" not in state_dict["image_proj"]:
-            raise NotImplementedError("only the plain IP-Adapter (ip-adapter_sd15.bin layout) is on the hot path")
-        num_tokens = 4
-        self.encoder_hid_proj = None
-        modules = dict(self.named_modules())
-        key_id = 1
-        for name in self.attn_processor_names():
-            if not name.endswith("attn2.processor") or "motion_modules" in name:
-                continue                                                                   # unet:1258-1262
-            attn = modules[name[: -len(".processor")]]
-            attn.install_ip_adapter(state_dict["ip_adapter"][f"{key_id}.to_k_ip.weight"],
-                                    state_dict["ip_adapter"][f"{key_id}.to_v_ip.weight"],
-                                    num_tokens=num_tokens, scale=1.0)
-            key_id += 2                                                                    # unet:1279
+    def _load_ip_adapter_weights(self, state_dict, num_image_tokens: Optional[int] = None):
+        """unet:1230-1287, branching on the file as the reference does: `proj.weight` is the plain IP-Adapter (4 image tokens through
+        ImageProjection); `proj.3.weight` is Full Face, which raises NotImplementedError; anything else is IP-Adapter Plus
+        (`latents.shape[1]` image tokens through the Resampler).  A Plus file is converted and validated, and the
+        Resampler built, before any module is touched: a missing or unexpected key, or a `to_q` whose rows are no multiple of 64, raises
+        ValueError naming the key; a geometry outside i2v_perceiver_attention_f16's envelope (more than 64 queries; with
+        `num_image_tokens` = the image encoder's token count given, more than 288 tokens + queries) raises NotImplementedError with the
+        limit.  More than 16 image tokens do load: i2v_cross_attn_fused_f16 takes at most 16, and the transformer blocks then run the
+        text and image attention through the un-fused kernels (BasicTransformerBlock's fall-back), slower per step."""
         ip = state_dict["image_proj"]
-        clip_dim = ip["proj.weight"].shape[-1]
-        cross_dim = ip["proj.weight"].shape[0] // 4
-        proj = ImageProjection(image_embed_dim=clip_dim, cross_attention_dim=cross_dim,
-                               num_image_text_embeds=num_tokens)
-        proj.load_state_dict({"image_embeds.weight": ip["proj.weight"], "image_embeds.bias": ip["proj.bias"],
-                              "norm.weight": ip["norm.weight"], "norm.bias": ip["norm.bias"]})
+        if "proj.weight" in ip:
+            num_tokens = 4
+            clip_dim = ip["proj.weight"].shape[-1]
+            cross_dim = ip["proj.weight"].shape[0] // 4
+            proj = ImageProjection(image_embed_dim=clip_dim, cross_attention_dim=cross_dim, num_image_text_embeds=num_tokens)
+            proj.load_state_dict({"image_embeds.weight": ip["proj.weight"], "image_embeds.bias": ip["proj.bias"],
+                                  "norm.weight": ip["norm.weight"], "norm.bias": ip["norm.bias"]})
+        elif "proj.3.weight" in ip:
+            raise NotImplementedError("IP-Adapter Full Face (257 image tokens through MLPProjection) is not implemented: the plain "
+                                      "IP-Adapter and IP-Adapter Plus are")
+        else:
+            kwargs, converted = convert_ip_adapter_plus_image_proj(ip)
+            num_tokens = kwargs["num_queries"]
+            proj = Resampler(**kwargs)
+            if num_image_tokens is not None:
+                proj.check_tokens(num_image_tokens)
+            proj.load_state_dict(converted)
+        modules = dict(self.named_modules())
+        targets = [modules[name[: -len(".processor")]] for name in self.attn_processor_names()
+                   if name.endswith("attn2.processor") and "motion_modules" not in name]      # unet:1258-1262
+        if isinstance(proj, Resampler) and proj.output_dims != self.config.cross_attention_dim:
+            raise ValueError(f"proj_out.weight: {proj.output_dims} output channels, the UNet's cross_attention_dim is "
+                             f"{self.config.cross_attention_dim}")
+        for i in range(len(targets)):
+            for k in (f"{2 * i + 1}.to_k_ip.weight", f"{2 * i + 1}.to_v_ip.weight"):        # key_id 1, 3, 5, ... (unet:1279)
+                if k not in state_dict["ip_adapter"]:
+                    raise ValueError(f"ip_adapter: missing key {k}")
+        self.encoder_hid_proj = None
+        for i, attn in enumerate(targets):
+            attn.install_ip_adapter(state_dict["ip_adapter"][f"{2 * i + 1}.to_k_ip.weight"],
+                                    state_dict["ip_adapter"][f"{2 * i + 1}.to_v_ip.weight"], num_tokens=num_tokens, scale=1.0)
         self.encoder_hid_proj = proj.to(device=self.device, dtype=self.dtype)
         self.config.encoder_hid_dim_type = "ip_image_proj"
 

@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define I2V_ABI_VERSION 20
+#define I2V_ABI_VERSION 21
 
 #define I2V_OK 0
 #define I2V_ERR_INVALID_ARG (-1)
@@ -760,6 +760,27 @@ int i2v_clip_vision_embed_f16(const void* cls, const void* patch, int64_t ld_pat
                               int32_t hidden, i2v_stream_t stream);
 int i2v_clip_vision_attention_f16(const void* qkv, int64_t ld_qkv, int32_t q_off, int32_t k_off, int32_t v_off, void* out, int64_t ld_out,
                                   int32_t batch, int32_t len, int32_t heads, int32_t head_dim, float scale, i2v_stream_t stream);
+
+/* (ABI 21) The attention of IP-Adapter Plus's Resampler (diffusers' Resampler / IPAdapterPlusImageProjection, the reference's unet:1234-1239: 16
+ * learned queries attend to the 257 penultimate hidden states of the image encoder AND to themselves).  Not per-step work: an image prompt is
+ * projected once per sample.
+ *   i2v_perceiver_attention_f16   multi-head attention of a short block of queries over the CONCATENATION of two row sources:
+ *           out[b * n_q + i, h * 64 + :] = softmax_j( scale * q[b, i, h, :] . k[b, j, h, :] ) v[b, j, h, :],   j < len_a + len_b
+ *           k / v[b, j] = row b * len_a + j of source A for j < len_a, row b * len_b + (j - len_a) of source B otherwise
+ *       q fp16 [batch * n_q, ld_q], head h in columns q_off + h * 64.  A source is the packed K | V result of a GEMM: fp16 [batch * len, ld],
+ *       head h of k / v in columns k_off / v_off + h * 64 (all offsets and strides multiples of 8).  kv_b may be NULL when len_b == 0.  q, A and B
+ *       are read-only and MAY ALIAS (in the Resampler B is the latents' packed q | k | v buffer, the memory q is read from); out fp16
+ *       [batch * n_q, ld_out] may overlap none of them, and only its rows < batch * n_q, columns < heads * 64 are written.
+ *       Grid (batch * heads): a workgroup of 4 waves owns all queries of one (batch, head) and stages the head's whole K and V^T (keys padded
+ *       with zeros to a multiple of 32) in 78 KB of LDS, A's rows then B's; after that nothing depends on where the A / B boundary was, so the
+ *       same keys split differently give bit-equal results.  Key j is visible iff j < len_a + len_b, by index compare; no row beyond a source's
+ *       batch * len is read.  Numerics as i2v_clip_vision_attention_f16: MFMA 16x16x32 with fp32 accumulation, softmax in fp32 in base 2 with the
+ *       logits scaled by scale * log2(e) in fp32, P rounded to fp16 for P V, the row sum taken over the unrounded P, one rounding at the store.
+ *       I2V_ERR_UNSUPPORTED (nothing launched): head_dim != 64, n_q > 64, len_a + len_b > 288.
+ *       I2V_ERR_INVALID_ARG (nothing launched): len_a < 1, len_b < 0, null / misaligned operands, out overlapping an input, bad strides or offsets. */
+int i2v_perceiver_attention_f16(const void* q, int64_t ld_q, int32_t q_off, const void* kv_a, int64_t ld_a, int32_t ka_off, int32_t va_off,
+                                int32_t len_a, const void* kv_b, int64_t ld_b, int32_t kb_off, int32_t vb_off, int32_t len_b, void* out,
+                                int64_t ld_out, int32_t batch, int32_t n_q, int32_t heads, int32_t head_dim, float scale, i2v_stream_t stream);
 
 /* First-frame-similarity prior and the initial add_noise of the sampling loop, pipe:647-656:
  *   prior   = mask * GaussianBlur3x3(cond) + (1 - mask) * cond, mask = (mask_uniform < strength), per frame (pipe:648-654)

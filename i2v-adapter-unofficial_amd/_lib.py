@@ -10,7 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # I2V_LIB_PATH selects another build of the same ABI (same-box A/B of two kernels, tools/ab_bench.sh); the in-tree
 # library is never overwritten by tooling
 LIB_PATH = os.environ.get("I2V_LIB_PATH") or os.path.join(_HERE, "libi2v_hip.so")
-ABI_VERSION = 21
+ABI_VERSION = 22
 
 I2V_EPI_NONE, I2V_EPI_GELU, I2V_EPI_GEGLU = 0, 1, 2
 I2V_STORE_ROWMAJOR, I2V_STORE_ROWPERM, I2V_STORE_VT, I2V_STORE_VT_T = 0, 1, 2, 3
@@ -19,6 +19,7 @@ I2V_LORA_MAX_ADAPTERS, I2V_LORA_MAX_RANK = 8, 256
 I2V_ROUTE_GENERIC, I2V_ROUTE_CONV_THIN, I2V_ROUTE_BIG_TILE, I2V_ROUTE_BIG_DEEP, I2V_ROUTE_BIG_SPLITK = 0, 1, 2, 3, 4
 I2V_EXTRA_NONE, I2V_EXTRA_LNF, I2V_EXTRA_HILO, I2V_EXTRA_GNS, I2V_EXTRA_UPF = 0, 1, 2, 4, 8
 I2V_TATTN_LDS_FORM, I2V_TATTN_REG_FORM = 0, 1
+I2V_ADD_RES_MAX = 16
 
 
 class HipLibraryError(RuntimeError):
@@ -230,6 +231,16 @@ class LnParams(C.Structure):
     ]
 
 
+class AddResidualsEntry(C.Structure):
+    _fields_ = [("dst", C.c_void_p), ("dst_lo", C.c_void_p), ("skip", C.c_void_p), ("skip_lo", C.c_void_p), ("res", C.c_void_p),
+                ("numel", C.c_int64)]
+
+
+class AddResidualsParams(C.Structure):
+    _fields_ = [("t", AddResidualsEntry * I2V_ADD_RES_MAX), ("n", C.c_int32), ("scale_rows", C.c_int32), ("scale_table", C.c_void_p),
+                ("step_idx", C.c_void_p)]
+
+
 # every symbol include/i2v_hip.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 SIGNATURES = {
@@ -333,6 +344,7 @@ SIGNATURES = {
     "i2v_perceiver_attention_f16": (C.c_int, [_P, C.c_int64, C.c_int32, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int64,
                                               C.c_int32, C.c_int32, C.c_int32, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                               C.c_float, _P]),
+    "i2v_add_residuals_f16": (C.c_int, [C.POINTER(AddResidualsParams), _P]),
     # the model handle: configuration, weight registry, plan, one captured step
     "i2v_unet_create": (C.c_int, [C.POINTER(UnetConfig), C.POINTER(_P)]),
     "i2v_unet_destroy": (C.c_int, [_P]),

@@ -333,6 +333,14 @@ def sample_buffers(unet, st):
     return out
 
 
+def _refuse_controlnet(pipe, what):
+    """the C handle's plans hold the UNet alone: a pipeline with a ControlNet has a step the plan format cannot describe yet"""
+    if getattr(pipe, "controlnet", None) is not None:
+        raise NotImplementedError(f"{what}: a pipeline with a ControlNet is not implemented for the C handle (its step launches a second "
+                                  "model whose weights and per-sample buffers the plan does not register); build the pipeline without "
+                                  "`controlnet` to export")
+
+
 def _step_problem(st):
     b, f, _c, hh, ww = st["latents"].shape
     return (st["copies"] * b, f, hh, ww, st["ctx_text"].shape[1], int(st["ctx_ip"] is not None))
@@ -348,6 +356,7 @@ def record_step_plan(pipe, st):
     (= st["x0_prev"], in / out: the previous step's data prediction; not read by the first step of a sample).
     With an LCMScheduler the step ends in i2v_lcm_cfg_step: STEP_COEF is fp32 [T, 6] and STEP_NOISE (the same slot) fp32
     [T - 1, B, F, C, H, W] (= st["noise"], read only: `LCMScheduler.step_noise`; absent for a single-step schedule)."""
+    _refuse_controlnet(pipe, "record_step_plan")
     if pipe._scheduler_kind() == "lcm":
         noise = st.get("noise")
         keep_lcm = (st["latents"].clone(), st["step_idx"].clone())
@@ -385,6 +394,7 @@ def record_prepare_plan(pipe, st, image_embeds=None):
     (i2v:527-532, unet:1263-1279) written into the state's `ctx_proj` buffers, and time_proj -> time_embedding -> silu -> the 22
     time_emb_proj of every timestep of the schedule (unet:1336-1343) written into `temb_table` -- as a launch plan.
     io: PREP_CONTEXT fp16 [2 B, L, D] (= st["ctx_text"]), PREP_TIMESTEPS fp32 [T] (= st["t_table"]), PREP_IMAGE_EMBEDS fp16 [2 B, clip]."""
+    _refuse_controlnet(pipe, "record_prepare_plan")
     unet = pipe.unet
     io = {PREP_CONTEXT: st["ctx_text"], PREP_TIMESTEPS: st["t_table"]}
     if image_embeds is not None:
@@ -535,6 +545,7 @@ def export_denoiser(pipe, out_dir, *, num_frames, latent_height, latent_width, b
                        DDIM coefficients) and the values baked into the step (guidance scale, CFG copies, table length)
     `pipe`: an `I2VAdapterPipeline` on the GPU (its UNet with or without the IP-Adapter: clip_dim = the image embeds' width, None
     without).  Returns the manifest.  A plan holds for this size, these switches and this library build."""
+    _refuse_controlnet(pipe, "export_denoiser")
     import json
     import os
     unet = pipe.unet

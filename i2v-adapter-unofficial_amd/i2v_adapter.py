@@ -86,7 +86,9 @@ class I2VAdapterTransformerBlock(HipModule):
                  norm_type: str = "layer_norm", norm_eps: float = 1e-5, final_dropout: bool = False,
                  attention_type: str = "default", positional_embeddings: Optional[str] = None,
                  num_positional_embeddings: Optional[int] = None, ff_inner_dim: Optional[int] = None,
-                 ff_bias: bool = True, attention_out_bias: bool = True, **_unused):
+                 ff_bias: bool = True, attention_out_bias: bool = True, with_adapter: bool = True, **_unused):
+        """with_adapter=False: the plain spatial block of a 2-D model (a ControlNet: no `i2v_adapter` sub-module, no such keys);
+        only the two-projection packs are built and `_fwd` always takes the enable_cross_frame_attn=False path."""
         super().__init__()
         if norm_type != "layer_norm" or only_cross_attention or double_self_attention or positional_embeddings:
             raise NotImplementedError("only the layer-norm spatial block of the hot path is implemented "
@@ -110,7 +112,7 @@ class I2VAdapterTransformerBlock(HipModule):
                               bias=ff_bias)
         self.i2v_adapter = Attention(query_dim=dim, heads=num_attention_heads, dim_head=attention_head_dim,
                                      dropout=dropout, bias=attention_bias, cross_attention_dim=dim,
-                                     out_bias=attention_out_bias)                           # i2v:409-418
+                                     out_bias=attention_out_bias) if with_adapter else None    # i2v:409-418
         self._plan = LnFoldPlan()
 
     def _pack(self):
@@ -118,13 +120,15 @@ class I2VAdapterTransformerBlock(HipModule):
         p = LazyPack(g1=w16(self.norm1.weight), b1=w16(self.norm1.bias), g3=w16(self.norm3.weight),
                      b3=w16(self.norm3.bias))
         # one GEMM: [attn1.to_q | attn1.to_k | i2v_adapter.to_q] (the first 2C rows alone when the adapter is off)
-        p["w_qkq"] = w16(torch.cat([a1.to_q.weight, a1.to_k.weight, ad.to_q.weight], dim=0))
+        qkq = [a1.to_q.weight, a1.to_k.weight] + ([ad.to_q.weight] if ad is not None else [])
+        p["w_qkq"] = w16(torch.cat(qkq, dim=0))
         p["w_v1"] = w16(a1.to_v.weight)
-        p["w_k_ad"], p["w_v_ad"] = w16(ad.to_k.weight), w16(ad.to_v.weight)
         p["w_o1"], p["b_o1"] = w16(a1.to_out[0].weight), w16(a1.to_out[0].bias)
-        # attn1.to_out and i2v_adapter.to_out as one GEMM over K = 2C with summed biases
-        p["w_o_dual"] = w16(torch.cat([a1.to_out[0].weight, ad.to_out[0].weight], dim=1))
-        p["b_o_dual"] = w16(a1.to_out[0].bias.float() + ad.to_out[0].bias.float())
+        if ad is not None:
+            p["w_k_ad"], p["w_v_ad"] = w16(ad.to_k.weight), w16(ad.to_v.weight)
+            # attn1.to_out and i2v_adapter.to_out as one GEMM over K = 2C with summed biases
+            p["w_o_dual"] = w16(torch.cat([a1.to_out[0].weight, ad.to_out[0].weight], dim=1))
+            p["b_o_dual"] = w16(a1.to_out[0].bias.float() + ad.to_out[0].bias.float())
         if self.attn2 is not None:
             p["g2"], p["b2"] = w16(self.norm2.weight), w16(self.norm2.bias)
             p["w_q2"] = w16(self.attn2.to_q.weight)
@@ -138,8 +142,7 @@ class I2VAdapterTransformerBlock(HipModule):
             p.lazy("b2_f32", lambda n2=self.norm2: n2.bias.detach().float().contiguous())
         # LayerNorm folded into the consuming projections (i2v:444-445 -> q | k | q_adapter and V^T; i2v:510 -> attn2.to_q;
         # i2v:539 -> GEGLU): operands (W o gamma, row sums, W beta + b) of the LayerNorm-folded GEMM
-        p["f_qkq"] = fold_layernorm(torch.cat([a1.to_q.weight, a1.to_k.weight, ad.to_q.weight], dim=0), None,
-                                    self.norm1.weight, self.norm1.bias)
+        p["f_qkq"] = fold_layernorm(torch.cat(qkq, dim=0), None, self.norm1.weight, self.norm1.bias)
         p["f_v1"] = fold_layernorm(a1.to_v.weight, None, self.norm1.weight, self.norm1.bias)
         p["f_ff"] = self.ff.fold_norm(self.norm3)
         p.lazy("g3_f32", lambda n3=self.norm3: n3.weight.detach().float().contiguous())
@@ -149,10 +152,11 @@ class I2VAdapterTransformerBlock(HipModule):
         if K.ln_qkv_supported(128, self.dim, 3 * self.dim, 128):
             p.lazy("g1_f32", lambda n1=self.norm1: n1.weight.detach().float().contiguous())
             p.lazy("b1_f32", lambda n1=self.norm1: n1.bias.detach().float().contiguous())
-            p.lazy("w_lnqkv3", lambda a1=a1, ad=ad: K.pack_ln_qkv(torch.cat([a1.to_q.weight, a1.to_k.weight, ad.to_q.weight], dim=0), a1.to_v.weight))
             p.lazy("w_lnqkv2", lambda a1=a1: K.pack_ln_qkv(torch.cat([a1.to_q.weight, a1.to_k.weight], dim=0), a1.to_v.weight))
-            # ... and the adapter's K0 | V0^T over the frame-0 rows (i2v:484-492) the same way
-            p.lazy("w_lnkv_ad", lambda ad=ad: K.pack_ln_qkv(ad.to_k.weight, ad.to_v.weight))
+            if ad is not None:
+                p.lazy("w_lnqkv3", lambda a1=a1, ad=ad: K.pack_ln_qkv(torch.cat([a1.to_q.weight, a1.to_k.weight, ad.to_q.weight], dim=0), a1.to_v.weight))
+                # ... and the adapter's K0 | V0^T over the frame-0 rows (i2v:484-492) the same way
+                p.lazy("w_lnkv_ad", lambda ad=ad: K.pack_ln_qkv(ad.to_k.weight, ad.to_v.weight))
         return p
 
     def _fold_ok(self, x, L, rows_qkq):
@@ -186,6 +190,8 @@ class I2VAdapterTransformerBlock(HipModule):
         cross-attention, where the halves start to differ (returns 2 * n_img images)."""
         p = self.packed()
         c = self.dim
+        if self.i2v_adapter is None:           # a plain 2-D block (ControlNet): there is no cross-frame branch to enable
+            enable_cross_frame_attn = False
         if enable_cross_frame_attn:
             if num_frames is None:
                 raise ValueError('`num_frames` must be provided when `enable_cross_frame_attn` is True.')
@@ -199,7 +205,7 @@ class I2VAdapterTransformerBlock(HipModule):
         overlap = x.shape[0] <= streams.MAX_ROWS
         # LayerNorm 1 (i2v:444-445): folded into the q|k|q_ad and V^T GEMMs (never materialised) where the library
         # implements the fold for this level, else one pass that both chains read
-        fused_qkv = FUSED_LN_QKV and "w_lnqkv3" in p and K.ln_qkv_supported(x.shape[0], c, rows_qkq, L)
+        fused_qkv = FUSED_LN_QKV and "w_lnqkv2" in p and K.ln_qkv_supported(x.shape[0], c, rows_qkq, L)
         n = None if (fold1 or fused_qkv) else K.layernorm(x, p["g1"], p["b1"], self.eps)
         k0 = v0t = None
         if fused_qkv:          # LayerNorm 1, q | k | q_adapter and V^T in one launch (64^2 level of SD-1.5): x is read once
@@ -343,7 +349,7 @@ class I2VAdapterTransformer2DModel(HipModule):
                  use_linear_projection: bool = False, only_cross_attention: bool = False,
                  double_self_attention: bool = False, upcast_attention: bool = False,
                  norm_type: str = "layer_norm", norm_elementwise_affine: bool = True, norm_eps: float = 1e-5,
-                 attention_type: str = "default", caption_channels: int = None):
+                 attention_type: str = "default", caption_channels: int = None, with_adapter: bool = True):
         super().__init__()
         if in_channels is None or num_vector_embeds is not None or patch_size is not None:
             raise NotImplementedError("only the continuous-input branch is on the hot path (SURVEY 8b)")
@@ -361,7 +367,8 @@ class I2VAdapterTransformer2DModel(HipModule):
                                        cross_attention_dim=cross_attention_dim, activation_fn=activation_fn,
                                        attention_bias=attention_bias, only_cross_attention=only_cross_attention,
                                        double_self_attention=double_self_attention, norm_type=norm_type,
-                                       norm_elementwise_affine=norm_elementwise_affine, norm_eps=norm_eps)
+                                       norm_elementwise_affine=norm_elementwise_affine, norm_eps=norm_eps,
+                                       with_adapter=with_adapter)
             for _ in range(num_layers)])
         if use_linear_projection:
             self.proj_out = nn.Linear(inner_dim, in_channels)

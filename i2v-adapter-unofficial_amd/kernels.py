@@ -1346,6 +1346,60 @@ def freeu(hidden, skip, b, s):
     return h_out, s_out
 
 
+def add_residuals(skips, residuals, scale=None, out=None):
+    """ControlNet residuals into skip tensors (i2v_add_residuals_f16; unet:1379-1389, 1402-1403): out_i = skip_i + s * residual_i for
+    a list of fp16 tensor pairs of any sizes (numel % 8 == 0), I2V_ADD_RES_MAX pairs per launch.  scale = None (s = 1) or
+    (table fp32 [rows], step_idx int32 [1] or None): s = table[clamp(*step_idx)], read on the device.  out = None: new tensors;
+    out = a list: written there (out[i] may be skips[i]: in place).  A skip of the precise residual stream (`lo_of`) is added as
+    hi + lo and the result carries a fresh low half (in place: the skip's own is rewritten).  Returns the list of results."""
+    lib = _lib.load()
+    skips, residuals = list(skips), list(residuals)
+    if len(skips) != len(residuals) or not skips:
+        raise ValueError(f"add_residuals: {len(skips)} skip tensors and {len(residuals)} residuals")
+    if out is not None and len(out) != len(skips):
+        raise ValueError(f"add_residuals: {len(out)} outputs for {len(skips)} skip tensors")
+    table = idx = None
+    if scale is not None:
+        table, idx = scale
+        _req(table, "scale table", dtype=torch.float32)
+        if table.dim() != 1 or table.numel() < 1 or not table.is_contiguous():
+            raise ValueError("add_residuals: the scale table is a contiguous fp32 vector")
+        if idx is not None:
+            _req(idx, "step_idx", dtype=torch.int32)
+    outs, los = [], []
+    for i, (s, r) in enumerate(zip(skips, residuals)):
+        _req(s, f"skips[{i}]")
+        _req(r, f"residuals[{i}]")
+        if s.shape != r.shape or not s.is_contiguous() or not r.is_contiguous():
+            raise ValueError(f"add_residuals: pair {i}: skip {tuple(s.shape)} and residual {tuple(r.shape)} must be contiguous tensors "
+                             "of one shape")
+        if s.numel() == 0 or s.numel() % 8 != 0:
+            raise ValueError(f"add_residuals: pair {i} has {s.numel()} values, not a positive multiple of 8")
+        lo = lo_of(s)
+        if lo is not None and (lo.shape != s.shape or lo.stride() != s.stride() or lo.dtype != f16):
+            raise ValueError("the low half of a stream tensor must be laid out like the tensor")
+        o = torch.empty_like(s) if out is None else _req(out[i], f"out[{i}]")
+        if o.shape != s.shape or not o.is_contiguous():
+            raise ValueError(f"add_residuals: out[{i}] must be contiguous {tuple(s.shape)}")
+        outs.append(o)
+        los.append(None if lo is None else (lo if o is s else torch.empty_like(s)))
+    for first in range(0, len(skips), _lib.I2V_ADD_RES_MAX):
+        p = _lib.AddResidualsParams()
+        n = min(_lib.I2V_ADD_RES_MAX, len(skips) - first)
+        for j in range(n):
+            i, e = first + j, p.t[j]
+            e.dst, e.dst_lo, e.skip, e.skip_lo, e.res = _p(outs[i]), _p(los[i]), _p(skips[i]), _p(lo_of(skips[i])), _p(residuals[i])
+            e.numel = skips[i].numel()
+        p.n = n
+        if table is not None:
+            p.scale_table, p.scale_rows, p.step_idx = _p(table), table.numel(), _p(idx)
+        _lib.check(lib.i2v_add_residuals_f16(C.byref(p), _stream()), "i2v_add_residuals_f16")
+    for o, lo in zip(outs, los):
+        if lo is not None:
+            o._i2v_lo = lo
+    return outs
+
+
 _freeinit_ws = {}
 
 

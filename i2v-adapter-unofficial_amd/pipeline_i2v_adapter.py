@@ -80,9 +80,12 @@ class I2VAdapterPipeline:
 
     def __init__(self, vae=None, text_encoder=None, tokenizer=None, unet=None, motion_adapter=None,
                  i2v_adapter=None, scheduler=None, feature_extractor=None,
-                 image_encoder=None):
+                 image_encoder=None, controlnet=None):
         if unet is None:
             raise ValueError("`unet` is required")
+        if isinstance(controlnet, (list, tuple)):
+            raise NotImplementedError("a list of ControlNets (diffusers' MultiControlNetModel) is not implemented: pass one ControlNetModel")
+        self.controlnet = controlnet
         if not isinstance(unet, UNetMotionCrossFrameAttnModel):
             unet = UNetMotionCrossFrameAttnModel.from_unet2d(unet, motion_adapter, i2v_adapter)     # pipe:96
         self.unet = unet
@@ -94,6 +97,8 @@ class I2VAdapterPipeline:
         if vae is not None:                                                                  # pipe:110-111
             self.vae_scale_factor = 2 ** (len(vae.config["block_out_channels"]) - 1)
         self.image_processor = VaeImageProcessor(vae_scale_factor=self.vae_scale_factor)
+        # control images stay in [0, 1] (diffusers' control_image_processor: do_normalize=False)
+        self.control_image_processor = VaeImageProcessor(vae_scale_factor=self.vae_scale_factor, do_normalize=False)
         self._vae_slicing = False
         self._graph = None
         self._graph_cache = {}
@@ -211,7 +216,7 @@ class I2VAdapterPipeline:
 
     def to(self, device=None, dtype=None):
         """move the models the pipeline holds (pipe:784); fp16 is the storage dtype of the HIP path."""
-        for name in ("unet", "vae", "text_encoder", "image_encoder"):
+        for name in ("unet", "vae", "text_encoder", "image_encoder", "controlnet"):
             m = getattr(self, name)
             if m is not None:
                 setattr(self, name, m.to(device=device, dtype=dtype))
@@ -343,17 +348,35 @@ class I2VAdapterPipeline:
         x = K.ddim_prep(st["latents"], st["cond"], unet.packed()["cin_pad"], st["copies"])    # pipe:668-673
         # the time-embedding chain of this step's timestep: one row of the table computed once per sample (_time_table)
         temb_proj = K.select_row(st["temb_table"], st["step_idx"])
+        control = {}
+        if st.get("cn_cond") is not None:
+            # the ControlNet reads the step's model input -- frame 0 already replaced by the condition latents, the tensor the UNet
+            # reads -- and writes its 12 + 1 residuals; the UNet adds them at this step's row of the scale table
+            down, mid = self.controlnet._fwd_tokens(x, K.select_row(st["cn_temb_table"], st["step_idx"]), st["cn_ctx_proj"], st["cn_cond"])
+            control = dict(down_residuals=down, mid_residual=mid, residual_scale=(st["cn_scale"], st["step_idx"]))
         # the CFG halves are copies of one tensor at one timestep (pipe:672-673): what does not depend on the prompt is
         # computed once (unet._fwd_tokens, cfg_shared)
         y = unet._fwd_tokens(x, None, True, st.get("ctx_proj") or st["ctx_text"], st["ctx_ip"],
                              st["num_frames"], cfg_shared=CFG_SHARED and st["copies"] == 2, temb_proj=temb_proj,
-                             forward_upsample_size=any(s % (2 ** unet.num_upsamplers) for s in st["latents"].shape[-2:]))   # pipe:676-683, unet:1304-1311
+                             forward_upsample_size=any(s % (2 ** unet.num_upsamplers) for s in st["latents"].shape[-2:]),
+                             **control)                                                          # pipe:676-683, unet:1304-1311
         if isinstance(self.scheduler, LCMScheduler):
             K.lcm_cfg_step(st["latents"], st["noise"], y, st["coef"], st["step_idx"], st["guidance"], st["copies"])
         elif isinstance(self.scheduler, DPMSolverMultistepScheduler):
             K.dpm_cfg_step(st["latents"], st["x0_prev"], y, st["coef"], st["step_idx"], st["guidance"], st["copies"])
         else:
             K.ddim_cfg_step(st["latents"], y, st["coef"], st["step_idx"], st["guidance"], st["copies"])  # pipe:686-691
+
+    def _project_once(self, st, into=False):
+        """what depends on the sample but not on the step, computed once before the steps: K / V^T of the context for every
+        cross-attention layer and the time-embedding chain of the whole schedule -- the UNet's and, with a ControlNet, the ControlNet's
+        own.  into: overwrite the buffers `st` already holds (a cached graph's static buffers)."""
+        old = (lambda name: st[name]) if into else (lambda name: None)
+        st["ctx_proj"] = self.unet.project_context(st["ctx_text"], st["ctx_ip"], out=old("ctx_proj"))
+        st["temb_table"] = self.unet.project_time_table(st["t_table"], out=old("temb_table"))
+        if st.get("cn_cond") is not None:
+            st["cn_ctx_proj"] = self.controlnet.project_context(st["ctx_text"], out=old("cn_ctx_proj"))
+            st["cn_temb_table"] = self.controlnet.project_time_table(st["t_table"], out=old("cn_temb_table"))
 
     def _graph_key(self, st):
         """everything a captured step has baked in besides the contents of the static buffers: shapes, the Python
@@ -368,14 +391,17 @@ class I2VAdapterPipeline:
         ips = tuple((a.ip_num_tokens, float(a.ip_scale)) for a in unet._cross_attention_layers())
         shp = lambda t: None if t is None else (tuple(t.shape), t.dtype)
         from .blocks import precise_stream      # (a captured step keeps the residual-stream mode it was captured in)
-        return (tuple(st["latents"].shape), st["copies"], st["num_frames"], st["guidance"], shp(st["t_table"]),
+        # a ControlNet's launches: its weights, the control tokens' and the scale table's shapes (the table's rows are a launch argument)
+        cn = None
+        if st.get("cn_cond") is not None:
+            cn = (hash(self.controlnet.weight_signature()), shp(st["cn_cond"]), shp(st["cn_scale"]))
+        return (cn, tuple(st["latents"].shape), st["copies"], st["num_frames"], st["guidance"], shp(st["t_table"]),
                 shp(st["ctx_text"]), shp(st["ctx_ip"]), str(st["latents"].device), wsig, ips, precise_stream(),
                 self._scheduler_kind(), shp(st["coef"]), unet.freeu_signature(), shp(st.get("noise")), unet.free_noise_launch_signature())
 
     def _run_steps(self, st, n_steps, use_graph):
         if not use_graph:
-            st["ctx_proj"] = self.unet.project_context(st["ctx_text"], st["ctx_ip"])
-            st["temb_table"] = self.unet.project_time_table(st["t_table"])
+            self._project_once(st)
             for _ in range(n_steps):
                 self._step(st)
             return st["latents"]
@@ -387,19 +413,18 @@ class I2VAdapterPipeline:
         hit = cache.get(key)
         if hit is not None:
             graph, gst = hit
-            for name in ("latents", "cond", "t_table", "coef", "ctx_text", "ctx_ip", "noise"):      # (noise: this sample's LCM draws)
+            for name in ("latents", "cond", "t_table", "coef", "ctx_text", "ctx_ip", "noise",      # (noise: this sample's LCM draws)
+                         "cn_cond", "cn_scale"):                                                   # (this sample's control frames)
                 if st.get(name) is not None:
                     gst[name].copy_(st[name])
             gst["step_idx"].zero_()
-            self.unet.project_context(gst["ctx_text"], gst["ctx_ip"], out=gst["ctx_proj"])
-            self.unet.project_time_table(gst["t_table"], out=gst["temb_table"])
+            self._project_once(gst, into=True)
         else:
             # one shape at a time (a graph pins its workspace): the old graph and its pool go before the new capture,
             # so two pools never coexist at the peak
             cache.clear()
             self._graph = None
-            st["ctx_proj"] = self.unet.project_context(st["ctx_text"], st["ctx_ip"])
-            st["temb_table"] = self.unet.project_time_table(st["t_table"])
+            self._project_once(st)
             # warm-up outside capture: packs weights, sizes the allocator; then restore the state it advanced
             saved = st["latents"].clone()
             self._step(st)
@@ -428,6 +453,58 @@ class I2VAdapterPipeline:
         if callback is not None:
             use_graph = False
         return output_type, use_graph
+
+    # ------------------------------------------------------------------------------------------ ControlNet
+    def _check_control_args(self, control_image, num_frames, scale, start, end, guess_mode):
+        """the ControlNet arguments of a call, checked on the host before anything is launched or encoded"""
+        if guess_mode:
+            raise NotImplementedError("guess_mode=True is not implemented")
+        if control_image is not None and self.controlnet is None:
+            raise ValueError("`control_image` was passed but the pipeline has no `controlnet`: build it with "
+                             "I2VAdapterPipeline(..., controlnet=ControlNetModel.from_pretrained(...))")
+        if self.controlnet is None:
+            return
+        if control_image is None:
+            raise ValueError("the pipeline has a `controlnet`: `control_image` is required (one control frame per frame of the clip)")
+        from .controlnet import controlnet_keep_table
+        controlnet_keep_table(1, scale, start, end)                    # 0 <= start < end <= 1, else ValueError
+        if isinstance(control_image, torch.Tensor):
+            if control_image.dim() not in (4, 5) or control_image.shape[-3] != 3:
+                raise ValueError(f"`control_image` must be [F, 3, H, W] or [B, F, 3, H, W], got {tuple(control_image.shape)}")
+            n = control_image.shape[-4]
+        elif isinstance(control_image, (list, tuple)):
+            n = len(control_image)
+        else:
+            raise ValueError(f"`control_image` must be a list of `num_frames` images or a tensor, got {type(control_image)}")
+        if n != num_frames:
+            raise ValueError(f"`control_image` holds {n} frames, `num_frames` is {num_frames}: a ControlNet runs per frame and needs one "
+                             "control frame for every frame of the clip")
+
+    def prepare_control_image(self, control_image, batch_size, num_frames, height, width):
+        """-> fp32 [batch_size * num_frames, 3, height, width] in [0, 1] on the host: PIL images resized by the image processor WITHOUT
+        the [-1, 1] normalisation (a ControlNet is trained on [0, 1] maps); tensors as they are (they must have that size); one clip
+        of control frames is shared by the batch."""
+        if isinstance(control_image, torch.Tensor):
+            t = control_image.detach().float().cpu()
+            if t.dim() == 4:
+                t = t[None].expand(batch_size, -1, -1, -1, -1)
+            if t.shape[0] != batch_size or t.shape[1] != num_frames:
+                raise ValueError(f"`control_image` {tuple(control_image.shape)} does not match batch {batch_size} x {num_frames} frames")
+            if tuple(t.shape[-2:]) != (height, width):
+                raise ValueError(f"`control_image` tensors must already be {height} x {width}, got {tuple(t.shape[-2:])}")
+            return t.reshape(batch_size * num_frames, 3, height, width).contiguous()
+        if len(control_image) != num_frames:
+            raise ValueError(f"`control_image` holds {len(control_image)} frames, `num_frames` is {num_frames}")
+        t = self.control_image_processor.preprocess(list(control_image), height=height, width=width)
+        if tuple(t.shape[-2:]) != (height, width):
+            raise ValueError(f"control frames of {tuple(t.shape[-2:])} after resizing, expected {height} x {width}")
+        return t[None].expand(batch_size, -1, -1, -1, -1).reshape(batch_size * num_frames, 3, height, width).contiguous()
+
+    @staticmethod
+    def _control_scale_table(n_steps, cn_args, device):
+        """fp32 [n_steps] on the device: conditioning scale x diffusers' `controlnet_keep` over the executed steps"""
+        from .controlnet import controlnet_keep_table
+        return torch.tensor(controlnet_keep_table(n_steps, *cn_args), dtype=torch.float32, device=device)
 
     # ------------------------------------------------------------------------------------------ encode_image
     def encode_image(self, image, device, num_images_per_prompt, output_hidden_states=None):
@@ -546,9 +623,15 @@ class I2VAdapterPipeline:
                  frame_similarity_sample_ratio: float = 1, frame_similarity_blurred_strength: float = 0.6,
                  condition_image_latents=None, image_embeds=None, negative_image_embeds=None,
                  prior_mask_generator=None, prior_noise_generator=None, blur_sigma: Optional[float] = None,
-                 use_graph: bool = True, precise_stream: Optional[bool] = None):
+                 use_graph: bool = True, precise_stream: Optional[bool] = None, control_image=None,
+                 controlnet_conditioning_scale: float = 1.0, control_guidance_start: float = 0.0, control_guidance_end: float = 1.0,
+                 guess_mode: bool = False):
         """pipe:537-711 (the arguments the reference's `__call__` takes; `use_graph`, the explicit prior generators and
-        `precise_stream` are additions).  precise_stream: True / False runs THIS call with / without the precise residual stream
+        `precise_stream` are additions, and so are the ControlNet arguments, which carry the names of diffusers'
+        StableDiffusionControlNetPipeline: `control_image` -- `num_frames` PIL images, a [F, 3, H, W] tensor in [0, 1] shared by the
+        batch or a [B, F, 3, H, W] tensor in [0, 1] --, `controlnet_conditioning_scale`, and the window
+        `control_guidance_start` .. `control_guidance_end` of the schedule, as fractions, in which the control acts).
+        precise_stream: True / False runs THIS call with / without the precise residual stream
         (fp16 hi + lo pairs between the UNet's modules, DESIGN 2.2: closer to the fp32 reference, +2.6 % step time); None keeps the
         process setting (`blocks.set_precise_stream`, I2V_STREAM_PRECISE)."""
         if precise_stream is not None:
@@ -573,6 +656,9 @@ class I2VAdapterPipeline:
                 return self.__call__(**kw)
             finally:
                 self.unet.set_lora_scale(prev)
+        # ControlNet: the arguments, before anything is launched or encoded
+        self._check_control_args(control_image, num_frames, controlnet_conditioning_scale, control_guidance_start, control_guidance_end,
+                                 guess_mode)
         # FreeNoise (enable_free_noise): the settings against this call's num_frames, before anything is launched or encoded
         fnz = self._free_noise_settings()
         if fnz is not None:
@@ -709,6 +795,14 @@ class I2VAdapterPipeline:
             ctx_text=prompt_embeds.to(dev, f16).contiguous(),
             ctx_ip=self.unet._project_image_embeds(
                 {"image_embeds": image_embeds.to(dev)} if image_embeds is not None else None))
+        if self.controlnet is not None:
+            # once per sample: the embedding of the B * F control frames (duplicated for the second CFG half) and the scale table;
+            # the ControlNet's context projection and time table are made where the UNet's are (_project_once)
+            frames = self.prepare_control_image(control_image, batch_size, num_frames, height, width).to(dev, f16)
+            tokens = self.controlnet.embed_condition(frames)
+            st["cn_cond"] = K.duplicate_batch(tokens) if copies == 2 else tokens
+            st["cn_args"] = (float(controlnet_conditioning_scale), float(control_guidance_start), float(control_guidance_end))
+            st["cn_scale"] = self._control_scale_table(len(timesteps), st["cn_args"], dev)
         if dpm:
             # the previous step's data prediction: the first step of a sample is first order and does not read it
             st["x0_prev"] = torch.empty_like(latents)
@@ -753,6 +847,8 @@ class I2VAdapterPipeline:
             timesteps, _ = self.get_timesteps(round_steps[rnd], ratio)
             st["t_table"] = timesteps.to(torch.float32).to(dev)
             st["coef"] = self.scheduler.step_coefficients(timesteps, eta).to(dev)
+            if st.get("cn_cond") is not None:      # the control window over THIS round's schedule (the time table follows t_table)
+                st["cn_scale"] = self._control_scale_table(len(timesteps), st["cn_args"], dev)
         else:
             timesteps, _ = self.get_timesteps(round_steps[rnd], ratio)
         b, f, c, h, w = prev.shape
@@ -778,8 +874,7 @@ class I2VAdapterPipeline:
                 warnings.warn("eta > 0: the stochastic DDIM update draws fresh noise on the host every step, so the steps run as "
                               "eager launches instead of the captured hipGraph (about 2x the step time)", RuntimeWarning, stacklevel=3)
             sigmas = None if fixed else self.scheduler.step_sigmas(timesteps, eta)
-            st["ctx_proj"] = self.unet.project_context(st["ctx_text"], st["ctx_ip"])
-            st["temb_table"] = self.unet.project_time_table(st["t_table"])
+            self._project_once(st)
             for i, t in enumerate(timesteps):                                                   # pipe:666-697
                 self._step(st)
                 if eta > 0 and not fixed:
@@ -882,7 +977,35 @@ def build_parser():
                         help="FreeNoise's initial noise behind the first window (diffusers' default: shuffle_context)")
     parser.add_argument("--free_init_fast", action="store_true",
                         help="FreeInit's use_fast_sampling: earlier rounds take fewer steps (every round re-captures the step)")
+    parser.add_argument("--controlnet", type=str, default=None, metavar="PATH",
+                        help="an SD-1.5 ControlNet folder (config.json + diffusion_pytorch_model.safetensors, e.g. "
+                             "control_v11p_sd15_openpose): every clip follows the control frames of --control_column")
+    parser.add_argument("--control_column", type=str, default=None, metavar="NAME",
+                        help="the CSV column that holds, per row, a directory of at least num_frames control images (taken in sorted "
+                             "order) or an animated GIF, relative to the CSV")
+    parser.add_argument("--controlnet_scale", type=float, default=1.0, metavar="S", help="controlnet_conditioning_scale (1.0)")
+    parser.add_argument("--control_guidance_start", type=float, default=0.0, metavar="A",
+                        help="fraction of the schedule at which the control starts to act (0.0)")
+    parser.add_argument("--control_guidance_end", type=float, default=1.0, metavar="B",
+                        help="fraction of the schedule at which the control stops acting (1.0)")
     return parser
+
+
+def load_control_frames(path, num_frames):
+    """the first `num_frames` control frames of a directory of images (sorted by name) or of an animated GIF, as RGB PIL images"""
+    import PIL.Image
+    import PIL.ImageSequence
+    if os.path.isdir(path):
+        names = sorted(f for f in os.listdir(path) if f.lower().endswith((".png", ".jpg", ".jpeg", ".bmp", ".webp")))
+        frames = [PIL.Image.open(os.path.join(path, f)).convert("RGB") for f in names[:num_frames]]
+    elif os.path.isfile(path):
+        with PIL.Image.open(path) as im:
+            frames = [fr.convert("RGB") for i, fr in enumerate(PIL.ImageSequence.Iterator(im)) if i < num_frames]
+    else:
+        raise FileNotFoundError(f"control frames: {path} is neither a directory nor a file")
+    if len(frames) < num_frames:
+        raise ValueError(f"control frames: {path} holds {len(frames)} frames, num_frames is {num_frames}")
+    return frames
 
 
 def main(argv=None):
@@ -916,6 +1039,9 @@ def main(argv=None):
         logger.error("Checkpoint `task_name` must be specified.")
         return -1
 
+    if (args.controlnet is None) != (args.control_column is None):
+        logger.error("--controlnet and --control_column come together.")
+        return -1
     i2v_adapter = None
     motion_adapter = MotionAdapter.from_pretrained(args.motion_adapter_path)                     # pipe:734
     checkpoint_path = os.path.join(args.checkpoint_root, args.task_name, f"epoch_{args.checkpoint_epoch}")
@@ -949,7 +1075,14 @@ def main(argv=None):
         emb = {}
         text_encoder, tokenizer = load_text_encoder(args.model_path)                             # pipe:752-753
 
-    pipe = I2VAdapterPipeline(vae, text_encoder, tokenizer, unet2d.to(device).half(), motion_adapter, i2v_adapter, scheduler)
+    controlnet = control_paths = None
+    if args.controlnet is not None:
+        from .controlnet import ControlNetModel
+        controlnet = ControlNetModel.from_pretrained(args.controlnet)
+        control_paths = [os.path.join(eval_data_dir, str(p)) for p in eval_data_df[args.control_column]]
+        logger.info(f"Successfully loaded ControlNetModel from {args.controlnet}.")
+    pipe = I2VAdapterPipeline(vae, text_encoder, tokenizer, unet2d.to(device).half(), motion_adapter, i2v_adapter, scheduler,
+                              controlnet=controlnet)
     if "image_embeds" in emb or args.ip_adapter:                                                 # pipe:783
         pipe.load_ip_adapter(args.ip_adapter_path, subfolder="models", weight_name=args.ip_adapter_weight_name)
         if args.ip_adapter_scale is not None:
@@ -990,7 +1123,12 @@ def main(argv=None):
             image = dict(image_embeds=emb["image_embeds"][ind: ind + 1])
         else:
             image = dict(ip_adapter_image=condition_images[ind]) if args.ip_adapter else {}      # pipe:796
-        out = pipe(**text, **image,
+        control = {}
+        if controlnet is not None:
+            control = dict(control_image=load_control_frames(control_paths[ind], args.num_frames),
+                           controlnet_conditioning_scale=args.controlnet_scale, control_guidance_start=args.control_guidance_start,
+                           control_guidance_end=args.control_guidance_end)
+        out = pipe(**text, **image, **control,
                    condition_image=condition_images[ind], num_frames=args.num_frames, guidance_scale=args.guidance_scale,
                    num_inference_steps=args.num_inference_steps, frame_similarity_sample_ratio=0.9,
                    height=args.height, width=args.width, output_type="pil", generator=g(0),

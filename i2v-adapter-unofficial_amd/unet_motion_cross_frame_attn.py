@@ -76,8 +76,8 @@ class CrossFrameAttnDownBlockMotion(nn.Module):
             x = resnet._fwd(x, temb_act.first_half() if shared else temb_act)         # unet:312
             x = attn._fwd(x, enable, num_frames, ctx_text, ctx_ip, cfg_expand=shared)   # unet:313-322
             x = motion._fwd(x, num_frames)                                            # unet:323-326
-            if i == n_layers - 1 and additional_residuals is not None:
-                raise NotImplementedError("additional_residuals (ControlNet) are not on the hot path")
+            if i == n_layers - 1 and additional_residuals is not None:                # unet:329-330
+                x, = K.add_residuals([x], [additional_residuals])
             states += (x,)
         if self.downsamplers is not None:                                             # unet:334-338
             for d in self.downsamplers:
@@ -93,7 +93,7 @@ class CrossFrameAttnDownBlockMotion(nn.Module):
         ta = K.silu(_as_f16_matrix(temb)) if temb is not None else None
         ct, ci = _split_ctx(self, encoder_hidden_states)
         x, states = self._fwd(to_tokens(hidden_states), ta, enable_cross_frame_attn, ct, ci, num_frames,
-                              additional_residuals)
+                              None if additional_residuals is None else to_tokens(additional_residuals))
         dt = hidden_states.dtype
         return from_tokens(x, dt), tuple(from_tokens(s, dt) for s in states)
 
@@ -796,10 +796,13 @@ class UNetMotionCrossFrameAttnModel(UNetLoraMixin, PretrainedMixin, HipModule):
         return K.gemm(K.silu(temb), wt, bt, out=out)
 
     def _fwd_tokens(self, x, temb, enable_cross_frame_attn, ctx_text, ctx_ip, num_frames, cfg_shared=False, temb_proj=None,
-                    forward_upsample_size=False):
+                    forward_upsample_size=False, down_residuals=None, mid_residual=None, residual_scale=None):
         """x: model-input tokens [B*F, H, W, cin_pad] fp16; temb [B, 4*C0] fp16 (pre-SiLU) -- or temb_proj [B or 1, sum Cout]:
         the resnets' time-embedding projections already computed (project_time_table); ctx_text [B, Lt, D]
-        (+ ctx_ip [B, 4, D]) or a ProjectedContext; returns noise-prediction tokens [B*F, H, W, out_channels]."""
+        (+ ctx_ip [B, 4, D]) or a ProjectedContext; returns noise-prediction tokens [B*F, H, W, out_channels].
+        down_residuals / mid_residual (a ControlNet's outputs, unet:1299-1300): token tensors shaped like the skip tensors (full
+        batch, also under cfg_shared) and like the mid block's output; residual_scale = (fp32 table, int32 step counter) on the
+        device, or None for scale 1 (K.add_residuals)."""
         if self._free_noise is not None:
             from .free_noise import check_num_frames
             check_num_frames(num_frames, self._free_noise)
@@ -828,7 +831,15 @@ class UNetMotionCrossFrameAttnModel(UNetLoraMixin, PretrainedMixin, HipModule):
             else:
                 x, r = blk._fwd(x, temb_act, num_frames)
             res += r
+        if down_residuals is not None:                                                  # unet:1379-1389
+            if len(down_residuals) != len(res):
+                raise ValueError(f"down_block_additional_residuals: {len(down_residuals)} tensors for {len(res)} skip tensors")
+            # new tensors: the last skip tensor IS the mid block's input, which takes no residual (no down-sampler after the last
+            # block); an in-place add would change what the mid block reads
+            res = tuple(K.add_residuals(res, down_residuals, scale=residual_scale))
         x = self.mid_block._fwd(x, temb_act, enable_cross_frame_attn, ctx_text, ctx_ip, num_frames)
+        if mid_residual is not None:                                                    # unet:1402-1403
+            x, = K.add_residuals([x], [mid_residual], scale=residual_scale, out=[x])
         upsample_size = None
         for bi, blk in enumerate(self.up_blocks):                                       # unet:1406-1436
             r = res[-len(blk.resnets):]
@@ -885,8 +896,6 @@ class UNetMotionCrossFrameAttnModel(UNetLoraMixin, PretrainedMixin, HipModule):
         self._sync_lora()      # (a LoRA change since the last call: merge before any weight or pack is read)
         if attention_mask is not None:
             raise NotImplementedError("attention masks are never passed on the hot path (SURVEY 8b)")
-        if down_block_additional_residuals is not None or mid_block_additional_residual is not None:
-            raise NotImplementedError("ControlNet residuals are not on the hot path")
         if not sample.is_cuda:
             raise HipLibraryError(f"sample is on {sample.device}: the HIP path has no CPU fallback")
         if sample.dim() != 5:
@@ -911,8 +920,14 @@ class UNetMotionCrossFrameAttnModel(UNetLoraMixin, PretrainedMixin, HipModule):
         p = self.packed()
         x = K.nchw_to_tokens(sample.reshape(b * num_frames, c, hh, ww), p["cin_pad"])     # unet:1358
         cfg_shared = bool(cross_attention_kwargs and cross_attention_kwargs.get("cfg_shared_prefix", False))
+        # ControlNet residuals (unet:1299-1300): NCHW (B * F, C, h, w) like the skip tensors -> tokens
+        down_res = mid_res = None
+        if down_block_additional_residuals is not None:
+            down_res = [K.nchw_to_tokens(r) for r in down_block_additional_residuals]
+        if mid_block_additional_residual is not None:
+            mid_res = K.nchw_to_tokens(mid_block_additional_residual)
         y = self._fwd_tokens(x, temb, enable_cross_frame_attn, ctx_text, ctx_ip, num_frames, cfg_shared=cfg_shared,
-                             forward_upsample_size=forward_upsample_size)
+                             forward_upsample_size=forward_upsample_size, down_residuals=down_res, mid_residual=mid_res)
         out_dt = sample.dtype if sample.dtype in (torch.float32, f16) else f16
         out = K.tokens_to_nchw(y, dtype=out_dt).reshape(b, num_frames, -1, hh, ww)        # unet:1446
         if not return_dict:

@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define I2V_ABI_VERSION 21
+#define I2V_ABI_VERSION 22
 
 #define I2V_OK 0
 #define I2V_ERR_INVALID_ARG (-1)
@@ -781,6 +781,37 @@ int i2v_clip_vision_attention_f16(const void* qkv, int64_t ld_qkv, int32_t q_off
 int i2v_perceiver_attention_f16(const void* q, int64_t ld_q, int32_t q_off, const void* kv_a, int64_t ld_a, int32_t ka_off, int32_t va_off,
                                 int32_t len_a, const void* kv_b, int64_t ld_b, int32_t kb_off, int32_t vb_off, int32_t len_b, void* out,
                                 int64_t ld_out, int32_t batch, int32_t n_q, int32_t heads, int32_t head_dim, float scale, i2v_stream_t stream);
+
+/* (ABI 22) ControlNet residuals (unet:1299-1300: down_block_additional_residuals / mid_block_additional_residual; the adds of unet:329-330,
+ * 1379-1389 and 1402-1403): up to I2V_ADD_RES_MAX (skip, residual) pairs of different sizes in one launch,
+ *           dst_i = skip_i + s * res_i,     s = scale_table[min(max(step_idx[0], 0), scale_rows - 1)]
+ *       scale_table fp32 [scale_rows] and step_idx (one int32) are DEVICE memory, read by the kernel: one captured launch serves a schedule
+ *       whose control is on for some steps and off for others.  step_idx NULL: row 0.  scale_table NULL: s = 1.
+ *       All tensors fp16, dense, numel values each; dst may be skip (in place) or other memory, and may not overlap anything else.
+ *       Arithmetic in fp32 with one rounding to fp16.  Where s * res is exactly zero the skip's bits are kept (s = 0: bit-equal, -0 included).
+ *       The precise residual stream (i2v_gemm_params.residual_lo / c_lo): skip_lo / dst_lo both given -- the sum is
+ *       (skip + skip_lo) + s * res in fp32, dst = rn16(sum), dst_lo = rn16(sum - dst), so the pair stays a pair.
+ *       Grid: at most 2048 workgroups of 256 lanes stride over 16 KB tiles (16 bytes per lane and access); a workgroup finds the tensor of a
+ *       tile through prefix sums carried in the launch's own parameter block -- no descriptor table in device memory, no allocation.
+ *       I2V_ERR_INVALID_ARG (nothing launched): n outside 1..I2V_ADD_RES_MAX, numel not a positive multiple of 8, a null dst / skip / res,
+ *       skip_lo and dst_lo not both given or both null, a pointer that is not 16-byte aligned, scale_table with scale_rows < 1. */
+#define I2V_ADD_RES_MAX 16
+typedef struct i2v_add_residuals_entry {
+  void* dst;
+  void* dst_lo;
+  const void* skip;
+  const void* skip_lo;
+  const void* res;
+  int64_t numel;
+} i2v_add_residuals_entry;
+typedef struct i2v_add_residuals_params {
+  i2v_add_residuals_entry t[I2V_ADD_RES_MAX];
+  int32_t n;
+  int32_t scale_rows;
+  const float* scale_table;
+  const int32_t* step_idx;
+} i2v_add_residuals_params;
+int i2v_add_residuals_f16(const i2v_add_residuals_params* p, i2v_stream_t stream);
 
 /* First-frame-similarity prior and the initial add_noise of the sampling loop, pipe:647-656:
  *   prior   = mask * GaussianBlur3x3(cond) + (1 - mask) * cond, mask = (mask_uniform < strength), per frame (pipe:648-654)

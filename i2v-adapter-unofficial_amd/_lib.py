@@ -10,7 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # I2V_LIB_PATH selects another build of the same ABI (same-box A/B of two kernels, tools/ab_bench.sh); the in-tree
 # library is never overwritten by tooling
 LIB_PATH = os.environ.get("I2V_LIB_PATH") or os.path.join(_HERE, "libi2v_hip.so")
-ABI_VERSION = 22
+ABI_VERSION = 23
 
 I2V_EPI_NONE, I2V_EPI_GELU, I2V_EPI_GEGLU = 0, 1, 2
 I2V_STORE_ROWMAJOR, I2V_STORE_ROWPERM, I2V_STORE_VT, I2V_STORE_VT_T = 0, 1, 2, 3
@@ -20,6 +20,7 @@ I2V_ROUTE_GENERIC, I2V_ROUTE_CONV_THIN, I2V_ROUTE_BIG_TILE, I2V_ROUTE_BIG_DEEP, 
 I2V_EXTRA_NONE, I2V_EXTRA_LNF, I2V_EXTRA_HILO, I2V_EXTRA_GNS, I2V_EXTRA_UPF = 0, 1, 2, 4, 8
 I2V_TATTN_LDS_FORM, I2V_TATTN_REG_FORM = 0, 1
 I2V_ADD_RES_MAX = 16
+I2V_TAESD_PREP_IDENTITY, I2V_TAESD_PREP_UNIT, I2V_TAESD_PREP_CLAMP = 0, 1, 2
 
 
 class HipLibraryError(RuntimeError):
@@ -241,6 +242,19 @@ class AddResidualsParams(C.Structure):
                 ("step_idx", C.c_void_p)]
 
 
+class ConvC64Params(C.Structure):
+    _fields_ = [
+        ("x", C.c_void_p), ("ldx", C.c_int64),
+        ("w", C.c_void_p), ("bias", C.c_void_p),
+        ("residual", C.c_void_p), ("ldr", C.c_int64),
+        ("out", C.c_void_p), ("ldo", C.c_int64),
+        ("n_img", C.c_int32), ("height", C.c_int32), ("width", C.c_int32),
+        ("cin", C.c_int32), ("cout", C.c_int32),
+        ("relu_mid", C.c_int32), ("relu_out", C.c_int32),
+        ("max_workgroups", C.c_int32),
+    ]
+
+
 # every symbol include/i2v_hip.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 SIGNATURES = {
@@ -345,6 +359,8 @@ SIGNATURES = {
                                               C.c_int32, C.c_int32, C.c_int32, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                               C.c_float, _P]),
     "i2v_add_residuals_f16": (C.c_int, [C.POINTER(AddResidualsParams), _P]),
+    "i2v_conv3x3_c64_f16": (C.c_int, [C.POINTER(ConvC64Params), _P]),
+    "i2v_taesd_prep_f16": (C.c_int, [_P, C.c_int32, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),
     # the model handle: configuration, weight registry, plan, one captured step
     "i2v_unet_create": (C.c_int, [C.POINTER(UnetConfig), C.POINTER(_P)]),
     "i2v_unet_destroy": (C.c_int, [_P]),

@@ -363,6 +363,92 @@ def conv3x3(x, w_packed, bias=None, *, stride=1, upsample=False, rowvec=None, ro
     return (out, stats) if gn_stats_groups else out
 
 
+def pack_conv_c64(weight: torch.Tensor) -> torch.Tensor:
+    """[64, Cin <= 64, 3, 3] -> the 36864 fp16 of `conv3x3_c64`'s weight in the kernel's MFMA-fragment order (include/i2v_hip.h,
+    i2v_conv_c64_params.w): Cin zero-padded to 64,
+        packed[tap, s, b, 16 g + l, j] = W[32 (b >> 1) + 8 (l >> 2) + 4 (b & 1) + (l & 3), 32 s + 8 g + j, tap]."""
+    co, ci = weight.shape[:2]
+    if co != 64 or ci > 64 or tuple(weight.shape[2:]) != (3, 3):
+        raise ValueError(f"pack_conv_c64 takes a [64, <= 64, 3, 3] weight, got {tuple(weight.shape)}")
+    w = torch.nn.functional.pad(weight.detach().reshape(64, ci, 9), (0, 0, 0, 64 - ci))       # [cout, cin, tap]
+    # cout = 32 bh + 8 q + 4 bl + e, cin = 32 s + 8 g + j  ->  [tap, s, (bh, bl), (g, (q, e)), j]
+    w = w.reshape(2, 4, 2, 4, 2, 4, 8, 9)                                                      # [bh, q, bl, e, s, g, j, tap]
+    return w.permute(7, 4, 0, 2, 5, 1, 3, 6).reshape(-1).to(f16).contiguous()
+
+
+def _pixel_stride(t, name):
+    """pixel stride of a token-major fp16 image view [N, H, W, C] whose pixels are `ld` elements apart and otherwise dense"""
+    _req(t, name)
+    if t.dim() != 4:
+        raise ValueError(f"{name} must be [N, H, W, C], got {tuple(t.shape)}")
+    n, h, w, c = t.shape
+    ld = t.stride(2) if w > 1 else (t.stride(1) if h > 1 else (t.stride(0) // (h * w) if n > 1 else max(c, t.stride(2))))
+    if t.stride(3) != 1 or (w > 1 and t.stride(2) != ld) or (h > 1 and t.stride(1) != w * ld) or (n > 1 and t.stride(0) != h * w * ld):
+        raise ValueError(f"{name} must be a token-major image with one pixel stride, got strides {t.stride()}")
+    return ld
+
+
+def conv3x3_c64(x, w_packed, bias=None, *, relu_mid=False, relu_out=False, residual=None, out=None, max_workgroups=None):
+    """out = act_out(act_mid(conv3x3(x) + bias) + residual): the 64 -> 64, stride 1, pad 1 convolution of AutoencoderTiny with its
+    epilogue in one launch (i2v_conv3x3_c64_f16).  x, out, residual: token-major fp16 [N, H, W, 64] views with a pixel stride >= 64
+    (a multiple of 8); w_packed from `pack_conv_c64`; bias fp16 [64].  `out` may be `residual`, never `x`.  max_workgroups caps the
+    persistent grid (a dispatch override, like the library's other ones: the result does not depend on it)."""
+    lib = _lib.load()
+    ldx = _pixel_stride(x, "x")
+    n, h, wd, c = x.shape
+    _req(w_packed, "w_packed")
+    if w_packed.numel() != 9 * 64 * 64 or not w_packed.is_contiguous():
+        raise ValueError(f"w_packed must be the {9 * 64 * 64} values of pack_conv_c64, got {tuple(w_packed.shape)}")
+    if out is None:
+        out = torch.empty((n, h, wd, c), dtype=f16, device=x.device)
+    ldo = _pixel_stride(out, "out")
+    if tuple(out.shape) != (n, h, wd, c):
+        raise ValueError(f"out must be {(n, h, wd, c)}, got {tuple(out.shape)}")
+    p = _lib.ConvC64Params()
+    p.x, p.ldx, p.w, p.out, p.ldo = _p(x), ldx, _p(w_packed), _p(out), ldo
+    if bias is not None:
+        _req(bias, "bias")
+        if bias.numel() != c or not bias.is_contiguous():
+            raise ValueError("bias must be a contiguous vector of Cout elements")
+        p.bias = _p(bias)
+    if residual is not None:
+        p.ldr = _pixel_stride(residual, "residual")
+        if tuple(residual.shape) != (n, h, wd, c):
+            raise ValueError(f"residual must be {(n, h, wd, c)}, got {tuple(residual.shape)}")
+        p.residual = _p(residual)
+    p.n_img, p.height, p.width, p.cin, p.cout = n, h, wd, c, c
+    p.relu_mid, p.relu_out = int(bool(relu_mid)), int(bool(relu_out))
+    p.max_workgroups = 0 if max_workgroups is None else int(max_workgroups)
+    if max_workgroups is not None and p.max_workgroups < 1:
+        raise ValueError(f"max_workgroups must be positive, got {max_workgroups}")
+    _lib.check(lib.i2v_conv3x3_c64_f16(C.byref(p), _stream()), "i2v_conv3x3_c64_f16")
+    return out
+
+
+TAESD_PREP_MODES = {"identity": _lib.I2V_TAESD_PREP_IDENTITY, "unit": _lib.I2V_TAESD_PREP_UNIT, "clamp": _lib.I2V_TAESD_PREP_CLAMP}
+
+
+def taesd_prep(src, mode="identity", out=None):
+    """AutoencoderTiny's entry mover (i2v_taesd_prep_f16): src [N, C <= 64, H, W] fp32 / fp16 through `mode` -- "identity",
+    "unit" (v + 1) / 2, "clamp" 3 tanh(v / 3) -- to token-major fp16 [N, H, W, 64] with channels C.. zero."""
+    lib = _lib.load()
+    _req(src, "src", dtype=None)
+    if src.dtype not in (torch.float32, f16) or src.dim() != 4:
+        raise TypeError("src must be a 4-D fp32 / fp16 tensor")
+    if mode not in TAESD_PREP_MODES:
+        raise ValueError(f"mode must be one of {sorted(TAESD_PREP_MODES)}, got {mode!r}")
+    src = src.contiguous()
+    n, c, h, w = src.shape
+    if out is None:
+        out = torch.empty((n, h, w, 64), dtype=f16, device=src.device)
+    ld = _pixel_stride(out, "out")
+    if tuple(out.shape) != (n, h, w, 64):
+        raise ValueError(f"out must be {(n, h, w, 64)}, got {tuple(out.shape)}")
+    _lib.check(lib.i2v_taesd_prep_f16(_p(src), 1 if src.dtype == torch.float32 else 0, _p(out), ld, n, c, h * w, TAESD_PREP_MODES[mode],
+                                      _stream()), "i2v_taesd_prep_f16")
+    return out
+
+
 def project_vt(tokens, w_v, batch_len, out=None, bias=None, ln=None, pe_t=None, pe_period=0, query_ln_support=False):
     """V^T[batch][channel][key] = (tokens W_v^T)^T, emitted directly by the GEMM epilogue (I2V_STORE_VT).
     tokens [batches * batch_len, K]; w_v [C, K]; returns [batches, C, pad8(batch_len)] (tail keys unwritten).

@@ -195,7 +195,7 @@ class I2VAdapterPipeline:
     def decode_latents(self, latents):
         """pipe:300-320: latents (B, F, 4, h, w) -> video (B, F, 3, 8h, 8w) float32 through the HIP VAE decoder."""
         if self.vae is None:
-            raise ValueError("decode_latents needs a `vae` (AutoencoderKL) -- or use output_type='latent'")
+            raise ValueError("decode_latents needs a `vae` (AutoencoderKL or AutoencoderTiny) -- or use output_type='latent'")
         latents = 1 / self.vae.config["scaling_factor"] * latents
         b, f, c, h, w = latents.shape
         flat = latents.reshape(b * f, c, h, w)
@@ -206,13 +206,18 @@ class I2VAdapterPipeline:
         return image[None, :].reshape((b, f, -1) + image.shape[2:]).float()
 
     def encode_condition_image(self, condition_image, height, width, generator=None):
-        """pipe:626-627: preprocess -> vae.encode(...).latent_dist.sample() * scaling_factor."""
+        """pipe:626-627: preprocess -> vae.encode(...).latent_dist.sample() * scaling_factor.  A deterministic VAE (AutoencoderTiny:
+        the result of `encode` has `latents` and no `latent_dist`) gives its latents as they are: nothing is sampled and `generator`
+        is not used."""
         if self.vae is None:
             raise ValueError("a `condition_image` needs a `vae` (AutoencoderKL) -- or pass `condition_image_latents`")
         img = self.image_processor.preprocess(condition_image, height=height, width=width).to(self.vae.device)
         if isinstance(generator, list):
             generator = generator[0]
-        return self.vae.encode(img).latent_dist.sample(generator) * self.vae.config["scaling_factor"]
+        enc = self.vae.encode(img)
+        if not hasattr(enc, "latent_dist") and hasattr(enc, "latents"):
+            return enc.latents * self.vae.config["scaling_factor"]
+        return enc.latent_dist.sample(generator) * self.vae.config["scaling_factor"]
 
     def to(self, device=None, dtype=None):
         """move the models the pipeline holds (pipe:784); fp16 is the storage dtype of the HIP path."""
@@ -962,6 +967,9 @@ def build_parser():
     parser.add_argument("--vae_tiling", action="store_true",
                         help="tile the VAE decode / condition-image encode above 512 px a side (pipe.enable_vae_tiling(); off by "
                              "default, as in the reference driver)")
+    parser.add_argument("--vae_tiny", type=str, default=None, metavar="PATH",
+                        help="an AutoencoderTiny (TAESD) folder (config.json + diffusion_pytorch_model.safetensors) loaded in place of "
+                             "<model_path>/vae: the cheap decode that goes with --scheduler lcm (no tiling: not with --vae_tiling)")
     parser.add_argument("--free_init", type=int, nargs="?", const=3, default=None, metavar="N",
                         help="FreeInit (pipe.enable_free_init): sample every clip N times (3 when given without a value), re-initialising "
                              "the noise's low frequencies from the previous round; off by default")
@@ -1058,7 +1066,12 @@ def main(argv=None):
 
     device = torch.device("cuda")                                # there is no CPU path (the reference falls back to it)
     unet2d = UNet2DConditionModel.from_pretrained(os.path.join(args.model_path, "unet"))         # pipe:751
-    vae = AutoencoderKL.from_pretrained(os.path.join(args.model_path, "vae"))                    # pipe:754
+    if args.vae_tiny is not None:
+        from .autoencoder_tiny import AutoencoderTiny
+        vae = AutoencoderTiny.from_pretrained(args.vae_tiny)
+        logger.info(f"Successfully loaded AutoencoderTiny from {args.vae_tiny}.")
+    else:
+        vae = AutoencoderKL.from_pretrained(os.path.join(args.model_path, "vae"))                # pipe:754
     scheduler = load_scheduler(args.model_path, args.scheduler)                                 # pipe:755-757
 
     eval_data_dir = os.path.dirname(args.eval_data_path)                                         # pipe:759-768

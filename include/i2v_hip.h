@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define I2V_ABI_VERSION 22
+#define I2V_ABI_VERSION 23
 
 #define I2V_OK 0
 #define I2V_ERR_INVALID_ARG (-1)
@@ -812,6 +812,46 @@ typedef struct i2v_add_residuals_params {
   const int32_t* step_idx;
 } i2v_add_residuals_params;
 int i2v_add_residuals_f16(const i2v_add_residuals_params* p, i2v_stream_t stream);
+
+/* (ABI 23) The layer of AutoencoderTiny (TAESD, diffusers' AutoencoderTiny): a 3x3 / pad 1 / stride 1 convolution with Cin = Cout = 64 on
+ * token-major fp16 images [n_img, height, width, 64] and its epilogue in one launch,
+ *           out = act_out( act_mid(conv(x) + bias) + residual ),      act = ReLU where relu_mid / relu_out is non-zero, else identity
+ *       fp32 arithmetic, one rounding to fp16.  bias (fp16 [64]) and residual are optional.  x, out and residual each have their own pixel
+ *       stride (ldx / ldo / ldr, in elements): >= 64, a multiple of 8, bases 16-byte aligned; only the 64 channels of a pixel are touched.
+ *       Any height, width >= 1: edge tiles are zero-filled inside the image's own halo and never read the neighbouring image.
+ *       w: the weight [64, 64, 3, 3] in the kernel's MFMA-fragment order, 36864 fp16 (`kernels.pack_conv_c64`; Cin < 64 zero-padded):
+ *           w[(((tap * 2 + s) * 4 + b) * 64 + 16 g + l) * 8 + j] = W[cout = 32 (b >> 1) + 8 (l >> 2) + 4 (b & 1) + (l & 3)][cin = 32 s + 8 g + j][tap]
+ *       out may BE residual (same base and stride); out overlapping x is refused (other workgroups read x as halo).
+ *       A halo-tile kernel with the whole weight resident in LDS (120 KB), persistent over 8 x 16-pixel tiles: one workgroup per CU walks
+ *       tiles b, b + grid, ...  max_workgroups > 0 caps the grid (a dispatch override: tests drive the multi-tile walk at tiny shapes);
+ *       0: one workgroup per CU.  The result does not depend on the grid.
+ *       I2V_ERR_INVALID_ARG (nothing launched): null / misaligned operands, cin or cout != 64, a bad stride, out overlapping x, w or (other
+ *       than being it) the residual.  I2V_ERR_UNSUPPORTED: the device refuses the kernel its LDS. */
+typedef struct i2v_conv_c64_params {
+  const void* x;
+  int64_t ldx;
+  const void* w;
+  const void* bias;
+  const void* residual;
+  int64_t ldr;
+  void* out;
+  int64_t ldo;
+  int32_t n_img, height, width;
+  int32_t cin, cout;
+  int32_t relu_mid, relu_out;
+  int32_t max_workgroups;
+} i2v_conv_c64_params;
+int i2v_conv3x3_c64_f16(const i2v_conv_c64_params* p, i2v_stream_t stream);
+/* (ABI 23) AutoencoderTiny's entry mover: src NCHW [n, c, hw] fp32 (src_is_f32) or fp16, c <= 64, through
+ *           I2V_TAESD_PREP_IDENTITY  v                 I2V_TAESD_PREP_UNIT  (v + 1) / 2  (the encoder's input)
+ *           I2V_TAESD_PREP_CLAMP     3 tanh(v / 3)     (the decoder's latent clamp)
+ *       in fp32, to token-major fp16 dst [n, hw, 64] with pixel stride ld_dst (>= 64, a multiple of 8, 16-byte aligned base); channels
+ *       c .. 63 are written as zeros.  I2V_ERR_INVALID_ARG: null / misaligned / overlapping operands, c outside 1..64, an unknown mode. */
+#define I2V_TAESD_PREP_IDENTITY 0
+#define I2V_TAESD_PREP_UNIT 1
+#define I2V_TAESD_PREP_CLAMP 2
+int i2v_taesd_prep_f16(const void* src, int32_t src_is_f32, void* dst, int64_t ld_dst, int32_t n, int32_t c, int32_t hw, int32_t mode,
+                       i2v_stream_t stream);
 
 /* First-frame-similarity prior and the initial add_noise of the sampling loop, pipe:647-656:
  *   prior   = mask * GaussianBlur3x3(cond) + (1 - mask) * cond, mask = (mask_uniform < strength), per frame (pipe:648-654)

@@ -1116,7 +1116,10 @@ class DownBlockMotion(nn.Module):
                                                          padding=downsample_padding, name="op")])
                              if add_downsample else None)
 
-    def _fwd(self, x, temb_act, num_frames):
+    def _fwd(self, x, temb_act, num_frames, additional_residuals=None, residual_scale=None):
+        """additional_residuals (a T2I-Adapter's feature map; diffusers' UNet2DConditionModel adds it to the hidden state a block
+        without cross-attention returns, in place): tokens shaped like that state or with a batch that divides it; the state is also
+        the block's last skip tensor, so both carry the sum.  residual_scale: K.add_broadcast_residual's."""
         states = ()
         for resnet, motion in zip(self.resnets, self.motion_modules):
             x = resnet._fwd(x, temb_act)
@@ -1126,6 +1129,8 @@ class DownBlockMotion(nn.Module):
             for d in self.downsamplers:
                 x = d._fwd(x)
             states += (x,)
+        if additional_residuals is not None:
+            K.add_broadcast_residual(x, additional_residuals, scale=residual_scale, out=x)
         return x, states
 
     def forward(self, hidden_states, temb=None, scale: float = 1.0, num_frames: int = 1):

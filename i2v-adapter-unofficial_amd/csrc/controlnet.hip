@@ -12,6 +12,7 @@
 // dst may be skip (each lane reads its chunk before it writes it, and no other lane touches that chunk).  The scale comes from
 // device memory so that a replayed graph can switch the control on and off over a schedule by its step counter.
 #include "common.h"
+#include "residual_chunk.h"
 
 namespace {
 
@@ -38,25 +39,7 @@ struct ArArgs {
   const int32_t* step_idx;
 };
 
-// one chunk: fp32 arithmetic, one rounding to fp16 (and the rounding's remainder as the new low half).  A product that is exactly
-// zero leaves the skip's bits (and its low half's) as they are: s = 0 switches the control off bit for bit, -0 included.
-template <bool HAS_LO>
-__device__ __forceinline__ void ar_chunk(const f16x8 hi, const f16x8 lo, const f16x8 r, float s, f16x8& out, f16x8& out_lo) {
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const float p = s * (float)r[j];
-    if (HAS_LO) {
-      const float sum = ((float)hi[j] + (float)lo[j]) + p;
-      const f16 h = (f16)sum;
-      const f16 l = (f16)(sum - (float)h);
-      out[j] = p == 0.0f ? hi[j] : h;
-      out_lo[j] = p == 0.0f ? lo[j] : l;
-    } else {
-      out[j] = p == 0.0f ? hi[j] : (f16)((float)hi[j] + p);
-    }
-  }
-}
-
+// (one chunk: ar_chunk, residual_chunk.h -- shared with the T2I-Adapter's broadcast add)
 template <bool HAS_LO>
 __device__ __forceinline__ void ar_tile(const ArTensor& t, int64_t first, float s) {
   f16x8 hi[AR_UNROLL], lo[AR_UNROLL], r[AR_UNROLL];

@@ -334,11 +334,15 @@ def sample_buffers(unet, st):
 
 
 def _refuse_controlnet(pipe, what):
-    """the C handle's plans hold the UNet alone: a pipeline with a ControlNet has a step the plan format cannot describe yet"""
+    """the C handle's plans hold the UNet alone: a pipeline with a ControlNet or a T2I-Adapter has a step the plan format cannot describe
+    yet"""
     if getattr(pipe, "controlnet", None) is not None:
         raise NotImplementedError(f"{what}: a pipeline with a ControlNet is not implemented for the C handle (its step launches a second "
                                   "model whose weights and per-sample buffers the plan does not register); build the pipeline without "
                                   "`controlnet` to export")
+    if getattr(pipe, "t2i_adapter", None) is not None:
+        raise NotImplementedError(f"{what}: a pipeline with a T2I-Adapter is not implemented for the C handle (its step adds per-sample "
+                                  "feature buffers that the plan does not register); build the pipeline without `t2i_adapter` to export")
 
 
 def _step_problem(st):

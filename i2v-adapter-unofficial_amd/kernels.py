@@ -1486,6 +1486,88 @@ def add_residuals(skips, residuals, scale=None, out=None):
     return outs
 
 
+# ---------------------------------------------------------------------------------------------- T2I-Adapter (t2i_adapter.py)
+def pixel_unshuffle8(src):
+    """PixelUnshuffle(8) of [N, C, H, W] fp32 / fp16 images (C = 1 or 3; H, W multiples of 8) -> tokens fp16 [N, H / 8, W / 8, 64 C] in
+    PyTorch's channel order c * 64 + dy * 8 + dx (i2v_pixel_unshuffle8_f16): one rounding."""
+    lib = _lib.load()
+    _req(src, "src", dtype=None)
+    if src.dtype not in (torch.float32, f16) or src.dim() != 4:
+        raise TypeError("src must be a 4-D fp32 / fp16 tensor")
+    n, c, h, w = src.shape
+    if c not in (1, 3) or n < 1 or h < 8 or w < 8 or h % 8 or w % 8:
+        raise ValueError(f"pixel_unshuffle8: src {tuple(src.shape)} must be [N, 1 or 3, H, W] with H and W positive multiples of 8")
+    src = src.contiguous()
+    dst = torch.empty((n, h // 8, w // 8, 64 * c), dtype=f16, device=src.device)
+    _lib.check(lib.i2v_pixel_unshuffle8_f16(_p(src), 1 if src.dtype == torch.float32 else 0, _p(dst), n, c, h, w, _stream()),
+               "i2v_pixel_unshuffle8_f16")
+    return dst
+
+
+def avgpool2x(x):
+    """AvgPool2d(2, stride 2, ceil_mode=True) of tokens [N, H, W, C] (C % 8 == 0) -> [N, ceil(H / 2), ceil(W / 2), C]: a window at the
+    edge of an odd size averages its in-bounds taps (i2v_avgpool2x_f16)."""
+    lib = _lib.load()
+    _req(x, "x")
+    if x.dim() != 4 or not x.is_contiguous() or x.numel() == 0 or x.shape[3] % 8:
+        raise ValueError(f"avgpool2x: x must be a contiguous [N, H, W, C] tensor with C % 8 == 0, got {tuple(x.shape)}")
+    n, h, w, c = x.shape
+    out = torch.empty((n, (h + 1) // 2, (w + 1) // 2, c), dtype=f16, device=x.device)
+    _lib.check(lib.i2v_avgpool2x_f16(_p(x), _p(out), n, h, w, c, _stream()), "i2v_avgpool2x_f16")
+    return out
+
+
+def relu(x, out=None):
+    """max(x, 0) of a contiguous fp16 tensor (numel % 8 == 0); out = x: in place (i2v_relu_f16)."""
+    lib = _lib.load()
+    _req(x, "x")
+    out = torch.empty_like(x) if out is None else _req(out, "out")
+    if not x.is_contiguous() or not out.is_contiguous() or out.shape != x.shape or x.numel() == 0 or x.numel() % 8:
+        raise ValueError(f"relu: x and out must be contiguous tensors of one shape with numel % 8 == 0, got {tuple(x.shape)}")
+    _lib.check(lib.i2v_relu_f16(_p(x), _p(out), x.numel(), _stream()), "i2v_relu_f16")
+    return out
+
+
+def add_broadcast_residual(x, feat, scale=None, out=None):
+    """A T2I-Adapter feature map into the UNet's down path (i2v_add_broadcast_residual_f16): out[i] = x[i] + s * feat[i mod feat.numel()]
+    for contiguous fp16 tensors with x.numel() % feat.numel() == 0 and feat.numel() % 8 == 0 -- `feat` is [N, H, W, C] and `x`
+    [k N, H, W, C]: one copy of the features serves every repetition of the batch.  scale = None (s = 1) or (table fp32 [rows],
+    step_idx int32 [1] or None): s = table[clamp(*step_idx)], read on the device.  out = None: a new tensor; out may be x (in place).
+    An x of the precise residual stream (`lo_of`) is added as hi + lo and the result carries a fresh low half (in place: x's own is
+    rewritten).  Per element the arithmetic, and the bits, are `add_residuals`'."""
+    lib = _lib.load()
+    _req(x, "x")
+    _req(feat, "feat")
+    if not x.is_contiguous() or not feat.is_contiguous():
+        raise ValueError("add_broadcast_residual: x and feat must be contiguous")
+    if feat.numel() == 0 or feat.numel() % 8 != 0 or x.numel() == 0 or x.numel() % feat.numel() != 0:
+        raise ValueError(f"add_broadcast_residual: x has {x.numel()} values and feat {feat.numel()}: feat must hold a positive multiple "
+                         "of 8 values that divides x's")
+    if tuple(x.shape[1:]) != tuple(feat.shape[1:]):
+        raise ValueError(f"add_broadcast_residual: x {tuple(x.shape)} and feat {tuple(feat.shape)} differ behind the batch dimension")
+    table = idx = None
+    if scale is not None:
+        table, idx = scale
+        _req(table, "scale table", dtype=torch.float32)
+        if table.dim() != 1 or table.numel() < 1 or not table.is_contiguous():
+            raise ValueError("add_broadcast_residual: the scale table is a contiguous fp32 vector")
+        if idx is not None:
+            _req(idx, "step_idx", dtype=torch.int32)
+    lo = lo_of(x)
+    if lo is not None and (lo.shape != x.shape or lo.stride() != x.stride() or lo.dtype != f16):
+        raise ValueError("the low half of a stream tensor must be laid out like the tensor")
+    o = torch.empty_like(x) if out is None else _req(out, "out")
+    if o.shape != x.shape or not o.is_contiguous():
+        raise ValueError(f"add_broadcast_residual: out must be contiguous {tuple(x.shape)}")
+    o_lo = None if lo is None else (lo if o is x else torch.empty_like(x))
+    _lib.check(lib.i2v_add_broadcast_residual_f16(_p(x), _p(lo), _p(feat), _p(o), _p(o_lo), x.numel(), feat.numel(), _p(table),
+                                                  0 if table is None else table.numel(), _p(idx), _stream()),
+               "i2v_add_broadcast_residual_f16")
+    if o_lo is not None:
+        o._i2v_lo = o_lo
+    return o
+
+
 _freeinit_ws = {}
 
 

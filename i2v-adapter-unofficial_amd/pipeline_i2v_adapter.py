@@ -80,12 +80,15 @@ class I2VAdapterPipeline:
 
     def __init__(self, vae=None, text_encoder=None, tokenizer=None, unet=None, motion_adapter=None,
                  i2v_adapter=None, scheduler=None, feature_extractor=None,
-                 image_encoder=None, controlnet=None):
+                 image_encoder=None, controlnet=None, t2i_adapter=None):
         if unet is None:
             raise ValueError("`unet` is required")
         if isinstance(controlnet, (list, tuple)):
             raise NotImplementedError("a list of ControlNets (diffusers' MultiControlNetModel) is not implemented: pass one ControlNetModel")
         self.controlnet = controlnet
+        if isinstance(t2i_adapter, (list, tuple)):
+            raise NotImplementedError("a list of T2I-Adapters (diffusers' MultiAdapter) is not implemented: pass one T2IAdapter")
+        self.t2i_adapter = t2i_adapter
         if not isinstance(unet, UNetMotionCrossFrameAttnModel):
             unet = UNetMotionCrossFrameAttnModel.from_unet2d(unet, motion_adapter, i2v_adapter)     # pipe:96
         self.unet = unet
@@ -221,7 +224,7 @@ class I2VAdapterPipeline:
 
     def to(self, device=None, dtype=None):
         """move the models the pipeline holds (pipe:784); fp16 is the storage dtype of the HIP path."""
-        for name in ("unet", "vae", "text_encoder", "image_encoder", "controlnet"):
+        for name in ("unet", "vae", "text_encoder", "image_encoder", "controlnet", "t2i_adapter"):
             m = getattr(self, name)
             if m is not None:
                 setattr(self, name, m.to(device=device, dtype=dtype))
@@ -359,6 +362,10 @@ class I2VAdapterPipeline:
             # reads -- and writes its 12 + 1 residuals; the UNet adds them at this step's row of the scale table
             down, mid = self.controlnet._fwd_tokens(x, K.select_row(st["cn_temb_table"], st["step_idx"]), st["cn_ctx_proj"], st["cn_cond"])
             control = dict(down_residuals=down, mid_residual=mid, residual_scale=(st["cn_scale"], st["step_idx"]))
+        if st.get("t2i_feats") is not None:
+            # the T2I-Adapter's four feature maps were computed once per sample: the step only adds them, at this step's row of the
+            # adapter's scale table (one copy of the features serves both CFG halves)
+            control.update(intrablock_residuals=st["t2i_feats"], intrablock_scale=(st["t2i_scale"], st["step_idx"]))
         # the CFG halves are copies of one tensor at one timestep (pipe:672-673): what does not depend on the prompt is
         # computed once (unet._fwd_tokens, cfg_shared)
         y = unet._fwd_tokens(x, None, True, st.get("ctx_proj") or st["ctx_text"], st["ctx_ip"],
@@ -400,6 +407,9 @@ class I2VAdapterPipeline:
         cn = None
         if st.get("cn_cond") is not None:
             cn = (hash(self.controlnet.weight_signature()), shp(st["cn_cond"]), shp(st["cn_scale"]))
+        # a T2I-Adapter's adds: the features' and the scale table's shapes (the features are static buffers, not launch arguments)
+        if st.get("t2i_feats") is not None:
+            cn = (cn, tuple(shp(t) for t in st["t2i_feats"]), shp(st["t2i_scale"]))
         return (cn, tuple(st["latents"].shape), st["copies"], st["num_frames"], st["guidance"], shp(st["t_table"]),
                 shp(st["ctx_text"]), shp(st["ctx_ip"]), str(st["latents"].device), wsig, ips, precise_stream(),
                 self._scheduler_kind(), shp(st["coef"]), unet.freeu_signature(), shp(st.get("noise")), unet.free_noise_launch_signature())
@@ -419,9 +429,11 @@ class I2VAdapterPipeline:
         if hit is not None:
             graph, gst = hit
             for name in ("latents", "cond", "t_table", "coef", "ctx_text", "ctx_ip", "noise",      # (noise: this sample's LCM draws)
-                         "cn_cond", "cn_scale"):                                                   # (this sample's control frames)
+                         "cn_cond", "cn_scale", "t2i_scale"):                                      # (this sample's control frames)
                 if st.get(name) is not None:
                     gst[name].copy_(st[name])
+            for dst, src in zip(gst.get("t2i_feats") or (), st.get("t2i_feats") or ()):             # (this sample's adapter features)
+                dst.copy_(src)
             gst["step_idx"].zero_()
             self._project_once(gst, into=True)
         else:
@@ -510,6 +522,71 @@ class I2VAdapterPipeline:
         """fp32 [n_steps] on the device: conditioning scale x diffusers' `controlnet_keep` over the executed steps"""
         from .controlnet import controlnet_keep_table
         return torch.tensor(controlnet_keep_table(n_steps, *cn_args), dtype=torch.float32, device=device)
+
+    # ------------------------------------------------------------------------------------------ T2I-Adapter
+    def _check_adapter_args(self, adapter_image, num_frames, scale, factor):
+        """the T2I-Adapter arguments of a call, checked on the host before anything is launched or encoded"""
+        if adapter_image is not None and self.t2i_adapter is None:
+            raise ValueError("`adapter_image` was passed but the pipeline has no `t2i_adapter`: build it with "
+                             "I2VAdapterPipeline(..., t2i_adapter=T2IAdapter.from_pretrained(...))")
+        if self.t2i_adapter is None:
+            return
+        if adapter_image is None:
+            raise ValueError("the pipeline has a `t2i_adapter`: `adapter_image` is required (one control frame per frame of the clip)")
+        from .t2i_adapter import adapter_scale_table
+        adapter_scale_table(1, scale, factor)                          # 0 <= factor <= 1, else ValueError
+        c = self.t2i_adapter.config.in_channels
+        if isinstance(adapter_image, torch.Tensor):
+            if adapter_image.dim() not in (4, 5):
+                raise ValueError(f"`adapter_image` must be [F, {c}, H, W] or [B, F, {c}, H, W], got {tuple(adapter_image.shape)}")
+            if adapter_image.shape[-3] != c:
+                raise ValueError(f"`adapter_image` has {adapter_image.shape[-3]} channels, the adapter's `in_channels` is {c}")
+            n = adapter_image.shape[-4]
+        elif isinstance(adapter_image, (list, tuple)):
+            n = len(adapter_image)
+        else:
+            raise ValueError(f"`adapter_image` must be a list of `num_frames` images or a tensor, got {type(adapter_image)}")
+        if n != num_frames:
+            raise ValueError(f"`adapter_image` holds {n} frames, `num_frames` is {num_frames}: a T2I-Adapter runs per frame and needs one "
+                             "control frame for every frame of the clip")
+
+    def prepare_adapter_image(self, adapter_image, batch_size, num_frames, height, width):
+        """-> fp32 [batch_size * num_frames, in_channels, height, width] in [0, 1] on the host, like `prepare_control_image` (no
+        [-1, 1] normalisation): PIL images are converted to "L" for a 1-channel adapter (canny, sketch) and to "RGB" for a 3-channel
+        one and resized; tensors are taken as they are (they must have that size); one clip of frames is shared by the batch."""
+        c = self.t2i_adapter.config.in_channels
+        if isinstance(adapter_image, torch.Tensor):
+            t = adapter_image.detach().float().cpu()
+            if t.dim() == 4:
+                t = t[None].expand(batch_size, -1, -1, -1, -1)
+            if t.shape[0] != batch_size or t.shape[1] != num_frames:
+                raise ValueError(f"`adapter_image` {tuple(adapter_image.shape)} does not match batch {batch_size} x {num_frames} frames")
+            if t.shape[2] != c:
+                raise ValueError(f"`adapter_image` has {t.shape[2]} channels, the adapter's `in_channels` is {c}")
+            if tuple(t.shape[-2:]) != (height, width):
+                raise ValueError(f"`adapter_image` tensors must already be {height} x {width}, got {tuple(t.shape[-2:])}")
+            return t.reshape(batch_size * num_frames, c, height, width).contiguous()
+        if len(adapter_image) != num_frames:
+            raise ValueError(f"`adapter_image` holds {len(adapter_image)} frames, `num_frames` is {num_frames}")
+        import numpy as np
+        import PIL.Image
+        frames = []
+        for im in adapter_image:
+            if not isinstance(im, PIL.Image.Image):
+                raise ValueError(f"`adapter_image` as a list holds PIL images, got {type(im)}")
+            im = im.convert("L" if c == 1 else "RGB")
+            if im.size != (width, height):
+                im = im.resize((width, height), resample=PIL.Image.LANCZOS)
+            arr = torch.from_numpy(np.asarray(im, dtype=np.float32) / 255.0)
+            frames.append(arr[None] if c == 1 else arr.permute(2, 0, 1))
+        t = torch.stack(frames)
+        return t[None].expand(batch_size, -1, -1, -1, -1).reshape(batch_size * num_frames, c, height, width).contiguous()
+
+    @staticmethod
+    def _adapter_scale_table(n_steps, t2i_args, device):
+        """fp32 [n_steps] on the device: the adapter's scale on the first int(n_steps * factor) executed steps, 0 afterwards"""
+        from .t2i_adapter import adapter_scale_table
+        return torch.tensor(adapter_scale_table(n_steps, *t2i_args), dtype=torch.float32, device=device)
 
     # ------------------------------------------------------------------------------------------ encode_image
     def encode_image(self, image, device, num_images_per_prompt, output_hidden_states=None):
@@ -630,12 +707,16 @@ class I2VAdapterPipeline:
                  prior_mask_generator=None, prior_noise_generator=None, blur_sigma: Optional[float] = None,
                  use_graph: bool = True, precise_stream: Optional[bool] = None, control_image=None,
                  controlnet_conditioning_scale: float = 1.0, control_guidance_start: float = 0.0, control_guidance_end: float = 1.0,
-                 guess_mode: bool = False):
+                 guess_mode: bool = False, adapter_image=None, adapter_conditioning_scale: float = 1.0,
+                 adapter_conditioning_factor: float = 1.0):
         """pipe:537-711 (the arguments the reference's `__call__` takes; `use_graph`, the explicit prior generators and
         `precise_stream` are additions, and so are the ControlNet arguments, which carry the names of diffusers'
         StableDiffusionControlNetPipeline: `control_image` -- `num_frames` PIL images, a [F, 3, H, W] tensor in [0, 1] shared by the
         batch or a [B, F, 3, H, W] tensor in [0, 1] --, `controlnet_conditioning_scale`, and the window
-        `control_guidance_start` .. `control_guidance_end` of the schedule, as fractions, in which the control acts).
+        `control_guidance_start` .. `control_guidance_end` of the schedule, as fractions, in which the control acts; and the
+        T2I-Adapter arguments of diffusers' StableDiffusionAdapterPipeline: `adapter_image` -- as `control_image`, with the adapter's
+        `in_channels` --, `adapter_conditioning_scale`, and `adapter_conditioning_factor`, the fraction of the steps, from the
+        first, on which the adapter's features are added).
         precise_stream: True / False runs THIS call with / without the precise residual stream
         (fp16 hi + lo pairs between the UNet's modules, DESIGN 2.2: closer to the fp32 reference, +2.6 % step time); None keeps the
         process setting (`blocks.set_precise_stream`, I2V_STREAM_PRECISE)."""
@@ -664,6 +745,7 @@ class I2VAdapterPipeline:
         # ControlNet: the arguments, before anything is launched or encoded
         self._check_control_args(control_image, num_frames, controlnet_conditioning_scale, control_guidance_start, control_guidance_end,
                                  guess_mode)
+        self._check_adapter_args(adapter_image, num_frames, adapter_conditioning_scale, adapter_conditioning_factor)
         # FreeNoise (enable_free_noise): the settings against this call's num_frames, before anything is launched or encoded
         fnz = self._free_noise_settings()
         if fnz is not None:
@@ -808,6 +890,13 @@ class I2VAdapterPipeline:
             st["cn_cond"] = K.duplicate_batch(tokens) if copies == 2 else tokens
             st["cn_args"] = (float(controlnet_conditioning_scale), float(control_guidance_start), float(control_guidance_end))
             st["cn_scale"] = self._control_scale_table(len(timesteps), st["cn_args"], dev)
+        if self.t2i_adapter is not None:
+            # once per sample: the adapter's four feature maps of the B * F control frames (ONE copy: the step's add wraps around for
+            # the second CFG half) and the scale table
+            frames = self.prepare_adapter_image(adapter_image, batch_size, num_frames, height, width).to(dev, f16)
+            st["t2i_feats"] = self.t2i_adapter.embed(frames)
+            st["t2i_args"] = (float(adapter_conditioning_scale), float(adapter_conditioning_factor))
+            st["t2i_scale"] = self._adapter_scale_table(len(timesteps), st["t2i_args"], dev)
         if dpm:
             # the previous step's data prediction: the first step of a sample is first order and does not read it
             st["x0_prev"] = torch.empty_like(latents)
@@ -854,6 +943,8 @@ class I2VAdapterPipeline:
             st["coef"] = self.scheduler.step_coefficients(timesteps, eta).to(dev)
             if st.get("cn_cond") is not None:      # the control window over THIS round's schedule (the time table follows t_table)
                 st["cn_scale"] = self._control_scale_table(len(timesteps), st["cn_args"], dev)
+            if st.get("t2i_feats") is not None:    # ... and the adapter's factor over THIS round's number of steps
+                st["t2i_scale"] = self._adapter_scale_table(len(timesteps), st["t2i_args"], dev)
         else:
             timesteps, _ = self.get_timesteps(round_steps[rnd], ratio)
         b, f, c, h, w = prev.shape
@@ -996,6 +1087,16 @@ def build_parser():
                         help="fraction of the schedule at which the control starts to act (0.0)")
     parser.add_argument("--control_guidance_end", type=float, default=1.0, metavar="B",
                         help="fraction of the schedule at which the control stops acting (1.0)")
+    parser.add_argument("--t2i_adapter", type=str, default=None, metavar="PATH",
+                        help="an SD-1.5 T2I-Adapter folder (config.json + diffusion_pytorch_model.safetensors, e.g. "
+                             "t2iadapter_depth_sd15v2): every clip follows the control frames of --adapter_column, at no per-step "
+                             "network cost")
+    parser.add_argument("--adapter_column", type=str, default=None, metavar="COL",
+                        help="the CSV column that holds, per row, a directory of at least num_frames control images (taken in sorted "
+                             "order) or an animated GIF, relative to the CSV")
+    parser.add_argument("--adapter_scale", type=float, default=1.0, metavar="S", help="adapter_conditioning_scale (1.0)")
+    parser.add_argument("--adapter_factor", type=float, default=1.0, metavar="F",
+                        help="adapter_conditioning_factor: the fraction of the steps, from the first, on which the adapter acts (1.0)")
     return parser
 
 
@@ -1050,6 +1151,9 @@ def main(argv=None):
     if (args.controlnet is None) != (args.control_column is None):
         logger.error("--controlnet and --control_column come together.")
         return -1
+    if (args.t2i_adapter is None) != (args.adapter_column is None):
+        logger.error("--t2i_adapter and --adapter_column come together.")
+        return -1
     i2v_adapter = None
     motion_adapter = MotionAdapter.from_pretrained(args.motion_adapter_path)                     # pipe:734
     checkpoint_path = os.path.join(args.checkpoint_root, args.task_name, f"epoch_{args.checkpoint_epoch}")
@@ -1094,8 +1198,14 @@ def main(argv=None):
         controlnet = ControlNetModel.from_pretrained(args.controlnet)
         control_paths = [os.path.join(eval_data_dir, str(p)) for p in eval_data_df[args.control_column]]
         logger.info(f"Successfully loaded ControlNetModel from {args.controlnet}.")
+    t2i_adapter = adapter_paths = None
+    if args.t2i_adapter is not None:
+        from .t2i_adapter import T2IAdapter
+        t2i_adapter = T2IAdapter.from_pretrained(args.t2i_adapter)
+        adapter_paths = [os.path.join(eval_data_dir, str(p)) for p in eval_data_df[args.adapter_column]]
+        logger.info(f"Successfully loaded T2IAdapter from {args.t2i_adapter}.")
     pipe = I2VAdapterPipeline(vae, text_encoder, tokenizer, unet2d.to(device).half(), motion_adapter, i2v_adapter, scheduler,
-                              controlnet=controlnet)
+                              controlnet=controlnet, t2i_adapter=t2i_adapter)
     if "image_embeds" in emb or args.ip_adapter:                                                 # pipe:783
         pipe.load_ip_adapter(args.ip_adapter_path, subfolder="models", weight_name=args.ip_adapter_weight_name)
         if args.ip_adapter_scale is not None:
@@ -1141,6 +1251,9 @@ def main(argv=None):
             control = dict(control_image=load_control_frames(control_paths[ind], args.num_frames),
                            controlnet_conditioning_scale=args.controlnet_scale, control_guidance_start=args.control_guidance_start,
                            control_guidance_end=args.control_guidance_end)
+        if t2i_adapter is not None:
+            control.update(adapter_image=load_control_frames(adapter_paths[ind], args.num_frames),
+                           adapter_conditioning_scale=args.adapter_scale, adapter_conditioning_factor=args.adapter_factor)
         out = pipe(**text, **image, **control,
                    condition_image=condition_images[ind], num_frames=args.num_frames, guidance_scale=args.guidance_scale,
                    num_inference_steps=args.num_inference_steps, frame_similarity_sample_ratio=0.9,

@@ -531,7 +531,7 @@ class UNetAdapterTrainer:
 
     @torch.no_grad()
     def forward(self, sample, timestep, encoder_hidden_states, added_cond_kwargs=None, down_block_additional_residuals=None,
-                mid_block_additional_residual=None):
+                mid_block_additional_residual=None, down_intrablock_additional_residuals=None):
         """sample (B, F, C, H, W) on the GPU; added_cond_kwargs={"image_embeds": ...} when the IP-Adapter is installed (the
         reference's training step passes them, train_image_to_video.py:843); returns the prediction as tokens fp32
         [B * F, H, W, 8] (4 channels + zeros)."""
@@ -539,6 +539,9 @@ class UNetAdapterTrainer:
         if down_block_additional_residuals is not None or mid_block_additional_residual is not None:
             raise NotImplementedError("ControlNet residuals are a sampling-time input: the training step has no backward through "
                                       "i2v_add_residuals_f16 (the reference's training step passes none)")
+        if down_intrablock_additional_residuals is not None:
+            raise NotImplementedError("T2I-Adapter features are a sampling-time input: the training step has no backward through "
+                                      "i2v_add_broadcast_residual_f16 (the reference's training step passes none)")
         if any(fs is not None for fs in u.freeu_signature()):
             raise NotImplementedError("FreeU (enable_freeu) is a sampling-time switch: the training step has no backward of "
                                       "i2v_freeu_f16 -- call unet.disable_freeu() before training")

@@ -66,9 +66,13 @@ class CrossFrameAttnDownBlockMotion(nn.Module):
                                                          padding=downsample_padding, name="op")])
                              if add_downsample else None)
 
-    def _fwd(self, x, temb_act, enable, ctx_text, ctx_ip, num_frames, additional_residuals=None, cfg_shared=False):
+    def _fwd(self, x, temb_act, enable, ctx_text, ctx_ip, num_frames, additional_residuals=None, cfg_shared=False,
+             residual_scale=None):
         """cfg_shared (first down block only, unet._fwd_tokens): x is ONE of the two identical CFG halves; the first resnet
-        and the prompt-independent stage of the first transformer run on it, the outputs carry both halves."""
+        and the prompt-independent stage of the first transformer run on it, the outputs carry both halves.
+        additional_residuals (unet:329-330; a T2I-Adapter's feature map): tokens shaped like the last layer's output, or with a
+        batch that divides it (one copy serves every repetition, K.add_broadcast_residual); residual_scale = (fp32 table, int32 step
+        counter) on the device, or None for scale 1."""
         states = ()
         n_layers = len(self.resnets)
         for i, (resnet, attn, motion) in enumerate(zip(self.resnets, self.attentions, self.motion_modules)):
@@ -77,7 +81,7 @@ class CrossFrameAttnDownBlockMotion(nn.Module):
             x = attn._fwd(x, enable, num_frames, ctx_text, ctx_ip, cfg_expand=shared)   # unet:313-322
             x = motion._fwd(x, num_frames)                                            # unet:323-326
             if i == n_layers - 1 and additional_residuals is not None:                # unet:329-330
-                x, = K.add_residuals([x], [additional_residuals])
+                x = K.add_broadcast_residual(x, additional_residuals, scale=residual_scale)
             states += (x,)
         if self.downsamplers is not None:                                             # unet:334-338
             for d in self.downsamplers:
@@ -796,16 +800,25 @@ class UNetMotionCrossFrameAttnModel(UNetLoraMixin, PretrainedMixin, HipModule):
         return K.gemm(K.silu(temb), wt, bt, out=out)
 
     def _fwd_tokens(self, x, temb, enable_cross_frame_attn, ctx_text, ctx_ip, num_frames, cfg_shared=False, temb_proj=None,
-                    forward_upsample_size=False, down_residuals=None, mid_residual=None, residual_scale=None):
+                    forward_upsample_size=False, down_residuals=None, mid_residual=None, residual_scale=None,
+                    intrablock_residuals=None, intrablock_scale=None):
         """x: model-input tokens [B*F, H, W, cin_pad] fp16; temb [B, 4*C0] fp16 (pre-SiLU) -- or temb_proj [B or 1, sum Cout]:
         the resnets' time-embedding projections already computed (project_time_table); ctx_text [B, Lt, D]
         (+ ctx_ip [B, 4, D]) or a ProjectedContext; returns noise-prediction tokens [B*F, H, W, out_channels].
         down_residuals / mid_residual (a ControlNet's outputs, unet:1299-1300): token tensors shaped like the skip tensors (full
         batch, also under cfg_shared) and like the mid block's output; residual_scale = (fp32 table, int32 step counter) on the
-        device, or None for scale 1 (K.add_residuals)."""
+        device, or None for scale 1 (K.add_residuals).
+        intrablock_residuals (a T2I-Adapter's features, diffusers' down_intrablock_additional_residuals): one token tensor per down
+        block, [n, h, w, C] of that block's level with n dividing the full batch (also under cfg_shared); intrablock_scale as
+        residual_scale.  A block with cross-attention adds its tensor to the output of its last layer, before that is recorded as a
+        skip tensor and before the down-sampler (unet:329-330); a block without adds it to the hidden state it returns, in place --
+        which is also its last skip tensor and, for the last block, the mid block's input."""
         if self._free_noise is not None:
             from .free_noise import check_num_frames
             check_num_frames(num_frames, self._free_noise)
+        if intrablock_residuals is not None:
+            intrablock_residuals = list(intrablock_residuals)
+            self._check_intrablock_residuals(intrablock_residuals, tuple(x.shape))
         p = self.packed()
         wt, bt, slices = self._temb_pack()
         # ResnetBlock2D: time_emb_proj(nonlinearity(temb)) of all 22 resnets in one GEMM
@@ -825,11 +838,12 @@ class UNetMotionCrossFrameAttnModel(UNetLoraMixin, PretrainedMixin, HipModule):
         x = K.conv3x3(x, p["w_in"], p["b_in"], precise=precise_stream())                # unet:1359
         res = (K.duplicate_batch(x) if cfg_shared else x,)
         for bi, blk in enumerate(self.down_blocks):                                     # unet:1362-1377
+            feat = None if intrablock_residuals is None else intrablock_residuals[bi]
             if getattr(blk, "has_cross_attention", False):
-                x, r = blk._fwd(x, temb_act, enable_cross_frame_attn, ctx_text, ctx_ip, num_frames,
-                                cfg_shared=cfg_shared and bi == 0)
+                x, r = blk._fwd(x, temb_act, enable_cross_frame_attn, ctx_text, ctx_ip, num_frames, additional_residuals=feat,
+                                cfg_shared=cfg_shared and bi == 0, residual_scale=intrablock_scale)
             else:
-                x, r = blk._fwd(x, temb_act, num_frames)
+                x, r = blk._fwd(x, temb_act, num_frames, additional_residuals=feat, residual_scale=intrablock_scale)
             res += r
         if down_residuals is not None:                                                  # unet:1379-1389
             if len(down_residuals) != len(res):
@@ -855,6 +869,24 @@ class UNetMotionCrossFrameAttnModel(UNetLoraMixin, PretrainedMixin, HipModule):
         # by up to 2 * guidance - 1, and the reference returns `sample`'s dtype (fp32 latents in its driver)
         return K.conv3x3(x, p["w_out"], p["b_out"], out_f32=True)                       # unet:1439-1443
 
+    def _check_intrablock_residuals(self, feats, x_shape):
+        """one tensor per down block, each [n, h, w, C] of the level where its block adds it, n dividing the batch; `x_shape`: the
+        model-input tokens [batch, H, W, cin_pad].  ValueError naming the level otherwise (before anything is launched)."""
+        if len(feats) != len(self.down_blocks):
+            raise ValueError(f"down_intrablock_additional_residuals: {len(feats)} tensors for {len(self.down_blocks)} down blocks "
+                             "(one per block)")
+        batch, hh, ww = x_shape[0], x_shape[1], x_shape[2]
+        for i, (blk, t) in enumerate(zip(self.down_blocks, feats)):
+            if not getattr(blk, "has_cross_attention", False) and blk.downsamplers is not None:
+                hh, ww = (hh + 1) // 2, (ww + 1) // 2          # (a block without cross-attention adds behind its down-sampler)
+            want = (hh, ww, self.config.block_out_channels[i])
+            if not isinstance(t, torch.Tensor) or t.dim() != 4 or tuple(t.shape[1:]) != want or t.shape[0] < 1 or batch % t.shape[0]:
+                got = tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__
+                raise ValueError(f"down_intrablock_additional_residuals: level {i} takes (n, height {want[0]}, width {want[1]}, "
+                                 f"channels {want[2]}) with n dividing the batch {batch}, got tokens {got}")
+            if getattr(blk, "has_cross_attention", False) and blk.downsamplers is not None:
+                hh, ww = (hh + 1) // 2, (ww + 1) // 2
+
     def _embed_time(self, timesteps_f32, t_index=None):
         """Timesteps -> TimestepEmbedding (unet:1336-1343); one row per sample (the per-frame repeat of unet:1344
         is index arithmetic in the conv epilogue)."""
@@ -876,8 +908,10 @@ class UNetMotionCrossFrameAttnModel(UNetLoraMixin, PretrainedMixin, HipModule):
                 timestep_cond=None, attention_mask=None, cross_attention_kwargs: Optional[Dict[str, Any]] = None,
                 added_cond_kwargs: Optional[Dict[str, torch.Tensor]] = None,
                 down_block_additional_residuals=None, mid_block_additional_residual=None,
-                return_dict: bool = True):
+                return_dict: bool = True, down_intrablock_additional_residuals=None):
         """unet:1289-1451.  sample (B, F, C, H, W) -> noise prediction (B, F, C, H, W) in sample's dtype.
+        `down_intrablock_additional_residuals` (diffusers' UNet2DConditionModel argument, a T2I-Adapter's output): one NCHW tensor per
+        down block, (n, C_i, h_i, w_i) with n = B * F or a divisor of it (see _fwd_tokens).
         `cross_attention_kwargs={"scale": s}`: the global LoRA scale of this call (lora.py).
         `cross_attention_kwargs={"cfg_shared_prefix": True}` (an addition; the reference ignores the dict on this path): the
         caller asserts that sample[B/2:] == sample[:B/2] and that all timesteps are equal -- the classifier-free-guidance
@@ -890,12 +924,22 @@ class UNetMotionCrossFrameAttnModel(UNetLoraMixin, PretrainedMixin, HipModule):
                 return self.forward(sample, timestep, enable_cross_frame_attn, encoder_hidden_states, timestep_cond=timestep_cond,
                                     attention_mask=attention_mask, cross_attention_kwargs=rest, added_cond_kwargs=added_cond_kwargs,
                                     down_block_additional_residuals=down_block_additional_residuals,
-                                    mid_block_additional_residual=mid_block_additional_residual, return_dict=return_dict)
+                                    mid_block_additional_residual=mid_block_additional_residual, return_dict=return_dict,
+                                    down_intrablock_additional_residuals=down_intrablock_additional_residuals)
             finally:
                 self.set_lora_scale(prev)
         self._sync_lora()      # (a LoRA change since the last call: merge before any weight or pack is read)
         if attention_mask is not None:
             raise NotImplementedError("attention masks are never passed on the hot path (SURVEY 8b)")
+        intra = down_intrablock_additional_residuals
+        if intra is not None and sample.dim() == 5:      # the adapter's features: checked on the host, before anything is launched
+            intra = list(intra)
+            for i, t in enumerate(intra):
+                if not isinstance(t, torch.Tensor) or t.dim() != 4:
+                    raise ValueError(f"down_intrablock_additional_residuals: level {i} must be a (n, channels, height, width) tensor, got "
+                                     f"{tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__}")
+            self._check_intrablock_residuals([t.permute(0, 2, 3, 1) for t in intra],
+                                             (sample.shape[0] * sample.shape[1],) + tuple(sample.shape[3:]))
         if not sample.is_cuda:
             raise HipLibraryError(f"sample is on {sample.device}: the HIP path has no CPU fallback")
         if sample.dim() != 5:
@@ -926,8 +970,11 @@ class UNetMotionCrossFrameAttnModel(UNetLoraMixin, PretrainedMixin, HipModule):
             down_res = [K.nchw_to_tokens(r) for r in down_block_additional_residuals]
         if mid_block_additional_residual is not None:
             mid_res = K.nchw_to_tokens(mid_block_additional_residual)
+        if intra is not None:
+            intra = [K.nchw_to_tokens(t) for t in intra]
         y = self._fwd_tokens(x, temb, enable_cross_frame_attn, ctx_text, ctx_ip, num_frames, cfg_shared=cfg_shared,
-                             forward_upsample_size=forward_upsample_size, down_residuals=down_res, mid_residual=mid_res)
+                             forward_upsample_size=forward_upsample_size, down_residuals=down_res, mid_residual=mid_res,
+                             intrablock_residuals=intra)
         out_dt = sample.dtype if sample.dtype in (torch.float32, f16) else f16
         out = K.tokens_to_nchw(y, dtype=out_dt).reshape(b, num_frames, -1, hh, ww)        # unet:1446
         if not return_dict:

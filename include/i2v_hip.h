@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define I2V_ABI_VERSION 23
+#define I2V_ABI_VERSION 24
 
 #define I2V_OK 0
 #define I2V_ERR_INVALID_ARG (-1)
@@ -852,6 +852,36 @@ int i2v_conv3x3_c64_f16(const i2v_conv_c64_params* p, i2v_stream_t stream);
 #define I2V_TAESD_PREP_CLAMP 2
 int i2v_taesd_prep_f16(const void* src, int32_t src_is_f32, void* dst, int64_t ld_dst, int32_t n, int32_t c, int32_t hw, int32_t mode,
                        i2v_stream_t stream);
+
+/* (ABI 24) T2I-Adapter (diffusers 0.24 `T2IAdapter`, adapter_type "full_adapter"; t2i_adapter.py).  The adapter reads the control frames
+ * only -- never the latents or the timestep -- so its network runs once per sample and a denoising step adds four stored feature maps to the
+ * UNet's down path (down_intrablock_additional_residuals; the hook of unet:329-330).  Three movers of the once-per-sample network and the
+ * per-step add.  All four: 16 bytes per lane and access, a capped grid that strides, no workspace, nothing allocated.
+ *
+ * PixelUnshuffle(8): src NCHW [n, c, h, w] fp32 (src_is_f32) or fp16, c = 1 or 3, h and w multiples of 8 -> tokens fp16
+ *       dst [n, h / 8, w / 8, 64 c] with PyTorch's channel order c * 64 + dy * 8 + dx; one rounding (fp32 -> fp16), none for fp16.
+ *       I2V_ERR_INVALID_ARG: null / misaligned (16 bytes) / overlapping operands, c not 1 or 3, h or w no positive multiple of 8. */
+int i2v_pixel_unshuffle8_f16(const void* src, int32_t src_is_f32, void* dst, int32_t n, int32_t c, int32_t h, int32_t w, i2v_stream_t stream);
+/* AvgPool2d(2, stride 2, ceil_mode=True) on tokens: src fp16 [n, h, w, c] -> dst fp16 [n, ceil(h / 2), ceil(w / 2), c], c % 8 == 0.  A window
+ *       at the edge of an odd size holds 2 taps or 1 and divides by that count: fp32 sum of the in-bounds taps times 1, 1/2 or 1/4, one
+ *       rounding.  I2V_ERR_INVALID_ARG: null / misaligned / overlapping operands, a size < 1, c no positive multiple of 8. */
+int i2v_avgpool2x_f16(const void* src, void* dst, int32_t n, int32_t h, int32_t w, int32_t c, i2v_stream_t stream);
+/* dst = max(src, 0), fp16, numel % 8 == 0; dst may be src (in place) and may not overlap it otherwise. */
+int i2v_relu_f16(const void* src, void* dst, int64_t numel, i2v_stream_t stream);
+/* The per-step add:   dst[i] = x[i] + s * feat[i mod feat_numel],     s = scale_table[min(max(step_idx[0], 0), scale_rows - 1)]
+ *       x, dst fp16 [numel], feat fp16 [feat_numel], numel % feat_numel == 0, feat_numel % 8 == 0: one copy of the features serves every
+ *       repetition of the batch (both classifier-free-guidance halves).  scale_table fp32 [scale_rows] and step_idx (one int32) are DEVICE
+ *       memory, read by the kernel (a captured launch follows a scale schedule by the step counter); step_idx NULL: row 0; scale_table
+ *       NULL: s = 1.  dst may be x (in place); dst may not overlap feat.
+ *       Per element the arithmetic is i2v_add_residuals_f16's, and the results are bit-equal to it on feat repeated numel / feat_numel
+ *       times: fp32, one rounding to fp16; where s * feat is exactly zero x's bits are kept (-0 included); with x_lo / dst_lo (both or
+ *       neither: the precise residual stream) the sum is (x + x_lo) + s * feat, dst = rn16(sum), dst_lo = rn16(sum - dst).
+ *       Grid: at most 2048 workgroups of 256 lanes stride over 16 KB tiles, four independent accesses per lane in flight; the wrap point of
+ *       feat is chunk-aligned, so no 16-byte access straddles it.
+ *       I2V_ERR_INVALID_ARG (nothing launched): a null x / feat / dst, x_lo and dst_lo not both given or both null, numel no multiple of
+ *       feat_numel, feat_numel no positive multiple of 8, a pointer not 16-byte aligned, dst overlapping feat, scale_table with scale_rows < 1. */
+int i2v_add_broadcast_residual_f16(const void* x, const void* x_lo, const void* feat, void* dst, void* dst_lo, int64_t numel, int64_t feat_numel,
+                                   const float* scale_table, int32_t scale_rows, const int32_t* step_idx, i2v_stream_t stream);
 
 /* First-frame-similarity prior and the initial add_noise of the sampling loop, pipe:647-656:
  *   prior   = mask * GaussianBlur3x3(cond) + (1 - mask) * cond, mask = (mask_uniform < strength), per frame (pipe:648-654)

@@ -363,7 +363,8 @@ class ControlNetModel(PretrainedMixin, HipModule):
         return [m for name, m in self.named_modules() if isinstance(m, Attention) and name.endswith("attn2")]
 
     def project_context(self, ctx_text, out: Optional[ProjectedContext] = None) -> ProjectedContext:
-        """K / V^T of the text context for the ControlNet's own attn2 layers, once per sample; `out`: a previous result whose buffers
+        """K / V^T of the text context (one per sample, or one per frame with prompt travel) for the ControlNet's own attn2 layers, once
+        per sample; `out`: a previous result whose buffers
         are overwritten in place (a captured graph keeps reading the same memory)."""
         pc = out if out is not None else ProjectedContext(ctx_text, None)
         if out is not None:
@@ -386,7 +387,8 @@ class ControlNetModel(PretrainedMixin, HipModule):
     # ------------------------------------------------------------------ forward
     def _fwd_tokens(self, x, temb_proj, ctx, cond_tokens, out_scale: float = 1.0):
         """x: model-input tokens [N, H, W, cin_pad] fp16; temb_proj [B or 1, sum Cout] (project_time_table rows); ctx [B, Lt, D] or a
-        ProjectedContext of THIS model (N % B == 0: the frames of a clip share a prompt); cond_tokens [N, H, W, C0]
+        ProjectedContext of THIS model (N % B == 0: the frames of a clip share a prompt; B = N with prompt travel, one context per frame
+        in the order of the token rows); cond_tokens [N, H, W, C0]
         (embed_condition).  Returns (12 down tensors, mid tensor), token-major fp16, each times out_scale."""
         p = self.packed()
         _, _, slices = self._temb_pack()

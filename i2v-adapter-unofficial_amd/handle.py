@@ -345,6 +345,17 @@ def _refuse_controlnet(pipe, what):
                                   "feature buffers that the plan does not register); build the pipeline without `t2i_adapter` to export")
 
 
+def _refuse_per_frame_context(st, what):
+    """prompt travel (one text context per frame, `st["ctx_text"]` of copies * B * F rows) changes the shape of the plan's context slot
+    and of every per-sample K / V^T buffer: the plan format describes one context per sample"""
+    b, f = st["latents"].shape[:2]
+    ctx = st.get("ctx_text")
+    if ctx is not None and f > 1 and ctx.shape[0] == st["copies"] * b * f:
+        raise NotImplementedError(f"{what}: per-frame text contexts (prompt travel: {ctx.shape[0]} context rows for {st['copies'] * b} "
+                                  "samples) are not implemented for the C handle (its plans hold one context per sample); pass one "
+                                  "prompt per sample to export")
+
+
 def _step_problem(st):
     b, f, _c, hh, ww = st["latents"].shape
     return (st["copies"] * b, f, hh, ww, st["ctx_text"].shape[1], int(st["ctx_ip"] is not None))
@@ -361,6 +372,7 @@ def record_step_plan(pipe, st):
     With an LCMScheduler the step ends in i2v_lcm_cfg_step: STEP_COEF is fp32 [T, 6] and STEP_NOISE (the same slot) fp32
     [T - 1, B, F, C, H, W] (= st["noise"], read only: `LCMScheduler.step_noise`; absent for a single-step schedule)."""
     _refuse_controlnet(pipe, "record_step_plan")
+    _refuse_per_frame_context(st, "record_step_plan")
     if pipe._scheduler_kind() == "lcm":
         noise = st.get("noise")
         keep_lcm = (st["latents"].clone(), st["step_idx"].clone())
@@ -399,6 +411,7 @@ def record_prepare_plan(pipe, st, image_embeds=None):
     time_emb_proj of every timestep of the schedule (unet:1336-1343) written into `temb_table` -- as a launch plan.
     io: PREP_CONTEXT fp16 [2 B, L, D] (= st["ctx_text"]), PREP_TIMESTEPS fp32 [T] (= st["t_table"]), PREP_IMAGE_EMBEDS fp16 [2 B, clip]."""
     _refuse_controlnet(pipe, "record_prepare_plan")
+    _refuse_per_frame_context(st, "record_prepare_plan")
     unet = pipe.unet
     io = {PREP_CONTEXT: st["ctx_text"], PREP_TIMESTEPS: st["t_table"]}
     if image_embeds is not None:
@@ -540,7 +553,7 @@ class UNetHandle:
 
 # ---- export for a host without Python: everything tests/c_host/denoise_host.c (or a service of the reader's own) loads
 def export_denoiser(pipe, out_dir, *, num_frames, latent_height, latent_width, batch=1, ctx_len=77, clip_dim=None,
-                    num_inference_steps=25, guidance_scale=7.5):
+                    num_inference_steps=25, guidance_scale=7.5, per_frame_context=False):
     """Writes the reference's denoising loop (pipe:663-700) for ONE problem size as files a C host runs through `i2v_unet_run`:
         prepare.plan   once per sample (`record_prepare_plan`)       step.plan   once per DDIM step (`record_step_plan`)
         weights.bin    every buffer the two plans name (`save_weights`: model weights by state-dict key / `<module>#<pack>`, per-sample
@@ -548,8 +561,12 @@ def export_denoiser(pipe, out_dir, *, num_frames, latent_height, latent_width, b
         manifest.json  the problem, the io slots of both plans with their dtypes and shapes, the schedule's tables (timesteps,
                        DDIM coefficients) and the values baked into the step (guidance scale, CFG copies, table length)
     `pipe`: an `I2VAdapterPipeline` on the GPU (its UNet with or without the IP-Adapter: clip_dim = the image embeds' width, None
-    without).  Returns the manifest.  A plan holds for this size, these switches and this library build."""
+    without).  Returns the manifest.  A plan holds for this size, these switches and this library build.
+    per_frame_context (prompt travel: one text context per frame) is refused: the plans hold one context per sample."""
     _refuse_controlnet(pipe, "export_denoiser")
+    if per_frame_context:
+        raise NotImplementedError("export_denoiser: per-frame text contexts (prompt travel) are not implemented for the C handle (its "
+                                  "plans and the C host's inputs file hold one context per sample)")
     import json
     import os
     unet = pipe.unet

@@ -1568,6 +1568,71 @@ def add_broadcast_residual(x, feat, scale=None, out=None):
     return o
 
 
+# ---------------------------------------------------------------------------------------------- prompt travel (pipeline)
+def interp_rows(src, lo, hi, w, out=None):
+    """out[r] = (1 - w[r]) * src[lo[r]] + w[r] * src[hi[r]] (i2v_interp_rows_f16): the per-frame text contexts of prompt travel from the
+    keyframes' embeddings, and with w = 0 a row gather.  src fp16 [n_src, ...] (a row = everything behind the leading dimension,
+    contiguous, a multiple of 8 values; the leading stride is free); lo, hi (ints) and w (floats) are HOST sequences of one length
+    n_out: they are range-checked here -- 0 <= lo, hi < n_src, 0 <= w <= 1 -- and uploaded (the C entry cannot check device tables).
+    out: fp16 [n_out, ...] of src's row shape (leading stride free), not overlapping src; None: a new contiguous tensor.
+    fp32 arithmetic, one rounding; w == 0 / w == 1 copy a row bit for bit and never read the other one."""
+    lib = _lib.load()
+    _req(src, "src")
+    if src.dim() < 2 or src.shape[0] < 1:
+        raise ValueError(f"interp_rows: src must be [n_src, ...] with n_src >= 1, got {tuple(src.shape)}")
+    row = tuple(src.shape[1:])
+    e = 1
+    for s in row:
+        e *= s
+
+    def rows_of(t, name):
+        if tuple(t.shape[1:]) != row or not t[0].is_contiguous():
+            raise ValueError(f"interp_rows: {name} must be [n, {', '.join(map(str, row))}] with contiguous rows, got {tuple(t.shape)} "
+                             f"with strides {t.stride()}")
+        ld = t.stride(0) if t.shape[0] > 1 else max(t.stride(0), e)
+        if ld < e or ld % 8:
+            raise ValueError(f"interp_rows: the row stride {ld} of {name} must be a multiple of 8 and at least the row length {e}")
+        return ld
+    if e < 8 or e % 8:
+        raise ValueError(f"interp_rows: a row holds {e} values, not a positive multiple of 8")
+    ld_src = rows_of(src, "src")
+    lo_t = torch.as_tensor(lo).reshape(-1)
+    hi_t = torch.as_tensor(hi).reshape(-1)
+    w_t = torch.as_tensor(w, dtype=torch.float32).reshape(-1)
+    if lo_t.is_cuda or hi_t.is_cuda or w_t.is_cuda:
+        raise ValueError("interp_rows: lo, hi and w are host tables (they are checked before the upload)")
+    n_out = lo_t.numel()
+    if n_out < 1 or hi_t.numel() != n_out or w_t.numel() != n_out:
+        raise ValueError(f"interp_rows: lo, hi and w must have one length >= 1, got {lo_t.numel()}, {hi_t.numel()}, {w_t.numel()}")
+    if lo_t.is_floating_point() or hi_t.is_floating_point() or lo_t.dtype == torch.bool or hi_t.dtype == torch.bool:
+        raise TypeError("interp_rows: lo and hi must hold integers")
+    n_src = src.shape[0]
+    for name, t in (("lo", lo_t), ("hi", hi_t)):
+        bad = ((t < 0) | (t >= n_src)).nonzero()
+        if bad.numel():
+            r = int(bad[0])
+            raise ValueError(f"interp_rows: {name}[{r}] = {int(t[r])} is outside src's {n_src} rows")
+    bad = (~((w_t >= 0) & (w_t <= 1))).nonzero()
+    if bad.numel():
+        r = int(bad[0])
+        raise ValueError(f"interp_rows: w[{r}] = {float(w_t[r])} is outside [0, 1]")
+    if out is None:
+        out = torch.empty((n_out,) + row, dtype=f16, device=src.device)
+    _req(out, "out")
+    if out.dim() != src.dim() or out.shape[0] != n_out or out.device != src.device:
+        raise ValueError(f"interp_rows: out must be [{n_out}, ...] on src's device, got {tuple(out.shape)}")
+    ld_out = rows_of(out, "out")
+    a0, a1 = src.data_ptr(), src.data_ptr() + ((n_src - 1) * ld_src + e) * 2
+    b0, b1 = out.data_ptr(), out.data_ptr() + ((n_out - 1) * ld_out + e) * 2
+    if a0 < b1 and b0 < a1:
+        raise ValueError("interp_rows: out must not overlap src")
+    dev = src.device
+    lo_d, hi_d, w_d = lo_t.to(torch.int32).to(dev), hi_t.to(torch.int32).to(dev), w_t.to(dev)
+    _lib.check(lib.i2v_interp_rows_f16(_p(src), ld_src, n_src, _p(lo_d), _p(hi_d), _p(w_d), _p(out), ld_out, n_out, e, _stream()),
+               "i2v_interp_rows_f16")
+    return out
+
+
 _freeinit_ws = {}
 
 

@@ -694,6 +694,95 @@ class I2VAdapterPipeline:
             negative_prompt_embeds = negative_prompt_embeds.view(batch_size * num_images_per_prompt, seq_len, -1)
         return prompt_embeds, negative_prompt_embeds
 
+    # ------------------------------------------------------------------------------------------ prompt travel
+    def _encode_texts(self, texts, clip_skip=None):
+        """[len(texts), L, D]: the text encoder's embeddings of a list of strings in ONE call, as `encode_prompt` makes them (padding to
+        `model_max_length`, truncation, `clip_skip` through the final LayerNorm)"""
+        if self.text_encoder is None or self.tokenizer is None:
+            raise ValueError("encoding a `prompt` needs both a `text_encoder` and a `tokenizer`: build the pipeline with them, or pass "
+                             "`prompt_embeds` (and `negative_prompt_embeds`)")
+        if getattr(self.text_encoder.config, "use_attention_mask", None):
+            raise NotImplementedError("text_encoder.config.use_attention_mask: padding attention masks are not implemented")
+        ids = self.tokenizer(texts, padding="max_length", max_length=self.tokenizer.model_max_length, truncation=True,
+                             return_tensors="pt").input_ids
+        if clip_skip is None:
+            return self.text_encoder(ids, attention_mask=None)[0]
+        hidden = self.text_encoder(ids, attention_mask=None, output_hidden_states=True)[-1][-(clip_skip + 1)]
+        return self.text_encoder.text_model.final_layer_norm(hidden)
+
+    def encode_prompt_travel(self, prompt, num_frames, device, num_videos_per_prompt, do_classifier_free_guidance, negative_prompt=None,
+                             clip_skip=None, interpolation_callback=None):
+        """Prompt travel (diffusers AnimateDiffFreeNoiseMixin `_encode_prompt_free_noise`): `prompt` and `negative_prompt` are each a
+        str, a keyframe dict {frame: text} (keys ints, the first 0, the last < num_frames; the last prompt is held to the end of the
+        clip) or a list of either with one entry per sample.  Returns (prompt_embeds, negative_prompt_embeds), each
+        [B * num_videos_per_prompt, num_frames, L, D] -- one context per frame; the second is None without classifier-free guidance.
+        Every keyframe text of the batch, negative ones included, goes through the text encoder in ONE call (K rows), and ONE
+        `K.interp_rows` launch makes all frames: frame f between the keyframes s < e gets (1 - w) E_s + w E_e with
+        w = float32(linspace(0, 1, e - s + 1)[f - s]); a keyframe's own frame is its embedding bit for bit.
+        interpolation_callback(start_frame, end_frame, start_embeds [L, D], end_embeds [L, D]) -> [end - start + 1, L, D] replaces the
+        linear rule for that segment (diffusers' `prompt_interpolation_callback`; as there, a later segment's first row overwrites the
+        shared keyframe's)."""
+        from . import prompt_travel as PT
+        if isinstance(prompt, (list, tuple)):
+            batch = len(prompt)
+        elif isinstance(negative_prompt, (list, tuple)):
+            batch = len(negative_prompt)
+        else:
+            batch = 1
+        if batch < 1:
+            raise ValueError("`prompt` is an empty list")
+        if prompt is None:
+            raise ValueError("`prompt` is required")
+        groups = [PT.per_sample_keyframes(prompt, batch, num_frames, "prompt")]
+        if do_classifier_free_guidance:
+            neg = "" if negative_prompt is None else negative_prompt
+            groups.insert(0, PT.per_sample_keyframes(neg, batch, num_frames, "negative_prompt"))
+        # the source rows: [negative keyframes of sample 0, 1, ... ; positive keyframes of sample 0, 1, ...], each sample's sorted by frame
+        texts, keyframes = [], []
+        for g in groups:
+            for d in g:
+                keys = sorted(d)
+                keyframes.append(keys)
+                texts.extend(d[k] for k in keys)
+        dtype = self.text_encoder.dtype if self.text_encoder is not None else f16
+        src = self._encode_texts(texts, clip_skip).to(device=device, dtype=dtype).contiguous()
+        if src.dtype != f16:
+            raise HipLibraryError(f"prompt travel interpolates fp16 embeddings (i2v_interp_rows_f16), the text encoder gives {src.dtype}")
+        lo, hi, w, n_src = PT.batch_tables(keyframes, num_frames, repeats=num_videos_per_prompt)
+        if interpolation_callback is not None:
+            # a segment's rows as the callback gives them: appended to the source, gathered with w = 0
+            extra, base, row = [], 0, 0
+            for keys in keyframes:
+                for i, (s, e) in enumerate(zip(keys[:-1], keys[1:])):
+                    seg = interpolation_callback(s, e, src[base + i], src[base + i + 1])
+                    if not isinstance(seg, torch.Tensor) or tuple(seg.shape) != (e - s + 1,) + tuple(src.shape[1:]):
+                        raise ValueError(f"interpolation_callback({s}, {e}, ...) must return a tensor {(e - s + 1,) + tuple(src.shape[1:])}, "
+                                         f"got {tuple(seg.shape) if isinstance(seg, torch.Tensor) else type(seg).__name__}")
+                    extra.append(seg.to(device=device, dtype=f16))
+                    first = n_src + sum(t.shape[0] for t in extra[:-1])
+                    for rep in range(num_videos_per_prompt):
+                        r0 = row + rep * num_frames
+                        lo[r0 + s: r0 + e + 1] = hi[r0 + s: r0 + e + 1] = range(first, first + e - s + 1)
+                        w[r0 + s: r0 + e + 1] = 0.0
+                base += len(keys)
+                row += num_videos_per_prompt * num_frames
+            if extra:
+                src = torch.cat([src] + extra).contiguous()
+        out = K.interp_rows(src, lo, hi, w).view(len(groups), batch * num_videos_per_prompt, num_frames, *src.shape[1:])
+        return (out[1], out[0]) if do_classifier_free_guidance else (out[0], None)
+
+    def _per_frame_embeds(self, embeds, num_frames, name):
+        """`embeds` as per-frame contexts [B, num_frames, L, D] fp16 on the UNet's device: a 4-D tensor as it is (its frame count
+        checked), a 3-D one [B, L, D] repeated for every frame (the w = 0 gather of K.interp_rows)"""
+        if embeds.dim() == 4:
+            if embeds.shape[1] != num_frames:
+                raise ValueError(f"`{name}` is [B, F, L, D] = {tuple(embeds.shape)} with F = {embeds.shape[1]} per-frame contexts, "
+                                 f"`num_frames` is {num_frames}")
+            return embeds.to(self.unet.device, f16).contiguous()
+        src = embeds.to(self.unet.device, f16).contiguous()
+        rows = torch.arange(src.shape[0]).repeat_interleave(num_frames)
+        return K.interp_rows(src, rows, rows, torch.zeros(rows.numel())).view(src.shape[0], num_frames, *src.shape[1:])
+
     # ------------------------------------------------------------------------------------------ __call__
     @torch.no_grad()
     def __call__(self, prompt=None, condition_image=None, num_frames: Optional[int] = 16,
@@ -717,6 +806,10 @@ class I2VAdapterPipeline:
         T2I-Adapter arguments of diffusers' StableDiffusionAdapterPipeline: `adapter_image` -- as `control_image`, with the adapter's
         `in_channels` --, `adapter_conditioning_scale`, and `adapter_conditioning_factor`, the fraction of the steps, from the
         first, on which the adapter's features are added).
+        Prompt travel (diffusers' AnimateDiffFreeNoiseMixin): `prompt` and `negative_prompt` are each a str, a keyframe dict
+        {frame: text} -- int keys, the first 0, the last < num_frames; the frames between two keyframes get interpolated embeddings
+        (`encode_prompt_travel`) -- or a list of either with one entry per sample; `prompt_embeds` / `negative_prompt_embeds` may be
+        4-D [B, num_frames, L, D], one context per frame.
         precise_stream: True / False runs THIS call with / without the precise residual stream
         (fp16 hi + lo pairs between the UNet's modules, DESIGN 2.2: closer to the fp32 reference, +2.6 % step time); None keeps the
         process setting (`blocks.set_precise_stream`, I2V_STREAM_PRECISE)."""
@@ -746,6 +839,15 @@ class I2VAdapterPipeline:
         self._check_control_args(control_image, num_frames, controlnet_conditioning_scale, control_guidance_start, control_guidance_end,
                                  guess_mode)
         self._check_adapter_args(adapter_image, num_frames, adapter_conditioning_scale, adapter_conditioning_factor)
+        # prompt travel: keyframe dicts are checked here, before anything is launched or encoded; a dict with one key is its text
+        from .prompt_travel import normalize_prompt
+        prompt, travels = normalize_prompt(prompt, num_frames, "prompt")
+        negative_prompt, neg_travels = normalize_prompt(negative_prompt, num_frames, "negative_prompt")
+        travels = prompt is not None and (travels or neg_travels)
+        for name, t in (("prompt_embeds", prompt_embeds), ("negative_prompt_embeds", negative_prompt_embeds)):
+            if t is not None and t.dim() == 4 and t.shape[1] != num_frames:
+                raise ValueError(f"`{name}` is [B, F, L, D] = {tuple(t.shape)} with F = {t.shape[1]} per-frame contexts, `num_frames` is "
+                                 f"{num_frames}")
         # FreeNoise (enable_free_noise): the settings against this call's num_frames, before anything is launched or encoded
         fnz = self._free_noise_settings()
         if fnz is not None:
@@ -776,16 +878,23 @@ class I2VAdapterPipeline:
             raise ValueError("Provide either `prompt` or `prompt_embeds`. Cannot leave both `prompt` and "
                              "`prompt_embeds` undefined.")
         if prompt is not None:                                                                  # pipe:595-609
-            if not isinstance(prompt, (str, list)):
-                raise ValueError(f"`prompt` has to be of type `str` or `list` but is {type(prompt)}")
+            if not isinstance(prompt, (str, list, dict)):
+                raise ValueError(f"`prompt` has to be of type `str`, `dict` or `list` but is {type(prompt)}")
             if self.text_encoder is None or self.tokenizer is None:
                 raise ValueError("a `prompt` needs both a `text_encoder` and a `tokenizer`: build the pipeline with them, or pass "
                                  "`prompt_embeds` and `negative_prompt_embeds`")
-            prompt_embeds, negative_prompt_embeds = self.encode_prompt(
-                prompt, self.unet.device, num_videos_per_prompt, guidance_scale > 1.0, negative_prompt,
-                prompt_embeds=None, negative_prompt_embeds=negative_prompt_embeds,
-                lora_scale=cross_attention_kwargs.get("scale", None) if cross_attention_kwargs is not None else None,
-                clip_skip=clip_skip)
+            if travels:
+                # keyframed prompts: one context per frame, [B, F, L, D] (a given `negative_prompt_embeds` is kept)
+                pe, ne = self.encode_prompt_travel(prompt, num_frames, self.unet.device, num_videos_per_prompt,
+                                                   guidance_scale > 1.0 and negative_prompt_embeds is None, negative_prompt,
+                                                   clip_skip=clip_skip)
+                prompt_embeds, negative_prompt_embeds = pe, ne if negative_prompt_embeds is None else negative_prompt_embeds
+            else:
+                prompt_embeds, negative_prompt_embeds = self.encode_prompt(
+                    prompt, self.unet.device, num_videos_per_prompt, guidance_scale > 1.0, negative_prompt,
+                    prompt_embeds=None, negative_prompt_embeds=negative_prompt_embeds,
+                    lora_scale=cross_attention_kwargs.get("scale", None) if cross_attention_kwargs is not None else None,
+                    clip_skip=clip_skip)
         if ip_adapter_image is not None:                                                        # pipe:616-622
             # once per sample, before the step is captured.  ImageProjection (plain IP-Adapter) takes the pooled embeds and a zero
             # negative; a Resampler (IP-Adapter Plus) the penultimate hidden states of the image and of a zero image
@@ -826,6 +935,12 @@ class I2VAdapterPipeline:
         batch_size = prompt_embeds.shape[0]
         do_cfg = guidance_scale > 1.0
         copies = 2 if do_cfg else 1
+        # per-frame contexts (prompt travel, or 4-D embeds passed in): [B, F, L, D] on both sides of the guidance
+        per_frame = prompt_embeds.dim() == 4 or (do_cfg and negative_prompt_embeds is not None and negative_prompt_embeds.dim() == 4)
+        if per_frame:
+            prompt_embeds = self._per_frame_embeds(prompt_embeds, num_frames, "prompt_embeds")
+            if do_cfg and negative_prompt_embeds is not None:
+                negative_prompt_embeds = self._per_frame_embeds(negative_prompt_embeds, num_frames, "negative_prompt_embeds")
         if do_cfg:
             if negative_prompt_embeds is None:
                 raise ValueError("classifier-free guidance needs `negative_prompt_embeds`")
@@ -882,6 +997,12 @@ class I2VAdapterPipeline:
             ctx_text=prompt_embeds.to(dev, f16).contiguous(),
             ctx_ip=self.unet._project_image_embeds(
                 {"image_embeds": image_embeds.to(dev)} if image_embeds is not None else None))
+        if per_frame:
+            # the step's context is [copies * B * F, L, D] in the order (CFG half, sample, frame) -- the order of the token rows, so
+            # every cross-attention runs with kv_group = 1; the IP-Adapter's image tokens, one set per sample, get one set per frame
+            # (the fused kernel indexes them with the text's context index)
+            st["ctx_text"] = st["ctx_text"].view(-1, *st["ctx_text"].shape[2:])
+            st["ctx_ip"] = self.unet._expand_image_tokens(st["ctx_ip"], st["ctx_text"].shape[0])
         if self.controlnet is not None:
             # once per sample: the embedding of the B * F control frames (duplicated for the second CFG half) and the scale table;
             # the ControlNet's context projection and time table are made where the UNet's are (_project_once)
@@ -1027,6 +1148,11 @@ def build_parser():
                              "<model_path>/text_encoder with <model_path>/tokenizer")
     parser.add_argument("--negative_prompt", type=str, default="",
                         help="the negative prompt of every row when the prompts are encoded here (no --embeds)")
+    parser.add_argument("--prompt_travel_column", type=str, default=None, metavar="COL",
+                        help="prompt travel: the CSV column that holds, per row, the keyframed prompts as JSON "
+                             "{\"0\": \"...\", \"32\": \"...\"} (frame index -> prompt; the first key is 0, the last below num_frames); "
+                             "the frames in between get interpolated embeddings.  An empty cell keeps the row's `name` prompt.  Not "
+                             "with --embeds")
     parser.add_argument("--model_path", type=str, default="./SG161222_Realistic_Vision_V5.1_noVAE/")
     parser.add_argument("--motion_adapter_path", type=str, default="./animatediff-motion-adapter-v1-5-2")
     parser.add_argument("--ip_adapter_path", type=str, default="./IP-Adapter/")
@@ -1154,6 +1280,9 @@ def main(argv=None):
     if (args.t2i_adapter is None) != (args.adapter_column is None):
         logger.error("--t2i_adapter and --adapter_column come together.")
         return -1
+    if args.prompt_travel_column is not None and args.embeds is not None:
+        logger.error("--prompt_travel_column needs the text encoder: it is not combined with --embeds.")
+        return -1
     i2v_adapter = None
     motion_adapter = MotionAdapter.from_pretrained(args.motion_adapter_path)                     # pipe:734
     checkpoint_path = os.path.join(args.checkpoint_root, args.task_name, f"epoch_{args.checkpoint_epoch}")
@@ -1183,6 +1312,14 @@ def main(argv=None):
     condition_images = [PIL.Image.open(os.path.join(eval_data_dir, p)) for p in eval_data_df["image_path"]]
     eval_prompts = eval_data_df["name"].tolist()
     n = len(eval_prompts)
+    travel_prompts = [None] * n
+    if args.prompt_travel_column is not None:
+        # checked for every row before any model is loaded
+        from .prompt_travel import check_keyframes, parse_travel_cell
+        for i, cell in enumerate(eval_data_df[args.prompt_travel_column]):
+            if isinstance(cell, str) and cell.strip():
+                travel_prompts[i] = parse_travel_cell(cell)
+                check_keyframes(travel_prompts[i], args.num_frames, f"{args.prompt_travel_column}[{i}]")
     text_encoder = tokenizer = None
     if args.embeds is not None:
         emb = load_file(args.embeds)
@@ -1241,7 +1378,8 @@ def main(argv=None):
             text = dict(prompt_embeds=emb["prompt_embeds"][ind: ind + 1],
                         negative_prompt_embeds=neg[ind: ind + 1] if neg.shape[0] == n else neg[:1])
         else:
-            text = dict(prompt=str(eval_prompts[ind]), negative_prompt=args.negative_prompt)
+            text = dict(prompt=travel_prompts[ind] if travel_prompts[ind] is not None else str(eval_prompts[ind]),
+                        negative_prompt=args.negative_prompt)
         if "image_embeds" in emb:
             image = dict(image_embeds=emb["image_embeds"][ind: ind + 1])
         else:

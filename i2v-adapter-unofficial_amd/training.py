@@ -549,6 +549,10 @@ class UNetAdapterTrainer:
             raise NotImplementedError("FreeNoise (enable_free_noise) is a sampling-time switch: the training step has no backward of "
                                       "the window gather / blend -- call unet.disable_free_noise() before training")
         b, F, c, hh, ww = sample.shape
+        if encoder_hidden_states.dim() == 4 or (F > 1 and encoder_hidden_states.shape[0] == b * F):
+            raise NotImplementedError("per-frame text contexts (prompt travel) are a sampling-time input: the training step's backward "
+                                      "sums the context gradients per sample (the reference's training step passes one context per "
+                                      "sample)")
         p = u.packed()
         t = timestep if torch.is_tensor(timestep) else torch.tensor([timestep])
         t = t.to(device=sample.device, dtype=torch.float32).reshape(-1).expand(b).contiguous()

@@ -904,12 +904,28 @@ class UNetMotionCrossFrameAttnModel(UNetLoraMixin, PretrainedMixin, HipModule):
             return self.encoder_hid_proj(added_cond_kwargs.get("image_embeds"))          # unet:1351-1352
         return None
 
+    def _expand_image_tokens(self, ctx_ip, rows):
+        """the IP-Adapter's projected image tokens [n, Li, D], one set per sample, as one set per context row [rows, Li, D] with
+        rows = n * F: row r reads sample r // F (the w = 0 gather of K.interp_rows).  Per-frame text contexts need it: the fused
+        cross-attention indexes the image fragments with the text's context index and `_cross` uses one kv_group for both.
+        None, or tokens that already have `rows` rows, pass through."""
+        if ctx_ip is None or ctx_ip.shape[0] == rows:
+            return ctx_ip
+        if rows % ctx_ip.shape[0] != 0:
+            raise ValueError(f"{ctx_ip.shape[0]} sets of image tokens do not divide {rows} text contexts")
+        idx = torch.arange(ctx_ip.shape[0]).repeat_interleave(rows // ctx_ip.shape[0])
+        return K.interp_rows(ctx_ip.contiguous(), idx, idx, torch.zeros(rows))
+
     def forward(self, sample, timestep, enable_cross_frame_attn: bool, encoder_hidden_states,
                 timestep_cond=None, attention_mask=None, cross_attention_kwargs: Optional[Dict[str, Any]] = None,
                 added_cond_kwargs: Optional[Dict[str, torch.Tensor]] = None,
                 down_block_additional_residuals=None, mid_block_additional_residual=None,
                 return_dict: bool = True, down_intrablock_additional_residuals=None):
         """unet:1289-1451.  sample (B, F, C, H, W) -> noise prediction (B, F, C, H, W) in sample's dtype.
+        `encoder_hidden_states`: [B, L, D], one context per sample (the reference's `repeat_interleave(num_frames)`, unet:1355, is index
+        arithmetic in the kernels) -- or [B * F, L, D], one context per frame in the order of the frames of `sample` (prompt travel:
+        every cross-attention then runs with kv_group = 1); with an IP-Adapter its image tokens, one set per sample, are repeated per
+        frame here.  A `ProjectedContext` made from either form is taken as it is.
         `down_intrablock_additional_residuals` (diffusers' UNet2DConditionModel argument, a T2I-Adapter's output): one NCHW tensor per
         down block, (n, C_i, h_i, w_i) with n = B * F or a divisor of it (see _fwd_tokens).
         `cross_attention_kwargs={"scale": s}`: the global LoRA scale of this call (lora.py).
@@ -961,6 +977,11 @@ class UNetMotionCrossFrameAttnModel(UNetLoraMixin, PretrainedMixin, HipModule):
         else:
             ctx_text = _as_f16_matrix(encoder_hidden_states)
             ctx_ip = self._project_image_embeds(added_cond_kwargs)
+            if ctx_text.dim() != 3 or ctx_text.shape[0] not in (b, b * num_frames):
+                raise ValueError(f"encoder_hidden_states must be [B, L, D] or [B * F, L, D] with B = {b}, F = {num_frames}, got "
+                                 f"{tuple(ctx_text.shape)}")
+            if ctx_text.shape[0] == b * num_frames:      # one context per frame
+                ctx_ip = self._expand_image_tokens(ctx_ip, ctx_text.shape[0])
         p = self.packed()
         x = K.nchw_to_tokens(sample.reshape(b * num_frames, c, hh, ww), p["cin_pad"])     # unet:1358
         cfg_shared = bool(cross_attention_kwargs and cross_attention_kwargs.get("cfg_shared_prefix", False))

@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define I2V_ABI_VERSION 24
+#define I2V_ABI_VERSION 25
 
 #define I2V_OK 0
 #define I2V_ERR_INVALID_ARG (-1)
@@ -882,6 +882,22 @@ int i2v_relu_f16(const void* src, void* dst, int64_t numel, i2v_stream_t stream)
  *       feat_numel, feat_numel no positive multiple of 8, a pointer not 16-byte aligned, dst overlapping feat, scale_table with scale_rows < 1. */
 int i2v_add_broadcast_residual_f16(const void* x, const void* x_lo, const void* feat, void* dst, void* dst_lo, int64_t numel, int64_t feat_numel,
                                    const float* scale_table, int32_t scale_rows, const int32_t* step_idx, i2v_stream_t stream);
+
+/* (ABI 25) Prompt travel (diffusers AnimateDiffFreeNoiseMixin: `prompt` as a dict {frame: text}; pipeline `encode_prompt_travel`): one text
+ * context per frame, interpolated between the keyframes' embeddings.
+ *       out[r] = (1 - w[r]) * src[lo[r]] + w[r] * src[hi[r]],      r = 0 .. n_out - 1
+ *       src fp16 [n_src, e] with row stride ld_src, out fp16 [n_out, e] with row stride ld_out (strides in values, >= e, multiples of 8);
+ *       e % 8 == 0: rows are read and written 16 bytes at a time.  lo, hi (int32 [n_out]) and w (fp32 [n_out]) are DEVICE memory.
+ *       Arithmetic: fp32, fma(w, src[hi], (1 - w) * src[lo]), one rounding to fp16.  A row with w == 0 is a copy of src[lo] and does not
+ *       read src[hi]; a row with w == 1 is a copy of src[hi] and does not read src[lo] -- bit-exact, and whatever the other row holds
+ *       (NaN included) does not reach the output.  With w = 0 everywhere the launch is a row gather.
+ *       PRECONDITION (not checked: the tables live on the device): 0 <= lo[r], hi[r] < n_src and w[r] finite.  The Python wrapper
+ *       builds the tables on the host and checks them before the upload.
+ *       Grid: at most 2048 workgroups of 256 lanes stride over the 16-byte chunks of all rows; no workspace, nothing allocated.
+ *       I2V_ERR_INVALID_ARG (nothing launched): a null pointer, src / out not 16-byte or a table not 4-byte aligned, n_src or n_out < 1,
+ *       e no positive multiple of 8, a stride below e or no multiple of 8, out overlapping src, n_out * e / 8 >= 2^31 - 2^19. */
+int i2v_interp_rows_f16(const void* src, int64_t ld_src, int32_t n_src, const int32_t* lo, const int32_t* hi, const float* w, void* out,
+                        int64_t ld_out, int32_t n_out, int32_t e, i2v_stream_t stream);
 
 /* First-frame-similarity prior and the initial add_noise of the sampling loop, pipe:647-656:
  *   prior   = mask * GaussianBlur3x3(cond) + (1 - mask) * cond, mask = (mask_uniform < strength), per frame (pipe:648-654)

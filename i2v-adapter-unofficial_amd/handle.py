@@ -356,6 +356,14 @@ def _refuse_per_frame_context(st, what):
                                   "prompt per sample to export")
 
 
+def _refuse_mask(st, what):
+    """video-to-video with a mask (`st["v2v_mask"]`) adds i2v_masked_renoise_f32 to the step and four per-sample buffers (source, noise,
+    mask, coefficient table) that the plan format has no entry id and no io slot for"""
+    if st.get("v2v_mask") is not None:
+        raise NotImplementedError(f"{what}: a step with a mask (`mask_image`: the masked re-noise launch and its source, noise, mask and "
+                                  "table buffers) is not implemented for the C handle; call without `mask_image` to export")
+
+
 def _step_problem(st):
     b, f, _c, hh, ww = st["latents"].shape
     return (st["copies"] * b, f, hh, ww, st["ctx_text"].shape[1], int(st["ctx_ip"] is not None))
@@ -373,6 +381,7 @@ def record_step_plan(pipe, st):
     [T - 1, B, F, C, H, W] (= st["noise"], read only: `LCMScheduler.step_noise`; absent for a single-step schedule)."""
     _refuse_controlnet(pipe, "record_step_plan")
     _refuse_per_frame_context(st, "record_step_plan")
+    _refuse_mask(st, "record_step_plan")
     if pipe._scheduler_kind() == "lcm":
         noise = st.get("noise")
         keep_lcm = (st["latents"].clone(), st["step_idx"].clone())
@@ -412,6 +421,7 @@ def record_prepare_plan(pipe, st, image_embeds=None):
     io: PREP_CONTEXT fp16 [2 B, L, D] (= st["ctx_text"]), PREP_TIMESTEPS fp32 [T] (= st["t_table"]), PREP_IMAGE_EMBEDS fp16 [2 B, clip]."""
     _refuse_controlnet(pipe, "record_prepare_plan")
     _refuse_per_frame_context(st, "record_prepare_plan")
+    _refuse_mask(st, "record_prepare_plan")
     unet = pipe.unet
     io = {PREP_CONTEXT: st["ctx_text"], PREP_TIMESTEPS: st["t_table"]}
     if image_embeds is not None:

@@ -1633,6 +1633,41 @@ def interp_rows(src, lo, hi, w, out=None):
     return out
 
 
+# ---------------------------------------------------------------------------------------------- video-to-video with a mask (pipeline)
+def masked_renoise(latents, source, noise, mask, coef, step_index):
+    """In place: latents = m * latents + (1 - m) * (coef[r][0] * source + coef[r][1] * noise) (i2v_masked_renoise_f32), diffusers'
+    inpainting update for a 4-channel UNet.  latents, source, noise fp32 [B, F, C, H, W] contiguous; mask fp32 [B, F, 1, H, W]
+    contiguous, one plane for all channels: 1 regenerates (the latent's bits are kept), 0 keeps the source, any float is taken;
+    coef fp32 [rows, 2] contiguous; step_index device int32 scalar, READ and not advanced: r = clamp(step_index, 0, rows - 1).
+    Table convention: the scheduler-step kernels have already advanced the counter, and they wrap it to 0 after the last row, so row 0
+    is (1, 0) -- the clean source after the last step -- and row r >= 1 is (sqrt(abar), sqrt(1 - abar)) of timesteps[r]; a one-step
+    schedule falls on row 0 (`I2VAdapterPipeline.renoise_table`).  m == 0 at the row (1, 0) gives the source's bits."""
+    lib = _lib.load()
+    for t, name in ((latents, "latents"), (source, "source"), (noise, "noise"), (mask, "mask"), (coef, "coef")):
+        _req(t, name, dtype=torch.float32)
+        if not t.is_contiguous():
+            raise ValueError(f"masked_renoise: {name} must be contiguous")
+    _req(step_index, "step_index", dtype=torch.int32)
+    if latents.dim() != 5 or latents.numel() < 1:
+        raise ValueError(f"masked_renoise: latents must be a non-empty [B, F, C, H, W], got {tuple(latents.shape)}")
+    b, f, c, h, w = latents.shape
+    if tuple(source.shape) != tuple(latents.shape) or tuple(noise.shape) != tuple(latents.shape):
+        raise ValueError(f"masked_renoise: source {tuple(source.shape)} and noise {tuple(noise.shape)} must have the latents' shape "
+                         f"{tuple(latents.shape)}")
+    if tuple(mask.shape) != (b, f, 1, h, w):
+        raise ValueError(f"masked_renoise: mask must be {(b, f, 1, h, w)}, got {tuple(mask.shape)}")
+    if coef.dim() != 2 or coef.shape[1] != 2 or coef.shape[0] < 1:
+        raise ValueError(f"masked_renoise: coef must be [rows >= 1, 2], got {tuple(coef.shape)}")
+    if step_index.numel() != 1:
+        raise ValueError("masked_renoise: step_index must hold one int32")
+    for t in (source, noise, mask, coef, step_index):
+        if t.device != latents.device:
+            raise ValueError("masked_renoise: all operands must be on the latents' device")
+    _lib.check(lib.i2v_masked_renoise_f32(_p(latents), _p(source), _p(noise), _p(mask), _p(coef), coef.shape[0], _p(step_index), b * f, c,
+                                          h * w, _stream()), "i2v_masked_renoise_f32")
+    return latents
+
+
 _freeinit_ws = {}
 
 

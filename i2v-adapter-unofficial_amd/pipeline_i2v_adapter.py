@@ -378,6 +378,10 @@ class I2VAdapterPipeline:
             K.dpm_cfg_step(st["latents"], st["x0_prev"], y, st["coef"], st["step_idx"], st["guidance"], st["copies"])
         else:
             K.ddim_cfg_step(st["latents"], y, st["coef"], st["step_idx"], st["guidance"], st["copies"])  # pipe:686-691
+        if st.get("v2v_mask") is not None:
+            # video-to-video with a mask: the same launch under the three schedulers.  The scheduler step has advanced the counter (and
+            # wrapped it after the last step), so the launch reads the row of the NEXT timestep -- row 0, the clean source, at the end
+            K.masked_renoise(st["latents"], st["v2v_source"], st["v2v_noise"], st["v2v_mask"], st["v2v_coef"], st["step_idx"])
 
     def _project_once(self, st, into=False):
         """what depends on the sample but not on the step, computed once before the steps: K / V^T of the context for every
@@ -410,6 +414,10 @@ class I2VAdapterPipeline:
         # a T2I-Adapter's adds: the features' and the scale table's shapes (the features are static buffers, not launch arguments)
         if st.get("t2i_feats") is not None:
             cn = (cn, tuple(shp(t) for t in st["t2i_feats"]), shp(st["t2i_scale"]))
+        # a mask's launch (video-to-video): the mask's and the table's shapes (the table's rows are a launch argument).  A source clip
+        # without a mask launches nothing of its own: its key is a plain call's
+        if st.get("v2v_mask") is not None:
+            cn = (cn, "masked_renoise", shp(st["v2v_mask"]), shp(st["v2v_coef"]))
         return (cn, tuple(st["latents"].shape), st["copies"], st["num_frames"], st["guidance"], shp(st["t_table"]),
                 shp(st["ctx_text"]), shp(st["ctx_ip"]), str(st["latents"].device), wsig, ips, precise_stream(),
                 self._scheduler_kind(), shp(st["coef"]), unet.freeu_signature(), shp(st.get("noise")), unet.free_noise_launch_signature())
@@ -429,7 +437,8 @@ class I2VAdapterPipeline:
         if hit is not None:
             graph, gst = hit
             for name in ("latents", "cond", "t_table", "coef", "ctx_text", "ctx_ip", "noise",      # (noise: this sample's LCM draws)
-                         "cn_cond", "cn_scale", "t2i_scale"):                                      # (this sample's control frames)
+                         "cn_cond", "cn_scale", "t2i_scale",                                       # (this sample's control frames)
+                         "v2v_source", "v2v_noise", "v2v_mask", "v2v_coef"):                       # (this sample's clip and mask)
                 if st.get(name) is not None:
                     gst[name].copy_(st[name])
             for dst, src in zip(gst.get("t2i_feats") or (), st.get("t2i_feats") or ()):             # (this sample's adapter features)
@@ -587,6 +596,172 @@ class I2VAdapterPipeline:
         """fp32 [n_steps] on the device: the adapter's scale on the first int(n_steps * factor) executed steps, 0 afterwards"""
         from .t2i_adapter import adapter_scale_table
         return torch.tensor(adapter_scale_table(n_steps, *t2i_args), dtype=torch.float32, device=device)
+
+    # ------------------------------------------------------------------------------------------ video-to-video, masked editing
+    def _check_video_args(self, video, video_latents, strength, mask_image, num_frames, num_inference_steps, ratio, eta):
+        """the video-to-video arguments of a call, checked on the host before anything is launched or encoded.  Returns (video,
+        video_latents, strength): the source clip cut to `num_frames` frames and the strength with its default (0.8 with a clip)."""
+        if video is not None and video_latents is not None:
+            raise ValueError("Cannot forward both `video` and `video_latents`. Please make sure to only forward one of the two.")
+        if video is None and video_latents is None:
+            if strength is not None:
+                raise ValueError(f"`strength` = {strength} was passed without a source clip: it is the fraction of the schedule a `video` "
+                                 "(or `video_latents`) is noised to")
+            if mask_image is not None:
+                raise ValueError("`mask_image` was passed without a source clip: it needs `video` (or `video_latents`), the clip whose "
+                                 "region outside the mask is kept")
+            return None, None, None
+        if video is not None:
+            if isinstance(video, torch.Tensor):
+                if video.dim() not in (4, 5) or video.shape[-3] != 3:
+                    raise ValueError(f"`video` must be [F, 3, H, W] or [B, F, 3, H, W], got {tuple(video.shape)}")
+                n = video.shape[-4]
+            elif isinstance(video, (list, tuple)):
+                n = len(video)
+            else:
+                raise ValueError(f"`video` must be a list of `num_frames` images or a tensor, got {type(video)}")
+        else:
+            if not isinstance(video_latents, torch.Tensor) or video_latents.dim() != 5:
+                raise ValueError("`video_latents` must be a [B, F, 4, h, w] tensor, got "
+                                 f"{tuple(video_latents.shape) if isinstance(video_latents, torch.Tensor) else type(video_latents)}")
+            n = video_latents.shape[1]
+        if n < num_frames:
+            raise ValueError(f"the source clip holds {n} frames, `num_frames` is {num_frames}: video-to-video needs one source frame for "
+                             "every frame of the clip")
+        if video_latents is not None:
+            video_latents = video_latents[:, :num_frames]
+        elif isinstance(video, torch.Tensor):
+            video = video[..., :num_frames, :, :, :]
+        else:
+            video = list(video[:num_frames])
+        strength = 0.8 if strength is None else float(strength)
+        if not 0.0 < strength <= 1.0:
+            raise ValueError(f"The value of strength should in (0.0, 1.0] but is {strength}")
+        steps = min(int(num_inference_steps * strength), num_inference_steps)
+        if steps < 1:
+            raise ValueError(f"After adjusting the num_inference_steps by strength parameter: {strength}, the number of pipeline "
+                             f"steps is {steps} which is < 1 and not appropriate for this pipeline.")
+        if ratio != 1:
+            raise ValueError(f"`frame_similarity_sample_ratio` = {ratio} with a source clip: `strength` decides where the schedule "
+                             "starts, leave the ratio at 1")
+        if self._free_init is not None:
+            raise ValueError("a source clip (`video` / `video_latents`) while FreeInit is enabled is not supported: "
+                             "disable_free_init() first")
+        if mask_image is not None and eta > 0 and self._scheduler_kind() == "ddim":
+            raise ValueError(f"`mask_image` with eta = {eta} > 0: the stochastic DDIM update adds its noise after the mask's blend and "
+                             "would noise the kept region -- use eta = 0")
+        if video is not None and self.vae is None:
+            raise ValueError("a `video` needs a `vae` (AutoencoderKL or AutoencoderTiny) -- or pass `video_latents`")
+        return video, video_latents, strength
+
+    def _video_frames(self, video, height, width):
+        """-> fp32 [B or 1, F, 3, height, width] in [-1, 1] on the host: PIL frames through `image_processor.preprocess` (resized, as the
+        condition image is); tensors in [0, 1] are normalised and must already have that size"""
+        if isinstance(video, torch.Tensor):
+            if video.dim() not in (4, 5) or video.shape[-3] != 3:
+                raise ValueError(f"`video` must be [F, 3, H, W] or [B, F, 3, H, W], got {tuple(video.shape)}")
+            t = video[None] if video.dim() == 4 else video
+            if tuple(t.shape[-2:]) != (height, width):
+                raise ValueError(f"`video` tensors must already be {height} x {width}, got {tuple(t.shape[-2:])}")
+            flat = self.image_processor.preprocess(t.reshape(-1, 3, height, width))
+            return flat.reshape(t.shape[0], t.shape[1], 3, height, width)
+        flat = self.image_processor.preprocess(list(video), height=height, width=width)
+        if tuple(flat.shape[-2:]) != (height, width):
+            raise ValueError(f"video frames of {tuple(flat.shape[-2:])} after resizing, expected {height} x {width}")
+        return flat[None]
+
+    def encode_video(self, video, height, width, generator=None):
+        """video (PIL frames, [F, 3, H, W] in [0, 1], or [B, F, 3, H, W]) -> latents [B, F, 4, height / 8, width / 8] fp32, scaled: all
+        B * F frames through `vae.encode` (frame by frame under `enable_vae_slicing`; tiled under `enable_vae_tiling`, as the condition
+        image is), then ONE draw of `latent_dist.sample` over the [B * F, 4, h, w] moments in (sample, frame) order (a list of generators:
+        generator b draws sample b's frames), times `scaling_factor`.  A deterministic VAE (AutoencoderTiny) gives its latents
+        undrawn."""
+        if self.vae is None:
+            raise ValueError("a `video` needs a `vae` (AutoencoderKL or AutoencoderTiny) -- or pass `video_latents`")
+        return self._encode_frames(self._video_frames(video, height, width), generator)
+
+    def _encode_frames(self, frames, generator=None):
+        """`encode_video` behind the preprocessing: frames fp32 [B, F, 3, H, W] in [-1, 1] on the host"""
+        b, f = frames.shape[:2]
+        flat = frames.reshape(b * f, *frames.shape[2:]).to(self.vae.device)
+        chunks = [flat[i: i + 1] for i in range(b * f)] if self._vae_slicing else [flat]
+        encs = [self.vae.encode(c) for c in chunks]
+        scale = self.vae.config["scaling_factor"]
+        if not hasattr(encs[0], "latent_dist") and hasattr(encs[0], "latents"):
+            lat = torch.cat([e.latents for e in encs])
+            return (lat * scale).reshape(b, f, *lat.shape[1:])
+        moments = torch.cat([e.latent_dist.parameters for e in encs]).contiguous()
+        n, c2, h, w = moments.shape
+        eps = _draw(torch.randn, (b, f, c2 // 2, h, w), generator, moments.device).reshape(n, c2 // 2, h, w).contiguous()
+        return (K.gaussian_sample(moments, eps) * scale).reshape(b, f, c2 // 2, h, w)
+
+    def prepare_video_latents(self, video_latents, noise, timestep):
+        """the initial latents of video-to-video: scheduler.add_noise(video_latents, noise, timestep) =
+        sqrt(abar_t) * video_latents + sqrt(1 - abar_t) * noise, on a copy of the source (fp32 [B, F, 4, h, w] on the device; K.axpby)"""
+        sa, sb = self._noise_level(timestep)
+        return K.axpby(video_latents.detach().to(torch.float32).clone(memory_format=torch.contiguous_format),
+                       noise.to(torch.float32).contiguous(), sa, sb)
+
+    def _noise_level(self, timestep):
+        """(sqrt(abar_t), sqrt(1 - abar_t)) as `add_noise` computes them: in fp32"""
+        a = self.scheduler.alphas_cumprod[int(timestep)].to(torch.float32)
+        return float(a ** 0.5), float((1 - a) ** 0.5)
+
+    def renoise_table(self, timesteps):
+        """fp32 [len(timesteps), 2]: the coefficient table of `K.masked_renoise`.  The scheduler-step kernels have already advanced the
+        step counter when the blend reads it, and they wrap it to 0 after the last row: row 0 = (1, 0), the clean source after the
+        last step; row r >= 1 = (sqrt(abar), sqrt(1 - abar)) of timesteps[r], the level the next step expects.  A one-step schedule
+        falls on row 0."""
+        rows = [(1.0, 0.0)] + [self._noise_level(t) for t in list(timesteps)[1:]]
+        return torch.tensor(rows, dtype=torch.float32)
+
+    def prepare_mask_latents(self, mask_image, batch_size, num_frames, height, width):
+        """-> fp32 [batch_size, num_frames, 1, height / 8, width / 8] on the host; 1 regenerates, 0 keeps the source.  `mask_image`: one
+        PIL image or [H, W] tensor for all frames, `num_frames` PIL images, [F, 1, H, W] or [B, F, 1, H, W] (values in [0, 1]; frames
+        beyond `num_frames` are dropped).  Converted to grey, resized to height x width (PIL: Lanczos; tensors: nearest), binarised at
+        >= 0.5, then taken to the latent resolution by torch.nn.functional.interpolate(mode="nearest").  A tensor already at
+        (height / 8, width / 8) is taken as it is, unbinarised: soft masks are allowed."""
+        import numpy as np
+        import PIL.Image
+        import torch.nn.functional as F
+        h, w = height // self.vae_scale_factor, width // self.vae_scale_factor
+        if isinstance(mask_image, PIL.Image.Image):
+            mask_image = [mask_image]
+        if isinstance(mask_image, (list, tuple)):
+            planes = []
+            for im in mask_image:
+                if not isinstance(im, PIL.Image.Image):
+                    raise ValueError(f"`mask_image` as a list holds PIL images, got {type(im)}")
+                im = im.convert("L")
+                if im.size != (width, height):
+                    im = im.resize((width, height), resample=PIL.Image.LANCZOS)
+                planes.append(torch.from_numpy(np.asarray(im, dtype=np.float32) / 255.0))
+            t = torch.stack(planes)[None, :, None]                                          # [1, F or 1, 1, H, W]
+        elif isinstance(mask_image, torch.Tensor):
+            t = mask_image.detach().float().cpu()
+            if t.dim() == 2:
+                t = t[None, None, None]
+            elif t.dim() == 4 and t.shape[1] == 1:
+                t = t[None]
+            elif not (t.dim() == 5 and t.shape[2] == 1):
+                raise ValueError(f"`mask_image` must be [H, W], [F, 1, H, W] or [B, F, 1, H, W], got {tuple(mask_image.shape)}")
+        else:
+            raise ValueError(f"`mask_image` must be a PIL image, a list of `num_frames` PIL images or a tensor, got {type(mask_image)}")
+        if t.shape[1] == 1:
+            t = t.expand(-1, num_frames, -1, -1, -1)
+        if t.shape[1] < num_frames:
+            raise ValueError(f"`mask_image` holds {t.shape[1]} frames, `num_frames` is {num_frames}")
+        t = t[:, :num_frames]
+        if t.shape[0] == 1:
+            t = t.expand(batch_size, -1, -1, -1, -1)
+        if t.shape[0] != batch_size:
+            raise ValueError(f"`mask_image` {tuple(t.shape)} does not match batch {batch_size}")
+        flat = t.reshape(batch_size * num_frames, 1, *t.shape[-2:])
+        if tuple(flat.shape[-2:]) != (h, w):
+            if tuple(flat.shape[-2:]) != (height, width):
+                flat = F.interpolate(flat, size=(height, width), mode="nearest")
+            flat = F.interpolate((flat >= 0.5).to(torch.float32), size=(h, w), mode="nearest")
+        return flat.reshape(batch_size, num_frames, 1, h, w).contiguous()
 
     # ------------------------------------------------------------------------------------------ encode_image
     def encode_image(self, image, device, num_images_per_prompt, output_hidden_states=None):
@@ -797,7 +972,8 @@ class I2VAdapterPipeline:
                  use_graph: bool = True, precise_stream: Optional[bool] = None, control_image=None,
                  controlnet_conditioning_scale: float = 1.0, control_guidance_start: float = 0.0, control_guidance_end: float = 1.0,
                  guess_mode: bool = False, adapter_image=None, adapter_conditioning_scale: float = 1.0,
-                 adapter_conditioning_factor: float = 1.0):
+                 adapter_conditioning_factor: float = 1.0, video=None, video_latents=None, strength: Optional[float] = None,
+                 mask_image=None):
         """pipe:537-711 (the arguments the reference's `__call__` takes; `use_graph`, the explicit prior generators and
         `precise_stream` are additions, and so are the ControlNet arguments, which carry the names of diffusers'
         StableDiffusionControlNetPipeline: `control_image` -- `num_frames` PIL images, a [F, 3, H, W] tensor in [0, 1] shared by the
@@ -810,6 +986,13 @@ class I2VAdapterPipeline:
         {frame: text} -- int keys, the first 0, the last < num_frames; the frames between two keyframes get interpolated embeddings
         (`encode_prompt_travel`) -- or a list of either with one entry per sample; `prompt_embeds` / `negative_prompt_embeds` may be
         4-D [B, num_frames, L, D], one context per frame.
+        Video-to-video (diffusers' AnimateDiffVideoToVideoPipeline): `video` -- `num_frames` PIL images, a [F, 3, H, W] tensor in [0, 1]
+        shared by the batch or [B, F, 3, H, W]; frames beyond `num_frames` are dropped -- is encoded by `encode_video`, or
+        `video_latents` [B, F, 4, h, w] (already scaled) is taken as given; the clip starts from the source noised to the level of
+        the first of the last int(num_inference_steps * strength) timesteps (`strength` in (0, 1], None: 0.8) instead of from the
+        first-frame prior, and without a condition image the source's first frame is the condition.  `mask_image` (the inpainting
+        pipelines': 1 regenerates, 0 keeps the source; one PIL image or [H, W] tensor for all frames, `num_frames` PIL images,
+        [F, 1, H, W] or [B, F, 1, H, W]) adds one `K.masked_renoise` launch to the captured step.
         precise_stream: True / False runs THIS call with / without the precise residual stream
         (fp16 hi + lo pairs between the UNet's modules, DESIGN 2.2: closer to the fp32 reference, +2.6 % step time); None keeps the
         process setting (`blocks.set_precise_stream`, I2V_STREAM_PRECISE)."""
@@ -839,6 +1022,10 @@ class I2VAdapterPipeline:
         self._check_control_args(control_image, num_frames, controlnet_conditioning_scale, control_guidance_start, control_guidance_end,
                                  guess_mode)
         self._check_adapter_args(adapter_image, num_frames, adapter_conditioning_scale, adapter_conditioning_factor)
+        # video-to-video: the arguments, before anything is launched or encoded; frames beyond num_frames are dropped here
+        video, video_latents, strength = self._check_video_args(video, video_latents, strength, mask_image, num_frames,
+                                                                num_inference_steps, frame_similarity_sample_ratio, eta)
+        has_clip = video is not None or video_latents is not None
         # prompt travel: keyframe dicts are checked here, before anything is launched or encoded; a dict with one key is its text
         from .prompt_travel import normalize_prompt
         prompt, travels = normalize_prompt(prompt, num_frames, "prompt")
@@ -910,13 +1097,23 @@ class I2VAdapterPipeline:
                         (f"IP-Adapter Plus is loaded (Resampler), which takes the image encoder's penultimate hidden states "
                          f"[batch, tokens, {self.unet.encoder_hid_proj.embed_dims}]" if plus else
                          "the plain IP-Adapter is loaded (ImageProjection), which takes the pooled image embeds [batch, embed_dim]"))
-        if condition_image is not None and condition_image_latents is None:                     # pipe:624-627
+        if (condition_image is not None and condition_image_latents is None) or video is not None:  # pipe:624-627
             if height is None or width is None:
                 height = height or self.unet.config.sample_size * self.vae_scale_factor         # pipe:568-569
                 width = width or self.unet.config.sample_size * self.vae_scale_factor
             if height % 8 != 0 or width % 8 != 0:                                               # pipe:213-214
                 raise ValueError(f"`height` and `width` have to be divisible by 8 but are {height} and {width}.")
+        if condition_image is not None and condition_image_latents is None:
             condition_image_latents = self.encode_condition_image(condition_image, height, width, generator)
+        if video is not None:
+            # after the condition image's draw from `generator` and before prepare_latents'; a clip shared by the batch is encoded for
+            # every sample (each takes its own draw)
+            frames = self._video_frames(video, height, width)
+            if frames.shape[0] == 1 and prompt_embeds.shape[0] > 1:
+                frames = frames.expand(prompt_embeds.shape[0], -1, -1, -1, -1)
+            video_latents = self._encode_frames(frames, generator)
+        if has_clip and condition_image_latents is None:
+            condition_image_latents = video_latents[:, 0]                 # the source's first frame is the condition
         if condition_image_latents is None:
             raise ValueError("`condition_image` (or `condition_image_latents`) is required: the reference's prior "
                              "(pipe:647-656) needs the condition image and crashes without it")
@@ -966,7 +1163,7 @@ class I2VAdapterPipeline:
         else:
             round_steps = [num_inference_steps] * rounds
         self.scheduler.set_timesteps(round_steps[0])                                            # pipe:630-631
-        timesteps, _ = self.get_timesteps(round_steps[0], frame_similarity_sample_ratio)
+        timesteps, _ = self.get_timesteps(round_steps[0], strength if has_clip else frame_similarity_sample_ratio)
 
         cond_dev = condition_image_latents.detach().to(dev, torch.float32).contiguous()
         latents = self.prepare_latents(batch_size, self.unet.config.in_channels, num_frames, height, width,
@@ -974,20 +1171,34 @@ class I2VAdapterPipeline:
         # first-frame-similarity prior + add_noise (pipe:647-656) in ONE HIP kernel; the reference overwrites the
         # latents drawn above (its `latents = self.scheduler.add_noise(...)`, pipe:656), and so does this.  The random
         # draws (blur sigma, mask, noise) take explicit generators (the reference uses the unseeded global RNG).
-        if blur_sigma is None:                                                                  # pipe:112
+        # With a source clip no prior is built: its blur sigma and mask are not drawn, the noise is drawn as the prior's is.
+        if blur_sigma is None and not has_clip:                                                 # pipe:112
             blur_sigma = draw_blur_sigma(prior_mask_generator[0] if isinstance(prior_mask_generator, (list, tuple))
                                          else prior_mask_generator)
         shape = (batch_size, num_frames) + tuple(cond_dev.shape[1:])
-        mask_u = _draw(torch.rand, shape, prior_mask_generator, dev)                            # pipe:652
+        if has_clip:
+            source = video_latents.detach().to(dev, torch.float32)
+            if source.shape[0] == 1 and batch_size > 1:
+                source = source.expand(batch_size, -1, -1, -1, -1)
+            if tuple(source.shape) != shape:
+                raise ValueError(f"the source clip's latents are {tuple(source.shape)}, the call's are {shape} "
+                                 "(batch, num_frames, the condition latents' channels and size)")
+            source = source.contiguous()
+        else:
+            mask_u = _draw(torch.rand, shape, prior_mask_generator, dev)                        # pipe:652
         if fnz is not None and num_frames > fnz.context_length:
             # FreeNoise: the frames behind the first window re-use its noise (repeated or shuffled: `free_noise.reschedule_noise`)
             from .free_noise import reschedule_noise
             noise = reschedule_noise(lambda shp, g: _draw(torch.randn, shp, g, dev), shape, fnz, prior_noise_generator)
         else:
             noise = _draw(torch.randn, shape, prior_noise_generator, dev)                       # pipe:655
-        a_t = float(self.scheduler.alphas_cumprod[int(timesteps[0])])
-        latents = K.first_frame_prior(cond_dev, mask_u.contiguous(), noise.contiguous(), blur_sigma,
-                                      frame_similarity_blurred_strength, a_t ** 0.5, (1.0 - a_t) ** 0.5)
+        noise = noise.contiguous()
+        if has_clip:
+            latents = self.prepare_video_latents(source, noise, timesteps[0])
+        else:
+            a_t = float(self.scheduler.alphas_cumprod[int(timesteps[0])])
+            latents = K.first_frame_prior(cond_dev, mask_u.contiguous(), noise, blur_sigma,
+                                          frame_similarity_blurred_strength, a_t ** 0.5, (1.0 - a_t) ** 0.5)
 
         st = dict(
             latents=latents, cond=cond_dev, copies=copies,
@@ -1018,6 +1229,12 @@ class I2VAdapterPipeline:
             st["t2i_feats"] = self.t2i_adapter.embed(frames)
             st["t2i_args"] = (float(adapter_conditioning_scale), float(adapter_conditioning_factor))
             st["t2i_scale"] = self._adapter_scale_table(len(timesteps), st["t2i_args"], dev)
+        if mask_image is not None:
+            # the inpainting update: after every scheduler step the kept region goes back to the source at the NEXT step's noise level
+            # (the same initial noise), after the last step to the clean source -- one launch inside the captured step (_step)
+            st["v2v_mask"] = self.prepare_mask_latents(mask_image, batch_size, num_frames, height, width).to(dev).contiguous()
+            st["v2v_source"], st["v2v_noise"] = source, noise
+            st["v2v_coef"] = self.renoise_table(timesteps).to(dev)
         if dpm:
             # the previous step's data prediction: the first step of a sample is first order and does not read it
             st["x0_prev"] = torch.empty_like(latents)
@@ -1223,7 +1440,28 @@ def build_parser():
     parser.add_argument("--adapter_scale", type=float, default=1.0, metavar="S", help="adapter_conditioning_scale (1.0)")
     parser.add_argument("--adapter_factor", type=float, default=1.0, metavar="F",
                         help="adapter_conditioning_factor: the fraction of the steps, from the first, on which the adapter acts (1.0)")
+    parser.add_argument("--video_column", type=str, default=None, metavar="COL",
+                        help="video-to-video: the CSV column that holds, per row, the source clip -- a directory of at least num_frames "
+                             "frames (taken in sorted order) or an animated GIF, relative to the CSV; the clip starts from the noised "
+                             "source instead of from the first-frame prior")
+    parser.add_argument("--strength", type=float, default=None, metavar="S",
+                        help="with --video_column: the fraction of the schedule the source is noised to, in (0, 1] (0.8); the last "
+                             "int(num_inference_steps * S) steps run")
+    parser.add_argument("--mask_column", type=str, default=None, metavar="COL",
+                        help="with --video_column: the CSV column that holds, per row, the mask -- one image for all frames, or a "
+                             "directory / animated GIF of num_frames masks; white is regenerated, black keeps the source")
     return parser
+
+
+def load_mask_frames(path, num_frames):
+    """the mask of a driver row: one grey PIL image for all frames (a single image file), or the first `num_frames` masks of a
+    directory of images / an animated GIF (`load_control_frames`)"""
+    import PIL.Image
+    if os.path.isfile(path):
+        with PIL.Image.open(path) as im:
+            if getattr(im, "n_frames", 1) == 1:
+                return im.convert("L")
+    return load_control_frames(path, num_frames)
 
 
 def load_control_frames(path, num_frames):
@@ -1283,6 +1521,9 @@ def main(argv=None):
     if args.prompt_travel_column is not None and args.embeds is not None:
         logger.error("--prompt_travel_column needs the text encoder: it is not combined with --embeds.")
         return -1
+    if args.video_column is None and (args.strength is not None or args.mask_column is not None):
+        logger.error("--strength and --mask_column need a source clip: --video_column.")
+        return -1
     i2v_adapter = None
     motion_adapter = MotionAdapter.from_pretrained(args.motion_adapter_path)                     # pipe:734
     checkpoint_path = os.path.join(args.checkpoint_root, args.task_name, f"epoch_{args.checkpoint_epoch}")
@@ -1341,6 +1582,11 @@ def main(argv=None):
         t2i_adapter = T2IAdapter.from_pretrained(args.t2i_adapter)
         adapter_paths = [os.path.join(eval_data_dir, str(p)) for p in eval_data_df[args.adapter_column]]
         logger.info(f"Successfully loaded T2IAdapter from {args.t2i_adapter}.")
+    video_paths = mask_paths = None
+    if args.video_column is not None:
+        video_paths = [os.path.join(eval_data_dir, str(p)) for p in eval_data_df[args.video_column]]
+        if args.mask_column is not None:
+            mask_paths = [os.path.join(eval_data_dir, str(p)) for p in eval_data_df[args.mask_column]]
     pipe = I2VAdapterPipeline(vae, text_encoder, tokenizer, unet2d.to(device).half(), motion_adapter, i2v_adapter, scheduler,
                               controlnet=controlnet, t2i_adapter=t2i_adapter)
     if "image_embeds" in emb or args.ip_adapter:                                                 # pipe:783
@@ -1392,9 +1638,16 @@ def main(argv=None):
         if t2i_adapter is not None:
             control.update(adapter_image=load_control_frames(adapter_paths[ind], args.num_frames),
                            adapter_conditioning_scale=args.adapter_scale, adapter_conditioning_factor=args.adapter_factor)
+        ratio = 0.9
+        if video_paths is not None:
+            # video-to-video: `strength` decides where the schedule starts, not the similarity ratio
+            ratio = 1
+            control.update(video=load_control_frames(video_paths[ind], args.num_frames), strength=args.strength)
+            if mask_paths is not None:
+                control.update(mask_image=load_mask_frames(mask_paths[ind], args.num_frames))
         out = pipe(**text, **image, **control,
                    condition_image=condition_images[ind], num_frames=args.num_frames, guidance_scale=args.guidance_scale,
-                   num_inference_steps=args.num_inference_steps, frame_similarity_sample_ratio=0.9,
+                   num_inference_steps=args.num_inference_steps, frame_similarity_sample_ratio=ratio,
                    height=args.height, width=args.width, output_type="pil", generator=g(0),
                    prior_mask_generator=g(1), prior_noise_generator=g(2))                        # pipe:790-799
         export_to_gif(out.frames[0], os.path.join(sample_save_dir, f"{eval_prompts[ind]}.gif"))  # pipe:806-807

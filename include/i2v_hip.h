@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define I2V_ABI_VERSION 25
+#define I2V_ABI_VERSION 26
 
 #define I2V_OK 0
 #define I2V_ERR_INVALID_ARG (-1)
@@ -898,6 +898,30 @@ int i2v_add_broadcast_residual_f16(const void* x, const void* x_lo, const void* 
  *       e no positive multiple of 8, a stride below e or no multiple of 8, out overlapping src, n_out * e / 8 >= 2^31 - 2^19. */
 int i2v_interp_rows_f16(const void* src, int64_t ld_src, int32_t n_src, const int32_t* lo, const int32_t* hi, const float* w, void* out,
                         int64_t ld_out, int32_t n_out, int32_t e, i2v_stream_t stream);
+
+/* (ABI 26) Video-to-video with a mask (diffusers' inpainting update for a 4-channel UNet; pipeline `video=` / `mask_image=`): the one launch
+ * inside a denoising step, after the scheduler-step kernel.  In place on the latents:
+ *       latents[n, c, p] = m * latents[n, c, p] + (1 - m) * (coef[r][0] * source[n, c, p] + coef[r][1] * noise[n, c, p])
+ *       m = mask[n, p]: one mask plane serves all channels; 1 regenerates (the latent stays), 0 keeps the source, any float is taken.
+ *       latents, source, noise fp32 [images, channels, hw] and mask fp32 [images, hw], all contiguous; images = batch * frames.
+ *       coef fp32 [coef_rows, 2] and step_idx (int32 [1]) are DEVICE memory; r = clamp(step_idx[0], 0, coef_rows - 1).  The kernel READS
+ *       the counter and does not advance it.
+ *       Table convention: the scheduler-step kernels (i2v_ddim_cfg_step, i2v_dpm_cfg_step, i2v_lcm_cfg_step) have already advanced the
+ *       counter when this kernel reads it, and they wrap it to 0 after the last row.  So row 0 = (1, 0): the clean source, after the
+ *       last step; row r >= 1 = (sqrt(abar), sqrt(1 - abar)) of timesteps[r], the noise level the next step expects.  A one-step
+ *       schedule falls on row 0.
+ *       Arithmetic, all fp32: t = coef[r][1] == 0 ? coef[r][0] * source : fma(coef[r][1], noise, coef[r][0] * source), where the
+ *       product with coef[r][0] == 1 is the source itself;
+ *       m == 1: the latent's bits are kept (nothing is computed: -0 survives, source and noise do not reach the output);
+ *       m == 0: the result is t, so with the row (1, 0) it is the source's bits; otherwise fma(1 - m, t, m * latent).
+ *       Grid: at most 2048 workgroups of 256 lanes stride over 16 KB tiles of 16-byte chunks, four chunks of every operand in flight
+ *       per lane; with hw % 4 != 0 (latent planes such as 5 x 7) every value finds its own mask value and the last numel % 4 values
+ *       take a scalar path.  No workspace, nothing allocated.
+ *       I2V_ERR_INVALID_ARG (nothing launched): a null pointer, images / channels / hw / coef_rows < 1, latents / source / noise / mask
+ *       not 16-byte or coef / step_idx not 4-byte aligned, latents overlapping source, noise or mask,
+ *       images * channels * hw >= 2^31 - 2^19. */
+int i2v_masked_renoise_f32(float* latents, const float* source, const float* noise, const float* mask, const float* coef, int32_t coef_rows,
+                           const int32_t* step_idx, int64_t images, int32_t channels, int32_t hw, i2v_stream_t stream);
 
 /* First-frame-similarity prior and the initial add_noise of the sampling loop, pipe:647-656:
  *   prior   = mask * GaussianBlur3x3(cond) + (1 - mask) * cond, mask = (mask_uniform < strength), per frame (pipe:648-654)

@@ -13,7 +13,8 @@ def __getattr__(name):
     # module classes are imported lazily so that `import i2v_adapter_unofficial_amd.kernels` stays light
     import importlib
     if name in ("blocks", "handle", "checkpoint", "sharding", "vae", "training", "profiling", "i2v_adapter", "unet_motion_cross_frame_attn",
-                "pipeline_i2v_adapter", "image_processor", "lora", "free_init", "free_noise", "clip_text", "clip_vision", "controlnet", "t2i_adapter", "autoencoder_tiny", "prompt_travel"):
+                "pipeline_i2v_adapter", "image_processor", "lora", "free_init", "free_noise", "clip_text", "clip_vision", "controlnet", "t2i_adapter", "autoencoder_tiny", "prompt_travel",
+                "prompt_weighting", "textual_inversion"):
         return importlib.import_module(f"{__name__}.{name}")
     for mod in ("i2v_adapter", "unet_motion_cross_frame_attn", "pipeline_i2v_adapter", "blocks", "sharding", "vae",
                 "image_processor", "checkpoint", "handle", "clip_text", "clip_vision", "controlnet", "t2i_adapter", "autoencoder_tiny"):

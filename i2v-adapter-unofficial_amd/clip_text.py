@@ -193,6 +193,27 @@ class CLIPTextModel(PretrainedMixin, HipModule):
             out[PREFIX + k if k not in target and PREFIX + k in target else k] = v
         return out
 
+    @torch.no_grad()
+    def resize_token_embeddings(self, new_num_tokens: int):
+        """transformers' `resize_token_embeddings` for the token table (textual inversion, textual_inversion.py): the table and
+        `config.vocab_size` grow (or shrink) to `new_num_tokens` rows.  The rows both tables have keep their bits; new rows are zero
+        until the loader writes them.  The kernel-layout pack is dropped (`i2v_clip_embed_f16` takes the row count as an argument
+        and the wrapper bounds-checks the ids against it on the host).  Returns the table."""
+        if isinstance(new_num_tokens, bool) or not isinstance(new_num_tokens, int) or new_num_tokens < 1:
+            raise ValueError(f"new_num_tokens must be an int >= 1, got {new_num_tokens!r}")
+        emb = self.text_model.embeddings
+        old = emb.token_embedding.weight
+        if new_num_tokens != old.shape[0]:
+            new = nn.Embedding(new_num_tokens, old.shape[1], device=old.device, dtype=old.dtype)
+            new.weight.zero_()
+            keep = min(new_num_tokens, old.shape[0])
+            new.weight[:keep] = old[:keep]
+            new.weight.requires_grad_(old.requires_grad)
+            emb.token_embedding = new
+            self.config["vocab_size"] = new_num_tokens
+        self._packed, self._packed_key = None, None
+        return emb.token_embedding
+
     # ------------------------------------------------------------------------------------------ kernel-layout weights
     def _pack(self):
         tm = self.text_model

@@ -1633,6 +1633,44 @@ def interp_rows(src, lo, hi, w, out=None):
     return out
 
 
+# ---------------------------------------------------------------------------------------------- prompt weighting (pipeline)
+def weight_embeds(src, weights, restore_mean=True, out=None):
+    """out[p, t, :] = fp16((src[p, t, :] * weights[p, t]) * r[p]) with r[p] = sum(src[p]) / sum(weights[p] * src[p]) over the whole
+    prompt in fp32, or exactly 1 without `restore_mean` (i2v_weight_embeds_f16).  src fp16 [P, T, D] with D a multiple of 8,
+    unit-stride rows and prompts T rows apart (the row stride is free: a column slice of a wider buffer is taken); weights fp32
+    [P, T] on src's device; out: as src, `src` itself for in place, None: a new contiguous tensor.  Returns (out, ratio) with ratio
+    fp32 [P] on the device; a ratio that is not finite left its prompt at src * weights -- the caller reads it and decides."""
+    lib = _lib.load()
+    _req(src, "src")
+    _req(weights, "weights", dtype=torch.float32)
+    if src.dim() != 3 or src.numel() < 1:
+        raise ValueError(f"weight_embeds: src must be a non-empty [P, T, D], got {tuple(src.shape)}")
+    n, t, d = src.shape
+    if d % 8:
+        raise ValueError(f"weight_embeds: D = {d} is not a multiple of 8")
+    if tuple(weights.shape) != (n, t) or weights.device != src.device:
+        raise ValueError(f"weight_embeds: weights must be [{n}, {t}] on src's device, got {tuple(weights.shape)} on {weights.device}")
+    weights = weights.contiguous()
+
+    def ld_of(x, name):
+        ld = x.stride(1) if t > 1 else max(x.stride(1), d)
+        if x.stride(2) != 1 or ld < d or ld % 8 or (n > 1 and x.stride(0) != t * ld):
+            raise ValueError(f"weight_embeds: {name} needs unit-stride rows, a row stride that is a multiple of 8 and at least {d}, and "
+                             f"prompts {t} rows apart; got strides {x.stride()}")
+        return ld
+    ld_src = ld_of(src, "src")
+    if out is None:
+        out = torch.empty((n, t, d), dtype=f16, device=src.device)
+    _req(out, "out")
+    if tuple(out.shape) != (n, t, d) or out.device != src.device:
+        raise ValueError(f"weight_embeds: out must be {(n, t, d)} on src's device, got {tuple(out.shape)}")
+    ld_out = ld_of(out, "out")
+    ratio = torch.empty(n, dtype=torch.float32, device=src.device)
+    _lib.check(lib.i2v_weight_embeds_f16(_p(src), _p(weights), _p(out), _p(ratio), n, t, d, ld_src, ld_out, 1 if restore_mean else 0,
+                                         _stream()), "i2v_weight_embeds_f16")
+    return out, ratio
+
+
 # ---------------------------------------------------------------------------------------------- video-to-video with a mask (pipeline)
 def masked_renoise(latents, source, noise, mask, coef, step_index):
     """In place: latents = m * latents + (1 - m) * (coef[r][0] * source + coef[r][1] * noise) (i2v_masked_renoise_f32), diffusers'

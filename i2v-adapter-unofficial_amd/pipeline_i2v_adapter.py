@@ -106,6 +106,146 @@ class I2VAdapterPipeline:
         self._graph = None
         self._graph_cache = {}
         self._free_init = None
+        self._prompt_weighting = None
+        self._textual_inversions = []
+
+    # ------------------------------------------------------------------------------------------ textual inversion
+    def load_textual_inversion(self, pretrained_model_name_or_path_or_dict, token=None, weight_name=None, subfolder=None):
+        """diffusers' `TextualInversionLoaderMixin.load_textual_inversion` (textual_inversion.py): a file (`.safetensors`,
+        or `.bin` / `.pt` through `torch.load(..., weights_only=True)`), a directory plus `weight_name`, a state dict, or a list of
+        these with a list of `token`.  Formats: {token: tensor [D] or [n, D]} with one key (diffusers) and {"string_to_param": {"*":
+        tensor [n, D]}, "name": str} (A1111); `token` overrides the file's.  n vectors add the tokens tok, tok_1, ... tok_{n-1} to the
+        tokenizer and n rows to the text encoder's token table (`CLIPTextModel.resize_token_embeddings`).  ValueError, with nothing
+        modified: an embedding whose width is not the text encoder's hidden size, a token (or one of its multi-vector names) the
+        tokenizer already has, a pipeline without text encoder or tokenizer, several keys without `token`."""
+        from . import textual_inversion as TI
+        TI.load(self, pretrained_model_name_or_path_or_dict, token=token, weight_name=weight_name, subfolder=subfolder)
+
+    def unload_textual_inversion(self, tokens=None):
+        """diffusers' `unload_textual_inversion`: all loaded inversions, or those whose token is in `tokens`.  With all of them gone the
+        token table and `config.vocab_size` are the original ones, bit for bit.  A tokenizer with `remove_tokens(list)` gives the ids
+        back (inversions that stay are re-added at compact ids); transformers' CLIPTokenizer cannot remove a token, so there the ids
+        stay RESERVED in the tokenizer -- an unloaded token's text still tokenises to its ids, which are past the table, and encoding
+        it raises -- and the table keeps its rows up to the last id still loaded."""
+        from . import textual_inversion as TI
+        TI.unload(self, tokens)
+
+    def maybe_convert_prompt(self, prompt, tokenizer):
+        """diffusers' `maybe_convert_prompt` (pipe:409, 491): every multi-vector token the tokenizer finds in the prompt (a str or a
+        list of str) is written out as `tok tok_1 ... tok_{n-1}`.  The prompt itself, unchanged, when nothing is loaded."""
+        from . import textual_inversion as TI
+        return TI.convert_prompt(self, prompt, tokenizer)
+
+    # ------------------------------------------------------------------------------------------ weighted and long prompts
+    def enable_prompt_weighting(self, max_embeddings_multiples: int = 3, restore_mean: bool = True):
+        """Weighted and long prompts (prompt_weighting.py): while enabled, `__call__` and `encode_prompt_travel` encode
+        through `encode_weighted_prompt` -- `(text)` x 1.1, `[text]` / 1.1, `(text:1.5)`, nested and escaped as in the SD-1.5 front
+        ends -- and a prompt may fill up to `max_embeddings_multiples` chunks of `model_max_length - 2` tokens (3: 225 tokens, a
+        context of 231 rows).  restore_mean: every prompt is rescaled to the mean it had before the weights.  A context longer than
+        `model_max_length` leaves the fused text cross-attention for `i2v_attention_f16` (README: the measured price).  The longest
+        context that path takes is `prompt_weighting.max_context_tokens()` -- 419 302 tokens at SD-1.5's 1280-wide K, from
+        i2v_attention_f16's 32-bit addressing of one K slice -- and a setting that can exceed it raises ValueError."""
+        from . import prompt_weighting as PW
+        PW.check_settings(max_embeddings_multiples, restore_mean)
+        if self.tokenizer is not None:
+            self._check_context_length(max_embeddings_multiples * self.tokenizer.model_max_length)
+        self._prompt_weighting = dict(max_embeddings_multiples=max_embeddings_multiples, restore_mean=restore_mean)
+
+    def disable_prompt_weighting(self):
+        self._prompt_weighting = None
+
+    @property
+    def prompt_weighting_enabled(self):
+        return self._prompt_weighting is not None
+
+    def _check_context_length(self, tokens):
+        from .prompt_weighting import max_context_tokens
+        cfg = getattr(self.unet, "config", None)
+        widest = max(getattr(cfg, "block_out_channels", None) or (1280,))
+        limit = max_context_tokens(widest)
+        if tokens > limit:
+            raise ValueError(f"a text context of {tokens} tokens exceeds the {limit} that the cross-attention takes (i2v_attention_f16 "
+                             f"addresses one K slice of {widest}-wide rows with 32 bits): lower `max_embeddings_multiples`")
+
+    def _encode_weighted_texts(self, groups, clip_skip=None):
+        """[sum(len(g)), n * M, D]: the weighted embeddings of lists of prompts, every list through the text encoder in one call of
+        [len(g) * n, M] ids (chunks in prompt-major order); n, the chunk count, is the largest any text of ANY list needs.  One
+        `K.weight_embeds` launch, in place, for all of them, and one read of the ratios."""
+        from . import prompt_weighting as PW
+        if self.text_encoder is None or self.tokenizer is None:
+            raise ValueError("encoding a `prompt` needs both a `text_encoder` and a `tokenizer`: build the pipeline with them, or pass "
+                             "`prompt_embeds` (and `negative_prompt_embeds`)")
+        if getattr(self.text_encoder.config, "use_attention_mask", None):
+            raise NotImplementedError("text_encoder.config.use_attention_mask: padding attention masks are not implemented")
+        cfg = self._prompt_weighting or dict(max_embeddings_multiples=3, restore_mean=True)
+        tok, m = self.tokenizer, self.tokenizer.model_max_length
+        bos, eos, pad = PW.special_ids(tok)
+        flat = [t for g in groups for t in g]
+        if not flat or not all(isinstance(t, str) for t in flat):
+            raise ValueError("a weighted prompt is a str (or a list of str)")
+        pairs = [PW.truncate(tok, *PW.token_weights(tok, self.maybe_convert_prompt(t, tok)), m, cfg["max_embeddings_multiples"])
+                 for t in flat]
+        n = max(PW.chunks_needed(len(ids), m) for ids, _ in pairs)
+        self._check_context_length(n * m)
+        rows = [PW.chunk(ids, w, m, bos, eos, pad, n) for ids, w in pairs]
+        embeds, first = [], 0
+        for g in groups:
+            ids = torch.tensor([r for id_rows, _ in rows[first: first + len(g)] for r in id_rows], dtype=torch.int64)
+            first += len(g)
+            if clip_skip is None:
+                e = self.text_encoder(ids, attention_mask=None)[0]
+            else:
+                e = self.text_encoder(ids, attention_mask=None, output_hidden_states=True)[-1][-(clip_skip + 1)]
+                e = self.text_encoder.text_model.final_layer_norm(e)
+            embeds.append(e.reshape(len(g), n * m, e.shape[-1]))
+        src = (embeds[0] if len(embeds) == 1 else torch.cat(embeds)).contiguous()
+        if src.dtype != f16:
+            raise HipLibraryError(f"prompt weighting scales fp16 embeddings (i2v_weight_embeds_f16), the text encoder gives {src.dtype}")
+        weights = torch.tensor([[x for r in w_rows for x in r] for _, w_rows in rows], dtype=torch.float32).to(src.device)
+        out, ratio = K.weight_embeds(src, weights, restore_mean=cfg["restore_mean"], out=src)
+        bad = (~torch.isfinite(ratio.cpu())).nonzero()
+        if bad.numel():
+            i = int(bad[0])
+            raise ValueError(f"prompt weighting: the weights of prompt {i} ({flat[i]!r}) cancel the mean of its embedding (the ratio "
+                             "unweighted mean / weighted mean is not finite): change the weights, or "
+                             "enable_prompt_weighting(restore_mean=False)")
+        return out
+
+    def encode_weighted_prompt(self, prompt, device, num_videos_per_prompt, do_classifier_free_guidance, negative_prompt=None,
+                               clip_skip=None):
+        """`encode_prompt` for weighted and long prompts: (prompt_embeds, negative_prompt_embeds), each [B * num_videos_per_prompt,
+        n * M, D] with M the tokenizer's `model_max_length` and n the chunk count of the longest text of the call, the negative
+        prompts included (None without classifier-free guidance).  Textual-inversion conversion first, then
+        `prompt_weighting.parse_prompt_attention`, every segment tokenised on its own, chunks of [bos] + M - 2 ids + [eos] + [pad]...,
+        ids beyond `max_embeddings_multiples` chunks dropped with a warning.  The prompts' chunks go through the text encoder in one
+        call and the negative prompts' in another -- the calls `encode_prompt` makes, so an unweighted prompt of at most M - 2 tokens
+        gives `encode_prompt`'s embeddings bit for bit (the library's GEMM routes depend on the row count) -- and ONE
+        `i2v_weight_embeds_f16` launch weighs all of them.  `clip_skip` as in `encode_prompt`.  ValueError: weights that cancel a
+        prompt's mean under `restore_mean`.  Works whether or not weighting is enabled (`enable_prompt_weighting` holds the settings;
+        the defaults otherwise)."""
+        if isinstance(prompt, str):
+            prompts = [prompt]
+        elif isinstance(prompt, (list, tuple)) and prompt:
+            prompts = list(prompt)
+        else:
+            raise ValueError(f"`prompt` has to be a `str` or a non-empty `list` but is {type(prompt)}")
+        groups = [prompts]
+        if do_classifier_free_guidance:
+            if negative_prompt is None:
+                negatives = [""] * len(prompts)
+            elif isinstance(negative_prompt, str):
+                negatives = [negative_prompt] * len(prompts)
+            elif len(negative_prompt) != len(prompts):
+                raise ValueError(f"`negative_prompt`: {negative_prompt} has batch size {len(negative_prompt)}, but `prompt`: {prompt} has "
+                                 f"batch size {len(prompts)}.")
+            else:
+                negatives = list(negative_prompt)
+            groups.append(negatives)
+        dtype = self.text_encoder.dtype if self.text_encoder is not None else f16
+        out = self._encode_weighted_texts(groups, clip_skip).to(device=device, dtype=dtype)
+        b = len(prompts)
+        rep = lambda t: t.repeat(1, num_videos_per_prompt, 1).view(b * num_videos_per_prompt, t.shape[1], -1)
+        return rep(out[:b]), (rep(out[b:]) if do_classifier_free_guidance else None)
 
     def enable_vae_slicing(self):
         """pipe:122-128: decode the frames one at a time (peak activation memory / num_frames)."""
@@ -797,8 +937,10 @@ class I2VAdapterPipeline:
         encoder (clip_text.CLIPTextModel on the HIP kernels), `clip_skip` (`hidden_states[-(clip_skip + 1)]` through
         `final_layer_norm`), the per-prompt repeat, and the negative prompt ("" when none is given) under classifier-free guidance.
         Returns (prompt_embeds, negative_prompt_embeds).  `lora_scale` is accepted and ignored (text-encoder LoRA keys are skipped and
-        reported by `load_lora_weights`); there is no textual inversion.  `self.tokenizer` is used as given: any object with
-        CLIPTokenizer's call interface and `model_max_length`."""
+        reported by `load_lora_weights`).  Textual inversion: `maybe_convert_prompt` on the prompt and on the negative prompt, as the
+        reference does (pipe:409, 491); with nothing loaded it returns them unchanged.  `self.tokenizer` is used as given: any object
+        with CLIPTokenizer's call interface and `model_max_length`.  A prompt beyond 77 tokens is truncated and `(text:1.3)` is literal
+        text here: `enable_prompt_weighting` / `encode_weighted_prompt` is the path for long and weighted prompts."""
         if prompt is not None and isinstance(prompt, str):
             batch_size = 1
         elif prompt is not None and isinstance(prompt, list):
@@ -813,6 +955,7 @@ class I2VAdapterPipeline:
             raise NotImplementedError("text_encoder.config.use_attention_mask: padding attention masks are not implemented")
 
         if prompt_embeds is None:
+            prompt = self.maybe_convert_prompt(prompt, self.tokenizer)                          # pipe:409 (textual inversion)
             text_inputs = self.tokenizer(prompt, padding="max_length", max_length=self.tokenizer.model_max_length, truncation=True,
                                          return_tensors="pt")
             text_input_ids = text_inputs.input_ids
@@ -856,6 +999,7 @@ class I2VAdapterPipeline:
                                  " the batch size of `prompt`.")
             else:
                 uncond_tokens = negative_prompt
+            uncond_tokens = self.maybe_convert_prompt(uncond_tokens, self.tokenizer)            # pipe:491 (textual inversion)
             max_length = prompt_embeds.shape[1]
             uncond_input = self.tokenizer(uncond_tokens, padding="max_length", max_length=max_length, truncation=True,
                                           return_tensors="pt")
@@ -878,6 +1022,7 @@ class I2VAdapterPipeline:
                              "`prompt_embeds` (and `negative_prompt_embeds`)")
         if getattr(self.text_encoder.config, "use_attention_mask", None):
             raise NotImplementedError("text_encoder.config.use_attention_mask: padding attention masks are not implemented")
+        texts = self.maybe_convert_prompt(texts, self.tokenizer)
         ids = self.tokenizer(texts, padding="max_length", max_length=self.tokenizer.model_max_length, truncation=True,
                              return_tensors="pt").input_ids
         if clip_skip is None:
@@ -920,7 +1065,10 @@ class I2VAdapterPipeline:
                 keyframes.append(keys)
                 texts.extend(d[k] for k in keys)
         dtype = self.text_encoder.dtype if self.text_encoder is not None else f16
-        src = self._encode_texts(texts, clip_skip).to(device=device, dtype=dtype).contiguous()
+        # (while prompt weighting is enabled the source rows are the weighted embeddings, [K, n * M, D]: every keyframe text of the
+        # batch padded to the chunk count of the longest)
+        encode = (lambda t, s: self._encode_weighted_texts([t], s)) if self._prompt_weighting is not None else self._encode_texts
+        src = encode(texts, clip_skip).to(device=device, dtype=dtype).contiguous()
         if src.dtype != f16:
             raise HipLibraryError(f"prompt travel interpolates fp16 embeddings (i2v_interp_rows_f16), the text encoder gives {src.dtype}")
         lo, hi, w, n_src = PT.batch_tables(keyframes, num_frames, repeats=num_videos_per_prompt)
@@ -1075,6 +1223,12 @@ class I2VAdapterPipeline:
                 pe, ne = self.encode_prompt_travel(prompt, num_frames, self.unet.device, num_videos_per_prompt,
                                                    guidance_scale > 1.0 and negative_prompt_embeds is None, negative_prompt,
                                                    clip_skip=clip_skip)
+                prompt_embeds, negative_prompt_embeds = pe, ne if negative_prompt_embeds is None else negative_prompt_embeds
+            elif self._prompt_weighting is not None:
+                # weighted and long prompts: contexts of n * 77 rows (a given `negative_prompt_embeds` is kept)
+                pe, ne = self.encode_weighted_prompt(prompt, self.unet.device, num_videos_per_prompt,
+                                                     guidance_scale > 1.0 and negative_prompt_embeds is None, negative_prompt,
+                                                     clip_skip=clip_skip)
                 prompt_embeds, negative_prompt_embeds = pe, ne if negative_prompt_embeds is None else negative_prompt_embeds
             else:
                 prompt_embeds, negative_prompt_embeds = self.encode_prompt(
@@ -1370,6 +1524,14 @@ def build_parser():
                              "{\"0\": \"...\", \"32\": \"...\"} (frame index -> prompt; the first key is 0, the last below num_frames); "
                              "the frames in between get interpolated embeddings.  An empty cell keeps the row's `name` prompt.  Not "
                              "with --embeds")
+    parser.add_argument("--prompt_weighting", type=int, nargs="?", const=3, default=None, metavar="N",
+                        help="weighted and long prompts (pipe.enable_prompt_weighting): `(text:1.3)` / `(text)` / `[text]` emphasis in the "
+                             "prompts, the negative prompt and the keyframes of --prompt_travel_column, and prompts of up to N chunks of "
+                             "75 tokens (3 when given without a value); off by default.  Not with --embeds")
+    parser.add_argument("--textual_inversion", action="append", default=[], metavar="PATH[:TOKEN]",
+                        help="a textual-inversion embedding (.safetensors / .bin / .pt; diffusers or A1111 format) added to the "
+                             "tokenizer and the text encoder, with an optional token that replaces the file's; repeatable.  Not with "
+                             "--embeds")
     parser.add_argument("--model_path", type=str, default="./SG161222_Realistic_Vision_V5.1_noVAE/")
     parser.add_argument("--motion_adapter_path", type=str, default="./animatediff-motion-adapter-v1-5-2")
     parser.add_argument("--ip_adapter_path", type=str, default="./IP-Adapter/")
@@ -1521,6 +1683,13 @@ def main(argv=None):
     if args.prompt_travel_column is not None and args.embeds is not None:
         logger.error("--prompt_travel_column needs the text encoder: it is not combined with --embeds.")
         return -1
+    if args.embeds is not None and (args.prompt_weighting is not None or args.textual_inversion):
+        flag = "--prompt_weighting" if args.prompt_weighting is not None else "--textual_inversion"
+        logger.error(f"{flag} needs the text encoder: it is not combined with --embeds.")
+        return -1
+    if args.prompt_weighting is not None and args.prompt_weighting < 1:
+        logger.error(f"--prompt_weighting {args.prompt_weighting}: the number of chunks is at least 1.")
+        return -1
     if args.video_column is None and (args.strength is not None or args.mask_column is not None):
         logger.error("--strength and --mask_column need a source clip: --video_column.")
         return -1
@@ -1595,6 +1764,12 @@ def main(argv=None):
             pipe.set_ip_adapter_scale(args.ip_adapter_scale)
     pipe.to(device, torch.float16)
     pipe.enable_vae_slicing()                                                                    # pipe:787
+    for spec in args.textual_inversion:
+        path, _, token = spec.rpartition(":") if ":" in spec and not os.path.exists(spec) else (spec, "", "")
+        pipe.load_textual_inversion(path, token=token or None)
+        logger.info(f"Successfully loaded the textual inversion {path}.")
+    if args.prompt_weighting is not None:
+        pipe.enable_prompt_weighting(max_embeddings_multiples=args.prompt_weighting)
     if args.freeu is not None:
         pipe.enable_freeu(*args.freeu)
     if args.vae_tiling:

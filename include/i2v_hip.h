@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define I2V_ABI_VERSION 26
+#define I2V_ABI_VERSION 27
 
 #define I2V_OK 0
 #define I2V_ERR_INVALID_ARG (-1)
@@ -922,6 +922,28 @@ int i2v_interp_rows_f16(const void* src, int64_t ld_src, int32_t n_src, const in
  *       images * channels * hw >= 2^31 - 2^19. */
 int i2v_masked_renoise_f32(float* latents, const float* source, const float* noise, const float* mask, const float* coef, int32_t coef_rows,
                            const int32_t* step_idx, int64_t images, int32_t channels, int32_t hw, i2v_stream_t stream);
+
+/* (ABI 27) Prompt weighting (the `(text:1.3)` / `[text]` emphasis syntax of SD-1.5 front ends; pipeline `enable_prompt_weighting` /
+ * `encode_weighted_prompt`): every token's embedding times its weight, then the prompt rescaled to its unweighted mean.  Once per sample.
+ *       S0[p] = sum src[p, t, c],  S1[p] = sum weights[p, t] * src[p, t, c]      over all tokens * dim values of prompt p, fp32
+ *       r[p]  = restore_mean ? S0[p] / S1[p] : exactly 1.0f
+ *       out[p, t, c] = fp16_rn((float(src[p, t, c]) * weights[p, t]) * r[p])      two fp32 multiplies in that order, one rounding
+ *       src fp16 [n_prompts, tokens, dim] and out the same, token rows ld_src / ld_out values apart (>= dim, multiples of 8; prompt p
+ *       starts at row p * tokens); weights fp32 [n_prompts, tokens] contiguous; ratio_out fp32 [n_prompts] or NULL receives r[p].
+ *       All DEVICE memory.  dim % 8 == 0: rows are read and written 16 bytes at a time.
+ *       A ratio that is not finite (the weights cancel the prompt's mean, or the mean is 0 / 0) is written to ratio_out as it is and
+ *       the outputs take r = 1: out = fp16_rn(src * w).  The caller reads ratio_out and decides (the pipeline raises ValueError).
+ *       Order of the sums, fixed: per lane over the 16-byte chunks q = lane, lane + 1024, ... (chunk q = token q / (dim / 8), its 8
+ *       values in order), then the wave's xor butterfly (1, 2, ... 32), then the 16 waves' partials in wave order.  Repeats are
+ *       bit-equal; with all weights 1 S1 is S0's sequence of operations, so r == 1.0f and out equals src bit for bit.
+ *       In place: out == src with ld_out == ld_src is allowed (a prompt belongs to one workgroup, whose barrier between the sums and
+ *       the apply orders every load of pass 1 before any store of pass 2); any other overlap is refused.
+ *       Grid: one workgroup of 1024 lanes per prompt, both passes in it; the apply re-reads src (L2).  No atomics, no workspace.
+ *       I2V_ERR_INVALID_ARG (nothing launched): a null src / weights / out, n_prompts or tokens < 1, dim no positive multiple of 8, a
+ *       stride below dim or no multiple of 8, src / out not 16-byte or weights / ratio_out not 4-byte aligned, tokens * stride >= 2^31
+ *       (the kernel indexes a prompt with 32 bits), out overlapping src other than in place, out overlapping weights or ratio_out. */
+int i2v_weight_embeds_f16(const void* src, const float* weights, void* out, float* ratio_out, int32_t n_prompts, int32_t tokens,
+                          int32_t dim, int64_t ld_src, int64_t ld_out, int32_t restore_mean, i2v_stream_t stream);
 
 /* First-frame-similarity prior and the initial add_noise of the sampling loop, pipe:647-656:
  *   prior   = mask * GaussianBlur3x3(cond) + (1 - mask) * cond, mask = (mask_uniform < strength), per frame (pipe:648-654)

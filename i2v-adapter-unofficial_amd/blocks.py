@@ -738,6 +738,9 @@ FUSED_FF_TAIL = os.environ.get("I2V_FF_TAIL", "1") != "0"       # proj_out (+ re
 # to_out (+ residual) inside the fused attention launches (r5: the fourth pass costs nearly what the HBM-bound GEMM it replaces
 # does -- same-box -0.1 .. -0.3 ms per step on every configuration, profiles/r5_attn_outproj.txt)
 FUSED_ATTN_OUT = os.environ.get("I2V_ATTN_OUTP", "1") != "0"
+# the 32^2 level's motion attention sub-block (C = 640, 16 frames) in one launch on 64-row tiles (K.motion_attn_wide; to_out and the
+# residual are always inside, so it also needs FUSED_MOTION_ATTN and FUSED_ATTN_OUT); 0: the un-fused chain at that level
+FUSED_MOTION_ATTN_WIDE = os.environ.get("I2V_MOTION_FUSED_WIDE", "1") != "0"
 
 
 class TemporalTransformerBlock(HipModule):
@@ -846,12 +849,18 @@ class TemporalTransformerBlock(HipModule):
         c = self.dim
         overlap = t.shape[0] <= streams.MAX_ROWS       # q|k beside V^T on two streams where neither fills the chip
         fused = FUSED_MOTION_ATTN and K.motion_attn_supported(t.shape[0], c, self.heads, self.dim_head, frames)
+        wide = (not fused and FUSED_MOTION_ATTN and FUSED_ATTN_OUT and FUSED_MOTION_ATTN_WIDE and self.free_noise is None and
+                K.motion_attn_wide_supported(t.shape[0], c, self.heads, self.dim_head, frames))
         for i in (1, 2):
-            if fused:      # LayerNorm + pe, q / k / v and the attention over the frames in one launch (64^2 level of SD-1.5)
+            if fused or wide:      # LayerNorm + pe, q / k / v and the attention over the frames in one launch
                 tab = self._ma_tables.get((i, frames))
                 if tab is None:
                     tab = self._ma_tables[(i, frames)] = K.motion_attn_tables(p[f"g{i}"], p[f"b{i}"], p["pe"], frames)
-                if FUSED_ATTN_OUT:
+                if wide:           # 32^2 level of SD-1.5: 64-row tiles, to_out + residual always inside
+                    t = K.motion_attn_wide(t, tab[0], tab[1], p[f"wqkv{i}"], heads=self.heads, head_dim=self.dim_head, frames=frames,
+                                           eps=self.eps, out_proj=p[f"wo_frag{i}"])
+                    continue
+                if FUSED_ATTN_OUT:     # (64^2 level)
                     t = K.motion_attn(t, tab[0], tab[1], p[f"wqkv{i}"], heads=self.heads, head_dim=self.dim_head, frames=frames,
                                       eps=self.eps, out_proj=p[f"wo_frag{i}"])
                     continue

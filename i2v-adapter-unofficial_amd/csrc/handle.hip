@@ -37,7 +37,7 @@ enum Entry {
   E_GEMM = 0, E_ATTN, E_TATTN, E_MOTION_ATTN, E_CROSS_ATTN_FUSED, E_LN_QKV, E_FF_FUSED, E_GROUPNORM, E_LAYERNORM,      // struct + stream
   E_GROUPNORM_FOLD, E_NCHW_TO_TOKENS, E_TOKENS_TO_NCHW, E_TIMESTEP_EMBEDDING, E_SILU, E_REPEAT_ROWS, E_COPY3D, E_SELECT_ROW,
   E_PACK_CTX_FRAGMENTS, E_DDIM_PREP, E_DDIM_CFG_STEP, E_DPM_CFG_STEP, E_FREEU, E_LCM_CFG_STEP, E_FREENOISE_GATHER,
-  E_FREENOISE_BLEND, E_COUNT
+  E_FREENOISE_BLEND, E_MOTION_ATTN_WIDE, E_COUNT
 };
 struct EntryInfo {
   const char* name;
@@ -70,6 +70,7 @@ const EntryInfo ENTRIES[E_COUNT] = {
     {"i2v_lcm_cfg_step", 0, 15},
     {"i2v_freenoise_gather_f16", 0, 10},
     {"i2v_freenoise_blend_f16", 0, 12},
+    {"i2v_motion_attn_wide_f16", sizeof(i2v_motion_attn_params), 0},
 };
 inline uint32_t pad8(uint32_t n) { return (n + 7u) & ~7u; }
 
@@ -425,6 +426,7 @@ extern "C" int i2v_unet_run(i2v_unet* h, const void* const* io_args, int32_t n_i
         rc = i2v_freenoise_blend_f16(P(0), I(1), P(2), I(3), reinterpret_cast<const int32_t*>(P(4)), reinterpret_cast<const float*>(P(5)), I(6),
                                      (int32_t)I(7), (int32_t)I(8), (int32_t)I(9), (int32_t)I(10), (int32_t)I(11), stream);
         break;
+      case E_MOTION_ATTN_WIDE: rc = i2v_motion_attn_wide_f16(reinterpret_cast<const i2v_motion_attn_params*>(buf), stream); break;
       default: I2V_FAIL(I2V_ERR_UNSUPPORTED, "i2v_unet_forward: launch %u names entry point %u", i, op.entry);
     }
     if (rc != I2V_OK) return rc;      // (i2v_last_error holds the entry point's own message)

@@ -28,6 +28,10 @@
 //   * the LayerNorm phase was a quarter of the tile (12k of 50k cycles: an HBM round trip, then 11 VALU operations per element):
 //     the next tile's rows are fetched into registers before the v pass and arrive under it, gamma and (beta + pe[frame]) come
 //     as fp32 tables (no conversions, one add less): 6.5 operations per element.
+//
+// The 32^2 level (C = 640, 8 heads of 80; i2v_motion_attn_wide_f16) is the same kernel on tiles of 64 rows (4 pixels): the two
+// panels are again 2 x 80 KB, a wave normalises 8 rows of the next tile, d = 80 is five whole channel tiles.  One launch of 117 us
+// for the sub-block against 177 us for the four launches it replaces (profiles/motion_attn_wide_ab.txt).
 #include <stdlib.h>
 
 #include <type_traits>
@@ -54,7 +58,7 @@ __device__ __forceinline__ int ma_opaque(int v) {
   return v;
 }
 
-constexpr int MA_PIX = 8;              // pixels per tile (x 16 frames = 128 rows)
+constexpr int MA_PIX = 8;              // pixels per tile (x 16 frames = 128 rows) of the C = 320 forms; a template parameter (PIX)
 constexpr int MA_F = 16;               // frames per pixel: one MFMA tile
 constexpr int MA_PD = 3;               // weight fragments in flight (K steps ahead)
 constexpr int MA_AD = 4;               // panel fragments in flight (reads ahead of the MFMAs that take them)
@@ -88,12 +92,18 @@ constexpr int MA_KT = 5;               // CROSS: key tiles of 16 (<= 80 context 
 //   outputs meet in the tile's panel once every wave has left it (barrier), a fourth pass projects them (wave w: output channels
 //   40 w .. + 39), the residual rows are requested while the attention runs and are the accumulators' initial values.  o never
 //   goes to memory (84 MB each way at the 64^2 level) and the HBM-bound 131072 x 320 x 320 + residual GEMM launch disappears.
-template <int C, int D, int H, bool CROSS, int F = 16, bool OUTP = false>
+// PIX: 16-row MFMA tiles ("pixels" at F = 16) per workgroup tile.  The two panels are 2 x 16 PIX x C halfs: 8 at C = 320 and 4 at
+//   C = 640 (the 32^2 level: 8 heads of 80, five channel tiles and no padding) are both the CU's 160 KB.  A wave normalises
+//   16 PIX / 8 rows of the next tile (8 at PIX = 4: one group of 8 rows instead of two) and holds PIX x DT accumulators per pass
+//   (4 x 5 against 8 x 3); per row the workgroup streams twice the weight fragments.
+template <int C, int D, int H, bool CROSS, int F = 16, bool OUTP = false, int PIX = MA_PIX>
 __global__ __launch_bounds__(64 * H) void motion_attn_kernel(const ma_args p, const float scale_log2, const int ntiles,
                                                              long long* __restrict__ stamps) {
   constexpr int DT = (D + 15) / 16, DP = 16 * DT, KS = C / 32, NJ = C / 64, PARTS = CROSS ? 1 : 3;
+  constexpr int RW = PIX * MA_F / H, HALVES = RW / 8;      // rows a wave fetches and normalises, in groups of 8 (one DMA instruction)
   static_assert(C % 64 == 0 && H == 8, "one wave per head, 8 lanes x C / 64 chunks per row in the LayerNorm pass");
   static_assert(F == 8 || F == 16 || F == 32, "frames per pixel");
+  static_assert(RW % 8 == 0 && PIX % (F == 32 ? 2 : 1) == 0, "whole groups of 8 rows per wave, whole pixels per tile");
   extern __shared__ __attribute__((aligned(16))) f16 panels[];       // 2 x [128][C], chunk index ^= row & 7
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // (wave-uniform: SGPR)
   const int g = lane >> 4, l15 = lane & 15, sub = lane & 7;
@@ -112,42 +122,49 @@ __global__ __launch_bounds__(64 * H) void motion_attn_kernel(const ma_args p, co
   // normalised in place: read whole into registers, then written to their swizzled places -- no register holds a row while the
   // DMA is in flight under the v pass of the previous tile (held in registers there, they spilled: 259 dwords, 121 -> 230 us).
   auto fetch_rows = [&](const int tile, f16* panel) {
-    const f16* base = X + ((int64_t)tile * (MA_PIX * MA_F) + 16 * wave) * p.ldx;        // (wave-uniform)
-    const auto rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<f16*>(base), 0, (int)((15 * p.ldx + C) * 2), 0x00020000);
+    const f16* base = X + ((int64_t)tile * (PIX * MA_F) + RW * wave) * p.ldx;        // (wave-uniform)
+    const auto rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<f16*>(base), 0, (int)(((RW - 1) * p.ldx + C) * 2), 0x00020000);
     const int ln = ma_opaque(lane);
     const unsigned voff = (unsigned)(((ln >> 3) * p.ldx + (ln & 7) * 8) * 2);      // the instruction's part is a scalar offset
 #pragma unroll
-    for (int half = 0; half < 2; ++half)
+    for (int half = 0; half < HALVES; ++half)
 #pragma unroll
       for (int j = 0; j < NJ; ++j)
-        ma_dma16(rs, panel + 16 * wave * C + (half * NJ + j) * 512, voff, (unsigned)((8 * half * p.ldx + 8 * j * 8) * 2));
+        ma_dma16(rs, panel + RW * wave * C + (half * NJ + j) * 512, voff, (unsigned)((8 * half * p.ldx + 8 * j * 8) * 2));
   };
+  // (NJ > 5, the C = 640 form: a row's slice is 80 values per lane, and gamma, the shift row and the values together would be 240
+  // registers -- there the two tables are read per 64-channel column where they are applied instead of ahead of the row's sums)
+  constexpr bool LATE_TABLES = NJ > 5;
   auto normalise_rows = [&](f16* panel) {
-    f16x8 xv[2][NJ];
+    f16x8 xv[HALVES][NJ];
 #pragma unroll
-    for (int half = 0; half < 2; ++half)
+    for (int half = 0; half < HALVES; ++half)
 #pragma unroll
-      for (int j = 0; j < NJ; ++j) xv[half][j] = *reinterpret_cast<const f16x8*>(panel + 16 * wave * C + ((half * NJ + j) * 64 + lane) * 8);
+      for (int j = 0; j < NJ; ++j) xv[half][j] = *reinterpret_cast<const f16x8*>(panel + RW * wave * C + ((half * NJ + j) * 64 + lane) * 8);
     // (the tables are loop invariants: without the opaque copies of their addresses the compiler keeps all 120 registers of
     // them live through the three passes of every tile -- 207 spilled dwords)
     const float* gp = gamma;
     const float* sp = shift;
     asm volatile("" : "+s"(gp), "+s"(sp));
     f32x4 ga[NJ][2];
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-      ga[j][0] = *reinterpret_cast<const f32x4*>(gp + (sub + 8 * j) * 8);
-      ga[j][1] = *reinterpret_cast<const f32x4*>(gp + (sub + 8 * j) * 8 + 4);
-    }
-#pragma unroll
-    for (int half = 0; half < 2; ++half) {
-      const int row = 16 * wave + 8 * half + (lane >> 3);
-      const float* sh = sp + (int64_t)((16 * wave + 8 * half + (lane >> 3)) & (F - 1)) * p.ld_shift;   // (tiles start at frame 0)
-      f32x4 sv[NJ][2];
+    if constexpr (!LATE_TABLES) {
 #pragma unroll
       for (int j = 0; j < NJ; ++j) {
-        sv[j][0] = *reinterpret_cast<const f32x4*>(sh + (sub + 8 * j) * 8);
-        sv[j][1] = *reinterpret_cast<const f32x4*>(sh + (sub + 8 * j) * 8 + 4);
+        ga[j][0] = *reinterpret_cast<const f32x4*>(gp + (sub + 8 * j) * 8);
+        ga[j][1] = *reinterpret_cast<const f32x4*>(gp + (sub + 8 * j) * 8 + 4);
+      }
+    }
+#pragma unroll
+    for (int half = 0; half < HALVES; ++half) {
+      const int row = RW * wave + 8 * half + (lane >> 3);
+      const float* sh = sp + (int64_t)((RW * wave + 8 * half + (lane >> 3)) & (F - 1)) * p.ld_shift;   // (tiles start at frame 0)
+      f32x4 sv[NJ][2];
+      if constexpr (!LATE_TABLES) {
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+          sv[j][0] = *reinterpret_cast<const f32x4*>(sh + (sub + 8 * j) * 8);
+          sv[j][1] = *reinterpret_cast<const f32x4*>(sh + (sub + 8 * j) * 8 + 4);
+        }
       }
       float v[NJ][8];
       float s = 0.f;
@@ -173,6 +190,12 @@ __global__ __launch_bounds__(64 * H) void motion_attn_kernel(const ma_args p, co
 #pragma unroll
       for (int j = 0; j < NJ; ++j) {
         const int ch = sub + 8 * j;
+        if constexpr (LATE_TABLES) {
+          ga[j][0] = *reinterpret_cast<const f32x4*>(gp + ch * 8);
+          ga[j][1] = *reinterpret_cast<const f32x4*>(gp + ch * 8 + 4);
+          sv[j][0] = *reinterpret_cast<const f32x4*>(sh + ch * 8);
+          sv[j][1] = *reinterpret_cast<const f32x4*>(sh + ch * 8 + 4);
+        }
         f16x8 o;
 #pragma unroll
         for (int e = 0; e < 8; ++e) o[e] = (f16)fmaf(v[j][e] * rstd, ga[j][e >> 2][e & 3], sv[j][e >> 2][e & 3]);
@@ -190,7 +213,7 @@ __global__ __launch_bounds__(64 * H) void motion_attn_kernel(const ma_args p, co
   // (chunk 4 s + g of a K step swizzled by the row: ((4 s + g) ^ sw) = 8 (s >> 1) + ((4 (s & 1) + g) ^ sw) -- TWO lane-dependent offsets
   //  and an immediate instead of one hoisted register per K step)
   const int swz[2] = {(g ^ sw) * 8, ((4 + g) ^ sw) * 8};
-  f32x4 acc[MA_PIX][DT];
+  f32x4 acc[PIX][DT];
   auto zero_init = [](const int, const int) { return f32x4{0.f, 0.f, 0.f, 0.f}; };
   // (wp: byte offset of the wave's fragments of this pass in `rs`; (DP C = KS DT 512 halfs per part) + (s DT + t) 1024)
   auto no_hook = []() {};
@@ -202,7 +225,7 @@ __global__ __launch_bounds__(64 * H) void motion_attn_kernel(const ma_args p, co
     const f16* alane = panel + l15 * C;                  // + (16 pix) C + (((4 s + g) ^ (l15 & 7)) * 8)
     f16x8 wf[MA_PD][DT];
 #pragma unroll
-    for (int pix = 0; pix < MA_PIX; ++pix)
+    for (int pix = 0; pix < PIX; ++pix)
 #pragma unroll
       for (int t = 0; t < DT; ++t) acc[pix][t] = init(pix, t);
 #pragma unroll
@@ -212,16 +235,16 @@ __global__ __launch_bounds__(64 * H) void motion_attn_kernel(const ma_args p, co
     // (r5: without this fence the scheduler may pair each of these loads with the first MFMA that takes it -- load, s_waitcnt vmcnt(0),
     //  MFMA, three L2 round trips in series at the top of the pass: seen in the v pass of the OUTP form)
     __builtin_amdgcn_sched_barrier(0);
-    constexpr int AD = MA_AD, NI = KS * MA_PIX;
+    constexpr int AD = MA_AD, NI = KS * PIX;
     auto lda = [&](const int i) {
-      return *reinterpret_cast<const f16x8*>(alane + 16 * (i % MA_PIX) * C + 64 * ((i / MA_PIX) >> 1) + swz[(i / MA_PIX) & 1]);
+      return *reinterpret_cast<const f16x8*>(alane + 16 * (i % PIX) * C + 64 * ((i / PIX) >> 1) + swz[(i / PIX) & 1]);
     };
     f16x8 af[AD + 1];
 #pragma unroll
     for (int i = 0; i < AD; ++i) af[i] = lda(i);
 #pragma unroll
     for (int i = 0; i < NI; ++i) {
-      const int s = i / MA_PIX, pix = i % MA_PIX;
+      const int s = i / PIX, pix = i % PIX;
       if (pix == 0 && s + MA_PD - 1 < KS) {
 #pragma unroll
         for (int t = 0; t < DT; ++t) wf[(s + MA_PD - 1) % MA_PD][t] = ldw(s + MA_PD - 1, t);
@@ -242,8 +265,28 @@ __global__ __launch_bounds__(64 * H) void motion_attn_kernel(const ma_args p, co
   // Output row of one query: lane (g, l15) holds channels 16 t + 4 g .. + 3 of query l15, 8 bytes per tile.  v_permlane16_swap
   // pairs the lane groups g, g ^ 1 so that even groups end with 8 consecutive channels of tile 0 and odd groups with 8 of tile 1
   // -- one 16-byte store per lane for two tiles (as 8-byte stores the output cost 6.5k of a tile's 50k cycles: issue-bound).
-  static_assert(DT == 3 && D == 40, "store pattern of three 16-channel tiles holding 40 channels");
+  // D = 80 (five full tiles): the pairs (0, 1) and (2, 3) as above, the last tile swapped with itself -- groups 0 and 2 end with its
+  // channels 0 .. 7 and 8 .. 15.
+  static_assert((DT == 3 && D == 40) || (DT == 5 && D == 80), "store pattern of three 16-channel tiles holding 40 channels, or of five full ones");
   auto store_tiles = [&](f16* orow, const int g, const u32x2 (&oh)[DT]) {      // (g: from an opaque copy of the lane index)
+    if constexpr (DT == 5) {
+      u32x2 a = oh[0], b = oh[1], c = oh[2], d = oh[3], e = oh[4], f = oh[4];
+      asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1\n\tv_permlane16_swap_b32 %2, %3\n\t"
+                   "v_permlane16_swap_b32 %4, %5\n\tv_permlane16_swap_b32 %6, %7\n\t"
+                   "v_permlane16_swap_b32 %8, %9\n\tv_permlane16_swap_b32 %10, %11"
+                   : "+v"(a[0]), "+v"(b[0]), "+v"(a[1]), "+v"(b[1]), "+v"(c[0]), "+v"(d[0]), "+v"(c[1]), "+v"(d[1]), "+v"(e[0]), "+v"(f[0]),
+                     "+v"(e[1]), "+v"(f[1]));
+      const int pair = (g & 1) ? 16 + 4 * (g - 1) : 4 * g;         // even g: first tile of a pair, channels 4 g .. + 7; odd g: second tile, 4 (g - 1) ..
+#ifdef I2V_MA_NOSTORE
+      if (p.ldo < 0)
+#endif
+      {
+        *reinterpret_cast<u32x4*>(orow + pair) = u32x4{a[0], a[1], b[0], b[1]};
+        *reinterpret_cast<u32x4*>(orow + 32 + pair) = u32x4{c[0], c[1], d[0], d[1]};
+        if ((g & 1) == 0) *reinterpret_cast<u32x4*>(orow + 64 + 4 * g) = u32x4{e[0], e[1], f[0], f[1]};
+      }
+      return;
+    }
     u32x2 a = oh[0], b = oh[1], c2 = oh[2], d2 = oh[2];
     asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1\n\tv_permlane16_swap_b32 %2, %3\n\t"
                  "v_permlane16_swap_b32 %4, %5\n\tv_permlane16_swap_b32 %6, %7"
@@ -274,8 +317,8 @@ __global__ __launch_bounds__(64 * H) void motion_attn_kernel(const ma_args p, co
   auto out_project = [&](const f16* pr, const int tile) {
     const auto rs_o = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.w_o), 0, H * DP * C * 2, 0x00020000);
     const auto rs_b = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.b_o), 0, C * 4, 0x00020000);
-    const f16* base = X + (int64_t)tile * (MA_PIX * MA_F) * p.ldx;                      // (wave-uniform)
-    const auto rs_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<f16*>(base), 0, (int)(((MA_PIX * MA_F - 1) * p.ldx + C) * 2), 0x00020000);
+    const f16* base = X + (int64_t)tile * (PIX * MA_F) * p.ldx;                      // (wave-uniform)
+    const auto rs_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<f16*>(base), 0, (int)(((PIX * MA_F - 1) * p.ldx + C) * 2), 0x00020000);
     const int ln = ma_opaque(lane), sg = ln >> 4, sl15 = ln & 15;
     f32x4 bo[DT];
 #pragma unroll
@@ -284,10 +327,10 @@ __global__ __launch_bounds__(64 * H) void motion_attn_kernel(const ma_args p, co
                                             rs_b, 16 * t + 4 * sg < D ? (unsigned)((wave * D + 16 * t + 4 * sg) * 4) : 0x80000000u, 0, 0));
     // the residual: this lane's slice of its rows (8 bytes per row and tile), requested BEHIND the pass's first weight fragments
     // (loads return in order: in front of them the pass would start with an HBM round trip) and added to the finished accumulators
-    u32x2 res[MA_PIX][DT];
+    u32x2 res[PIX][DT];
     project(pr, rs_o, wave * (DP * C * 2), std::true_type{}, [&](const int, const int t) { return bo[t]; }, [&]() {
 #pragma unroll
-      for (int pix = 0; pix < MA_PIX; ++pix)
+      for (int pix = 0; pix < PIX; ++pix)
 #pragma unroll
         for (int t = 0; t < DT; ++t) {
 #ifdef I2V_MA_NORES
@@ -298,9 +341,9 @@ __global__ __launch_bounds__(64 * H) void motion_attn_kernel(const ma_args p, co
 #endif
         }
     });
-    f16* __restrict__ O = reinterpret_cast<f16*>(p.out) + (int64_t)tile * (MA_PIX * MA_F) * p.ldo + wave * D;
+    f16* __restrict__ O = reinterpret_cast<f16*>(p.out) + (int64_t)tile * (PIX * MA_F) * p.ldo + wave * D;
 #pragma unroll
-    for (int pix = 0; pix < MA_PIX; ++pix) {
+    for (int pix = 0; pix < PIX; ++pix) {
       u32x2 oh[DT];
 #pragma unroll
       for (int t = 0; t < DT; ++t) {
@@ -321,10 +364,10 @@ __global__ __launch_bounds__(64 * H) void motion_attn_kernel(const ma_args p, co
   MA_STAMP(1);
   lds_barrier();
   for (int it = 0; tile < ntiles; tile += gridDim.x, ++it) {
-    f16* panel = panels + (it & 1) * (MA_PIX * MA_F * C);
+    f16* panel = panels + (it & 1) * (PIX * MA_F * C);
     const int next = tile + (int)gridDim.x;
     // (the other panel was last read in the previous iteration, which every wave has left through the barrier at its end)
-    f16* other = panels + ((it + 1) & 1) * (MA_PIX * MA_F * C);
+    f16* other = panels + ((it + 1) & 1) * (PIX * MA_F * C);
     MA_STAMP(2);
     if constexpr (CROSS) {      // one pass only: the next tile's rows leave HBM now and land under it (see below)
       if (next < ntiles) fetch_rows(next, other);
@@ -332,11 +375,11 @@ __global__ __launch_bounds__(64 * H) void motion_attn_kernel(const ma_args p, co
     }
 
     // q^T [channel][frame]
-    f16x4 qh[MA_PIX][DT];
+    f16x4 qh[PIX][DT];
     project(panel, rs_w, w_wave, std::true_type{}, zero_init, no_hook);
     // (CROSS: softmax scale * log2 e goes into the fp16 q, as in i2v_attention_f16 -- 24 multiplies per tile instead of 160)
 #pragma unroll
-    for (int pix = 0; pix < MA_PIX; ++pix)
+    for (int pix = 0; pix < PIX; ++pix)
 #pragma unroll
       for (int t = 0; t < DT; ++t) qh[pix][t] = to_half(CROSS ? acc[pix][t] * scale_log2 : acc[pix][t]);
     MA_STAMP(3);
@@ -372,10 +415,10 @@ __global__ __launch_bounds__(64 * H) void motion_attn_kernel(const ma_args p, co
       }
       MA_STAMP(4);
       MA_STAMP(5);
-      f16* __restrict__ O = reinterpret_cast<f16*>(p.out) + (int64_t)tile * (MA_PIX * MA_F) * p.ldo + wave * D;
+      f16* __restrict__ O = reinterpret_cast<f16*>(p.out) + (int64_t)tile * (PIX * MA_F) * p.ldo + wave * D;
       const int sln = ma_opaque(lane), sg = sln >> 4, sl15 = sln & 15;
 #pragma unroll
-      for (int pix = 0; pix < MA_PIX; ++pix) {
+      for (int pix = 0; pix < PIX; ++pix) {
         float sv[MA_KT][4];
         float mx = -INFINITY;
 #pragma unroll
@@ -456,10 +499,10 @@ __global__ __launch_bounds__(64 * H) void motion_attn_kernel(const ma_args p, co
     // k^T, then S^T[key][query] and the softmax over the keys.  NB = 16-row tiles per pixel (F = 32: two -- the keys of a query
     // are the 8 accumulator rows of two score blocks and the 4 lane groups); ph[key tile][query tile of the same pixel]
     constexpr int NB = F == 32 ? 2 : 1;
-    f16x4 ph[MA_PIX][NB];
+    f16x4 ph[PIX][NB];
     project(panel, rs_w, w_wave + DP * C * 2, std::true_type{}, zero_init, no_hook);
 #pragma unroll
-    for (int px = 0; px < MA_PIX; px += NB) {
+    for (int px = 0; px < PIX; px += NB) {
 #pragma unroll
       for (int jq = 0; jq < NB; ++jq) {
         float sv[NB][4];
@@ -504,10 +547,10 @@ __global__ __launch_bounds__(64 * H) void motion_attn_kernel(const ma_args p, co
     project(panel, rs_w, w_wave + 2 * (DP * C * 2), std::false_type{}, zero_init, no_hook);
     MA_STAMP(5);
     if constexpr (OUTP) lds_barrier();               // the v pass was the panel's last reader: every wave has left it
-    f16* __restrict__ O = reinterpret_cast<f16*>(p.out) + (int64_t)tile * (MA_PIX * MA_F) * p.ldo + wave * D;
+    f16* __restrict__ O = reinterpret_cast<f16*>(p.out) + (int64_t)tile * (PIX * MA_F) * p.ldo + wave * D;
     const int sln = ma_opaque(lane), sg = sln >> 4, sl15 = sln & 15;
 #pragma unroll
-    for (int px = 0; px < MA_PIX; px += NB)
+    for (int px = 0; px < PIX; px += NB)
 #pragma unroll
       for (int jq = 0; jq < NB; ++jq) {
         u32x2 oh[DT];
@@ -543,24 +586,24 @@ __global__ __launch_bounds__(64 * H) void motion_attn_kernel(const ma_args p, co
 #undef MA_STAMP
 }
 
-template <int C, int D, int H, bool CROSS, int F = 16, bool OUTP = false>
+template <int C, int D, int H, bool CROSS, int F = 16, bool OUTP = false, int PIX = MA_PIX>
 int ma_cus() {       // CUs of the current device once it has granted this kernel its two panels of LDS; 0: refused (runtime.hip)
-  return i2v_big_lds_kernel_cus(reinterpret_cast<const void*>(motion_attn_kernel<C, D, H, CROSS, F, OUTP>), 2 * (size_t)MA_PIX * MA_F * C * sizeof(f16));
+  return i2v_big_lds_kernel_cus(reinterpret_cast<const void*>(motion_attn_kernel<C, D, H, CROSS, F, OUTP, PIX>), 2 * (size_t)PIX * MA_F * C * sizeof(f16));
 }
 
-template <int C, int D, int H, bool CROSS, int F = 16, bool OUTP = false>
+template <int C, int D, int H, bool CROSS, int F = 16, bool OUTP = false, int PIX = MA_PIX>
 int launch_ma(const ma_args& p, int64_t rows, float scale, hipStream_t s, const char* what) {
-  const size_t lds = 2 * (size_t)MA_PIX * MA_F * C * sizeof(f16);
-  const int cus = ma_cus<C, D, H, CROSS, F, OUTP>();
+  const size_t lds = 2 * (size_t)PIX * MA_F * C * sizeof(f16);
+  const int cus = ma_cus<C, D, H, CROSS, F, OUTP, PIX>();
   if (cus <= 0) I2V_FAIL(I2V_ERR_UNSUPPORTED, "%s: %zu bytes of LDS refused by this device", what, lds);
-  const int ntiles = (int)(rows / (MA_PIX * MA_F));
+  const int ntiles = (int)(rows / (PIX * MA_F));
   // one workgroup per CU (160 KB of LDS each), every workgroup the same number of tiles where the count allows it
   const int grid = i2v_persistent_grid(ntiles, cus);
   long long* stamps = nullptr;
 #ifdef I2V_MA_STAMPS
   stamps = getenv("I2V_MA_STAMP_PTR") ? reinterpret_cast<long long*>(strtoull(getenv("I2V_MA_STAMP_PTR"), nullptr, 0)) : nullptr;
 #endif
-  hipLaunchKernelGGL((motion_attn_kernel<C, D, H, CROSS, F, OUTP>), dim3((unsigned)grid), dim3(64 * H), lds, s, p, scale * 1.4426950408889634f,
+  hipLaunchKernelGGL((motion_attn_kernel<C, D, H, CROSS, F, OUTP, PIX>), dim3((unsigned)grid), dim3(64 * H), lds, s, p, scale * 1.4426950408889634f,
                      ntiles, stamps);
   return i2v_check_launch(what);
 }
@@ -604,6 +647,35 @@ extern "C" int i2v_motion_attn_f16(const i2v_motion_attn_params* pp, i2v_stream_
   if (p.frames == 8) return launch_ma<320, 40, 8, false, 8>(a, p.rows, p.scale, s, "i2v_motion_attn_f16");
   if (p.frames == 32) return launch_ma<320, 40, 8, false, 32>(a, p.rows, p.scale, s, "i2v_motion_attn_f16");
   return launch_ma<320, 40, 8, false, 16>(a, p.rows, p.scale, s, "i2v_motion_attn_f16");
+}
+
+// The 32^2 level of SD-1.5: C = 640, 8 heads of 80, 16 frames, 64-row tiles (MA_WIDE_PIX pixels), to_out + residual always inside.
+constexpr int MA_WIDE_PIX = 4;
+
+extern "C" int32_t i2v_motion_attn_wide_supported(int64_t rows, int32_t channels, int32_t heads, int32_t head_dim, int32_t frames) {
+  return rows > 0 && rows % (MA_WIDE_PIX * MA_F) == 0 && rows / (MA_WIDE_PIX * MA_F) < (1 << 24) && channels == 640 && heads == 8 &&
+         head_dim == 80 && frames == 16 && ma_cus<640, 80, 8, false, 16, true, MA_WIDE_PIX>() > 0;
+}
+
+extern "C" int i2v_motion_attn_wide_f16(const i2v_motion_attn_params* pp, i2v_stream_t stream) {
+  I2V_CHECK_ARG(pp != nullptr, "i2v_motion_attn_wide_f16: null params");
+  const i2v_motion_attn_params& p = *pp;
+  I2V_CHECK_ARG(p.x && p.gamma && p.shift && p.w_qkv && p.out, "i2v_motion_attn_wide_f16: null pointer");
+  I2V_CHECK_ARG(p.w_o && p.b_o, "i2v_motion_attn_wide_f16: w_o and b_o are required (this form exists only with the out-projection inside)");
+  I2V_CHECK_ARG(i2v_motion_attn_wide_supported(p.rows, p.channels, p.heads, p.head_dim, p.frames),
+                "i2v_motion_attn_wide_f16: rows %lld channels %d heads %d head_dim %d frames %d is not a fused shape "
+                "(i2v_motion_attn_wide_supported)", (long long)p.rows, p.channels, p.heads, p.head_dim, p.frames);
+  I2V_CHECK_ARG(p.ldx >= p.channels && p.ldx % 8 == 0 && p.ldo >= p.channels && p.ldo % 8 == 0 && p.ld_shift >= p.channels &&
+                p.ld_shift % 4 == 0, "i2v_motion_attn_wide_f16: row strides");
+  I2V_CHECK_ARG(i2v_al16(p.x) && i2v_al16(p.gamma) && i2v_al16(p.shift) && i2v_al16(p.w_qkv) && i2v_al16(p.out) && i2v_al16(p.w_o) &&
+                i2v_al16(p.b_o), "i2v_motion_attn_wide_f16: pointers must be 16-byte aligned");
+  // (the residual rows go through a buffer descriptor and per-lane offsets of 32 bits)
+  I2V_CHECK_ARG(p.ldx < (1 << 23), "i2v_motion_attn_wide_f16: ldx (%lld) must be below 2^23", (long long)p.ldx);
+  ma_args a = {};
+  a.x = p.x; a.ldx = p.ldx; a.gamma = p.gamma; a.shift = p.shift; a.ld_shift = p.ld_shift; a.w = p.w_qkv; a.out = p.out;
+  a.ldo = p.ldo; a.eps = p.eps; a.w_o = p.w_o; a.b_o = p.b_o;
+  return launch_ma<640, 80, 8, false, 16, true, MA_WIDE_PIX>(a, p.rows, p.scale, reinterpret_cast<hipStream_t>(stream),
+                                                              "i2v_motion_attn_wide_f16");
 }
 
 extern "C" int32_t i2v_cross_attn_fused_supported(int64_t rows, int32_t channels, int32_t heads, int32_t head_dim, int32_t ctx_len,

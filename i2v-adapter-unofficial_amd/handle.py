@@ -36,7 +36,8 @@ ENTRY_IDS = {name: i for i, name in enumerate((
 LATER_ENTRY_IDS = {name: len(ENTRY_IDS) + i for i, name in enumerate((
     "i2v_freeu_f16",                                                # ABI 11
     "i2v_lcm_cfg_step",                                             # ABI 14
-    "i2v_freenoise_gather_f16", "i2v_freenoise_blend_f16"))}       # ABI 16
+    "i2v_freenoise_gather_f16", "i2v_freenoise_blend_f16",         # ABI 16
+    "i2v_motion_attn_wide_f16"))}                                   # ABI 28
 # ENTRY_NAMES is the id -> name table as it stood at ABI 11 and stays that table (tests/test_freeu.py pins its 22 ids); `entry_name`
 # covers every id.
 ENTRY_NAMES = {i: n for n, i in {**ENTRY_IDS, "i2v_freeu_f16": LATER_ENTRY_IDS["i2v_freeu_f16"]}.items()}

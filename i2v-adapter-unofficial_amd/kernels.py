@@ -843,7 +843,23 @@ def motion_attn_tables(gamma, beta, pe, frames):
             (beta.detach().float()[None, :] + pe.detach().float()[:frames]).contiguous())
 
 
-def motion_attn(x, gamma32, shift32, w_qkv, *, heads, head_dim, frames, eps, scale=None, out=None, out_proj=None):
+def motion_attn_wide_supported(rows, channels, heads, head_dim, frames):
+    """is the 64-row-tile form of the fused motion attention sub-block (C = 640, to_out + residual inside) implemented for this shape?"""
+    return bool(_lib.load().i2v_motion_attn_wide_supported(rows, channels, heads, head_dim, frames))
+
+
+def motion_attn_wide(x, gamma32, shift32, w_qkv, *, heads, head_dim, frames, eps, out_proj, scale=None, out=None):
+    """x + to_out(temporal attention of LayerNorm(x) + pe) at the 32^2 level (i2v_motion_attn_wide_f16): the arguments of
+    `motion_attn`, `out_proj` (`pack_attn_out`) required.  (Goes through `motion_attn`, so a KernelProfile times and tags it like the
+    64^2 launch -- `motion_attn 32768x640 F16 h8 d80 (...)` -- with the same FLOP and byte accounting.)"""
+    if out_proj is None:
+        raise ValueError("motion_attn_wide: out_proj is required (pack_attn_out)")
+    return motion_attn(x, gamma32, shift32, w_qkv, heads=heads, head_dim=head_dim, frames=frames, eps=eps, scale=scale, out=out,
+                       out_proj=out_proj, _entry="i2v_motion_attn_wide_f16")
+
+
+def motion_attn(x, gamma32, shift32, w_qkv, *, heads, head_dim, frames, eps, scale=None, out=None, out_proj=None,
+                _entry="i2v_motion_attn_f16"):
     """o = temporal attention over the `frames` rows of each pixel of LayerNorm(x) + pe, q / k / v projected inside
     (i2v_motion_attn_f16); x [rows, C] in (batch, pixel, frame) order, (gamma32, shift32) from `motion_attn_tables`,
     w_qkv from `pack_motion_qkv`."""
@@ -873,7 +889,7 @@ def motion_attn(x, gamma32, shift32, w_qkv, *, heads, head_dim, frames, eps, sca
     p.eps, p.scale = float(eps), float(head_dim) ** -0.5 if scale is None else float(scale)
     if out_proj is not None:      # out = x + o Wo^T + bo in the same launch (`pack_attn_out`)
         p.w_o, p.b_o = _attn_out_operands(out_proj, c, heads, head_dim, "motion_attn")
-    _lib.check(lib.i2v_motion_attn_f16(C.byref(p), _stream()), "i2v_motion_attn_f16")
+    _lib.check(getattr(lib, _entry)(C.byref(p), _stream()), _entry)
     return out
 
 

@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define I2V_ABI_VERSION 27
+#define I2V_ABI_VERSION 28
 
 #define I2V_OK 0
 #define I2V_ERR_INVALID_ARG (-1)
@@ -329,6 +329,13 @@ typedef struct i2v_motion_attn_params {
 int32_t i2v_motion_attn_supported(int64_t rows, int32_t channels, int32_t heads, int32_t head_dim, int32_t frames);
 int32_t i2v_motion_attn_pack_rows(int32_t heads, int32_t head_dim);
 int i2v_motion_attn_f16(const i2v_motion_attn_params* p, i2v_stream_t stream);
+
+/* (ABI 28) The same sub-block at the SD-1.5 32^2 level -- channels 640, 8 heads of 80, 16 frames, rows a multiple of 64 -- on
+ * 64-row tiles, always WITH the out-projection and residual (w_o and b_o are required).  Same parameter struct, same weight
+ * layouts (head_dim 80 is five whole 16-row tiles: no padding rows); i2v_motion_attn_supported / i2v_motion_attn_f16 answer
+ * for the 64^2 level as before. */
+int32_t i2v_motion_attn_wide_supported(int64_t rows, int32_t channels, int32_t heads, int32_t head_dim, int32_t frames);
+int i2v_motion_attn_wide_f16(const i2v_motion_attn_params* p, i2v_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * `norm2 -> attn2` of the spatial transformer block (i2v:510-533) up to (not including) to_out, for a context that fits

@@ -235,6 +235,56 @@ class ProjectedTemb:
         return self if r == 1 else ProjectedTemb(self.all_proj[: r // 2], self.slices)
 
 
+class SampleProjectionMixin:
+    """What a denoiser computes once per sample instead of once per step, shared by the UNet and the ControlNet: the K / V^T of the
+    context for its cross-attention layers and the resnets' time-embedding projections of a whole schedule.  The model provides
+    `_cross_attention_layers()` and `_embed_time(timesteps_f32)`."""
+
+    def _sync_lora(self):
+        """hook, called before a weight is read: a model with mergeable adapters (the UNet, lora.UNetLoraMixin) brings its weights
+        up to date here; any other model has nothing to do"""
+
+    def project_context(self, ctx_text, ctx_ip=None, out: Optional[ProjectedContext] = None) -> ProjectedContext:
+        """K / V^T of the text (+ image; the UNet's IP-Adapter branch only) context for every cross-attention layer, computed ONCE per
+        sample instead of in every call of the model (they do not depend on the latents or the timestep); one context per sample, or
+        one per frame with prompt travel.  `out`: a previous result whose buffers are overwritten in place (a captured hipGraph keeps
+        reading the same memory for the next sample)."""
+        self._sync_lora()
+        pc = out if out is not None else ProjectedContext(ctx_text, ctx_ip)
+        if out is not None:
+            pc.text, pc.ip = ctx_text, ctx_ip
+        for attn in self._cross_attention_layers():
+            pc.kv[attn] = attn.project_kv(ctx_text, ctx_ip, out=pc.kv.get(attn))
+            attn.refresh_context_fragments(pc)       # (the fused text cross-attention's packed K / V, where a forward made them)
+        return pc
+
+    def _temb_pack(self):
+        """time_emb_proj weights of all resnets concatenated ([sum Cout, 4 C0]) + the column slice of each resnet."""
+        self._sync_lora()
+        resnets = [m for m in self.modules() if isinstance(m, ResnetBlock2D) and m.time_emb_proj is not None]
+        key = tuple((r.time_emb_proj.weight.data_ptr(), r.time_emb_proj.weight._version, r.time_emb_proj.bias._version)
+                    for r in resnets)
+        if getattr(self, "_temb_packed_key", None) != key:
+            with torch.no_grad():
+                w = w16(torch.cat([r.time_emb_proj.weight for r in resnets], dim=0))
+                b = w16(torch.cat([r.time_emb_proj.bias for r in resnets], dim=0))
+            slices, off = {}, 0
+            for r in resnets:
+                slices[r] = (off, r.out_channels)
+                off += r.out_channels
+            self._temb_packed, self._temb_packed_key = (w, b, slices), key
+        return self._temb_packed
+
+    def project_time_table(self, timesteps_f32, out=None):
+        """[T, sum Cout] fp16: `time_emb_proj(silu(time_embedding(time_proj(t))))` of every ResnetBlock2D (unet:1336-1343,
+        SURVEY A2) for ALL T timesteps of a schedule at once.  The chain depends on t only -- not on the latents -- so the
+        pipeline computes it once per sample (like `project_context`) and a replayed step selects its row by the device-side
+        step counter (`K.select_row`): 6 launches of M = 1 products per step become one 40 KB copy."""
+        wt, bt, _ = self._temb_pack()
+        temb = self._embed_time(timesteps_f32.to(torch.float32).contiguous())
+        return K.gemm(K.silu(temb), wt, bt, out=out)
+
+
 GN_FOLD = os.environ.get("I2V_GN_FOLD", "1") != "0"
 GN_FOLD_RATIO = float(os.environ.get("I2V_GN_FOLD_RATIO", "4"))   # fold when activations >= ratio x the weight stack
 

@@ -16,8 +16,8 @@ from torch import nn
 
 from . import kernels as K
 from ._lib import HipLibraryError
-from .blocks import (Attention, Downsample2D, HipModule, ProjectedContext, ProjectedTemb, ResnetBlock2D, TimestepEmbedding, Timesteps,
-                     _as_f16_matrix, pack_conv3x3, set_precise_stream, w16)
+from .blocks import (Attention, Downsample2D, HipModule, ProjectedTemb, ResnetBlock2D, SampleProjectionMixin, TimestepEmbedding,
+                     Timesteps, _as_f16_matrix, pack_conv3x3, set_precise_stream, w16)
 from .checkpoint import PretrainedMixin
 from .i2v_adapter import I2VAdapterTransformer2DModel
 from .unet_motion_cross_frame_attn import _Config
@@ -165,7 +165,7 @@ def _zero_conv(channels):
     return conv
 
 
-class ControlNetModel(PretrainedMixin, HipModule):
+class ControlNetModel(SampleProjectionMixin, PretrainedMixin, HipModule):
     """diffusers 0.24 ControlNetModel (SD-1.5 layout)."""
 
     def __init__(self, in_channels: int = 4, conditioning_channels: int = 3, flip_sin_to_cos: bool = True, freq_shift: int = 0,
@@ -329,24 +329,6 @@ class ControlNetModel(PretrainedMixin, HipModule):
             self._packed_key = key
         return self._packed
 
-    def _resnets(self):
-        return [m for m in self.modules() if isinstance(m, ResnetBlock2D) and m.time_emb_proj is not None]
-
-    def _temb_pack(self):
-        """time_emb_proj weights of all resnets concatenated ([sum Cout, 4 C0]) + the column slice of each resnet."""
-        resnets = self._resnets()
-        key = tuple((r.time_emb_proj.weight.data_ptr(), r.time_emb_proj.weight._version, r.time_emb_proj.bias._version) for r in resnets)
-        if getattr(self, "_temb_packed_key", None) != key:
-            with torch.no_grad():
-                w = w16(torch.cat([r.time_emb_proj.weight for r in resnets], dim=0))
-                b = w16(torch.cat([r.time_emb_proj.bias for r in resnets], dim=0))
-            slices, off = {}, 0
-            for r in resnets:
-                slices[r] = (off, r.out_channels)
-                off += r.out_channels
-            self._temb_packed, self._temb_packed_key = (w, b, slices), key
-        return self._temb_packed
-
     def weight_signature(self):
         """identity and versions of every parameter: what a captured step that launches this model was captured against"""
         return tuple((q.data_ptr(), q._version) for q in self.parameters())
@@ -362,27 +344,8 @@ class ControlNetModel(PretrainedMixin, HipModule):
     def _cross_attention_layers(self):
         return [m for name, m in self.named_modules() if isinstance(m, Attention) and name.endswith("attn2")]
 
-    def project_context(self, ctx_text, out: Optional[ProjectedContext] = None) -> ProjectedContext:
-        """K / V^T of the text context (one per sample, or one per frame with prompt travel) for the ControlNet's own attn2 layers, once
-        per sample; `out`: a previous result whose buffers
-        are overwritten in place (a captured graph keeps reading the same memory)."""
-        pc = out if out is not None else ProjectedContext(ctx_text, None)
-        if out is not None:
-            pc.text, pc.ip = ctx_text, None
-        for attn in self._cross_attention_layers():
-            pc.kv[attn] = attn.project_kv(ctx_text, None, out=pc.kv.get(attn))
-            attn.refresh_context_fragments(pc)
-        return pc
-
     def _embed_time(self, timesteps_f32):
         return self.time_embedding(K.timestep_embedding(timesteps_f32, self.config.block_out_channels[0]))
-
-    def project_time_table(self, timesteps_f32, out=None):
-        """[T, sum Cout] fp16: `time_emb_proj(silu(time_embedding(time_proj(t))))` of every resnet of the ControlNet for all T
-        timesteps of a schedule; a replayed step selects its row by the device-side step counter."""
-        wt, bt, _ = self._temb_pack()
-        temb = self._embed_time(timesteps_f32.to(torch.float32).contiguous())
-        return K.gemm(K.silu(temb), wt, bt, out=out)
 
     # ------------------------------------------------------------------ forward
     def _fwd_tokens(self, x, temb_proj, ctx, cond_tokens, out_scale: float = 1.0):

@@ -19,12 +19,14 @@ pipe:348-527) when the pipeline holds a `text_encoder` and a `tokenizer`; `promp
 (clip_vision.CLIPVisionModelWithProjection; `load_ip_adapter` loads it from `<path>/<subfolder>/image_encoder`) and the UNet an
 IP-Adapter; `image_embeds` / `negative_image_embeds` are taken as given.
 """
+import contextlib
 import logging
 import os
 from typing import Optional
 
 import torch
 
+from . import blocks
 from . import kernels as K
 from ._lib import HipLibraryError
 from .blocks import DDIMScheduler, DPMSolverMultistepScheduler, ImageProjection, LCMScheduler, Resampler
@@ -67,6 +69,89 @@ def _draw(fn, shape, generator, device):
         return torch.cat([_draw(fn, (1,) + tuple(shape[1:]), g, device) for g in generator], dim=0)
     gdev = generator.device if generator is not None else torch.device("cpu")
     return fn(shape, generator=generator, dtype=torch.float32, device=gdev).to(device)
+
+
+# The per-sample device buffers a captured step reads, by their key in the state dict `st`: each a tensor, a tuple of tensors
+# (t2i_feats) or absent / None.  The ONE list of them: a graph-cache hit copies exactly these into the graph's static buffers
+# (`_copy_sample_inputs`, in this order) and `_graph_key` holds the shape and dtype of exactly these, so what is copied in always
+# fits.  Not listed: `x0_prev` (DPM-Solver++) is the step's own history, not a sample input -- the first step of a sample does not
+# read it; `ctx_proj`, `temb_table` and the ControlNet's pair are projected from these into the static buffers (`_project_once`).
+SAMPLE_INPUTS = ("latents", "cond", "t_table", "coef", "ctx_text", "ctx_ip", "noise",      # (noise: this sample's LCM draws)
+                 "cn_cond", "cn_scale", "t2i_scale",                                       # (this sample's control frames)
+                 "v2v_source", "v2v_noise", "v2v_mask", "v2v_coef",                        # (this sample's clip and mask)
+                 "t2i_feats")                                                              # (this sample's adapter features)
+
+
+def _copy_sample_inputs(gst, st):
+    """a graph-cache hit: this sample's inputs `st` into the static buffers `gst` of the captured step, in place (the graph keeps
+    reading the same memory), and the step counter back to 0.  Entries `st` does not hold are left as they are."""
+    for name in SAMPLE_INPUTS:
+        src = st.get(name)
+        if src is None:
+            continue
+        for dst, t in zip(gst[name], src) if isinstance(src, (tuple, list)) else ((gst[name], src),):
+            dst.copy_(t)
+    gst["step_idx"].zero_()
+
+
+def _sample_input_shapes(st):
+    """the shape and dtype of every entry of SAMPLE_INPUTS (None where `st` holds none): their part of the graph key"""
+    one = lambda t: (tuple(t.shape), t.dtype)
+    shp = lambda v: None if v is None else tuple(one(t) for t in v) if isinstance(v, (tuple, list)) else one(v)
+    return tuple(shp(st.get(name)) for name in SAMPLE_INPUTS)
+
+
+@contextlib.contextmanager
+def _set_for_call(setter, value):
+    """`setter(value)` now and `setter(previous)` on the way out, exceptions included; `setter` returns the value it replaces"""
+    prev = setter(value)
+    try:
+        yield
+    finally:
+        setter(prev)
+
+
+def _frame_count(frames, name, channels, channel_owner=None):
+    """the number of frames of a per-frame image input: a list of PIL images, [F, C, H, W] shared by the batch or [B, F, C, H, W].
+    ValueError for anything else and for a tensor whose channel count is not `channels` -- worded "`name` has n channels, {channel_owner}
+    is C" where a model decides C (the adapter's `in_channels`), else by the accepted layouts."""
+    if isinstance(frames, torch.Tensor):
+        if frames.dim() not in (4, 5) or (channel_owner is None and frames.shape[-3] != channels):
+            raise ValueError(f"`{name}` must be [F, {channels}, H, W] or [B, F, {channels}, H, W], got {tuple(frames.shape)}")
+        if frames.shape[-3] != channels:
+            raise ValueError(f"`{name}` has {frames.shape[-3]} channels, {channel_owner} is {channels}")
+        return frames.shape[-4]
+    if isinstance(frames, (list, tuple)):
+        return len(frames)
+    raise ValueError(f"`{name}` must be a list of `num_frames` images or a tensor, got {type(frames)}")
+
+
+def _frame_tensor(frames, name, height, width, batch_size=None, num_frames=None, channels=None, channel_owner=None):
+    """a per-frame image input given as a tensor -> fp32 [B, F, C, height, width] on the host, values untouched.  With `batch_size`,
+    [F, C, H, W] is expanded over the batch and the batch and frame counts are checked (without: [1, F, C, H, W], the caller
+    expands); `channel_owner` as in `_frame_count`; the frames must already have the size."""
+    t = frames.detach().float().cpu()
+    if t.dim() == 4:
+        t = t[None] if batch_size is None else t[None].expand(batch_size, -1, -1, -1, -1)
+    if batch_size is not None and (t.shape[0] != batch_size or t.shape[1] != num_frames):
+        raise ValueError(f"`{name}` {tuple(frames.shape)} does not match batch {batch_size} x {num_frames} frames")
+    if channel_owner is not None and t.shape[2] != channels:
+        raise ValueError(f"`{name}` has {t.shape[2]} channels, {channel_owner} is {channels}")
+    if tuple(t.shape[-2:]) != (height, width):
+        raise ValueError(f"`{name}` tensors must already be {height} x {width}, got {tuple(t.shape[-2:])}")
+    return t
+
+
+def _pil_plane(im, name, mode, height, width):
+    """one PIL image of the list `name` -> fp32 [height, width] ("L") or [height, width, 3] ("RGB") in [0, 1], Lanczos-resized"""
+    import numpy as np
+    import PIL.Image
+    if not isinstance(im, PIL.Image.Image):
+        raise ValueError(f"`{name}` as a list holds PIL images, got {type(im)}")
+    im = im.convert(mode)
+    if im.size != (width, height):
+        im = im.resize((width, height), resample=PIL.Image.LANCZOS)
+    return torch.from_numpy(np.asarray(im, dtype=np.float32) / 255.0)
 
 
 class I2VAdapterPipeline:
@@ -167,16 +252,29 @@ class I2VAdapterPipeline:
             raise ValueError(f"a text context of {tokens} tokens exceeds the {limit} that the cross-attention takes (i2v_attention_f16 "
                              f"addresses one K slice of {widest}-wide rows with 32 bits): lower `max_embeddings_multiples`")
 
-    def _encode_weighted_texts(self, groups, clip_skip=None):
-        """[sum(len(g)), n * M, D]: the weighted embeddings of lists of prompts, every list through the text encoder in one call of
-        [len(g) * n, M] ids (chunks in prompt-major order); n, the chunk count, is the largest any text of ANY list needs.  One
-        `K.weight_embeds` launch, in place, for all of them, and one read of the ratios."""
-        from . import prompt_weighting as PW
+    def _require_text_encoder(self):
+        """the two refusals of everything that encodes text here: no text encoder or tokenizer, a text encoder that wants padding masks"""
         if self.text_encoder is None or self.tokenizer is None:
             raise ValueError("encoding a `prompt` needs both a `text_encoder` and a `tokenizer`: build the pipeline with them, or pass "
                              "`prompt_embeds` (and `negative_prompt_embeds`)")
         if getattr(self.text_encoder.config, "use_attention_mask", None):
             raise NotImplementedError("text_encoder.config.use_attention_mask: padding attention masks are not implemented")
+
+    def _embed_ids(self, ids, clip_skip=None):
+        """the text encoder's embeddings [N, L, D] of token ids [N, L]: its last hidden state, or with `clip_skip` the hidden state
+        `clip_skip` layers earlier, `hidden_states[-(clip_skip + 1)]`, through the final LayerNorm -- which the last hidden state has
+        been through as well (pipe:445-453)"""
+        if clip_skip is None:
+            return self.text_encoder(ids, attention_mask=None)[0]
+        hidden = self.text_encoder(ids, attention_mask=None, output_hidden_states=True)[-1][-(clip_skip + 1)]
+        return self.text_encoder.text_model.final_layer_norm(hidden)
+
+    def _encode_weighted_texts(self, groups, clip_skip=None):
+        """[sum(len(g)), n * M, D]: the weighted embeddings of lists of prompts, every list through the text encoder in one call of
+        [len(g) * n, M] ids (chunks in prompt-major order); n, the chunk count, is the largest any text of ANY list needs.  One
+        `K.weight_embeds` launch, in place, for all of them, and one read of the ratios."""
+        from . import prompt_weighting as PW
+        self._require_text_encoder()
         cfg = self._prompt_weighting or dict(max_embeddings_multiples=3, restore_mean=True)
         tok, m = self.tokenizer, self.tokenizer.model_max_length
         bos, eos, pad = PW.special_ids(tok)
@@ -192,11 +290,7 @@ class I2VAdapterPipeline:
         for g in groups:
             ids = torch.tensor([r for id_rows, _ in rows[first: first + len(g)] for r in id_rows], dtype=torch.int64)
             first += len(g)
-            if clip_skip is None:
-                e = self.text_encoder(ids, attention_mask=None)[0]
-            else:
-                e = self.text_encoder(ids, attention_mask=None, output_hidden_states=True)[-1][-(clip_skip + 1)]
-                e = self.text_encoder.text_model.final_layer_norm(e)
+            e = self._embed_ids(ids, clip_skip)
             embeds.append(e.reshape(len(g), n * m, e.shape[-1]))
         src = (embeds[0] if len(embeds) == 1 else torch.cat(embeds)).contiguous()
         if src.dtype != f16:
@@ -541,26 +635,17 @@ class I2VAdapterPipeline:
         scheduler's update (a scheduler swapped between calls re-captures) and FreeU's four scales (launch arguments: enabling,
         changing or disabling FreeU re-captures) and the LCM noise table's shape (its row count is a launch argument: another step
         count re-captures) and FreeNoise's window settings (they decide the launches of every motion module: enabling, changing or
-        disabling FreeNoise re-captures; its noise_type only shapes the initial noise and does not)"""
+        disabling FreeNoise re-captures; its noise_type only shapes the initial noise and does not).  The shapes and dtypes are those
+        of SAMPLE_INPUTS, all of them: which of the optional ones are present says which launches the step has (a ControlNet's, a
+        T2I-Adapter's adds, a mask's blend -- a source clip without a mask launches nothing of its own and leaves no entry: its key is
+        a plain call's), and the tables' row counts are launch arguments.  With a ControlNet, its weights as the UNet's."""
         unet = self.unet
         wsig = hash(tuple((p.data_ptr(), p._version) for p in unet.parameters()))
+        cn_wsig = hash(self.controlnet.weight_signature()) if st.get("cn_cond") is not None else None
         ips = tuple((a.ip_num_tokens, float(a.ip_scale)) for a in unet._cross_attention_layers())
-        shp = lambda t: None if t is None else (tuple(t.shape), t.dtype)
-        from .blocks import precise_stream      # (a captured step keeps the residual-stream mode it was captured in)
-        # a ControlNet's launches: its weights, the control tokens' and the scale table's shapes (the table's rows are a launch argument)
-        cn = None
-        if st.get("cn_cond") is not None:
-            cn = (hash(self.controlnet.weight_signature()), shp(st["cn_cond"]), shp(st["cn_scale"]))
-        # a T2I-Adapter's adds: the features' and the scale table's shapes (the features are static buffers, not launch arguments)
-        if st.get("t2i_feats") is not None:
-            cn = (cn, tuple(shp(t) for t in st["t2i_feats"]), shp(st["t2i_scale"]))
-        # a mask's launch (video-to-video): the mask's and the table's shapes (the table's rows are a launch argument).  A source clip
-        # without a mask launches nothing of its own: its key is a plain call's
-        if st.get("v2v_mask") is not None:
-            cn = (cn, "masked_renoise", shp(st["v2v_mask"]), shp(st["v2v_coef"]))
-        return (cn, tuple(st["latents"].shape), st["copies"], st["num_frames"], st["guidance"], shp(st["t_table"]),
-                shp(st["ctx_text"]), shp(st["ctx_ip"]), str(st["latents"].device), wsig, ips, precise_stream(),
-                self._scheduler_kind(), shp(st["coef"]), unet.freeu_signature(), shp(st.get("noise")), unet.free_noise_launch_signature())
+        # (a captured step keeps the residual-stream mode it was captured in)
+        return (cn_wsig, st["copies"], st["num_frames"], st["guidance"], str(st["latents"].device), wsig, ips, blocks.precise_stream(),
+                self._scheduler_kind(), unet.freeu_signature(), unet.free_noise_launch_signature()) + _sample_input_shapes(st)
 
     def _run_steps(self, st, n_steps, use_graph):
         if not use_graph:
@@ -576,14 +661,7 @@ class I2VAdapterPipeline:
         hit = cache.get(key)
         if hit is not None:
             graph, gst = hit
-            for name in ("latents", "cond", "t_table", "coef", "ctx_text", "ctx_ip", "noise",      # (noise: this sample's LCM draws)
-                         "cn_cond", "cn_scale", "t2i_scale",                                       # (this sample's control frames)
-                         "v2v_source", "v2v_noise", "v2v_mask", "v2v_coef"):                       # (this sample's clip and mask)
-                if st.get(name) is not None:
-                    gst[name].copy_(st[name])
-            for dst, src in zip(gst.get("t2i_feats") or (), st.get("t2i_feats") or ()):             # (this sample's adapter features)
-                dst.copy_(src)
-            gst["step_idx"].zero_()
+            _copy_sample_inputs(gst, st)
             self._project_once(gst, into=True)
         else:
             # one shape at a time (a graph pins its workspace): the old graph and its pool go before the new capture,
@@ -634,14 +712,7 @@ class I2VAdapterPipeline:
             raise ValueError("the pipeline has a `controlnet`: `control_image` is required (one control frame per frame of the clip)")
         from .controlnet import controlnet_keep_table
         controlnet_keep_table(1, scale, start, end)                    # 0 <= start < end <= 1, else ValueError
-        if isinstance(control_image, torch.Tensor):
-            if control_image.dim() not in (4, 5) or control_image.shape[-3] != 3:
-                raise ValueError(f"`control_image` must be [F, 3, H, W] or [B, F, 3, H, W], got {tuple(control_image.shape)}")
-            n = control_image.shape[-4]
-        elif isinstance(control_image, (list, tuple)):
-            n = len(control_image)
-        else:
-            raise ValueError(f"`control_image` must be a list of `num_frames` images or a tensor, got {type(control_image)}")
+        n = _frame_count(control_image, "control_image", 3)
         if n != num_frames:
             raise ValueError(f"`control_image` holds {n} frames, `num_frames` is {num_frames}: a ControlNet runs per frame and needs one "
                              "control frame for every frame of the clip")
@@ -651,26 +722,15 @@ class I2VAdapterPipeline:
         the [-1, 1] normalisation (a ControlNet is trained on [0, 1] maps); tensors as they are (they must have that size); one clip
         of control frames is shared by the batch."""
         if isinstance(control_image, torch.Tensor):
-            t = control_image.detach().float().cpu()
-            if t.dim() == 4:
-                t = t[None].expand(batch_size, -1, -1, -1, -1)
-            if t.shape[0] != batch_size or t.shape[1] != num_frames:
-                raise ValueError(f"`control_image` {tuple(control_image.shape)} does not match batch {batch_size} x {num_frames} frames")
+            t = _frame_tensor(control_image, "control_image", height, width, batch_size, num_frames)
+        else:
+            if len(control_image) != num_frames:
+                raise ValueError(f"`control_image` holds {len(control_image)} frames, `num_frames` is {num_frames}")
+            t = self.control_image_processor.preprocess(list(control_image), height=height, width=width)
             if tuple(t.shape[-2:]) != (height, width):
-                raise ValueError(f"`control_image` tensors must already be {height} x {width}, got {tuple(t.shape[-2:])}")
-            return t.reshape(batch_size * num_frames, 3, height, width).contiguous()
-        if len(control_image) != num_frames:
-            raise ValueError(f"`control_image` holds {len(control_image)} frames, `num_frames` is {num_frames}")
-        t = self.control_image_processor.preprocess(list(control_image), height=height, width=width)
-        if tuple(t.shape[-2:]) != (height, width):
-            raise ValueError(f"control frames of {tuple(t.shape[-2:])} after resizing, expected {height} x {width}")
-        return t[None].expand(batch_size, -1, -1, -1, -1).reshape(batch_size * num_frames, 3, height, width).contiguous()
-
-    @staticmethod
-    def _control_scale_table(n_steps, cn_args, device):
-        """fp32 [n_steps] on the device: conditioning scale x diffusers' `controlnet_keep` over the executed steps"""
-        from .controlnet import controlnet_keep_table
-        return torch.tensor(controlnet_keep_table(n_steps, *cn_args), dtype=torch.float32, device=device)
+                raise ValueError(f"control frames of {tuple(t.shape[-2:])} after resizing, expected {height} x {width}")
+            t = t[None].expand(batch_size, -1, -1, -1, -1)
+        return t.reshape(batch_size * num_frames, 3, height, width).contiguous()
 
     # ------------------------------------------------------------------------------------------ T2I-Adapter
     def _check_adapter_args(self, adapter_image, num_frames, scale, factor):
@@ -684,17 +744,7 @@ class I2VAdapterPipeline:
             raise ValueError("the pipeline has a `t2i_adapter`: `adapter_image` is required (one control frame per frame of the clip)")
         from .t2i_adapter import adapter_scale_table
         adapter_scale_table(1, scale, factor)                          # 0 <= factor <= 1, else ValueError
-        c = self.t2i_adapter.config.in_channels
-        if isinstance(adapter_image, torch.Tensor):
-            if adapter_image.dim() not in (4, 5):
-                raise ValueError(f"`adapter_image` must be [F, {c}, H, W] or [B, F, {c}, H, W], got {tuple(adapter_image.shape)}")
-            if adapter_image.shape[-3] != c:
-                raise ValueError(f"`adapter_image` has {adapter_image.shape[-3]} channels, the adapter's `in_channels` is {c}")
-            n = adapter_image.shape[-4]
-        elif isinstance(adapter_image, (list, tuple)):
-            n = len(adapter_image)
-        else:
-            raise ValueError(f"`adapter_image` must be a list of `num_frames` images or a tensor, got {type(adapter_image)}")
+        n = _frame_count(adapter_image, "adapter_image", self.t2i_adapter.config.in_channels, "the adapter's `in_channels`")
         if n != num_frames:
             raise ValueError(f"`adapter_image` holds {n} frames, `num_frames` is {num_frames}: a T2I-Adapter runs per frame and needs one "
                              "control frame for every frame of the clip")
@@ -705,37 +755,13 @@ class I2VAdapterPipeline:
         one and resized; tensors are taken as they are (they must have that size); one clip of frames is shared by the batch."""
         c = self.t2i_adapter.config.in_channels
         if isinstance(adapter_image, torch.Tensor):
-            t = adapter_image.detach().float().cpu()
-            if t.dim() == 4:
-                t = t[None].expand(batch_size, -1, -1, -1, -1)
-            if t.shape[0] != batch_size or t.shape[1] != num_frames:
-                raise ValueError(f"`adapter_image` {tuple(adapter_image.shape)} does not match batch {batch_size} x {num_frames} frames")
-            if t.shape[2] != c:
-                raise ValueError(f"`adapter_image` has {t.shape[2]} channels, the adapter's `in_channels` is {c}")
-            if tuple(t.shape[-2:]) != (height, width):
-                raise ValueError(f"`adapter_image` tensors must already be {height} x {width}, got {tuple(t.shape[-2:])}")
-            return t.reshape(batch_size * num_frames, c, height, width).contiguous()
-        if len(adapter_image) != num_frames:
-            raise ValueError(f"`adapter_image` holds {len(adapter_image)} frames, `num_frames` is {num_frames}")
-        import numpy as np
-        import PIL.Image
-        frames = []
-        for im in adapter_image:
-            if not isinstance(im, PIL.Image.Image):
-                raise ValueError(f"`adapter_image` as a list holds PIL images, got {type(im)}")
-            im = im.convert("L" if c == 1 else "RGB")
-            if im.size != (width, height):
-                im = im.resize((width, height), resample=PIL.Image.LANCZOS)
-            arr = torch.from_numpy(np.asarray(im, dtype=np.float32) / 255.0)
-            frames.append(arr[None] if c == 1 else arr.permute(2, 0, 1))
-        t = torch.stack(frames)
-        return t[None].expand(batch_size, -1, -1, -1, -1).reshape(batch_size * num_frames, c, height, width).contiguous()
-
-    @staticmethod
-    def _adapter_scale_table(n_steps, t2i_args, device):
-        """fp32 [n_steps] on the device: the adapter's scale on the first int(n_steps * factor) executed steps, 0 afterwards"""
-        from .t2i_adapter import adapter_scale_table
-        return torch.tensor(adapter_scale_table(n_steps, *t2i_args), dtype=torch.float32, device=device)
+            t = _frame_tensor(adapter_image, "adapter_image", height, width, batch_size, num_frames, c, "the adapter's `in_channels`")
+        else:
+            if len(adapter_image) != num_frames:
+                raise ValueError(f"`adapter_image` holds {len(adapter_image)} frames, `num_frames` is {num_frames}")
+            planes = [_pil_plane(im, "adapter_image", "L" if c == 1 else "RGB", height, width) for im in adapter_image]
+            t = torch.stack([p[None] if c == 1 else p.permute(2, 0, 1) for p in planes])[None].expand(batch_size, -1, -1, -1, -1)
+        return t.reshape(batch_size * num_frames, c, height, width).contiguous()
 
     # ------------------------------------------------------------------------------------------ video-to-video, masked editing
     def _check_video_args(self, video, video_latents, strength, mask_image, num_frames, num_inference_steps, ratio, eta):
@@ -752,14 +778,7 @@ class I2VAdapterPipeline:
                                  "region outside the mask is kept")
             return None, None, None
         if video is not None:
-            if isinstance(video, torch.Tensor):
-                if video.dim() not in (4, 5) or video.shape[-3] != 3:
-                    raise ValueError(f"`video` must be [F, 3, H, W] or [B, F, 3, H, W], got {tuple(video.shape)}")
-                n = video.shape[-4]
-            elif isinstance(video, (list, tuple)):
-                n = len(video)
-            else:
-                raise ValueError(f"`video` must be a list of `num_frames` images or a tensor, got {type(video)}")
+            n = _frame_count(video, "video", 3)
         else:
             if not isinstance(video_latents, torch.Tensor) or video_latents.dim() != 5:
                 raise ValueError("`video_latents` must be a [B, F, 4, h, w] tensor, got "
@@ -798,11 +817,8 @@ class I2VAdapterPipeline:
         """-> fp32 [B or 1, F, 3, height, width] in [-1, 1] on the host: PIL frames through `image_processor.preprocess` (resized, as the
         condition image is); tensors in [0, 1] are normalised and must already have that size"""
         if isinstance(video, torch.Tensor):
-            if video.dim() not in (4, 5) or video.shape[-3] != 3:
-                raise ValueError(f"`video` must be [F, 3, H, W] or [B, F, 3, H, W], got {tuple(video.shape)}")
-            t = video[None] if video.dim() == 4 else video
-            if tuple(t.shape[-2:]) != (height, width):
-                raise ValueError(f"`video` tensors must already be {height} x {width}, got {tuple(t.shape[-2:])}")
+            _frame_count(video, "video", 3)
+            t = _frame_tensor(video, "video", height, width)
             flat = self.image_processor.preprocess(t.reshape(-1, 3, height, width))
             return flat.reshape(t.shape[0], t.shape[1], 3, height, width)
         flat = self.image_processor.preprocess(list(video), height=height, width=width)
@@ -861,21 +877,13 @@ class I2VAdapterPipeline:
         beyond `num_frames` are dropped).  Converted to grey, resized to height x width (PIL: Lanczos; tensors: nearest), binarised at
         >= 0.5, then taken to the latent resolution by torch.nn.functional.interpolate(mode="nearest").  A tensor already at
         (height / 8, width / 8) is taken as it is, unbinarised: soft masks are allowed."""
-        import numpy as np
         import PIL.Image
         import torch.nn.functional as F
         h, w = height // self.vae_scale_factor, width // self.vae_scale_factor
         if isinstance(mask_image, PIL.Image.Image):
             mask_image = [mask_image]
         if isinstance(mask_image, (list, tuple)):
-            planes = []
-            for im in mask_image:
-                if not isinstance(im, PIL.Image.Image):
-                    raise ValueError(f"`mask_image` as a list holds PIL images, got {type(im)}")
-                im = im.convert("L")
-                if im.size != (width, height):
-                    im = im.resize((width, height), resample=PIL.Image.LANCZOS)
-                planes.append(torch.from_numpy(np.asarray(im, dtype=np.float32) / 255.0))
+            planes = [_pil_plane(im, "mask_image", "L", height, width) for im in mask_image]
             t = torch.stack(planes)[None, :, None]                                          # [1, F or 1, 1, H, W]
         elif isinstance(mask_image, torch.Tensor):
             t = mask_image.detach().float().cpu()
@@ -948,11 +956,8 @@ class I2VAdapterPipeline:
         else:
             batch_size = prompt_embeds.shape[0]
         needs_encoder = prompt_embeds is None or (do_classifier_free_guidance and negative_prompt_embeds is None)
-        if needs_encoder and (self.text_encoder is None or self.tokenizer is None):
-            raise ValueError("encoding a `prompt` needs both a `text_encoder` and a `tokenizer`: build the pipeline with them, or pass "
-                             "`prompt_embeds` (and `negative_prompt_embeds`)")
-        if needs_encoder and getattr(self.text_encoder.config, "use_attention_mask", None):
-            raise NotImplementedError("text_encoder.config.use_attention_mask: padding attention masks are not implemented")
+        if needs_encoder:
+            self._require_text_encoder()
 
         if prompt_embeds is None:
             prompt = self.maybe_convert_prompt(prompt, self.tokenizer)                          # pipe:409 (textual inversion)
@@ -964,15 +969,7 @@ class I2VAdapterPipeline:
                 removed_text = self.tokenizer.batch_decode(untruncated_ids[:, self.tokenizer.model_max_length - 1: -1])
                 logger.warning("The following part of your input was truncated because CLIP can only handle sequences up to"
                                f" {self.tokenizer.model_max_length} tokens: {removed_text}")
-            if clip_skip is None:
-                prompt_embeds = self.text_encoder(text_input_ids, attention_mask=None)
-                prompt_embeds = prompt_embeds[0]
-            else:
-                prompt_embeds = self.text_encoder(text_input_ids, attention_mask=None, output_hidden_states=True)
-                # the tuple of all hidden states, then the desired layer's; the final LayerNorm is applied here, as to the
-                # `last_hidden_state` the default path takes (pipe:445-453)
-                prompt_embeds = prompt_embeds[-1][-(clip_skip + 1)]
-                prompt_embeds = self.text_encoder.text_model.final_layer_norm(prompt_embeds)
+            prompt_embeds = self._embed_ids(text_input_ids, clip_skip)                          # pipe:438-453
 
         if self.text_encoder is not None:
             prompt_embeds_dtype = self.text_encoder.dtype
@@ -1003,8 +1000,7 @@ class I2VAdapterPipeline:
             max_length = prompt_embeds.shape[1]
             uncond_input = self.tokenizer(uncond_tokens, padding="max_length", max_length=max_length, truncation=True,
                                           return_tensors="pt")
-            negative_prompt_embeds = self.text_encoder(uncond_input.input_ids, attention_mask=None)
-            negative_prompt_embeds = negative_prompt_embeds[0]
+            negative_prompt_embeds = self._embed_ids(uncond_input.input_ids)                    # (no clip_skip here: pipe:508-512)
 
         if do_classifier_free_guidance:
             seq_len = negative_prompt_embeds.shape[1]
@@ -1017,18 +1013,11 @@ class I2VAdapterPipeline:
     def _encode_texts(self, texts, clip_skip=None):
         """[len(texts), L, D]: the text encoder's embeddings of a list of strings in ONE call, as `encode_prompt` makes them (padding to
         `model_max_length`, truncation, `clip_skip` through the final LayerNorm)"""
-        if self.text_encoder is None or self.tokenizer is None:
-            raise ValueError("encoding a `prompt` needs both a `text_encoder` and a `tokenizer`: build the pipeline with them, or pass "
-                             "`prompt_embeds` (and `negative_prompt_embeds`)")
-        if getattr(self.text_encoder.config, "use_attention_mask", None):
-            raise NotImplementedError("text_encoder.config.use_attention_mask: padding attention masks are not implemented")
+        self._require_text_encoder()
         texts = self.maybe_convert_prompt(texts, self.tokenizer)
         ids = self.tokenizer(texts, padding="max_length", max_length=self.tokenizer.model_max_length, truncation=True,
                              return_tensors="pt").input_ids
-        if clip_skip is None:
-            return self.text_encoder(ids, attention_mask=None)[0]
-        hidden = self.text_encoder(ids, attention_mask=None, output_hidden_states=True)[-1][-(clip_skip + 1)]
-        return self.text_encoder.text_model.final_layer_norm(hidden)
+        return self._embed_ids(ids, clip_skip)
 
     def encode_prompt_travel(self, prompt, num_frames, device, num_videos_per_prompt, do_classifier_free_guidance, negative_prompt=None,
                              clip_skip=None, interpolation_callback=None):
@@ -1144,46 +1133,72 @@ class I2VAdapterPipeline:
         precise_stream: True / False runs THIS call with / without the precise residual stream
         (fp16 hi + lo pairs between the UNet's modules, DESIGN 2.2: closer to the fp32 reference, +2.6 % step time); None keeps the
         process setting (`blocks.set_precise_stream`, I2V_STREAM_PRECISE)."""
-        if precise_stream is not None:
-            kw = dict(locals())
-            for k in ("self", "precise_stream"):
-                kw.pop(k)
-            from . import blocks
-            prev = blocks.set_precise_stream(precise_stream)
-            try:
-                return self.__call__(**kw)
-            finally:
-                blocks.set_precise_stream(prev)
-        if cross_attention_kwargs and cross_attention_kwargs.get("scale") is not None:
-            # the LoRA scale of THIS call (diffusers: cross_attention_kwargs={"scale": s}); the previous one comes back afterwards.  A
-            # changed scale re-merges the weights and so re-captures the step once (_graph_key hashes the weights' versions)
-            kw = dict(locals())
-            for k in ("self", "precise_stream"):
-                kw.pop(k)
-            kw["cross_attention_kwargs"] = {k: v for k, v in cross_attention_kwargs.items() if k != "scale"}
-            prev = self.unet.set_lora_scale(cross_attention_kwargs["scale"])
-            try:
-                return self.__call__(**kw)
-            finally:
-                self.unet.set_lora_scale(prev)
-        # ControlNet: the arguments, before anything is launched or encoded
-        self._check_control_args(control_image, num_frames, controlnet_conditioning_scale, control_guidance_start, control_guidance_end,
-                                 guess_mode)
-        self._check_adapter_args(adapter_image, num_frames, adapter_conditioning_scale, adapter_conditioning_factor)
-        # video-to-video: the arguments, before anything is launched or encoded; frames beyond num_frames are dropped here
+        with contextlib.ExitStack() as restore:
+            # the per-call switches: set now, the previous values back on the way out (last set, first restored), also when the call raises
+            if precise_stream is not None:
+                restore.enter_context(_set_for_call(blocks.set_precise_stream, precise_stream))
+            if cross_attention_kwargs and cross_attention_kwargs.get("scale") is not None:
+                # the LoRA scale of THIS call (diffusers: cross_attention_kwargs={"scale": s}), before `_sync_lora` below.  A changed
+                # scale re-merges the weights and so re-captures the step once (_graph_key hashes the weights' versions)
+                restore.enter_context(_set_for_call(self.unet.set_lora_scale, cross_attention_kwargs["scale"]))
+                cross_attention_kwargs = {k: v for k, v in cross_attention_kwargs.items() if k != "scale"}
+            prompt, negative_prompt, travels, video, video_latents, strength = self._check_call_args(
+                prompt, negative_prompt, prompt_embeds, negative_prompt_embeds, ip_adapter_image, image_embeds, num_frames,
+                num_inference_steps, eta, frame_similarity_sample_ratio,
+                (control_image, num_frames, controlnet_conditioning_scale, control_guidance_start, control_guidance_end, guess_mode),
+                (adapter_image, num_frames, adapter_conditioning_scale, adapter_conditioning_factor),
+                video, video_latents, strength, mask_image)
+            output_type, use_graph = self._resolve_call_defaults(output_type, callback, use_graph)
+            do_cfg = guidance_scale > 1.0
+            self.unet._sync_lora()      # before anything reads a weight, a pack or the weights' versions (_graph_key)
+            prompt_embeds, negative_prompt_embeds, image_embeds, negative_image_embeds = self._encode_contexts(
+                prompt, negative_prompt, travels, prompt_embeds, negative_prompt_embeds, ip_adapter_image, image_embeds,
+                negative_image_embeds, num_frames, num_videos_per_prompt, do_cfg, clip_skip,
+                cross_attention_kwargs.get("scale", None) if cross_attention_kwargs is not None else None)
+            batch_size = prompt_embeds.shape[0]
+            height, width, condition_image_latents, video_latents = self._resolve_size_and_sources(
+                condition_image, condition_image_latents, video, video_latents, height, width, batch_size, generator)
+            assert 0 < frame_similarity_sample_ratio <= 1, (
+                f'"frame_similarity_sample_ratio" for img2vid must in (0, 1]. But receive {frame_similarity_sample_ratio}.')
+            prompt_embeds, image_embeds, per_frame = self._stack_guidance_halves(
+                prompt_embeds, negative_prompt_embeds, image_embeds, negative_image_embeds, num_frames, do_cfg)
+            round_steps = self._round_steps(num_inference_steps)
+            latents, cond, noise, source, timesteps = self._initial_latents(
+                condition_image_latents, video_latents, batch_size, num_frames, height, width, round_steps[0],
+                frame_similarity_sample_ratio if video_latents is None else strength, frame_similarity_blurred_strength, generator,
+                latents, prior_mask_generator, prior_noise_generator, blur_sigma)
+            st = self._assemble_state(
+                latents, cond, timesteps, eta, prompt_embeds, image_embeds, per_frame, 2 if do_cfg else 1, num_frames, guidance_scale,
+                batch_size, height, width, control_image,
+                (float(controlnet_conditioning_scale), float(control_guidance_start), float(control_guidance_end)), adapter_image,
+                (float(adapter_conditioning_scale), float(adapter_conditioning_factor)), mask_image, source, noise, generator)
+            latents = self._run_rounds(st, timesteps, round_steps, noise, use_graph, callback, callback_steps, eta, generator,
+                                       frame_similarity_sample_ratio)
+            return self._output(latents, output_type, return_dict)
+
+    # the phases of a call, in the order `__call__` runs them
+    def _check_call_args(self, prompt, negative_prompt, prompt_embeds, negative_prompt_embeds, ip_adapter_image, image_embeds,
+                         num_frames, num_inference_steps, eta, ratio, control_args, adapter_args, video, video_latents, strength,
+                         mask_image):
+        """Phase 1, the arguments: every check that needs no encoding, on the host, before anything is launched or encoded.  Reads the
+        call's arguments (control_args / adapter_args: the argument lists of `_check_control_args` / `_check_adapter_args`) and the
+        pipeline's parts and settings (FreeNoise, FreeInit).  Returns (prompt, negative_prompt, travels, video, video_latents,
+        strength): the prompts with one-key keyframe dicts turned into their text, whether the call has keyframed prompts, the source
+        clip cut to `num_frames` frames and the strength with its default."""
+        self._check_control_args(*control_args)
+        self._check_adapter_args(*adapter_args)
+        # frames beyond num_frames are dropped here
         video, video_latents, strength = self._check_video_args(video, video_latents, strength, mask_image, num_frames,
-                                                                num_inference_steps, frame_similarity_sample_ratio, eta)
-        has_clip = video is not None or video_latents is not None
-        # prompt travel: keyframe dicts are checked here, before anything is launched or encoded; a dict with one key is its text
+                                                                num_inference_steps, ratio, eta)
+        # prompt travel: a keyframe dict with one key is its text
         from .prompt_travel import normalize_prompt
         prompt, travels = normalize_prompt(prompt, num_frames, "prompt")
         negative_prompt, neg_travels = normalize_prompt(negative_prompt, num_frames, "negative_prompt")
-        travels = prompt is not None and (travels or neg_travels)
         for name, t in (("prompt_embeds", prompt_embeds), ("negative_prompt_embeds", negative_prompt_embeds)):
             if t is not None and t.dim() == 4 and t.shape[1] != num_frames:
                 raise ValueError(f"`{name}` is [B, F, L, D] = {tuple(t.shape)} with F = {t.shape[1]} per-frame contexts, `num_frames` is "
                                  f"{num_frames}")
-        # FreeNoise (enable_free_noise): the settings against this call's num_frames, before anything is launched or encoded
+        # FreeNoise (enable_free_noise): the settings against this call's num_frames
         fnz = self._free_noise_settings()
         if fnz is not None:
             from .free_init import MAX_FRAMES, MAX_HW
@@ -1192,7 +1207,6 @@ class I2VAdapterPipeline:
             if self._free_init is not None and num_frames > MAX_FRAMES:
                 raise ValueError(f"FreeNoise with FreeInit: num_frames {num_frames} exceeds FreeInit's {MAX_FRAMES} x {MAX_HW} x {MAX_HW} "
                                  "limit (frames x latent height x width of i2v_freeinit_mix) -- disable_free_init() for longer clips")
-        self.unet._sync_lora()      # before anything reads a weight, a pack or the weights' versions (_graph_key)
         if ip_adapter_image is not None:
             if image_embeds is not None:
                 raise ValueError("Cannot forward both `ip_adapter_image` and `image_embeds`. Please make sure to only forward one of "
@@ -1218,30 +1232,36 @@ class I2VAdapterPipeline:
             if self.text_encoder is None or self.tokenizer is None:
                 raise ValueError("a `prompt` needs both a `text_encoder` and a `tokenizer`: build the pipeline with them, or pass "
                                  "`prompt_embeds` and `negative_prompt_embeds`")
-            if travels:
-                # keyframed prompts: one context per frame, [B, F, L, D] (a given `negative_prompt_embeds` is kept)
-                pe, ne = self.encode_prompt_travel(prompt, num_frames, self.unet.device, num_videos_per_prompt,
-                                                   guidance_scale > 1.0 and negative_prompt_embeds is None, negative_prompt,
-                                                   clip_skip=clip_skip)
-                prompt_embeds, negative_prompt_embeds = pe, ne if negative_prompt_embeds is None else negative_prompt_embeds
-            elif self._prompt_weighting is not None:
-                # weighted and long prompts: contexts of n * 77 rows (a given `negative_prompt_embeds` is kept)
-                pe, ne = self.encode_weighted_prompt(prompt, self.unet.device, num_videos_per_prompt,
-                                                     guidance_scale > 1.0 and negative_prompt_embeds is None, negative_prompt,
-                                                     clip_skip=clip_skip)
-                prompt_embeds, negative_prompt_embeds = pe, ne if negative_prompt_embeds is None else negative_prompt_embeds
-            else:
-                prompt_embeds, negative_prompt_embeds = self.encode_prompt(
-                    prompt, self.unet.device, num_videos_per_prompt, guidance_scale > 1.0, negative_prompt,
-                    prompt_embeds=None, negative_prompt_embeds=negative_prompt_embeds,
-                    lora_scale=cross_attention_kwargs.get("scale", None) if cross_attention_kwargs is not None else None,
-                    clip_skip=clip_skip)
+        return prompt, negative_prompt, prompt is not None and (travels or neg_travels), video, video_latents, strength
+
+    def _encode_contexts(self, prompt, negative_prompt, travels, prompt_embeds, negative_prompt_embeds, ip_adapter_image, image_embeds,
+                         negative_image_embeds, num_frames, num_videos_per_prompt, do_cfg, clip_skip, lora_scale):
+        """Phase 2, the text and image contexts: a `prompt` through the text encoder (keyframed: `encode_prompt_travel`; while prompt
+        weighting is enabled: `encode_weighted_prompt`; else `encode_prompt`) and an `ip_adapter_image` through the image encoder,
+        once per sample; embeddings that were passed in are taken as given (a given `negative_prompt_embeds` is kept beside an encoded
+        prompt), `image_embeds` with their rank checked against the loaded IP-Adapter.  Returns (prompt_embeds,
+        negative_prompt_embeds, image_embeds, negative_image_embeds), the halves of the guidance still apart."""
+        dev = self.unet.device
+        encode_negative = do_cfg and negative_prompt_embeds is None
+        if travels:
+            # keyframed prompts: one context per frame, [B, F, L, D]
+            pe, ne = self.encode_prompt_travel(prompt, num_frames, dev, num_videos_per_prompt, encode_negative, negative_prompt,
+                                               clip_skip=clip_skip)
+            prompt_embeds, negative_prompt_embeds = pe, ne if negative_prompt_embeds is None else negative_prompt_embeds
+        elif prompt is not None and self._prompt_weighting is not None:
+            # weighted and long prompts: contexts of n * 77 rows
+            pe, ne = self.encode_weighted_prompt(prompt, dev, num_videos_per_prompt, encode_negative, negative_prompt,
+                                                 clip_skip=clip_skip)
+            prompt_embeds, negative_prompt_embeds = pe, ne if negative_prompt_embeds is None else negative_prompt_embeds
+        elif prompt is not None:
+            prompt_embeds, negative_prompt_embeds = self.encode_prompt(
+                prompt, dev, num_videos_per_prompt, do_cfg, negative_prompt, prompt_embeds=None,
+                negative_prompt_embeds=negative_prompt_embeds, lora_scale=lora_scale, clip_skip=clip_skip)
         if ip_adapter_image is not None:                                                        # pipe:616-622
             # once per sample, before the step is captured.  ImageProjection (plain IP-Adapter) takes the pooled embeds and a zero
             # negative; a Resampler (IP-Adapter Plus) the penultimate hidden states of the image and of a zero image
             output_hidden_state = not isinstance(self.unet.encoder_hid_proj, ImageProjection)
-            image_embeds, negative_image_embeds = self.encode_image(ip_adapter_image, self.unet.device, num_videos_per_prompt,
-                                                                    output_hidden_state)
+            image_embeds, negative_image_embeds = self.encode_image(ip_adapter_image, dev, num_videos_per_prompt, output_hidden_state)
         elif image_embeds is not None and self.unet.encoder_hid_proj is not None:
             plus = isinstance(self.unet.encoder_hid_proj, Resampler)
             for name, t in (("image_embeds", image_embeds), ("negative_image_embeds", negative_image_embeds)):
@@ -1251,6 +1271,14 @@ class I2VAdapterPipeline:
                         (f"IP-Adapter Plus is loaded (Resampler), which takes the image encoder's penultimate hidden states "
                          f"[batch, tokens, {self.unet.encoder_hid_proj.embed_dims}]" if plus else
                          "the plain IP-Adapter is loaded (ImageProjection), which takes the pooled image embeds [batch, embed_dim]"))
+        return prompt_embeds, negative_prompt_embeds, image_embeds, negative_image_embeds
+
+    def _resolve_size_and_sources(self, condition_image, condition_image_latents, video, video_latents, height, width, batch_size,
+                                  generator):
+        """Phase 3, the size and the encoded inputs: `height` / `width` from the arguments, the UNet's sample size or the condition
+        latents; a `condition_image` and then a `video` through the VAE (in that order: each may draw from `generator`; a clip shared
+        by the batch is encoded for every sample, each with its own draw); with a source clip and no condition its first frame is the
+        condition.  Refuses a UNet that is not on the GPU.  Returns (height, width, condition_image_latents, video_latents)."""
         if (condition_image is not None and condition_image_latents is None) or video is not None:  # pipe:624-627
             if height is None or width is None:
                 height = height or self.unet.config.sample_size * self.vae_scale_factor         # pipe:568-569
@@ -1260,33 +1288,29 @@ class I2VAdapterPipeline:
         if condition_image is not None and condition_image_latents is None:
             condition_image_latents = self.encode_condition_image(condition_image, height, width, generator)
         if video is not None:
-            # after the condition image's draw from `generator` and before prepare_latents'; a clip shared by the batch is encoded for
-            # every sample (each takes its own draw)
             frames = self._video_frames(video, height, width)
-            if frames.shape[0] == 1 and prompt_embeds.shape[0] > 1:
-                frames = frames.expand(prompt_embeds.shape[0], -1, -1, -1, -1)
+            if frames.shape[0] == 1 and batch_size > 1:
+                frames = frames.expand(batch_size, -1, -1, -1, -1)
             video_latents = self._encode_frames(frames, generator)
-        if has_clip and condition_image_latents is None:
+        if video_latents is not None and condition_image_latents is None:
             condition_image_latents = video_latents[:, 0]                 # the source's first frame is the condition
         if condition_image_latents is None:
             raise ValueError("`condition_image` (or `condition_image_latents`) is required: the reference's prior "
                              "(pipe:647-656) needs the condition image and crashes without it")
-        output_type, use_graph = self._resolve_call_defaults(output_type, callback, use_graph)
-        dev = self.unet.device
-        if dev.type != "cuda":
-            raise HipLibraryError(f"unet is on {dev}: the HIP path has no CPU fallback")
+        if self.unet.device.type != "cuda":
+            raise HipLibraryError(f"unet is on {self.unet.device}: the HIP path has no CPU fallback")
         h_lat, w_lat = condition_image_latents.shape[-2:]
         height = height or h_lat * self.vae_scale_factor
         width = width or w_lat * self.vae_scale_factor
         if height % 8 != 0 or width % 8 != 0:                                                   # pipe:213-214
             raise ValueError(f"`height` and `width` have to be divisible by 8 but are {height} and {width}.")
         # (latent sizes that are not multiples of 8 take the UNet's forward_upsample_size path, unet:1304-1311)
-        assert 0 < frame_similarity_sample_ratio <= 1, (
-            f'"frame_similarity_sample_ratio" for img2vid must in (0, 1]. But receive {frame_similarity_sample_ratio}.')
-        batch_size = prompt_embeds.shape[0]
-        do_cfg = guidance_scale > 1.0
-        copies = 2 if do_cfg else 1
-        # per-frame contexts (prompt travel, or 4-D embeds passed in): [B, F, L, D] on both sides of the guidance
+        return height, width, condition_image_latents, video_latents
+
+    def _stack_guidance_halves(self, prompt_embeds, negative_prompt_embeds, image_embeds, negative_image_embeds, num_frames, do_cfg):
+        """between phases 3 and 4, the contexts as the step's batch reads them: per-frame contexts (prompt travel, or 4-D embeds passed
+        in) made [B, F, L, D] on both sides of the guidance, then under classifier-free guidance [negative ; positive] along the
+        batch, for the image embeds too (a missing negative is zeros).  Returns (prompt_embeds, image_embeds, per_frame)."""
         per_frame = prompt_embeds.dim() == 4 or (do_cfg and negative_prompt_embeds is not None and negative_prompt_embeds.dim() == 4)
         if per_frame:
             prompt_embeds = self._per_frame_embeds(prompt_embeds, num_frames, "prompt_embeds")
@@ -1304,32 +1328,40 @@ class I2VAdapterPipeline:
                 if negative_image_embeds is None:
                     negative_image_embeds = torch.zeros_like(image_embeds)                      # pipe:343
                 image_embeds = torch.cat([negative_image_embeds, image_embeds])                 # pipe:621-622
+        return prompt_embeds, image_embeds, per_frame
 
-        kind = self._scheduler_kind()
-        dpm, lcm = kind == "dpmsolver++", kind == "lcm"
-        # FreeInit (enable_free_init): `rounds` sampling passes; with fast sampling round i has its own, shorter schedule
+    def _round_steps(self, num_inference_steps):
+        """the step count of every sampling round: one round, or FreeInit's `num_iters` (enable_free_init), where with fast sampling
+        round i has its own, shorter schedule"""
         fi = self._free_init
         rounds = fi["num_iters"] if fi is not None else 1
-        fast = fi is not None and fi["use_fast_sampling"] and rounds > 1
-        if fast:
+        if fi is not None and fi["use_fast_sampling"] and rounds > 1:
             from .free_init import round_inference_steps
-            round_steps = [round_inference_steps(num_inference_steps, rounds, i) for i in range(rounds)]
-        else:
-            round_steps = [num_inference_steps] * rounds
-        self.scheduler.set_timesteps(round_steps[0])                                            # pipe:630-631
-        timesteps, _ = self.get_timesteps(round_steps[0], strength if has_clip else frame_similarity_sample_ratio)
+            return [round_inference_steps(num_inference_steps, rounds, i) for i in range(rounds)]
+        return [num_inference_steps] * rounds
 
+    def _initial_latents(self, condition_image_latents, video_latents, batch_size, num_frames, height, width, num_steps, strength,
+                         blurred_strength, generator, latents, prior_mask_generator, prior_noise_generator, blur_sigma):
+        """Phase 4, the first round's schedule and the latents it starts from.  `strength`: the fraction of the `num_steps` schedule
+        that runs (the similarity ratio without a source clip).  The draws, in this order: `prepare_latents` (`generator`), the blur
+        sigma and the prior's mask (`prior_mask_generator`; neither with a source clip), the noise (`prior_noise_generator`;
+        rescheduled by FreeNoise behind its first window).  Without a source clip the first-frame-similarity prior + add_noise
+        (pipe:647-656) in ONE HIP kernel -- the reference overwrites the latents drawn above (its `latents = self.scheduler.
+        add_noise(...)`, pipe:656), and so does this; its random draws take explicit generators (the reference uses the unseeded
+        global RNG) --, with one the source noised to the first timestep's level.  Returns (latents, cond, noise, source, timesteps):
+        fp32 on the UNet's device, `source` None without a clip."""
+        dev = self.unet.device
+        has_clip = video_latents is not None
+        self.scheduler.set_timesteps(num_steps)                                                 # pipe:630-631
+        timesteps, _ = self.get_timesteps(num_steps, strength)
         cond_dev = condition_image_latents.detach().to(dev, torch.float32).contiguous()
         latents = self.prepare_latents(batch_size, self.unet.config.in_channels, num_frames, height, width,
                                        torch.float32, dev, generator, latents)                  # pipe:635-645
-        # first-frame-similarity prior + add_noise (pipe:647-656) in ONE HIP kernel; the reference overwrites the
-        # latents drawn above (its `latents = self.scheduler.add_noise(...)`, pipe:656), and so does this.  The random
-        # draws (blur sigma, mask, noise) take explicit generators (the reference uses the unseeded global RNG).
-        # With a source clip no prior is built: its blur sigma and mask are not drawn, the noise is drawn as the prior's is.
         if blur_sigma is None and not has_clip:                                                 # pipe:112
             blur_sigma = draw_blur_sigma(prior_mask_generator[0] if isinstance(prior_mask_generator, (list, tuple))
                                          else prior_mask_generator)
         shape = (batch_size, num_frames) + tuple(cond_dev.shape[1:])
+        source = None
         if has_clip:
             source = video_latents.detach().to(dev, torch.float32)
             if source.shape[0] == 1 and batch_size > 1:
@@ -1340,6 +1372,7 @@ class I2VAdapterPipeline:
             source = source.contiguous()
         else:
             mask_u = _draw(torch.rand, shape, prior_mask_generator, dev)                        # pipe:652
+        fnz = self._free_noise_settings()
         if fnz is not None and num_frames > fnz.context_length:
             # FreeNoise: the frames behind the first window re-use its noise (repeated or shuffled: `free_noise.reschedule_noise`)
             from .free_noise import reschedule_noise
@@ -1351,13 +1384,39 @@ class I2VAdapterPipeline:
             latents = self.prepare_video_latents(source, noise, timesteps[0])
         else:
             a_t = float(self.scheduler.alphas_cumprod[int(timesteps[0])])
-            latents = K.first_frame_prior(cond_dev, mask_u.contiguous(), noise, blur_sigma,
-                                          frame_similarity_blurred_strength, a_t ** 0.5, (1.0 - a_t) ** 0.5)
+            latents = K.first_frame_prior(cond_dev, mask_u.contiguous(), noise, blur_sigma, blurred_strength, a_t ** 0.5,
+                                          (1.0 - a_t) ** 0.5)
+        return latents, cond_dev, noise, source, timesteps
 
+    def _schedule_tables(self, st, timesteps, eta):
+        """the tables of a schedule, fp32 on the device of st["latents"], written into `st`: `t_table` and `coef`
+        (`scheduler.step_coefficients`), and one row per executed step for each feature the state holds -- `cn_scale` (conditioning
+        scale x diffusers' `controlnet_keep` window, from st["cn_args"]) with a ControlNet's `cn_cond`, `t2i_scale` (the adapter's scale
+        on the first int(steps * factor) steps, from st["t2i_args"]) with a T2I-Adapter's `t2i_feats`, `v2v_coef` (`renoise_table`)
+        with a mask.  Round 0 of a call and every round of FreeInit's fast sampling call it: the tables then change shape, and so
+        does the graph key."""
+        dev = st["latents"].device
+        st["t_table"] = timesteps.to(torch.float32).to(dev)
+        st["coef"] = self.scheduler.step_coefficients(timesteps, eta).to(dev)
+        if st.get("cn_cond") is not None:
+            from .controlnet import controlnet_keep_table
+            st["cn_scale"] = torch.tensor(controlnet_keep_table(len(timesteps), *st["cn_args"]), dtype=torch.float32, device=dev)
+        if st.get("t2i_feats") is not None:
+            from .t2i_adapter import adapter_scale_table
+            st["t2i_scale"] = torch.tensor(adapter_scale_table(len(timesteps), *st["t2i_args"]), dtype=torch.float32, device=dev)
+        if st.get("v2v_mask") is not None:
+            st["v2v_coef"] = self.renoise_table(timesteps).to(dev)
+
+    def _assemble_state(self, latents, cond, timesteps, eta, prompt_embeds, image_embeds, per_frame, copies, num_frames, guidance_scale,
+                        batch_size, height, width, control_image, cn_args, adapter_image, t2i_args, mask_image, source, noise, generator):
+        """Phase 5, the state dict `st` of the captured step (SAMPLE_INPUTS and the launch scalars), everything on the device: the
+        contexts (the IP-Adapter's image tokens projected here), once per sample the ControlNet's embedding of the control frames and
+        the T2I-Adapter's feature maps, the mask at the latent resolution with the source and the noise its blend reads, the tables of
+        the first round's schedule (`_schedule_tables`), DPM-Solver++'s history buffer and, last, LCM's noise table -- the one draw
+        here, from `generator`, after the prior's.  cn_args / t2i_args are kept in `st` for later rounds' tables."""
+        dev = latents.device
         st = dict(
-            latents=latents, cond=cond_dev, copies=copies,
-            num_frames=num_frames, guidance=float(guidance_scale),
-            t_table=timesteps.to(torch.float32).to(dev), coef=self.scheduler.step_coefficients(timesteps, eta).to(dev),
+            latents=latents, cond=cond, copies=copies, num_frames=num_frames, guidance=float(guidance_scale),
             step_idx=torch.zeros(1, dtype=torch.int32, device=dev),
             ctx_text=prompt_embeds.to(dev, f16).contiguous(),
             ctx_ip=self.unet._project_image_embeds(
@@ -1369,44 +1428,50 @@ class I2VAdapterPipeline:
             st["ctx_text"] = st["ctx_text"].view(-1, *st["ctx_text"].shape[2:])
             st["ctx_ip"] = self.unet._expand_image_tokens(st["ctx_ip"], st["ctx_text"].shape[0])
         if self.controlnet is not None:
-            # once per sample: the embedding of the B * F control frames (duplicated for the second CFG half) and the scale table;
-            # the ControlNet's context projection and time table are made where the UNet's are (_project_once)
+            # once per sample: the embedding of the B * F control frames (duplicated for the second CFG half); the scale table comes
+            # with the schedule's, and the ControlNet's context projection and time table are made where the UNet's are (_project_once)
             frames = self.prepare_control_image(control_image, batch_size, num_frames, height, width).to(dev, f16)
             tokens = self.controlnet.embed_condition(frames)
-            st["cn_cond"] = K.duplicate_batch(tokens) if copies == 2 else tokens
-            st["cn_args"] = (float(controlnet_conditioning_scale), float(control_guidance_start), float(control_guidance_end))
-            st["cn_scale"] = self._control_scale_table(len(timesteps), st["cn_args"], dev)
+            st["cn_cond"], st["cn_args"] = K.duplicate_batch(tokens) if copies == 2 else tokens, cn_args
         if self.t2i_adapter is not None:
             # once per sample: the adapter's four feature maps of the B * F control frames (ONE copy: the step's add wraps around for
-            # the second CFG half) and the scale table
+            # the second CFG half)
             frames = self.prepare_adapter_image(adapter_image, batch_size, num_frames, height, width).to(dev, f16)
-            st["t2i_feats"] = self.t2i_adapter.embed(frames)
-            st["t2i_args"] = (float(adapter_conditioning_scale), float(adapter_conditioning_factor))
-            st["t2i_scale"] = self._adapter_scale_table(len(timesteps), st["t2i_args"], dev)
+            st["t2i_feats"], st["t2i_args"] = self.t2i_adapter.embed(frames), t2i_args
         if mask_image is not None:
             # the inpainting update: after every scheduler step the kept region goes back to the source at the NEXT step's noise level
             # (the same initial noise), after the last step to the clean source -- one launch inside the captured step (_step)
             st["v2v_mask"] = self.prepare_mask_latents(mask_image, batch_size, num_frames, height, width).to(dev).contiguous()
             st["v2v_source"], st["v2v_noise"] = source, noise
-            st["v2v_coef"] = self.renoise_table(timesteps).to(dev)
-        if dpm:
+        self._schedule_tables(st, timesteps, eta)
+        kind = self._scheduler_kind()
+        if kind == "dpmsolver++":
             # the previous step's data prediction: the first step of a sample is first order and does not read it
             st["x0_prev"] = torch.empty_like(latents)
-        if lcm:
+        if kind == "lcm":
             # every step's fresh noise (diffusers draws it inside `step`, from `generator`, after prepare_latents' draw): one table per
             # sample, drawn after the prior's draws, read on the device by the step counter -- the steps stay captured
             st["noise"] = self.scheduler.step_noise(timesteps, tuple(latents.shape), generator, dev)
-        # K / V^T of the prompt (+ image) context for all 16 cross-attention layers: once per sample, not once per step
-        # (projected where it is consumed: a graph-cache hit projects straight into the graph's static buffers)
-        # (DPM-Solver++ has no stochastic form here: the reference passes `eta` only to a scheduler whose step takes it,
-        # pipe:184-199, so it is ignored and the steps stay captured; LCM's step takes no eta either, and its noise is in the table)
-        fixed = dpm or lcm
-        for rnd in range(rounds):
+        return st
+
+    def _run_rounds(self, st, timesteps, round_steps, init_noise, use_graph, callback, callback_steps, eta, generator, ratio):
+        """Phase 6, the sampling rounds: one pass over `timesteps`, and with FreeInit one more per further entry of `round_steps`, each
+        from `_free_init_round`'s re-initialised latents; after every round frame 0 is the condition again.  K / V^T of the context
+        for all 16 cross-attention layers is projected once per sample where it is consumed (`_run_steps`: a graph-cache hit projects
+        straight into the graph's static buffers).  DPM-Solver++ has no stochastic form here (the reference passes `eta` only to a
+        scheduler whose step takes it, pipe:184-199), and LCM's step takes no eta either, its noise is in the table: with both `eta`
+        is ignored and the steps stay captured.  Returns the final latents."""
+        fixed = self._scheduler_kind() in ("dpmsolver++", "lcm")
+        for rnd in range(len(round_steps)):
             if rnd > 0:
-                timesteps = self._free_init_round(st, rnd, round_steps, fast, noise, generator, frame_similarity_sample_ratio, eta, lcm)
+                timesteps = self._free_init_round(st, rnd, round_steps, init_noise, generator, ratio, eta)
             self._sample_round(st, timesteps, use_graph, callback, callback_steps, eta, fixed, generator)
             latents = st["latents"]
             latents[:, 0] = st["cond"]                                                          # pipe:699-700
+        return latents
+
+    def _output(self, latents, output_type, return_dict):
+        """Phase 7, the output: the latents as they are ("latent"), or decoded by the VAE to a tensor ("pt") or through `tensor2vid`"""
         if output_type == "latent":                                                             # pipe:702-703
             video = latents
         else:
@@ -1417,9 +1482,10 @@ class I2VAdapterPipeline:
             return (video,)
         return I2VAdapterPipelineOutput(frames=video)
 
-    def _free_init_round(self, st, rnd, round_steps, fast, init_noise, generator, ratio, eta, lcm):
+    def _free_init_round(self, st, rnd, round_steps, init_noise, generator, ratio, eta):
         """FreeInit between round rnd - 1 and round rnd >= 1 (diffusers `_apply_free_init`), in the order of the draws: the fresh noise
-        z_rand from the call's `generator` (after everything the previous round drew), this round's schedule under fast sampling, the
+        z_rand from the call's `generator` (after everything the previous round drew), this round's schedule and its tables under fast
+        sampling (`_schedule_tables`), the
         mix -- st["latents"], the clip as the call would return it, re-noised with the round-0 noise to the level of this round's first
         timestep (the level the prior noises to, pipe:656, and the one the round's first step expects) and low-passed against z_rand
         --, then an LCM round's noise table.  The state goes through `_run_steps`' copy-in path like a new sample's: same graph key
@@ -1428,22 +1494,16 @@ class I2VAdapterPipeline:
         from .free_init import free_init_filter
         fi, prev, dev = self._free_init, st["latents"], st["latents"].device
         z_rand = _draw(torch.randn, tuple(prev.shape), generator, dev).to(torch.float32).contiguous()
-        if fast:
+        if fi["use_fast_sampling"]:
             self.scheduler.set_timesteps(round_steps[rnd])
-            timesteps, _ = self.get_timesteps(round_steps[rnd], ratio)
-            st["t_table"] = timesteps.to(torch.float32).to(dev)
-            st["coef"] = self.scheduler.step_coefficients(timesteps, eta).to(dev)
-            if st.get("cn_cond") is not None:      # the control window over THIS round's schedule (the time table follows t_table)
-                st["cn_scale"] = self._control_scale_table(len(timesteps), st["cn_args"], dev)
-            if st.get("t2i_feats") is not None:    # ... and the adapter's factor over THIS round's number of steps
-                st["t2i_scale"] = self._adapter_scale_table(len(timesteps), st["t2i_args"], dev)
-        else:
-            timesteps, _ = self.get_timesteps(round_steps[rnd], ratio)
+        timesteps, _ = self.get_timesteps(round_steps[rnd], ratio)
+        if fi["use_fast_sampling"]:
+            self._schedule_tables(st, timesteps, eta)
         b, f, c, h, w = prev.shape
         lpf = free_init_filter((f, h, w), fi["method"], fi["order"], fi["spatial_stop_frequency"], fi["temporal_stop_frequency"], device=dev)
         a_t = float(self.scheduler.alphas_cumprod[int(timesteps[0])])
         st["latents"] = K.freeinit_mix(prev.contiguous(), init_noise.contiguous(), z_rand, lpf, a_t ** 0.5, (1.0 - a_t) ** 0.5)
-        if lcm:
+        if self._scheduler_kind() == "lcm":
             st["noise"] = self.scheduler.step_noise(timesteps, tuple(prev.shape), generator, dev)
         st["step_idx"] = torch.zeros(1, dtype=torch.int32, device=dev)
         return timesteps

@@ -17,8 +17,8 @@ from torch import nn
 from . import kernels as K
 from ._lib import HipLibraryError
 from .blocks import (Attention, DownBlockMotion, Downsample2D, HipModule, ImageProjection, MotionAdapter, Resampler,
-                     ProjectedContext, ProjectedTemb, ResnetBlock2D, TimestepEmbedding, Timesteps, UpBlockMotion, freeu_scales,
-                     Upsample2D, _as_f16_matrix, _motion, from_tokens, pack_conv3x3, precise_stream, to_tokens, w16)
+                     ProjectedContext, ProjectedTemb, ResnetBlock2D, SampleProjectionMixin, TimestepEmbedding, Timesteps,
+                     UpBlockMotion, freeu_scales, Upsample2D, _as_f16_matrix, _motion, from_tokens, pack_conv3x3, precise_stream, to_tokens, w16)
 from .checkpoint import PretrainedMixin
 from .i2v_adapter import I2VAdapterModule, I2VAdapterTransformer2DModel
 from .lora import UNetLoraMixin
@@ -364,7 +364,7 @@ def convert_ip_adapter_plus_image_proj(image_proj):
     return kwargs, out
 
 
-class UNetMotionCrossFrameAttnModel(UNetLoraMixin, PretrainedMixin, HipModule):
+class UNetMotionCrossFrameAttnModel(UNetLoraMixin, SampleProjectionMixin, PretrainedMixin, HipModule):
     """unet:696-1451."""
 
     def __init__(self, sample_size: Optional[int] = None, in_channels: int = 4, out_channels: int = 4,
@@ -759,45 +759,6 @@ class UNetMotionCrossFrameAttnModel(UNetLoraMixin, PretrainedMixin, HipModule):
         modules = dict(self.named_modules())
         return [modules[n[: -len(".processor")]] for n in self.attn_processor_names()
                 if n.endswith("attn2.processor") and "motion_modules" not in n]
-
-    def project_context(self, ctx_text, ctx_ip=None, out: Optional[ProjectedContext] = None) -> ProjectedContext:
-        """K / V^T of the text (+ image) context for every cross-attention layer, computed ONCE per sample instead of in
-        every UNet call (they do not depend on the latents or the timestep).  `out`: a previous result whose buffers
-        are overwritten in place (a captured hipGraph keeps reading the same memory for the next sample)."""
-        self._sync_lora()
-        pc = out if out is not None else ProjectedContext(ctx_text, ctx_ip)
-        if out is not None:
-            pc.text, pc.ip = ctx_text, ctx_ip
-        for attn in self._cross_attention_layers():
-            pc.kv[attn] = attn.project_kv(ctx_text, ctx_ip, out=pc.kv.get(attn))
-            attn.refresh_context_fragments(pc)       # (the fused text cross-attention's packed K / V, where a forward made them)
-        return pc
-
-    def _temb_pack(self):
-        """time_emb_proj weights of all resnets concatenated ([sum Cout, 4 C0]) + the column slice of each resnet."""
-        self._sync_lora()
-        resnets = [m for m in self.modules() if isinstance(m, ResnetBlock2D) and m.time_emb_proj is not None]
-        key = tuple((r.time_emb_proj.weight.data_ptr(), r.time_emb_proj.weight._version, r.time_emb_proj.bias._version)
-                    for r in resnets)
-        if getattr(self, "_temb_packed_key", None) != key:
-            with torch.no_grad():
-                w = w16(torch.cat([r.time_emb_proj.weight for r in resnets], dim=0))
-                b = w16(torch.cat([r.time_emb_proj.bias for r in resnets], dim=0))
-            slices, off = {}, 0
-            for r in resnets:
-                slices[r] = (off, r.out_channels)
-                off += r.out_channels
-            self._temb_packed, self._temb_packed_key = (w, b, slices), key
-        return self._temb_packed
-
-    def project_time_table(self, timesteps_f32, out=None):
-        """[T, sum Cout] fp16: `time_emb_proj(silu(time_embedding(time_proj(t))))` of every ResnetBlock2D (unet:1336-1343,
-        SURVEY A2) for ALL T timesteps of a schedule at once.  The chain depends on t only -- not on the latents -- so the
-        pipeline computes it once per sample (like `project_context`) and a replayed step selects its row by the device-side
-        step counter (`K.select_row`): 6 launches of M = 1 products per step become one 40 KB copy."""
-        wt, bt, _ = self._temb_pack()
-        temb = self._embed_time(timesteps_f32.to(torch.float32).contiguous())
-        return K.gemm(K.silu(temb), wt, bt, out=out)
 
     def _fwd_tokens(self, x, temb, enable_cross_frame_attn, ctx_text, ctx_ip, num_frames, cfg_shared=False, temb_proj=None,
                     forward_upsample_size=False, down_residuals=None, mid_residual=None, residual_scale=None,

@@ -1,6 +1,6 @@
 // The CLIP text tower's two own kernels (transformers CLIPTextModel as the pipeline calls it, pipe:412-453): everything else of the
 // tower -- the QKV / out / fc1 / fc2 projections, the LayerNorms -- runs on the GEMM and LayerNorm entry points the UNet uses, its
-// causal attention on the kernel it shares with the vision tower (clip_attention.hip).
+// causal attention on the kernel it shares with the vision tower (short_attention.hip).
 //
 //   embed        out[b*L + l, :] = fp16(float(tok[ids[b, l], :]) + float(pos[l, :]))      one 16-byte chunk of one row per lane
 //   quick-GELU   y = fp16(x * sigmoid(1.702 x)) in fp32, any n, in place or not

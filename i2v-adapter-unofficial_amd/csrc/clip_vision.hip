@@ -2,7 +2,7 @@
 // IP-Adapter's image encoder is OpenCLIP ViT-H/14: 32 pre-LN layers, width 1280, 16 heads of 80, 16 x 16 patches of 14 px + a class token
 // = 257 tokens).  Everything else of the tower -- the patch embedding itself, the q|k|v / out / fc1 / fc2 projections, the LayerNorms,
 // the visual projection -- runs on the GEMM and LayerNorm entry points the UNet uses, its bidirectional attention on the kernel it
-// shares with the text tower (clip_attention.hip).
+// shares with the text tower (short_attention.hip).
 //
 //   patchify     pixel_values [B, C, S, S] -> rows [B * (S/p)^2, ld]: row b P + py (S/p) + px is patch (py, px) in column order (c, dy, dx)
 //                (the order of patch_embedding.weight.flatten(1)), columns C p p .. ld - 1 written as zero: the im2col of the strided

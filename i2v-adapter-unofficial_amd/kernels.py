@@ -1102,23 +1102,35 @@ def clip_embed(token_embedding, position_embedding, input_ids):
     return out
 
 
+def _attn_operand(t, name, rows, hidden, *offsets):
+    """a packed operand of csrc/short_attention.hip's entries, fp16 [rows, >= offset + hidden] for each offset -> (tensor, row stride)"""
+    t, ld = _mat(t, name)
+    if t.shape[0] != rows or max(offsets) + hidden > t.shape[1]:
+        raise ValueError(f"{name} is {tuple(t.shape)}: expected [{rows}, >= offset + {hidden}]")
+    return t, ld
+
+
+def _attn_out(out, rows, hidden, device):
+    """their `out`: the caller's [rows, hidden] view or a new tensor -> (tensor, row stride)"""
+    if out is None:
+        out = torch.empty((rows, hidden), dtype=f16, device=device)
+    out, ldo = _mat(out, "out")
+    if out.shape != (rows, hidden):
+        raise ValueError(f"out must be {(rows, hidden)}, got {tuple(out.shape)}")
+    return out, ldo
+
+
 def _clip_attention(entry_name, qkv, *, batch, length, heads, head_dim, q_off=None, k_off=None, v_off=None, scale=None, out=None):
-    """what `clip_attention` and `clip_vision_attention` share (csrc/clip_attention.hip: one kernel, one set of argument checks): qkv
+    """what `clip_attention` and `clip_vision_attention` share (csrc/short_attention.hip: one kernel, one set of argument checks): qkv
     fp16 [batch * length, >= 3 * hidden], head h of q / k / v in columns q_off / k_off / v_off + h * head_dim (default 0, hidden,
     2 * hidden) -> fp16 [batch * length, hidden]; `entry_name` is the C entry point, which holds the envelope."""
     lib = _lib.load()
-    qkv, ld = _mat(qkv, "qkv")
     hidden = heads * head_dim
     q_off = 0 if q_off is None else q_off
     k_off = hidden if k_off is None else k_off
     v_off = 2 * hidden if v_off is None else v_off
-    if qkv.shape[0] != batch * length or max(q_off, k_off, v_off) + hidden > qkv.shape[1]:
-        raise ValueError(f"qkv is {tuple(qkv.shape)}: expected [{batch * length}, >= offset + {hidden}]")
-    if out is None:
-        out = torch.empty((batch * length, hidden), dtype=f16, device=qkv.device)
-    out, ldo = _mat(out, "out")
-    if out.shape != (batch * length, hidden):
-        raise ValueError(f"out must be {(batch * length, hidden)}, got {tuple(out.shape)}")
+    qkv, ld = _attn_operand(qkv, "qkv", batch * length, hidden, q_off, k_off, v_off)
+    out, ldo = _attn_out(out, batch * length, hidden, qkv.device)
     scale = float(head_dim) ** -0.5 if scale is None else float(scale)
     _lib.check(getattr(lib, entry_name)(_p(qkv), ld, q_off, k_off, v_off, _p(out), ldo, batch, length, heads, head_dim, scale, _stream()),
                entry_name)
@@ -1205,29 +1217,19 @@ def perceiver_attention(q, kv_a, kv_b=None, *, batch, n_q, len_a, len_b=0, heads
     len_a + len_b <= 288 only (anything else raises)."""
     lib = _lib.load()
     hidden = heads * head_dim
-    q, ldq = _mat(q, "q")
-    kv_a, lda = _mat(kv_a, "kv_a")
     va_off = hidden if va_off is None else va_off
     kb_off = hidden if kb_off is None else kb_off
     vb_off = 2 * hidden if vb_off is None else vb_off
-    if q.shape[0] != batch * n_q or q_off + hidden > q.shape[1]:
-        raise ValueError(f"q is {tuple(q.shape)}: expected [{batch * n_q}, >= {q_off} + {hidden}]")
-    if kv_a.shape[0] != batch * len_a or max(ka_off, va_off) + hidden > kv_a.shape[1]:
-        raise ValueError(f"kv_a is {tuple(kv_a.shape)}: expected [{batch * len_a}, >= offset + {hidden}]")
+    q, ldq = _attn_operand(q, "q", batch * n_q, hidden, q_off)
+    kv_a, lda = _attn_operand(kv_a, "kv_a", batch * len_a, hidden, ka_off, va_off)
     if len_b > 0:
         if kv_b is None:
             raise ValueError(f"len_b = {len_b} needs kv_b")
-        kv_b, ldb = _mat(kv_b, "kv_b")
-        if kv_b.shape[0] != batch * len_b or max(kb_off, vb_off) + hidden > kv_b.shape[1]:
-            raise ValueError(f"kv_b is {tuple(kv_b.shape)}: expected [{batch * len_b}, >= offset + {hidden}]")
+        kv_b, ldb = _attn_operand(kv_b, "kv_b", batch * len_b, hidden, kb_off, vb_off)
         pb = _p(kv_b)
     else:
         pb, ldb, kb_off, vb_off = None, 0, 0, 0
-    if out is None:
-        out = torch.empty((batch * n_q, hidden), dtype=f16, device=q.device)
-    out, ldo = _mat(out, "out")
-    if out.shape != (batch * n_q, hidden):
-        raise ValueError(f"out must be {(batch * n_q, hidden)}, got {tuple(out.shape)}")
+    out, ldo = _attn_out(out, batch * n_q, hidden, q.device)
     scale = float(head_dim) ** -0.5 if scale is None else float(scale)
     _lib.check(lib.i2v_perceiver_attention_f16(_p(q), ldq, q_off, _p(kv_a), lda, ka_off, va_off, len_a, pb, ldb, kb_off, vb_off, len_b,
                                                _p(out), ldo, batch, n_q, heads, head_dim, scale, _stream()),

@@ -723,7 +723,7 @@ int i2v_freenoise_blend_f16(const void* src, int64_t ld_src, void* dst, int64_t 
  *       q, k and v are read in place from the packed result of one QKV GEMM: qkv fp16 [batch * len, ld_qkv], head h of q / k / v of a row in
  *       columns q_off / k_off / v_off + h * 64 (offsets multiples of 8); out fp16 [batch * len, ld_out].  No transposed V, no mask tensor: key j
  *       is visible to query i iff j <= i (and j < len), by index compare, so no row is ever fully masked.  The kernel is
- *       i2v_clip_vision_attention_f16's with the causal mask (csrc/clip_attention.hip): grid (batch * heads, ceil(len / 64)), the head's whole K
+ *       i2v_clip_vision_attention_f16's with the causal mask (csrc/short_attention.hip): grid (batch * heads, ceil(len / 64)), the head's whole K
  *       and V^T staged in LDS, padded to the MFMA tile there only (nothing at or beyond row batch * len is read or written).
  *       Numerics: Q K^T and P V on MFMA with fp32 accumulation, softmax in fp32 in base 2 with the logits scaled by scale * log2(e) in fp32, P
  *       rounded to fp16 for P V, the row sum taken over the unrounded P.
@@ -754,7 +754,7 @@ int i2v_quick_gelu_f16(const void* x, void* y, int64_t n, i2v_stream_t stream);
  *       The argument list is i2v_clip_attention_f16's: q, k, v read in place from the packed result of one QKV GEMM (qkv fp16 [batch * len,
  *       ld_qkv], head h of q / k / v in columns q_off / k_off / v_off + h * head_dim, offsets multiples of 8), out fp16 [batch * len, ld_out].
  *       Grid (batch * heads, ceil(len / 64)): a workgroup of 4 waves owns 64 queries and stages the head's whole K (head_dim padded with zeros to
- *       the MFMA K-step, 80 -> 96) and V^T (keys padded with zeros to a multiple of 32) in LDS, 114 KB.  Key j is visible iff j < len, by index
+ *       the MFMA K-step, 80 -> 96) and V^T (keys padded with zeros to a multiple of 32) in LDS, 78 KB (d 80: 105 KB).  Key j is visible iff j < len, by index
  *       compare (P of a pad key is exactly 0; key 0 is always visible, so no row is fully masked); rows at or beyond batch * len are never
  *       read, only queries < len are stored.  Numerics as i2v_clip_attention_f16 (the same kernel without the causal mask): MFMA 16x16x32
  *       with fp32 accumulation, softmax in fp32 in base 2 with the logits scaled by scale * log2(e) in fp32, P rounded to fp16 for P V, the
@@ -778,6 +778,8 @@ int i2v_clip_vision_attention_f16(const void* qkv, int64_t ld_qkv, int32_t q_off
  *       head h of k / v in columns k_off / v_off + h * 64 (all offsets and strides multiples of 8).  kv_b may be NULL when len_b == 0.  q, A and B
  *       are read-only and MAY ALIAS (in the Resampler B is the latents' packed q | k | v buffer, the memory q is read from); out fp16
  *       [batch * n_q, ld_out] may overlap none of them, and only its rows < batch * n_q, columns < heads * 64 are written.
+ *       The kernel is i2v_clip_vision_attention_f16's at head_dim 64 (csrc/short_attention.hip: one kernel for the three entry points), with a
+ *       query block of its own and the key rows taken from two sources.
  *       Grid (batch * heads): a workgroup of 4 waves owns all queries of one (batch, head) and stages the head's whole K and V^T (keys padded
  *       with zeros to a multiple of 32) in 78 KB of LDS, A's rows then B's; after that nothing depends on where the A / B boundary was, so the
  *       same keys split differently give bit-equal results.  Key j is visible iff j < len_a + len_b, by index compare; no row beyond a source's

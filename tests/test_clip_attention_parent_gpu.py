@@ -1,7 +1,7 @@
 """Both CLIP attention entry points, bit for bit against the library that had one attention kernel per tower.
 
 tests/golden/clip_attention_parent.json (tools/record_clip_attention.py) holds, per case, the sha256 of the fp16 output of
-`kernels.clip_attention` / `kernels.clip_vision_attention` as that library computed it on MI355X.  csrc/clip_attention.hip's one kernel
+`kernels.clip_attention` / `kernels.clip_vision_attention` as that library computed it on MI355X.  csrc/short_attention.hip's one kernel
 does every query's arithmetic in the same order -- the causal instantiation skips the key tiles right of the diagonal, which add an
 exact + 0.f to the row sum -- so each digest must still match: no tolerance.  The inputs are rebuilt from integers by the same numpy
 code the recorder used (tests/clip_attention_cases.py)."""

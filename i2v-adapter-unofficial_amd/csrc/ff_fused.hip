@@ -29,35 +29,21 @@
 
 #include <type_traits>
 
-#include "common.h"
+#include "ln_panel.h"
 
 namespace {
-
-__device__ __forceinline__ void ff_dma16(__amdgpu_buffer_rsrc_t rsrc, f16* lds_wave_base, unsigned voff, unsigned soff = 0) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)lds_wave_base, 16, voff, soff, 0, 0);
-}
-// a copy of a lane-dependent value that the compiler cannot see through: address arithmetic derived from it is redone where it
-// is used instead of being hoisted out of the tile loop as a loop invariant.  (r5: hoisted, the ten DMA offsets and the sixteen
-// store addresses of a tile were SPILLED, and every reload was followed by `s_waitcnt vmcnt(0)` -- scratch loads count on vmcnt --
-// so each DMA instruction and each store waited for the one before it to complete: ten HBM round trips in series per tile.)
-__device__ __forceinline__ int opaque(int v) {
-  asm volatile("" : "+v"(v));
-  return v;
-}
 
 constexpr int FF_PIX = 8;              // 16-row tiles per workgroup tile (128 rows)
 constexpr int FF_CH = 128;             // inner channels per chunk: 8 waves x 2 tiles x 8 (value, gate) pairs
 constexpr int FF_U = 2;                // W1 tiles per wave and chunk: a panel fragment read feeds FF_U MFMAs (with one, FF1 ran at
                                        // 28 % of the MFMA rate: 357k of a workgroup's 704k cycles)
-constexpr int FF_PD = 3;               // W1 fragments in flight (K steps ahead)
-constexpr int FF_AD = 4;               // panel fragments in flight
 
 // HILO (PROJ only; i2v_ff_fused_params.res2_lo / out_lo): the module's residual stream as an fp16 pair -- the low halves of the outer
 // residual rows are added with the high ones and the low half of the result is stored beside it (see i2v_gemm_params.residual_lo).
 template <int C, int INNER, int H, bool PROJ, bool HILO = false>
 __global__ __launch_bounds__(64 * H) void ff_fused_kernel(const i2v_ff_fused_params p, const int ntiles, long long* __restrict__ stamps) {
-  constexpr int KS = C / 32, NJ = C / 64, NCH = INNER / FF_CH, DN = C / H, DT = (DN + 15) / 16;
-  static_assert(C % 64 == 0 && H == 8 && INNER % FF_CH == 0 && DT == 3 && DN == 40, "SD-1.5 64^2 level: C = 320, inner = 1280");
+  constexpr int KS = C / 32, RW = FF_PIX * 16 / H, NCH = INNER / FF_CH, DN = C / H, DT = (DN + 15) / 16;
+  static_assert(H == 8 && INNER % FF_CH == 0 && DT == 3 && DN == 40, "SD-1.5 64^2 level: C = 320, inner = 1280");
   static_assert(PROJ || !HILO, "the precise stream enters and leaves through the tail");
   extern __shared__ __attribute__((aligned(16))) f16 lds[];
   f16* panel = lds;                                   // [128][C], 16-byte chunk index ^= row & 7
@@ -65,23 +51,14 @@ __global__ __launch_bounds__(64 * H) void ff_fused_kernel(const i2v_ff_fused_par
   f16* raw = lds + FF_PIX * 16 * C;                   // ... and, between two tiles' chunk loops, the next tile's raw rows [128][C]
   static_assert(2 * FF_PIX * 16 * FF_CH <= FF_PIX * 16 * C, "the raw rows of a tile cover the chunk buffers (160 KB of LDS in all)");
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int g = lane >> 4, l15 = lane & 15, sub = lane & 7, sw = l15 & 7;
-  // (chunk 4 s + g of a K step swizzled by the row: ((4 s + g) ^ sw) = 8 (s >> 1) + ((4 (s & 1) + g) ^ sw) -- TWO lane-dependent offsets
-  //  and an immediate instead of one hoisted (and spilled) register per K step)
-  const int swz[2] = {(g ^ sw) * 8, ((4 + g) ^ sw) * 8};
+  const int g = lane >> 4, l15 = lane & 15;
+  int swz[2];
+  panel_fragment_offsets(lane, swz);
   const f16* __restrict__ X = reinterpret_cast<const f16*>(p.x);
 
-  // ---- rows of a tile by LDS-DMA into the wave's own 10 KB of the panel, normalised in place (as motion_attn.hip)
+  // ---- rows of a tile by LDS-DMA into the wave's own 10 KB of `raw`, normalised from there into the panel (ln_panel.h)
   auto fetch_rows = [&](const int tile) {
-    const f16* base = X + ((int64_t)tile * (FF_PIX * 16) + 16 * wave) * p.ldx;
-    const auto rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<f16*>(base), 0, (int)((15 * p.ldx + C) * 2), 0x00020000);
-    const int ln = opaque(lane);
-    const unsigned voff = (unsigned)(((ln >> 3) * p.ldx + (ln & 7) * 8) * 2);        // the instruction's part is a scalar offset
-#pragma unroll
-    for (int half = 0; half < 2; ++half)
-#pragma unroll
-      for (int j = 0; j < NJ; ++j)
-        ff_dma16(rs, raw + 16 * wave * C + (half * NJ + j) * 512, voff, (unsigned)((8 * half * p.ldx + 8 * j * 8) * 2));
+    panel_fetch_rows<C, RW>(X + ((int64_t)tile * (FF_PIX * 16) + RW * wave) * p.ldx, p.ldx, raw + RW * wave * C, lane);
   };
   // the wave's 16 rows again, this time to their SWIZZLED places in the panel (row r of the panel, 16-byte chunk c at position
   // c ^ (r & 7)): the destination of an LDS-DMA is lane-linear (64 consecutive 16-byte slots per instruction), so the swizzle is
@@ -91,63 +68,16 @@ __global__ __launch_bounds__(64 * H) void ff_fused_kernel(const i2v_ff_fused_par
     const auto rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<f16*>(base), 0, (int)((15 * p.ldx + C) * 2), 0x00020000);
     constexpr int CPR = C / 8;                         // 16-byte chunks per row
     static_assert((16 * CPR) % 64 == 0 && CPR % 8 == 0, "whole DMA instructions per wave, swizzle inside groups of 8 chunks");
-    const int ln = opaque(lane);
+    const int ln = panel_opaque(lane);
 #pragma unroll
     for (int i = 0; i < 16 * CPR / 64; ++i) {
       const int q = i * 64 + ln, r = q / CPR, cp = q - r * CPR;
-      ff_dma16(rs, panel + 16 * wave * C + i * 512, (unsigned)((r * p.ldx + (cp ^ (r & 7)) * 8) * 2));
+      panel_dma16(rs, panel + 16 * wave * C + i * 512, (unsigned)((r * p.ldx + (cp ^ (r & 7)) * 8) * 2));
     }
   };
   auto normalise_rows = [&]() {
-    f16x8 xv[2][NJ];
-#pragma unroll
-    for (int half = 0; half < 2; ++half)
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) xv[half][j] = *reinterpret_cast<const f16x8*>(raw + 16 * wave * C + ((half * NJ + j) * 64 + lane) * 8);
-    const float* gp = reinterpret_cast<const float*>(p.gamma);
-    const float* bp = reinterpret_cast<const float*>(p.beta);
-    asm volatile("" : "+s"(gp), "+s"(bp));             // (loop invariants: keep their 80 registers out of the chunk loop)
-    f32x4 ga[NJ][2], be[NJ][2];
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-      ga[j][0] = *reinterpret_cast<const f32x4*>(gp + (sub + 8 * j) * 8);
-      ga[j][1] = *reinterpret_cast<const f32x4*>(gp + (sub + 8 * j) * 8 + 4);
-      be[j][0] = *reinterpret_cast<const f32x4*>(bp + (sub + 8 * j) * 8);
-      be[j][1] = *reinterpret_cast<const f32x4*>(bp + (sub + 8 * j) * 8 + 4);
-    }
-#pragma unroll
-    for (int half = 0; half < 2; ++half) {
-      const int row = 16 * wave + 8 * half + (lane >> 3);
-      float v[NJ][8];
-      float s = 0.f;
-#pragma unroll
-      for (int j = 0; j < NJ; ++j)
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          v[j][e] = (float)xv[half][j][e];
-          s += v[j][e];
-        }
-      s = sum_lanes8(s);
-      const float mean = s / (float)C;
-      float q = 0.f;
-#pragma unroll
-      for (int j = 0; j < NJ; ++j)
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          v[j][e] -= mean;
-          q = fmaf(v[j][e], v[j][e], q);
-        }
-      q = sum_lanes8(q);
-      const float rstd = rsqrtf(q / (float)C + p.eps);
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) {
-        const int ch = sub + 8 * j;
-        f16x8 o;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) o[e] = (f16)fmaf(v[j][e] * rstd, ga[j][e >> 2][e & 3], be[j][e >> 2][e & 3]);
-        *reinterpret_cast<f16x8*>(panel + row * C + ((ch ^ (row & 7)) * 8)) = o;
-      }
-    }
+    panel_normalise_rows<C, RW>(raw + RW * wave * C, panel, RW * wave, lane, reinterpret_cast<const float*>(p.gamma),
+                                reinterpret_cast<const float*>(p.beta), p.eps, panel_one_table{});
   };
 
   // weights: fragment order, one buffer descriptor each; the lane offset in one register, the fragment's place in the scalar offset
@@ -241,28 +171,30 @@ __global__ __launch_bounds__(64 * H) void ff_fused_kernel(const i2v_ff_fused_par
 #pragma unroll
         for (int pix = 0; pix < FF_PIX; ++pix) acc1[u][pix] = bias1;
       }
-      f16x8 wf[FF_PD][FF_U];
+      // (FF1 and the tail's pass keep K loops of their own, in the form of ln_panel.h's `panel_project` -- ring of PANEL_PD weight
+      //  fragment sets, PANEL_AD panel fragments in flight, one fence per step.  Through `panel_project` the compiler ordered the
+      //  loads and waits of the two tail instantiations differently, 120 places in FF1 alone, and single figures of theirs lay up
+      //  to 0.3 % above the range of the private loops' own runs: profiles/ln_panel_ab.txt.  These loops compile to the
+      //  instruction sequence they had before the header existed.)
+      f16x8 wf[PANEL_PD][FF_U];
 #pragma unroll
-      for (int s = 0; s < FF_PD - 1; ++s)
+      for (int s = 0; s < PANEL_PD - 1; ++s)
 #pragma unroll
         for (int u = 0; u < FF_U; ++u) wf[s][u] = ldw1(u, s);
       constexpr int NI = KS * FF_PIX;
-      auto lda = [&](const int i) {
-        return *reinterpret_cast<const f16x8*>(alane + 16 * (i % FF_PIX) * C + 64 * ((i / FF_PIX) >> 1) + swz[(i / FF_PIX) & 1]);
-      };
-      f16x8 af[FF_AD + 1];
+      f16x8 af[PANEL_AD + 1];
 #pragma unroll
-      for (int i = 0; i < FF_AD; ++i) af[i] = lda(i);
+      for (int i = 0; i < PANEL_AD; ++i) af[i] = panel_lda<C, FF_PIX>(alane, swz, i);
 #pragma unroll
       for (int i = 0; i < NI; ++i) {
         const int s = i / FF_PIX, pix = i % FF_PIX;
-        if (pix == 0 && s + FF_PD - 1 < KS) {
+        if (pix == 0 && s + PANEL_PD - 1 < KS) {
 #pragma unroll
-          for (int u = 0; u < FF_U; ++u) wf[(s + FF_PD - 1) % FF_PD][u] = ldw1(u, s + FF_PD - 1);
+          for (int u = 0; u < FF_U; ++u) wf[(s + PANEL_PD - 1) % PANEL_PD][u] = ldw1(u, s + PANEL_PD - 1);
         }
-        if (i + FF_AD < NI) af[(i + FF_AD) % (FF_AD + 1)] = lda(i + FF_AD);
+        if (i + PANEL_AD < NI) af[(i + PANEL_AD) % (PANEL_AD + 1)] = panel_lda<C, FF_PIX>(alane, swz, i + PANEL_AD);
 #pragma unroll
-        for (int u = 0; u < FF_U; ++u) acc1[u][pix] = mfma16x16x32(wf[s % FF_PD][u], af[i % (FF_AD + 1)], acc1[u][pix]);
+        for (int u = 0; u < FF_U; ++u) acc1[u][pix] = mfma16x16x32(wf[s % PANEL_PD][u], af[i % (PANEL_AD + 1)], acc1[u][pix]);
         __builtin_amdgcn_sched_barrier(0);
       }
       FF_T(t_ff1);
@@ -334,9 +266,9 @@ __global__ __launch_bounds__(64 * H) void ff_fused_kernel(const i2v_ff_fused_par
 
     // ---- epilogue: + b2 + x (from the panel, in the accumulator layout).  This lane's places in the panel (row 16 pix + l15,
     // channels 40 wave + 16 t + 4 g .. + 3): the 8-byte half (g & 1) of chunk 5 wave + 2 t + (g >> 1), swizzled by the row -- from an
-    // opaque copy of the lane index (see `opaque`)
+    // opaque copy of the lane index (see `panel_opaque`)
     static_assert(DN == 40, "5 chunks of 8 channels per wave");
-    const int eln = opaque(lane), eg = eln >> 4, el15 = eln & 15;
+    const int eln = panel_opaque(lane), eg = eln >> 4, el15 = eln & 15;
     int res_off[DT];
 #pragma unroll
     for (int t = 0; t < DT; ++t) res_off[t] = el15 * C + (((5 * wave + 2 * t + (eg >> 1)) ^ (el15 & 7)) * 8) + 4 * (eg & 1);
@@ -431,32 +363,30 @@ __global__ __launch_bounds__(64 * H) void ff_fused_kernel(const i2v_ff_fused_par
         auto ldw3 = [&](const int s, const int t) {
           return __builtin_bit_cast(f16x8, __builtin_amdgcn_raw_buffer_load_b128(rs_w3, w_lane, w3o + (s * DT + t) * 1024, 0));
         };
-        f16x8 wf[FF_PD][DT];
+        // (a K loop of its own, as FF1's: see there)
+        constexpr int PD = PANEL_PD, AD = PANEL_AD, NI = KS * FF_PIX;
+        f16x8 wf[PD][DT];
 #pragma unroll
-        for (int s = 0; s < FF_PD - 1; ++s)
+        for (int s = 0; s < PD - 1; ++s)
 #pragma unroll
           for (int t = 0; t < DT; ++t) wf[s][t] = ldw3(s, t);
-        constexpr int NI = KS * FF_PIX;
-        auto lda = [&](const int i) {
-          return *reinterpret_cast<const f16x8*>(alane + 16 * (i % FF_PIX) * C + 64 * ((i / FF_PIX) >> 1) + swz[(i / FF_PIX) & 1]);
-        };
-        f16x8 af[FF_AD + 1];
+        f16x8 af[AD + 1];
 #pragma unroll
-        for (int i = 0; i < FF_AD; ++i) af[i] = lda(i);
+        for (int i = 0; i < AD; ++i) af[i] = panel_lda<C, FF_PIX>(alane, swz, i);
 #pragma unroll
         for (int i = 0; i < NI; ++i) {
           const int s = i / FF_PIX, pix = i % FF_PIX;
-          if (pix == 0 && s + FF_PD - 1 < KS) {
+          if (pix == 0 && s + PD - 1 < KS) {
 #pragma unroll
-            for (int t = 0; t < DT; ++t) wf[(s + FF_PD - 1) % FF_PD][t] = ldw3(s + FF_PD - 1, t);
+            for (int t = 0; t < DT; ++t) wf[(s + PD - 1) % PD][t] = ldw3(s + PD - 1, t);
           }
-          if (pix == 0 && s + FF_PD - 1 == KS - 1) {      // the last weight fragments are on their way: now the HBM requests
+          if (pix == 0 && s + PD - 1 == KS - 1) {      // the last weight fragments are on their way: now the HBM requests
             if (next < ntiles) fetch_rows(next);
             load_res2(0);
           }
-          if (i + FF_AD < NI) af[(i + FF_AD) % (FF_AD + 1)] = lda(i + FF_AD);
+          if (i + AD < NI) af[(i + AD) % (AD + 1)] = panel_lda<C, FF_PIX>(alane, swz, i + AD);
 #pragma unroll
-          for (int t = 0; t < DT; ++t) acc3[pix][t] = mfma16x16x32(wf[s % FF_PD][t], af[i % (FF_AD + 1)], acc3[pix][t]);
+          for (int t = 0; t < DT; ++t) acc3[pix][t] = mfma16x16x32(wf[s % PD][t], af[i % (AD + 1)], acc3[pix][t]);
           __builtin_amdgcn_sched_barrier(0);
         }
       }

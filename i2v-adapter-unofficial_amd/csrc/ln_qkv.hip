@@ -18,156 +18,59 @@
 
 #include <type_traits>
 
-#include "common.h"
+#include "ln_panel.h"
 
 namespace {
-
-__device__ __forceinline__ void lq_dma16(__amdgpu_buffer_rsrc_t rsrc, f16* lds_wave_base, unsigned voff, unsigned soff) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)lds_wave_base, 16, voff, soff, 0, 0);
-}
-// (a lane index the compiler cannot see through: address arithmetic derived from it is redone where it is used instead of being
-//  hoisted out of the tile loop and spilled -- a reload from scratch is followed by `s_waitcnt vmcnt(0)`, see ff_fused.hip)
-__device__ __forceinline__ int lq_opaque(int v) {
-  asm volatile("" : "+v"(v));
-  return v;
-}
 
 constexpr int LQ_PIX = 8;              // 16-row MFMA tiles per workgroup tile (128 rows)
 constexpr int LQ_TPW = 10;             // 16-column tiles per wave (160 columns)
 constexpr int LQ_DT = 4;               // ... of which a pass takes 4, 4, 2
-constexpr int LQ_PD = 2;               // weight fragment sets in flight beyond the one in use (K steps ahead)
-constexpr int LQ_AD = 4;               // panel fragments in flight
 
 template <int C, int H>
 __global__ __launch_bounds__(64 * H) void ln_qkv_kernel(const i2v_ln_qkv_params p, const int ntiles) {
-  constexpr int KS = C / 32, NJ = C / 64, DT = LQ_DT;
-  static_assert(LQ_TPW == 10 && C % 64 == 0 && H == 8, "8 lanes x C / 64 chunks per row in the LayerNorm pass");
+  constexpr int DT = LQ_DT, RW = LQ_PIX * 16 / H;
+  static_assert(LQ_TPW == 10 && H == 8, "ten 16-column tiles per wave: 8 waves take [q | k | q_adapter | v]");
   extern __shared__ __attribute__((aligned(16))) f16 panels[];       // 2 x [128][C], chunk index ^= row & 7
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int g = lane >> 4, l15 = lane & 15, sub = lane & 7;
   const f16* __restrict__ X = reinterpret_cast<const f16*>(p.x);
   const float* __restrict__ gamma = reinterpret_cast<const float*>(p.gamma);
   const float* __restrict__ beta = reinterpret_cast<const float*>(p.beta);
   const int qk_waves = p.n_qk / (16 * LQ_TPW), live_waves = (p.n_qk + p.channels) / (16 * LQ_TPW);     // 6 / 8 (4 / 6)
 
-  // ---- LayerNorm of the wave's 16 rows into a panel (as motion_attn.hip: raw rows by LDS-DMA into the wave's own 10 KB, then
-  // normalised in place)
+  // ---- LayerNorm of the wave's 16 rows into a panel (ln_panel.h: raw rows by LDS-DMA into the wave's own 10 KB, normalised in place)
   auto fetch_rows = [&](const int tile, f16* panel) {
-    int64_t r0 = (int64_t)tile * (LQ_PIX * 16) + 16 * wave;            // (images are whole tiles: a wave's 16 rows are in one)
+    int64_t r0 = (int64_t)tile * (LQ_PIX * 16) + RW * wave;            // (images are whole tiles: a wave's 16 rows are in one)
     const f16* base = X + r0 * p.ldx;
     if (p.x_image_stride > 0) {                                         // images at their own stride (frame-0 rows in place)
       const int64_t img = r0 / p.rows_per_image;
       base = X + img * p.x_image_stride + (r0 - img * p.rows_per_image) * p.ldx;
     }
-    const auto rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<f16*>(base), 0, (int)((15 * p.ldx + C) * 2), 0x00020000);
-    const int ln = lq_opaque(lane);
-    const unsigned voff = (unsigned)(((ln >> 3) * p.ldx + (ln & 7) * 8) * 2);
-#pragma unroll
-    for (int half = 0; half < 2; ++half)
-#pragma unroll
-      for (int j = 0; j < NJ; ++j)
-        lq_dma16(rs, panel + 16 * wave * C + (half * NJ + j) * 512, voff, (unsigned)((8 * half * p.ldx + 8 * j * 8) * 2));
+    panel_fetch_rows<C, RW>(base, p.ldx, panel + RW * wave * C, lane);
   };
   auto normalise_rows = [&](f16* panel) {
-    f16x8 xv[2][NJ];
-#pragma unroll
-    for (int half = 0; half < 2; ++half)
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) xv[half][j] = *reinterpret_cast<const f16x8*>(panel + 16 * wave * C + ((half * NJ + j) * 64 + lane) * 8);
-    const float* gp = gamma;
-    const float* bp = beta;
-    asm volatile("" : "+s"(gp), "+s"(bp));          // (loop invariants: keep their 80 registers out of the passes)
-    f32x4 ga[NJ][2], be[NJ][2];
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-      ga[j][0] = *reinterpret_cast<const f32x4*>(gp + (sub + 8 * j) * 8);
-      ga[j][1] = *reinterpret_cast<const f32x4*>(gp + (sub + 8 * j) * 8 + 4);
-      be[j][0] = *reinterpret_cast<const f32x4*>(bp + (sub + 8 * j) * 8);
-      be[j][1] = *reinterpret_cast<const f32x4*>(bp + (sub + 8 * j) * 8 + 4);
-    }
-#pragma unroll
-    for (int half = 0; half < 2; ++half) {
-      const int row = 16 * wave + 8 * half + (lane >> 3);
-      float v[NJ][8];
-      float s = 0.f;
-#pragma unroll
-      for (int j = 0; j < NJ; ++j)
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          v[j][e] = (float)xv[half][j][e];
-          s += v[j][e];
-        }
-      s = sum_lanes8(s);
-      const float mean = s / (float)C;
-      float q = 0.f;
-#pragma unroll
-      for (int j = 0; j < NJ; ++j)
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          v[j][e] -= mean;
-          q = fmaf(v[j][e], v[j][e], q);
-        }
-      q = sum_lanes8(q);
-      const float rstd = rsqrtf(q / (float)C + p.eps);
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) {
-        const int ch = sub + 8 * j;
-        f16x8 o;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) o[e] = (f16)fmaf(v[j][e] * rstd, ga[j][e >> 2][e & 3], be[j][e >> 2][e & 3]);
-        *reinterpret_cast<f16x8*>(panel + row * C + ((ch ^ (row & 7)) * 8)) = o;
-      }
-    }
+    panel_normalise_rows<C, RW>(panel + RW * wave * C, panel, RW * wave, lane, gamma, beta, p.eps, panel_one_table{});
   };
 
   // ---- NTL tiles of 16 output columns (the wave's tiles t0 .. t0 + NTL - 1) against the 128 rows of the panel;
   // weights [wave][tile of the wave][K step][lane][8]
   const auto rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.w), 0, live_waves * (LQ_TPW * 16 * C * 2), 0x00020000);
   const int w_lane = lane * 16;
-  const int sw = l15 & 7;
-  const int swz[2] = {(g ^ sw) * 8, ((4 + g) ^ sw) * 8};
+  int swz[2];
+  panel_fragment_offsets(lane, swz);
   f32x4 acc[LQ_PIX][DT];
   auto project = [&](const f16* panel, const int t0, auto ntl, auto transposed) {
-    constexpr bool TR = decltype(transposed)::value;
     constexpr int NTL = decltype(ntl)::value;
     const int wp = (wave * LQ_TPW + t0) * (16 * C * 2);       // bytes; + t (16 C 2) + s 1024
-    auto ldw = [&](const int s, const int t) {
-      return __builtin_bit_cast(f16x8, __builtin_amdgcn_raw_buffer_load_b128(rs_w, w_lane, wp + t * (16 * C * 2) + s * 1024, 0));
-    };
-    const f16* alane = panel + l15 * C;
-    f16x8 wf[LQ_PD + 1][NTL];
 #pragma unroll
     for (int pix = 0; pix < LQ_PIX; ++pix)
 #pragma unroll
       for (int t = 0; t < NTL; ++t) acc[pix][t] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int s = 0; s < LQ_PD; ++s)
-#pragma unroll
-      for (int t = 0; t < NTL; ++t) wf[s][t] = ldw(s, t);
-    constexpr int AD = LQ_AD, NI = KS * LQ_PIX;
-    // (chunk 4 s + g swizzled by the row: ((4 s + g) ^ sw) = 8 (s >> 1) + ((4 (s & 1) + g) ^ sw) -- TWO lane-dependent offsets and an
-    //  immediate, not one precomputed register per K step: those ten were hoisted out of the tile loop and spilled)
-    auto lda = [&](const int i) {
-      const int s = i / LQ_PIX;
-      return *reinterpret_cast<const f16x8*>(alane + 16 * (i % LQ_PIX) * C + 64 * (s >> 1) + swz[s & 1]);
-    };
-    f16x8 af[AD + 1];
-#pragma unroll
-    for (int i = 0; i < AD; ++i) af[i] = lda(i);
-#pragma unroll
-    for (int i = 0; i < NI; ++i) {
-      const int s = i / LQ_PIX, pix = i % LQ_PIX;
-      if (pix == 0 && s + LQ_PD < KS) {
-#pragma unroll
-        for (int t = 0; t < NTL; ++t) wf[(s + LQ_PD) % (LQ_PD + 1)][t] = ldw(s + LQ_PD, t);
-      }
-      if (i + AD < NI) af[(i + AD) % (AD + 1)] = lda(i + AD);
-#pragma unroll
-      for (int t = 0; t < NTL; ++t)
-        acc[pix][t] = TR ? mfma16x16x32(wf[s % (LQ_PD + 1)][t], af[i % (AD + 1)], acc[pix][t])
-                         : mfma16x16x32(af[i % (AD + 1)], wf[s % (LQ_PD + 1)][t], acc[pix][t]);
-      __builtin_amdgcn_sched_barrier(0);
-    }
+    panel_project<C, LQ_PIX, NTL, decltype(transposed)::value, false>(
+        panel, swz, lane,
+        [&](const int s, const int t) {
+          return __builtin_bit_cast(f16x8, __builtin_amdgcn_raw_buffer_load_b128(rs_w, w_lane, wp + t * (16 * C * 2) + s * 1024, 0));
+        },
+        [&](const int pix, const int t) -> f32x4& { return acc[pix][t]; }, [](const int) {});
   };
   auto to_half = [](const f32x4 a) { return __builtin_bit_cast(u32x2, f16x4{(f16)a[0], (f16)a[1], (f16)a[2], (f16)a[3]}); };
   // v_permlane16_swap: the odd 16-lane rows of the first operand change places with the even rows of the second
@@ -202,7 +105,7 @@ __global__ __launch_bounds__(64 * H) void ln_qkv_kernel(const i2v_ln_qkv_params 
     auto store_qk = [&](const int t0, auto ntl) {
       constexpr int NTL = decltype(ntl)::value;
       static_assert(NTL % 2 == 0, "tiles are stored in pairs");
-      const int sln = lq_opaque(lane), sg = sln >> 4, sl15 = sln & 15;
+      const int sln = panel_opaque(lane), sg = sln >> 4, sl15 = sln & 15;
       f16* __restrict__ O = reinterpret_cast<f16*>(p.qk) + (row0 + sl15) * p.ld_qk + (wave * LQ_TPW + t0) * 16;
 #pragma unroll
       for (int pix = 0; pix < LQ_PIX; ++pix) {
@@ -222,7 +125,7 @@ __global__ __launch_bounds__(64 * H) void ln_qkv_kernel(const i2v_ln_qkv_params 
     // over two 16-row steps: even g ends with keys 4 g .. + 7 of step pix, odd g with keys 4 (g - 1) .. + 7 of step pix + 1
     auto store_vt = [&](const int t0, auto ntl) {
       constexpr int NTL = decltype(ntl)::value;
-      const int sln = lq_opaque(lane), sg = sln >> 4, sl15 = sln & 15;
+      const int sln = panel_opaque(lane), sg = sln >> 4, sl15 = sln & 15;
       const int64_t img = row0 / p.rows_per_image;
       const int key0 = (int)(row0 - img * p.rows_per_image);
       f16* __restrict__ VT = reinterpret_cast<f16*>(p.vt) + img * p.vt_batch_stride + key0 +

@@ -36,7 +36,7 @@
 
 #include <type_traits>
 
-#include "common.h"
+#include "ln_panel.h"
 
 namespace {
 
@@ -44,24 +44,8 @@ __device__ __forceinline__ f32x4 mfma16x16x16(f16x4 a, f16x4 b, f32x4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x16f16(a, b, c, 0, 0, 0);
 }
 
-// buffer_load_dwordx4 ... offen lds: 16 bytes per lane, global -> LDS at (wave-uniform LDS base) + 16 * lane (a plain function
-// on purpose, as in gemm_big.hip: called directly from the kernel template, the builtin makes hipcc drop the launch stub)
-__device__ __forceinline__ void ma_dma16(__amdgpu_buffer_rsrc_t rsrc, f16* lds_wave_base, unsigned voff, unsigned soff) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)lds_wave_base, 16, voff, soff, 0, 0);
-}
-// a copy of a lane-dependent value that the compiler cannot see through: address arithmetic derived from it is redone where it is
-// used instead of being hoisted out of the tile loop.  (r5: hoisted, the ten DMA offsets of `fetch_rows` and the output rows' store
-// addresses were SPILLED, and each reload was followed by `s_waitcnt vmcnt(0)` -- scratch loads count on vmcnt -- so every DMA
-// instruction waited for the one before it to land and every store for the weight fragments in flight.)
-__device__ __forceinline__ int ma_opaque(int v) {
-  asm volatile("" : "+v"(v));
-  return v;
-}
-
 constexpr int MA_PIX = 8;              // pixels per tile (x 16 frames = 128 rows) of the C = 320 forms; a template parameter (PIX)
 constexpr int MA_F = 16;               // frames per pixel: one MFMA tile
-constexpr int MA_PD = 3;               // weight fragments in flight (K steps ahead)
-constexpr int MA_AD = 4;               // panel fragments in flight (reads ahead of the MFMAs that take them)
 
 // what both entry points hand the kernel (the fields of i2v_motion_attn_params / i2v_cross_attn_fused_params)
 struct ma_args {
@@ -99,14 +83,14 @@ constexpr int MA_KT = 5;               // CROSS: key tiles of 16 (<= 80 context 
 template <int C, int D, int H, bool CROSS, int F = 16, bool OUTP = false, int PIX = MA_PIX>
 __global__ __launch_bounds__(64 * H) void motion_attn_kernel(const ma_args p, const float scale_log2, const int ntiles,
                                                              long long* __restrict__ stamps) {
-  constexpr int DT = (D + 15) / 16, DP = 16 * DT, KS = C / 32, NJ = C / 64, PARTS = CROSS ? 1 : 3;
-  constexpr int RW = PIX * MA_F / H, HALVES = RW / 8;      // rows a wave fetches and normalises, in groups of 8 (one DMA instruction)
-  static_assert(C % 64 == 0 && H == 8, "one wave per head, 8 lanes x C / 64 chunks per row in the LayerNorm pass");
+  constexpr int DT = (D + 15) / 16, DP = 16 * DT, PARTS = CROSS ? 1 : 3;
+  constexpr int RW = PIX * MA_F / H;      // rows a wave fetches and normalises
+  static_assert(H == 8, "one wave per head");
   static_assert(F == 8 || F == 16 || F == 32, "frames per pixel");
   static_assert(RW % 8 == 0 && PIX % (F == 32 ? 2 : 1) == 0, "whole groups of 8 rows per wave, whole pixels per tile");
   extern __shared__ __attribute__((aligned(16))) f16 panels[];       // 2 x [128][C], chunk index ^= row & 7
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // (wave-uniform: SGPR)
-  const int g = lane >> 4, l15 = lane & 15, sub = lane & 7;
+  const int g = lane >> 4, l15 = lane & 15;
   const f16* __restrict__ X = reinterpret_cast<const f16*>(p.x);
   const float* __restrict__ gamma = reinterpret_cast<const float*>(p.gamma);
   const float* __restrict__ shift = reinterpret_cast<const float*>(p.shift);
@@ -117,149 +101,36 @@ __global__ __launch_bounds__(64 * H) void motion_attn_kernel(const ma_args p, co
 #define MA_STAMP(k)
 #endif
 
-  // ---- LayerNorm (+ positional table) of the wave's 16 rows into a panel: 8 lanes per row, two groups of 8 rows.  The raw rows
-  // come by LDS-DMA into the wave's own 10 KB of the panel (16 rows x 640 B, in [group][chunk column][lane] order) and are
-  // normalised in place: read whole into registers, then written to their swizzled places -- no register holds a row while the
-  // DMA is in flight under the v pass of the previous tile (held in registers there, they spilled: 259 dwords, 121 -> 230 us).
+  // ---- LayerNorm (+ positional table) of the wave's RW rows into a panel (ln_panel.h): the raw rows come by LDS-DMA into the wave's
+  // own 10 KB of the panel and are normalised in place; the second table is shift[frame of the row] (tiles start at frame 0)
   auto fetch_rows = [&](const int tile, f16* panel) {
-    const f16* base = X + ((int64_t)tile * (PIX * MA_F) + RW * wave) * p.ldx;        // (wave-uniform)
-    const auto rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<f16*>(base), 0, (int)(((RW - 1) * p.ldx + C) * 2), 0x00020000);
-    const int ln = ma_opaque(lane);
-    const unsigned voff = (unsigned)(((ln >> 3) * p.ldx + (ln & 7) * 8) * 2);      // the instruction's part is a scalar offset
-#pragma unroll
-    for (int half = 0; half < HALVES; ++half)
-#pragma unroll
-      for (int j = 0; j < NJ; ++j)
-        ma_dma16(rs, panel + RW * wave * C + (half * NJ + j) * 512, voff, (unsigned)((8 * half * p.ldx + 8 * j * 8) * 2));
+    panel_fetch_rows<C, RW>(X + ((int64_t)tile * (PIX * MA_F) + RW * wave) * p.ldx, p.ldx, panel + RW * wave * C, lane);
   };
-  // (NJ > 5, the C = 640 form: a row's slice is 80 values per lane, and gamma, the shift row and the values together would be 240
-  // registers -- there the two tables are read per 64-channel column where they are applied instead of ahead of the row's sums)
-  constexpr bool LATE_TABLES = NJ > 5;
   auto normalise_rows = [&](f16* panel) {
-    f16x8 xv[HALVES][NJ];
-#pragma unroll
-    for (int half = 0; half < HALVES; ++half)
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) xv[half][j] = *reinterpret_cast<const f16x8*>(panel + RW * wave * C + ((half * NJ + j) * 64 + lane) * 8);
-    // (the tables are loop invariants: without the opaque copies of their addresses the compiler keeps all 120 registers of
-    // them live through the three passes of every tile -- 207 spilled dwords)
-    const float* gp = gamma;
-    const float* sp = shift;
-    asm volatile("" : "+s"(gp), "+s"(sp));
-    f32x4 ga[NJ][2];
-    if constexpr (!LATE_TABLES) {
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) {
-        ga[j][0] = *reinterpret_cast<const f32x4*>(gp + (sub + 8 * j) * 8);
-        ga[j][1] = *reinterpret_cast<const f32x4*>(gp + (sub + 8 * j) * 8 + 4);
-      }
-    }
-#pragma unroll
-    for (int half = 0; half < HALVES; ++half) {
-      const int row = RW * wave + 8 * half + (lane >> 3);
-      const float* sh = sp + (int64_t)((RW * wave + 8 * half + (lane >> 3)) & (F - 1)) * p.ld_shift;   // (tiles start at frame 0)
-      f32x4 sv[NJ][2];
-      if constexpr (!LATE_TABLES) {
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) {
-          sv[j][0] = *reinterpret_cast<const f32x4*>(sh + (sub + 8 * j) * 8);
-          sv[j][1] = *reinterpret_cast<const f32x4*>(sh + (sub + 8 * j) * 8 + 4);
-        }
-      }
-      float v[NJ][8];
-      float s = 0.f;
-#pragma unroll
-      for (int j = 0; j < NJ; ++j)
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          v[j][e] = (float)xv[half][j][e];
-          s += v[j][e];
-        }
-      s = sum_lanes8(s);
-      const float mean = s / (float)C;
-      float q = 0.f;
-#pragma unroll
-      for (int j = 0; j < NJ; ++j)
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          v[j][e] -= mean;
-          q = fmaf(v[j][e], v[j][e], q);
-        }
-      q = sum_lanes8(q);
-      const float rstd = rsqrtf(q / (float)C + p.eps);
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) {
-        const int ch = sub + 8 * j;
-        if constexpr (LATE_TABLES) {
-          ga[j][0] = *reinterpret_cast<const f32x4*>(gp + ch * 8);
-          ga[j][1] = *reinterpret_cast<const f32x4*>(gp + ch * 8 + 4);
-          sv[j][0] = *reinterpret_cast<const f32x4*>(sh + ch * 8);
-          sv[j][1] = *reinterpret_cast<const f32x4*>(sh + ch * 8 + 4);
-        }
-        f16x8 o;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) o[e] = (f16)fmaf(v[j][e] * rstd, ga[j][e >> 2][e & 3], sv[j][e >> 2][e & 3]);
-        *reinterpret_cast<f16x8*>(panel + row * C + ((ch ^ (row & 7)) * 8)) = o;
-      }
-    }
+    panel_normalise_rows<C, RW>(panel + RW * wave * C, panel, RW * wave, lane, gamma, shift, p.eps,
+                                [&](const float* table, const int row) { return table + (int64_t)(row & (F - 1)) * p.ld_shift; });
   };
 
   // ---- wave = head: projections with a panel as one operand and the head's weight fragments (global) as the other
-  // (buffer loads: lane offset in ONE register, the fragment's place in the scalar offset -- as flat loads the 90 fragment
-  // addresses of a tile are loop invariants that the compiler hoists as 64-bit pairs: 180 registers, spilled)
   const auto rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.w), 0, H * PARTS * DP * C * 2, 0x00020000);
   const int w_lane = lane * 16, w_wave = wave * (PARTS * DP * C * 2);
-  const int sw = l15 & 7;
-  // (chunk 4 s + g of a K step swizzled by the row: ((4 s + g) ^ sw) = 8 (s >> 1) + ((4 (s & 1) + g) ^ sw) -- TWO lane-dependent offsets
-  //  and an immediate instead of one hoisted register per K step)
-  const int swz[2] = {(g ^ sw) * 8, ((4 + g) ^ sw) * 8};
+  int swz[2];
+  panel_fragment_offsets(lane, swz);
   f32x4 acc[PIX][DT];
   auto zero_init = [](const int, const int) { return f32x4{0.f, 0.f, 0.f, 0.f}; };
-  // (wp: byte offset of the wave's fragments of this pass in `rs`; (DP C = KS DT 512 halfs per part) + (s DT + t) 1024)
-  auto no_hook = []() {};
+  auto no_hook = [](const int) {};
+  // (wp: byte offset of the wave's fragments of this pass in `rs`; (DP C = C / 32 x DT x 512 halfs per part) + (s DT + t) 1024)
   auto project = [&](const f16* panel, const __amdgpu_buffer_rsrc_t rs, const int wp, auto transposed, auto init, auto hook) {
-    constexpr bool TR = decltype(transposed)::value;
-    auto ldw = [&](const int s, const int t) {
-      return __builtin_bit_cast(f16x8, __builtin_amdgcn_raw_buffer_load_b128(rs, w_lane, wp + (s * DT + t) * 1024, 0));
-    };
-    const f16* alane = panel + l15 * C;                  // + (16 pix) C + (((4 s + g) ^ (l15 & 7)) * 8)
-    f16x8 wf[MA_PD][DT];
 #pragma unroll
     for (int pix = 0; pix < PIX; ++pix)
 #pragma unroll
       for (int t = 0; t < DT; ++t) acc[pix][t] = init(pix, t);
-#pragma unroll
-    for (int s = 0; s < MA_PD - 1; ++s)
-#pragma unroll
-      for (int t = 0; t < DT; ++t) wf[s][t] = ldw(s, t);
-    // (r5: without this fence the scheduler may pair each of these loads with the first MFMA that takes it -- load, s_waitcnt vmcnt(0),
-    //  MFMA, three L2 round trips in series at the top of the pass: seen in the v pass of the OUTP form)
-    __builtin_amdgcn_sched_barrier(0);
-    constexpr int AD = MA_AD, NI = KS * PIX;
-    auto lda = [&](const int i) {
-      return *reinterpret_cast<const f16x8*>(alane + 16 * (i % PIX) * C + 64 * ((i / PIX) >> 1) + swz[(i / PIX) & 1]);
-    };
-    f16x8 af[AD + 1];
-#pragma unroll
-    for (int i = 0; i < AD; ++i) af[i] = lda(i);
-#pragma unroll
-    for (int i = 0; i < NI; ++i) {
-      const int s = i / PIX, pix = i % PIX;
-      if (pix == 0 && s + MA_PD - 1 < KS) {
-#pragma unroll
-        for (int t = 0; t < DT; ++t) wf[(s + MA_PD - 1) % MA_PD][t] = ldw(s + MA_PD - 1, t);
-      }
-#ifndef I2V_MA_HOOK_S
-#define I2V_MA_HOOK_S 0
-#endif
-      if (pix == 0 && s == I2V_MA_HOOK_S) hook();       // (memory requests that may return behind the K steps' fragments requested so far)
-      if (i + AD < NI) af[(i + AD) % (AD + 1)] = lda(i + AD);
-#pragma unroll
-      for (int t = 0; t < DT; ++t)
-        acc[pix][t] = TR ? mfma16x16x32(wf[s % MA_PD][t], af[i % (AD + 1)], acc[pix][t])
-                         : mfma16x16x32(af[i % (AD + 1)], wf[s % MA_PD][t], acc[pix][t]);
-      __builtin_amdgcn_sched_barrier(0);      // (unfenced, the scheduler hoists every load of the pass to its top: 947 spills)
-    }
+    panel_project<C, PIX, DT, decltype(transposed)::value, true>(
+        panel, swz, lane,
+        [&](const int s, const int t) {
+          return __builtin_bit_cast(f16x8, __builtin_amdgcn_raw_buffer_load_b128(rs, w_lane, wp + (s * DT + t) * 1024, 0));
+        },
+        [&](const int pix, const int t) -> f32x4& { return acc[pix][t]; }, hook);
   };
   auto to_half = [](const f32x4 a) { return f16x4{(f16)a[0], (f16)a[1], (f16)a[2], (f16)a[3]}; };
   // Output row of one query: lane (g, l15) holds channels 16 t + 4 g .. + 3 of query l15, 8 bytes per tile.  v_permlane16_swap
@@ -308,7 +179,7 @@ __global__ __launch_bounds__(64 * H) void motion_attn_kernel(const ma_args p, co
   // the bias, the residual added at the end.
   static_assert(D % 8 == 0, "a head's channels are whole 16-byte chunks of a panel row");
   auto stash_o = [&](f16* pw, const int pix, const u32x2 (&oh)[DT]) {
-    const int ln = ma_opaque(lane), g2 = ln >> 4, r15 = ln & 15;
+    const int ln = panel_opaque(lane), g2 = ln >> 4, r15 = ln & 15;
     f16* dst = pw + (16 * pix + r15) * C + 4 * (g2 & 1);
 #pragma unroll
     for (int t = 0; t < DT; ++t)        // (the padding channels D .. DP of the last tile belong to the next head)
@@ -319,7 +190,7 @@ __global__ __launch_bounds__(64 * H) void motion_attn_kernel(const ma_args p, co
     const auto rs_b = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.b_o), 0, C * 4, 0x00020000);
     const f16* base = X + (int64_t)tile * (PIX * MA_F) * p.ldx;                      // (wave-uniform)
     const auto rs_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<f16*>(base), 0, (int)(((PIX * MA_F - 1) * p.ldx + C) * 2), 0x00020000);
-    const int ln = ma_opaque(lane), sg = ln >> 4, sl15 = ln & 15;
+    const int ln = panel_opaque(lane), sg = ln >> 4, sl15 = ln & 15;
     f32x4 bo[DT];
 #pragma unroll
     for (int t = 0; t < DT; ++t)
@@ -328,7 +199,11 @@ __global__ __launch_bounds__(64 * H) void motion_attn_kernel(const ma_args p, co
     // the residual: this lane's slice of its rows (8 bytes per row and tile), requested BEHIND the pass's first weight fragments
     // (loads return in order: in front of them the pass would start with an HBM round trip) and added to the finished accumulators
     u32x2 res[PIX][DT];
-    project(pr, rs_o, wave * (DP * C * 2), std::true_type{}, [&](const int, const int t) { return bo[t]; }, [&]() {
+#ifndef I2V_MA_HOOK_S
+#define I2V_MA_HOOK_S 0
+#endif
+    project(pr, rs_o, wave * (DP * C * 2), std::true_type{}, [&](const int, const int t) { return bo[t]; }, [&](const int s) {
+      if (s != I2V_MA_HOOK_S) return;
 #pragma unroll
       for (int pix = 0; pix < PIX; ++pix)
 #pragma unroll
@@ -416,7 +291,7 @@ __global__ __launch_bounds__(64 * H) void motion_attn_kernel(const ma_args p, co
       MA_STAMP(4);
       MA_STAMP(5);
       f16* __restrict__ O = reinterpret_cast<f16*>(p.out) + (int64_t)tile * (PIX * MA_F) * p.ldo + wave * D;
-      const int sln = ma_opaque(lane), sg = sln >> 4, sl15 = sln & 15;
+      const int sln = panel_opaque(lane), sg = sln >> 4, sl15 = sln & 15;
 #pragma unroll
       for (int pix = 0; pix < PIX; ++pix) {
         float sv[MA_KT][4];
@@ -548,7 +423,7 @@ __global__ __launch_bounds__(64 * H) void motion_attn_kernel(const ma_args p, co
     MA_STAMP(5);
     if constexpr (OUTP) lds_barrier();               // the v pass was the panel's last reader: every wave has left it
     f16* __restrict__ O = reinterpret_cast<f16*>(p.out) + (int64_t)tile * (PIX * MA_F) * p.ldo + wave * D;
-    const int sln = ma_opaque(lane), sg = sln >> 4, sl15 = sln & 15;
+    const int sln = panel_opaque(lane), sg = sln >> 4, sl15 = sln & 15;
 #pragma unroll
     for (int px = 0; px < PIX; px += NB)
 #pragma unroll
@@ -608,6 +483,36 @@ int launch_ma(const ma_args& p, int64_t rows, float scale, hipStream_t s, const 
   return i2v_check_launch(what);
 }
 
+// The fields of ma_args that every entry point fills ...
+ma_args ma_common_args(const void* x, int64_t ldx, const void* gamma, const void* shift, int64_t ld_shift, const void* w, void* out, int64_t ldo,
+                       float eps, const void* w_o, const void* b_o) {
+  ma_args a = {};
+  a.x = x; a.ldx = ldx; a.gamma = gamma; a.shift = shift; a.ld_shift = ld_shift; a.w = w; a.out = out; a.ldo = ldo; a.eps = eps;
+  a.w_o = w_o; a.b_o = b_o;
+  return a;
+}
+
+// ... and the operand checks of every entry point, in one order (`what`: the entry point's name; `shape`: its own checks between the
+// null pointers and the strides -- "is not a fused shape").  MA_CROSS: ctx_frag is an operand and the second table is one row
+// (ld_shift 0); MA_WIDE: the out-projection is part of the form, its operands are checked with the others.
+enum ma_form { MA_MOTION, MA_WIDE, MA_CROSS };
+template <class Shape>
+int ma_check(const char* what, const ma_form form, const ma_args& a, const int32_t channels, Shape shape) {
+  const bool cross = form == MA_CROSS, wide = form == MA_WIDE;
+  I2V_CHECK_ARG(a.x && a.gamma && a.shift && a.w && a.out && (!cross || a.ctx_frag), "%s: null pointer", what);
+  if (const int rc = shape()) return rc;
+  I2V_CHECK_ARG(a.ldx >= channels && a.ldx % 8 == 0 && a.ldo >= channels && a.ldo % 8 == 0 &&
+                (cross || (a.ld_shift >= channels && a.ld_shift % 4 == 0)), "%s: row strides", what);
+  I2V_CHECK_ARG(i2v_al16(a.x) && i2v_al16(a.gamma) && i2v_al16(a.shift) && i2v_al16(a.w) && i2v_al16(a.out) && i2v_al16(a.ctx_frag) &&
+                i2v_al16(a.ip_frag) && (!wide || (i2v_al16(a.w_o) && i2v_al16(a.b_o))), "%s: pointers must be 16-byte aligned", what);
+  I2V_CHECK_ARG(a.ip_frag == nullptr || (a.ip_len >= 1 && a.ip_len <= 16), "%s: ip_len (%d) must be in [1, 16]", what, a.ip_len);
+  // (OUTP: the residual rows go through a buffer descriptor and per-lane offsets of 32 bits, ADVICE r5)
+  I2V_CHECK_ARG(a.w_o == nullptr || a.ldx < (1 << 23), "%s: ldx (%lld) must be below 2^23%s", what, (long long)a.ldx,
+                wide ? "" : " with the out-projection");
+  I2V_CHECK_ARG((a.w_o == nullptr) == (a.b_o == nullptr) && i2v_al16(a.w_o) && i2v_al16(a.b_o), "%s: w_o and b_o come together, 16-byte aligned", what);
+  return I2V_OK;
+}
+
 }  // namespace
 
 extern "C" int32_t i2v_motion_attn_supported(int64_t rows, int32_t channels, int32_t heads, int32_t head_dim, int32_t frames) {
@@ -622,22 +527,14 @@ extern "C" int32_t i2v_motion_attn_pack_rows(int32_t heads, int32_t head_dim) { 
 extern "C" int i2v_motion_attn_f16(const i2v_motion_attn_params* pp, i2v_stream_t stream) {
   I2V_CHECK_ARG(pp != nullptr, "i2v_motion_attn_f16: null params");
   const i2v_motion_attn_params& p = *pp;
-  I2V_CHECK_ARG(p.x && p.gamma && p.shift && p.w_qkv && p.out, "i2v_motion_attn_f16: null pointer");
-  I2V_CHECK_ARG(i2v_motion_attn_supported(p.rows, p.channels, p.heads, p.head_dim, p.frames),
-                "i2v_motion_attn_f16: rows %lld channels %d heads %d head_dim %d frames %d is not a fused shape "
-                "(i2v_motion_attn_supported)", (long long)p.rows, p.channels, p.heads, p.head_dim, p.frames);
-  I2V_CHECK_ARG(p.ldx >= p.channels && p.ldx % 8 == 0 && p.ldo >= p.channels && p.ldo % 8 == 0 && p.ld_shift >= p.channels &&
-                p.ld_shift % 4 == 0, "i2v_motion_attn_f16: row strides");
-  I2V_CHECK_ARG(i2v_al16(p.x) && i2v_al16(p.gamma) && i2v_al16(p.shift) && i2v_al16(p.w_qkv) && i2v_al16(p.out),
-                "i2v_motion_attn_f16: pointers must be 16-byte aligned");
-  ma_args a = {};
-  a.x = p.x; a.ldx = p.ldx; a.gamma = p.gamma; a.shift = p.shift; a.ld_shift = p.ld_shift; a.w = p.w_qkv; a.out = p.out;
-  a.ldo = p.ldo; a.eps = p.eps;
-  // (OUTP: the residual rows go through a buffer descriptor and per-lane offsets of 32 bits, ADVICE r5)
-  I2V_CHECK_ARG(p.w_o == nullptr || p.ldx < (1 << 23), "i2v_motion_attn_f16: ldx (%lld) must be below 2^23 with the out-projection", (long long)p.ldx);
-  I2V_CHECK_ARG((p.w_o == nullptr) == (p.b_o == nullptr) && i2v_al16(p.w_o) && i2v_al16(p.b_o),
-                "i2v_motion_attn_f16: w_o and b_o come together, 16-byte aligned");
-  a.w_o = p.w_o; a.b_o = p.b_o;
+  const ma_args a = ma_common_args(p.x, p.ldx, p.gamma, p.shift, p.ld_shift, p.w_qkv, p.out, p.ldo, p.eps, p.w_o, p.b_o);
+  if (const int rc = ma_check("i2v_motion_attn_f16", MA_MOTION, a, p.channels, [&]() {
+        I2V_CHECK_ARG(i2v_motion_attn_supported(p.rows, p.channels, p.heads, p.head_dim, p.frames),
+                      "i2v_motion_attn_f16: rows %lld channels %d heads %d head_dim %d frames %d is not a fused shape "
+                      "(i2v_motion_attn_supported)", (long long)p.rows, p.channels, p.heads, p.head_dim, p.frames);
+        return I2V_OK;
+      }))
+    return rc;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   if (p.w_o != nullptr) {
     if (p.frames == 8) return launch_ma<320, 40, 8, false, 8, true>(a, p.rows, p.scale, s, "i2v_motion_attn_f16");
@@ -660,20 +557,15 @@ extern "C" int32_t i2v_motion_attn_wide_supported(int64_t rows, int32_t channels
 extern "C" int i2v_motion_attn_wide_f16(const i2v_motion_attn_params* pp, i2v_stream_t stream) {
   I2V_CHECK_ARG(pp != nullptr, "i2v_motion_attn_wide_f16: null params");
   const i2v_motion_attn_params& p = *pp;
-  I2V_CHECK_ARG(p.x && p.gamma && p.shift && p.w_qkv && p.out, "i2v_motion_attn_wide_f16: null pointer");
-  I2V_CHECK_ARG(p.w_o && p.b_o, "i2v_motion_attn_wide_f16: w_o and b_o are required (this form exists only with the out-projection inside)");
-  I2V_CHECK_ARG(i2v_motion_attn_wide_supported(p.rows, p.channels, p.heads, p.head_dim, p.frames),
-                "i2v_motion_attn_wide_f16: rows %lld channels %d heads %d head_dim %d frames %d is not a fused shape "
-                "(i2v_motion_attn_wide_supported)", (long long)p.rows, p.channels, p.heads, p.head_dim, p.frames);
-  I2V_CHECK_ARG(p.ldx >= p.channels && p.ldx % 8 == 0 && p.ldo >= p.channels && p.ldo % 8 == 0 && p.ld_shift >= p.channels &&
-                p.ld_shift % 4 == 0, "i2v_motion_attn_wide_f16: row strides");
-  I2V_CHECK_ARG(i2v_al16(p.x) && i2v_al16(p.gamma) && i2v_al16(p.shift) && i2v_al16(p.w_qkv) && i2v_al16(p.out) && i2v_al16(p.w_o) &&
-                i2v_al16(p.b_o), "i2v_motion_attn_wide_f16: pointers must be 16-byte aligned");
-  // (the residual rows go through a buffer descriptor and per-lane offsets of 32 bits)
-  I2V_CHECK_ARG(p.ldx < (1 << 23), "i2v_motion_attn_wide_f16: ldx (%lld) must be below 2^23", (long long)p.ldx);
-  ma_args a = {};
-  a.x = p.x; a.ldx = p.ldx; a.gamma = p.gamma; a.shift = p.shift; a.ld_shift = p.ld_shift; a.w = p.w_qkv; a.out = p.out;
-  a.ldo = p.ldo; a.eps = p.eps; a.w_o = p.w_o; a.b_o = p.b_o;
+  const ma_args a = ma_common_args(p.x, p.ldx, p.gamma, p.shift, p.ld_shift, p.w_qkv, p.out, p.ldo, p.eps, p.w_o, p.b_o);
+  if (const int rc = ma_check("i2v_motion_attn_wide_f16", MA_WIDE, a, p.channels, [&]() {
+        I2V_CHECK_ARG(p.w_o && p.b_o, "i2v_motion_attn_wide_f16: w_o and b_o are required (this form exists only with the out-projection inside)");
+        I2V_CHECK_ARG(i2v_motion_attn_wide_supported(p.rows, p.channels, p.heads, p.head_dim, p.frames),
+                      "i2v_motion_attn_wide_f16: rows %lld channels %d heads %d head_dim %d frames %d is not a fused shape "
+                      "(i2v_motion_attn_wide_supported)", (long long)p.rows, p.channels, p.heads, p.head_dim, p.frames);
+        return I2V_OK;
+      }))
+    return rc;
   return launch_ma<640, 80, 8, false, 16, true, MA_WIDE_PIX>(a, p.rows, p.scale, reinterpret_cast<hipStream_t>(stream),
                                                               "i2v_motion_attn_wide_f16");
 }
@@ -694,27 +586,18 @@ extern "C" int64_t i2v_cross_attn_fused_ctx_elems(int32_t n_ctx, int32_t heads, 
 extern "C" int i2v_cross_attn_fused_f16(const i2v_cross_attn_fused_params* pp, i2v_stream_t stream) {
   I2V_CHECK_ARG(pp != nullptr, "i2v_cross_attn_fused_f16: null params");
   const i2v_cross_attn_fused_params& p = *pp;
-  I2V_CHECK_ARG(p.x && p.gamma && p.beta && p.w_q && p.ctx_frag && p.out, "i2v_cross_attn_fused_f16: null pointer");
-  I2V_CHECK_ARG(i2v_cross_attn_fused_supported(p.rows, p.channels, p.heads, p.head_dim, p.ctx_len, p.rows_per_ctx),
-                "i2v_cross_attn_fused_f16: rows %lld channels %d heads %d head_dim %d ctx_len %d rows_per_ctx %lld is not a fused shape "
-                "(i2v_cross_attn_fused_supported)", (long long)p.rows, p.channels, p.heads, p.head_dim, p.ctx_len,
-                (long long)p.rows_per_ctx);
-  I2V_CHECK_ARG(p.ldx >= p.channels && p.ldx % 8 == 0 && p.ldo >= p.channels && p.ldo % 8 == 0, "i2v_cross_attn_fused_f16: row strides");
-  I2V_CHECK_ARG(i2v_al16(p.x) && i2v_al16(p.gamma) && i2v_al16(p.beta) && i2v_al16(p.w_q) && i2v_al16(p.out) && i2v_al16(p.ctx_frag) && i2v_al16(p.ip_frag),
-                "i2v_cross_attn_fused_f16: pointers must be 16-byte aligned");
-  I2V_CHECK_ARG(p.ip_frag == nullptr || (p.ip_len >= 1 && p.ip_len <= 16), "i2v_cross_attn_fused_f16: ip_len (%d) must be in [1, 16]",
-                p.ip_len);
-  ma_args a = {};
-  a.x = p.x; a.ldx = p.ldx; a.gamma = p.gamma; a.shift = p.beta; a.ld_shift = 0; a.w = p.w_q; a.out = p.out; a.ldo = p.ldo;
-  a.eps = p.eps;
+  ma_args a = ma_common_args(p.x, p.ldx, p.gamma, p.beta, 0, p.w_q, p.out, p.ldo, p.eps, p.w_o, p.b_o);
   a.ctx_frag = p.ctx_frag; a.lt = p.ctx_len;
   a.ip_frag = p.ip_frag; a.ip_len = p.ip_frag ? p.ip_len : 0; a.ip_scale = p.ip_scale;
+  if (const int rc = ma_check("i2v_cross_attn_fused_f16", MA_CROSS, a, p.channels, [&]() {
+        I2V_CHECK_ARG(i2v_cross_attn_fused_supported(p.rows, p.channels, p.heads, p.head_dim, p.ctx_len, p.rows_per_ctx),
+                      "i2v_cross_attn_fused_f16: rows %lld channels %d heads %d head_dim %d ctx_len %d rows_per_ctx %lld is not a fused shape "
+                      "(i2v_cross_attn_fused_supported)", (long long)p.rows, p.channels, p.heads, p.head_dim, p.ctx_len,
+                      (long long)p.rows_per_ctx);
+        return I2V_OK;
+      }))
+    return rc;
   a.tiles_per_ctx = (int32_t)(p.rows_per_ctx / (MA_PIX * MA_F));
-  // (OUTP: the residual rows go through a buffer descriptor and per-lane offsets of 32 bits, ADVICE r5)
-  I2V_CHECK_ARG(p.w_o == nullptr || p.ldx < (1 << 23), "i2v_cross_attn_fused_f16: ldx (%lld) must be below 2^23 with the out-projection", (long long)p.ldx);
-  I2V_CHECK_ARG((p.w_o == nullptr) == (p.b_o == nullptr) && i2v_al16(p.w_o) && i2v_al16(p.b_o),
-                "i2v_cross_attn_fused_f16: w_o and b_o come together, 16-byte aligned");
-  a.w_o = p.w_o; a.b_o = p.b_o;
   if (p.w_o != nullptr)
     return launch_ma<320, 40, 8, true, 16, true>(a, p.rows, p.scale, reinterpret_cast<hipStream_t>(stream), "i2v_cross_attn_fused_f16");
   return launch_ma<320, 40, 8, true>(a, p.rows, p.scale, reinterpret_cast<hipStream_t>(stream), "i2v_cross_attn_fused_f16");

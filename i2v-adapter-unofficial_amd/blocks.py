@@ -1683,3 +1683,209 @@ class LCMScheduler:
         while sa.dim() < original_samples.dim():
             sa, sb = sa.unsqueeze(-1), sb.unsqueeze(-1)
         return sa * original_samples + sb * noise
+
+
+class _SigmaScheduler:
+    """What EulerDiscreteScheduler and EulerAncestralDiscreteScheduler share: samplers in sigma space (x = x0 + sigma noise), restated
+    from diffusers 0.24 for epsilon prediction (parity with diffusers itself is unpinned: tests/euler_reference.py is the
+    specification).  Names, config keys and defaults are diffusers' (linear betas 0.0001 .. 0.02, linspace spacing, steps_offset=0):
+    `from_config(pipe.scheduler.config)` carries a DDIM, DPM-Solver++, LCM or PNDM config's betas over; keys the class does not know
+    are ignored, an unsupported value of one it knows raises NotImplementedError.
+
+    The timesteps are fractional (fp32) and the noise levels are interpolated between the training steps'; the model input is the
+    latents divided by sqrt(sigma^2 + 1) (`i2v_sigma_prep`), and "noise a clean clip to timestep t" is x0 + sigma_t noise
+    (`noise_level`).  The step kernel `i2v_euler_cfg_step` reads the rows of `step_coefficients`."""
+
+    order = 1
+    _CLASS_NAME = None
+    _ANCESTRAL = False
+    _SUPPORTED = {"prediction_type": ("epsilon",), "beta_schedule": ("linear", "scaled_linear"),
+                  "timestep_spacing": ("linspace", "leading", "trailing"), "interpolation_type": ("linear",)}
+
+    def _init(self, config):
+        self.config = config
+        for key, allowed in self._SUPPORTED.items():
+            if key in config and config[key] not in allowed:
+                raise NotImplementedError(f"{self._CLASS_NAME}: {key}={config[key]!r} is not supported (supported: "
+                                          f"{', '.join(repr(a) for a in allowed)})")
+        if config["trained_betas"] is not None:
+            raise NotImplementedError(f"{self._CLASS_NAME}: trained_betas is not supported")
+        T, b0, b1 = config["num_train_timesteps"], config["beta_start"], config["beta_end"]
+        if config["beta_schedule"] == "scaled_linear":
+            self.betas = torch.linspace(b0 ** 0.5, b1 ** 0.5, T, dtype=torch.float32) ** 2
+        else:
+            self.betas = torch.linspace(b0, b1, T, dtype=torch.float32)
+        self.num_train_timesteps = T
+        self.alphas_cumprod = torch.cumprod(1.0 - self.betas, dim=0)
+        self.timestep_spacing, self.steps_offset = config["timestep_spacing"], config["steps_offset"]
+        self.use_karras_sigmas = bool(config.get("use_karras_sigmas", False))
+        # sigma of every training step, as diffusers holds it: from the fp32 alphas_cumprod, then float64 for the interpolation
+        self._train_sigmas = (((1 - self.alphas_cumprod) / self.alphas_cumprod) ** 0.5).numpy().astype("float64")
+        self.num_inference_steps = None
+        self.timesteps = torch.arange(T - 1, -1, -1, dtype=torch.float32)
+        self.sigmas = torch.cat([torch.from_numpy(self._train_sigmas[::-1].copy()), torch.zeros(1, dtype=torch.float64)]).to(torch.float32)
+
+    @classmethod
+    def from_config(cls, config: dict, **overrides):
+        """diffusers' `SchedulerMixin.from_config`: keys starting with `_` and unknown keys are ignored."""
+        cfg = {k: v for k, v in dict(config).items() if not k.startswith("_")}
+        cfg.update(overrides)
+        return cls(**cfg)
+
+    @classmethod
+    def from_pretrained(cls, pretrained_model_path: str, subfolder: Optional[str] = None, **overrides):
+        """scheduler_config.json (of any scheduler class: an SD-1.5 checkpoint ships PNDM's) + keyword overrides."""
+        import json
+        import os
+        path = os.path.join(pretrained_model_path, subfolder) if subfolder else pretrained_model_path
+        with open(os.path.join(path, "scheduler_config.json")) as f:
+            return cls.from_config(json.load(f), **overrides)
+
+    def save_pretrained(self, save_directory: str):
+        import json
+        import os
+        os.makedirs(save_directory, exist_ok=True)
+        with open(os.path.join(save_directory, "scheduler_config.json"), "w") as f:
+            json.dump({"_class_name": self._CLASS_NAME, **self.config}, f, indent=2, sort_keys=True)
+
+    def _sigma_to_t(self, sigma):
+        """the piecewise-linear inverse of log sigma over the training steps (diffusers `_sigma_to_t`), for an array of sigmas"""
+        import numpy as np
+        log_train = np.log(self._train_sigmas)
+        log_sigma = np.log(np.maximum(sigma, 1e-10))
+        low = np.cumsum(log_sigma - log_train[:, None] >= 0, axis=0).argmax(axis=0).clip(max=len(log_train) - 2)
+        high = low + 1
+        w = np.clip((log_train[low] - log_sigma) / (log_train[low] - log_train[high]), 0, 1)
+        return (1 - w) * low + w * high
+
+    def set_timesteps(self, num_inference_steps: int, device=None):
+        """N fractional timesteps from the top of the training schedule down (fp32) and the noise level of each, interpolated between
+        the training steps' sigma = sqrt((1 - abar) / abar), plus a final 0; with `use_karras_sigmas` the levels are Karras et al.'s
+        rho = 7 ramp between the first and the last of those and the timesteps are the ramp's through `_sigma_to_t`."""
+        import numpy as np
+        T, N = self.num_train_timesteps, int(num_inference_steps)
+        if N < 1:
+            raise ValueError(f"num_inference_steps {num_inference_steps} must be at least 1")
+        if self.timestep_spacing == "linspace":
+            ts = np.linspace(0, T - 1, N, dtype=np.float32)[::-1].copy()
+        elif self.timestep_spacing == "leading":
+            ts = (np.arange(0, N) * (T // N)).round()[::-1].copy().astype(np.float32) + self.steps_offset
+        else:
+            ts = np.arange(T, 0, -T / N).round().copy().astype(np.float32) - 1
+        sigmas = np.interp(ts, np.arange(0, T), self._train_sigmas)
+        if self.use_karras_sigmas:
+            rho, s_min, s_max = 7.0, float(sigmas[-1]), float(sigmas[0])
+            sigmas = (s_max ** (1 / rho) + np.linspace(0, 1, N) * (s_min ** (1 / rho) - s_max ** (1 / rho))) ** rho
+            ts = self._sigma_to_t(sigmas)
+        self.timesteps = torch.from_numpy(np.asarray(ts, dtype=np.float32))
+        self.sigmas = torch.from_numpy(np.concatenate([sigmas, [0.0]]).astype(np.float32))
+        self.num_inference_steps = N
+
+    @property
+    def init_noise_sigma(self):
+        s_max = float(self.sigmas.max())
+        return s_max if self.timestep_spacing in ("linspace", "trailing") else (s_max ** 2 + 1) ** 0.5
+
+    def _index_of(self, timestep):
+        """the position of `timestep` in the schedule (the first, should two entries coincide); floats compared as floats"""
+        hits = (self.timesteps == float(timestep)).nonzero()
+        if len(hits) == 0:
+            raise ValueError(f"timestep {float(timestep)} is not in the scheduler's timesteps (set_timesteps first)")
+        return int(hits[0])
+
+    def _start_index(self, timesteps):
+        full = [float(v) for v in self.timesteps]
+        sub = [float(v) for v in timesteps]
+        if not sub or sub[0] not in full or full[full.index(sub[0]):] != sub:
+            raise ValueError("timesteps must be a tail of the scheduler's timesteps (set_timesteps first)")
+        return full.index(sub[0])
+
+    def scale_model_input(self, sample, timestep):
+        sigma = float(self.sigmas[self._index_of(timestep)])
+        return sample / ((sigma ** 2 + 1) ** 0.5)
+
+    def noise_level(self, timestep):
+        """(a, b) of "noise a clean clip to this timestep's level", a x0 + b noise: (1, sigma_t)"""
+        return 1.0, float(self.sigmas[self._index_of(timestep)])
+
+    def add_noise(self, original_samples, noise, timesteps):
+        sigma = torch.stack([self.sigmas[self._index_of(t)] for t in torch.as_tensor(timesteps).flatten()])
+        sigma = sigma.to(device=original_samples.device, dtype=original_samples.dtype)
+        while sigma.dim() < original_samples.dim():
+            sigma = sigma.unsqueeze(-1)
+        return original_samples + noise * sigma
+
+    def _step_sigmas(self, i):
+        """(sigma, sigma_to, sigma_up) of the step from schedule entry i, in float64 from the fp32-rounded sigmas"""
+        s, s_next = float(self.sigmas[i]), float(self.sigmas[i + 1])
+        if not self._ANCESTRAL:
+            return s, s_next, 0.0
+        s_up = math.sqrt(s_next ** 2 * (s ** 2 - s_next ** 2) / s ** 2)
+        return s, math.sqrt(s_next ** 2 - s_up ** 2), s_up
+
+    def step_coefficients(self, timesteps, eta: float = 0.0) -> torch.Tensor:
+        """[len(timesteps), 4] fp32 rows {sigma, 1 / sqrt(sigma^2 + 1), sigma_to, sigma_up} of `i2v_sigma_prep` (column 1) and
+        `i2v_euler_cfg_step`, built in float64 from the fp32-rounded sigmas.  Row k is the step from timesteps[k] (`timesteps` is the
+        full list or a tail of it: frame_similarity_sample_ratio < 1, strength < 1):
+            x' = x + eps (sigma_to - sigma) + sigma_up z
+        Euler: sigma_to = sigma_next, sigma_up = 0.  Ancestral: sigma_up = sqrt(sigma_next^2 (sigma^2 - sigma_next^2) / sigma^2),
+        sigma_to = sigma_down = sqrt(sigma_next^2 - sigma_up^2); its last row has both 0.  `eta` is ignored, as for DPM-Solver++."""
+        start = self._start_index(timesteps)
+        rows = []
+        for i in range(start, len(self.timesteps)):
+            s, s_to, s_up = self._step_sigmas(i)
+            rows.append([s, 1.0 / math.sqrt(s * s + 1.0), s_to, s_up])
+        return torch.tensor(rows, dtype=torch.float64).to(torch.float32)
+
+    def step(self, model_output, timestep, sample, s_churn: float = 0.0, s_tmin: float = 0.0, s_tmax: float = float("inf"),
+             s_noise: float = 1.0, generator=None, eta: float = 0.0):
+        """one update on the host, in the sample's dtype (the captured step does this in `i2v_euler_cfg_step`); the ancestral sampler
+        draws one randn of the model output's shape from `generator`, the last step included.  Returns the latents."""
+        if s_churn > 0:
+            raise NotImplementedError(f"{self._CLASS_NAME}: s_churn={s_churn!r} is not supported (supported: 0.0)")
+        s, s_to, s_up = self._step_sigmas(self._index_of(timestep))
+        out = sample + model_output * (s_to - s)
+        if self._ANCESTRAL:
+            from .pipeline_i2v_adapter import _draw
+            out = out + _draw(torch.randn, tuple(model_output.shape), generator, model_output.device).to(model_output.dtype) * s_up
+        return out
+
+
+class EulerDiscreteScheduler(_SigmaScheduler):
+    """"Euler": the first-order ODE sampler in sigma space, x' = x + eps (sigma_next - sigma); deterministic, so the whole step stays
+    one captured hipGraph with no state beyond the latents.  `use_karras_sigmas=True` spaces the noise levels by Karras et al.'s ramp.
+    Not supported (NotImplementedError): prediction types other than epsilon, trained_betas, interpolation_type="log_linear", s_churn."""
+
+    _CLASS_NAME = "EulerDiscreteScheduler"
+
+    def __init__(self, num_train_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule="linear", trained_betas=None,
+                 prediction_type="epsilon", interpolation_type="linear", use_karras_sigmas=False, timestep_spacing="linspace",
+                 steps_offset=0, **_unused):
+        self._init(dict(num_train_timesteps=num_train_timesteps, beta_start=beta_start, beta_end=beta_end, beta_schedule=beta_schedule,
+                        trained_betas=trained_betas, prediction_type=prediction_type, interpolation_type=interpolation_type,
+                        use_karras_sigmas=use_karras_sigmas, timestep_spacing=timestep_spacing, steps_offset=steps_offset))
+
+
+class EulerAncestralDiscreteScheduler(_SigmaScheduler):
+    """"Euler a": the Euler step to sigma_down followed by fresh noise at sigma_up, x' = x + eps (sigma_down - sigma) + sigma_up z.  The
+    draws of a whole sample are made before its first step (`step_noise`) and read on the device by the step counter, as LCM's are, so
+    the step stays one captured hipGraph."""
+
+    _CLASS_NAME = "EulerAncestralDiscreteScheduler"
+    _ANCESTRAL = True
+
+    def __init__(self, num_train_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule="linear", trained_betas=None,
+                 prediction_type="epsilon", timestep_spacing="linspace", steps_offset=0, **_unused):
+        self._init(dict(num_train_timesteps=num_train_timesteps, beta_start=beta_start, beta_end=beta_end, beta_schedule=beta_schedule,
+                        trained_betas=trained_betas, prediction_type=prediction_type, timestep_spacing=timestep_spacing,
+                        steps_offset=steps_offset))
+
+    def step_noise(self, timesteps, shape, generator=None, device=None):
+        """The noise table of `i2v_euler_cfg_step`: one randn draw of `shape` (the latents') per step of `timesteps`, the last
+        included (its sigma_up is 0: diffusers draws there too, and the generator's stream after a sample is then what the host loop
+        leaves), in step order from `generator`; draw order and lists of generators as `LCMScheduler.step_noise`.  fp32
+        [len(timesteps), *shape] on `device`."""
+        from .pipeline_i2v_adapter import _draw
+        n_draws = len(self.timesteps) - self._start_index(timesteps)
+        device = device if device is not None else torch.device("cpu")
+        return torch.stack([_draw(torch.randn, tuple(shape), generator, device) for _ in range(n_draws)]).to(torch.float32).contiguous()

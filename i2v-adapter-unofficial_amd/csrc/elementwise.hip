@@ -115,10 +115,17 @@ __global__ __launch_bounds__(256) void copy3d_kernel(const f16* __restrict__ src
 }
 
 // latents fp32 [b, f, c, hw]; cond fp32 [b, c, hw]; model_in fp16 [copies*b*f, hw, c_pad]
+// SCALED (i2v_sigma_prep; Euler's scale_model_input): model_in = fp16(v * coef[step][1]) with coef fp32 [n_steps][ld_coef] and the
+// step counter read, not advanced; latents[:, 0] = cond is written unscaled.  SCALED = false is the DDIM prep: it reads none of the
+// three extra arguments.
+template <bool SCALED>
 __global__ __launch_bounds__(256) void ddim_prep_kernel(float* __restrict__ latents, const float* __restrict__ cond,
                                                         f16* __restrict__ model_in, int b, int f, int c, int hw, int c_pad,
-                                                        int copies) {
+                                                        int copies, const float* __restrict__ coef, int ld_coef, int n_steps,
+                                                        const int32_t* __restrict__ step_index) {
   const int64_t per_copy = (int64_t)b * f * hw * c_pad;
+  float scale = 1.f;
+  if constexpr (SCALED) scale = coef[(int64_t)ld_coef * min(max(*step_index, 0), n_steps - 1) + 1];
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < per_copy; i += (int64_t)gridDim.x * 256) {
     const int ch = (int)(i % c_pad);
     int64_t t = i / c_pad;
@@ -136,7 +143,11 @@ __global__ __launch_bounds__(256) void ddim_prep_kernel(float* __restrict__ late
         v = latents[li];
       }
     }
-    const f16 hv = (f16)v;
+    f16 hv;
+    if constexpr (SCALED)
+      hv = (f16)(v * scale);
+    else
+      hv = (f16)v;
     for (int k = 0; k < copies; ++k) model_in[k * per_copy + i] = hv;
   }
 }
@@ -281,6 +292,53 @@ __global__ __launch_bounds__(256) void lcm_step_kernel(float* __restrict__ laten
       load_f32v<V>(z + g * V, zz);
 #pragma unroll
       for (int j = 0; j < V; ++j) out[j] += sb_p * zz[j];
+    }
+    store_f32v<V>(latents + g * V, out);
+  }
+}
+
+// Euler / Euler-ancestral update in sigma space with the same CFG combine and the same V-pixels-per-thread form as lcm_step_kernel.
+// Row {sigma, 1 / sqrt(sigma^2 + 1), sigma_to, sigma_up} (column 1 is the prep kernel's):
+//   x' = x + eps (sigma_to - sigma) + sigma_up z,  z = noise[min(step, n_noise - 1)].
+// sigma_to is sigma_next for Euler (sigma_up = 0, noise NULL) and sigma_down for the ancestral sampler.  A row with sigma_up == 0 (every
+// Euler row, the ancestral sampler's last) never reads the table.
+template <typename NP, int V>
+__global__ __launch_bounds__(256) void euler_step_kernel(float* __restrict__ latents, const float* __restrict__ noise, int n_noise,
+                                                         const NP* __restrict__ np, int64_t ld_np, const float* __restrict__ coef,
+                                                         int n_steps, const int32_t* __restrict__ step_index, float guidance,
+                                                         int b, int f, int c, int hw, int copies) {
+  const int hwv = hw / V;
+  const int64_t groups = (int64_t)b * f * c * hwv;
+  const int step = min(max(*step_index, 0), n_steps - 1);
+  const float* cf = coef + 4 * (int64_t)step;
+  const float dsig = cf[2] - cf[0], s_up = cf[3];
+  const bool renoise = s_up != 0.f && noise != nullptr && n_noise > 0;
+  const float* z = renoise ? noise + (int64_t)min(step, n_noise - 1) * (groups * V) : nullptr;
+  const int64_t bf = (int64_t)b * f;
+  for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < groups; g += (int64_t)gridDim.x * 256) {
+    const int p0 = (int)(g % hwv) * V;
+    const int64_t t = g / hwv;
+    const int ch = (int)(t % c);
+    const int64_t img = t / c;  // b * f + fr
+    float x[V], out[V];
+    load_f32v<V>(latents + g * V, x);
+#pragma unroll
+    for (int j = 0; j < V; ++j) {
+      float eps;
+      if (copies == 2) {
+        const float u = (float)np[(img * hw + p0 + j) * ld_np + ch];
+        const float cnd = (float)np[((bf + img) * hw + p0 + j) * ld_np + ch];
+        eps = u + guidance * (cnd - u);
+      } else {
+        eps = (float)np[(img * hw + p0 + j) * ld_np + ch];
+      }
+      out[j] = x[j] + eps * dsig;
+    }
+    if (renoise) {
+      float zz[V];
+      load_f32v<V>(z + g * V, zz);
+#pragma unroll
+      for (int j = 0; j < V; ++j) out[j] += s_up * zz[j];
     }
     store_f32v<V>(latents + g * V, out);
   }
@@ -474,10 +532,25 @@ extern "C" int i2v_ddim_prep(float* latents, const float* cond, void* model_in, 
   I2V_CHECK_ARG(latents && cond && model_in && b > 0 && f > 0 && c > 0 && hw > 0 && c_pad >= c,
                 "i2v_ddim_prep: bad arguments");
   I2V_CHECK_ARG(cfg_copies == 1 || cfg_copies == 2, "i2v_ddim_prep: cfg_copies must be 1 or 2");
-  hipLaunchKernelGGL(ddim_prep_kernel, dim3(ew_blocks((int64_t)b * f * hw * c_pad)), dim3(256), 0,
+  hipLaunchKernelGGL(ddim_prep_kernel<false>, dim3(ew_blocks((int64_t)b * f * hw * c_pad)), dim3(256), 0,
                      reinterpret_cast<hipStream_t>(stream), latents, cond, reinterpret_cast<f16*>(model_in), b, f, c, hw,
-                     c_pad, cfg_copies);
+                     c_pad, cfg_copies, nullptr, 0, 0, nullptr);
   return i2v_check_launch("i2v_ddim_prep");
+}
+
+extern "C" int i2v_sigma_prep(float* latents, const float* cond, void* model_in, const float* coef, int32_t ld_coef, int32_t n_steps,
+                              const int32_t* step_index, int32_t b, int32_t f, int32_t c, int32_t hw, int32_t c_pad,
+                              int32_t cfg_copies, i2v_stream_t stream) {
+  I2V_CHECK_ARG(latents && cond && model_in && coef && step_index, "i2v_sigma_prep: null pointer");
+  I2V_CHECK_ARG(b > 0 && f > 0 && c > 0 && hw > 0 && c_pad >= c, "i2v_sigma_prep: b %d f %d c %d hw %d c_pad %d: all positive, c_pad >= c",
+                b, f, c, hw, c_pad);
+  I2V_CHECK_ARG(ld_coef >= 2, "i2v_sigma_prep: ld_coef %d must be at least 2 (the scale is column 1)", ld_coef);
+  I2V_CHECK_ARG(n_steps >= 1, "i2v_sigma_prep: n_steps %d must be at least 1", n_steps);
+  I2V_CHECK_ARG(cfg_copies == 1 || cfg_copies == 2, "i2v_sigma_prep: cfg_copies must be 1 or 2");
+  hipLaunchKernelGGL(ddim_prep_kernel<true>, dim3(ew_blocks((int64_t)b * f * hw * c_pad)), dim3(256), 0,
+                     reinterpret_cast<hipStream_t>(stream), latents, cond, reinterpret_cast<f16*>(model_in), b, f, c, hw,
+                     c_pad, cfg_copies, coef, ld_coef, n_steps, step_index);
+  return i2v_check_launch("i2v_sigma_prep");
 }
 
 extern "C" int i2v_ddim_cfg_step(float* latents, const void* noise_pred, int32_t np_is_f32, int64_t ld_np,
@@ -566,6 +639,42 @@ extern "C" int i2v_lcm_cfg_step(float* latents, const float* noise, int32_t n_no
                        cfg_copies, s);
   hipLaunchKernelGGL(bump_step_kernel, dim3(1), dim3(64), 0, s, step_index, n_steps);
   return i2v_check_launch("i2v_lcm_cfg_step");
+}
+
+template <int V>
+static void launch_euler_step(float* latents, const float* noise, int32_t n_noise, const void* noise_pred, int32_t np_is_f32,
+                              int64_t ld_np, const float* coef, int32_t n_steps, int32_t* step_index, float guidance_scale, int32_t b,
+                              int32_t f, int32_t c, int32_t hw, int32_t cfg_copies, hipStream_t s) {
+  const dim3 grid(ew_blocks((int64_t)b * f * c * (hw / V))), block(256);
+  if (np_is_f32)
+    hipLaunchKernelGGL((euler_step_kernel<float, V>), grid, block, 0, s, latents, noise, n_noise, reinterpret_cast<const float*>(noise_pred),
+                       ld_np, coef, n_steps, step_index, guidance_scale, b, f, c, hw, cfg_copies);
+  else
+    hipLaunchKernelGGL((euler_step_kernel<f16, V>), grid, block, 0, s, latents, noise, n_noise, reinterpret_cast<const f16*>(noise_pred),
+                       ld_np, coef, n_steps, step_index, guidance_scale, b, f, c, hw, cfg_copies);
+}
+
+extern "C" int i2v_euler_cfg_step(float* latents, const float* noise, int32_t n_noise, const void* noise_pred, int32_t np_is_f32,
+                                  int64_t ld_np, const float* coef, int32_t n_steps, int32_t* step_index, float guidance_scale,
+                                  int32_t b, int32_t f, int32_t c, int32_t hw, int32_t cfg_copies, i2v_stream_t stream) {
+  I2V_CHECK_ARG(latents && noise_pred && coef && step_index, "i2v_euler_cfg_step: null pointer");
+  I2V_CHECK_ARG(b > 0 && f > 0 && c > 0 && hw > 0, "i2v_euler_cfg_step: b %d f %d c %d hw %d must be positive", b, f, c, hw);
+  I2V_CHECK_ARG(n_steps >= 1, "i2v_euler_cfg_step: n_steps %d must be at least 1", n_steps);
+  I2V_CHECK_ARG(ld_np >= c, "i2v_euler_cfg_step: ld_np %lld < c %d", (long long)ld_np, c);
+  I2V_CHECK_ARG(cfg_copies == 1 || cfg_copies == 2, "i2v_euler_cfg_step: cfg_copies must be 1 or 2");
+  // the coefficient table lives on the device: a NULL noise table with a row whose sigma_up != 0 is refused where the table is known
+  // (the Python wrapper, the pipeline); here a table that is given must have a row for every step
+  I2V_CHECK_ARG(noise == nullptr || n_noise >= n_steps, "i2v_euler_cfg_step: n_noise %d < n_steps %d", n_noise, n_steps);
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const bool vec4 = hw % 4 == 0 && (reinterpret_cast<uintptr_t>(latents) & 15) == 0 && (reinterpret_cast<uintptr_t>(noise) & 15) == 0;
+  if (vec4)
+    launch_euler_step<4>(latents, noise, n_noise, noise_pred, np_is_f32, ld_np, coef, n_steps, step_index, guidance_scale, b, f, c, hw,
+                         cfg_copies, s);
+  else
+    launch_euler_step<1>(latents, noise, n_noise, noise_pred, np_is_f32, ld_np, coef, n_steps, step_index, guidance_scale, b, f, c, hw,
+                         cfg_copies, s);
+  hipLaunchKernelGGL(bump_step_kernel, dim3(1), dim3(64), 0, s, step_index, n_steps);
+  return i2v_check_launch("i2v_euler_cfg_step");
 }
 
 extern "C" int i2v_first_frame_prior_f32(const float* cond, const float* mask_uniform, const float* noise, float* latents,

@@ -365,6 +365,14 @@ def _refuse_mask(st, what):
                                   "table buffers) is not implemented for the C handle; call without `mask_image` to export")
 
 
+def _refuse_sigma_scheduler(pipe, what):
+    """the Euler samplers' step launches i2v_sigma_prep and i2v_euler_cfg_step, which the plan format has no entry ids for"""
+    if pipe._scheduler_kind() in ("euler", "euler_ancestral"):
+        raise NotImplementedError(f"{what}: {type(pipe.scheduler).__name__} is not implemented for the C handle (its step launches "
+                                  "i2v_sigma_prep and i2v_euler_cfg_step, which a launch plan cannot carry yet); use DDIMScheduler, "
+                                  "DPMSolverMultistepScheduler or LCMScheduler to export")
+
+
 def _step_problem(st):
     b, f, _c, hh, ww = st["latents"].shape
     return (st["copies"] * b, f, hh, ww, st["ctx_text"].shape[1], int(st["ctx_ip"] is not None))
@@ -383,6 +391,7 @@ def record_step_plan(pipe, st):
     _refuse_controlnet(pipe, "record_step_plan")
     _refuse_per_frame_context(st, "record_step_plan")
     _refuse_mask(st, "record_step_plan")
+    _refuse_sigma_scheduler(pipe, "record_step_plan")
     if pipe._scheduler_kind() == "lcm":
         noise = st.get("noise")
         keep_lcm = (st["latents"].clone(), st["step_idx"].clone())
@@ -575,6 +584,7 @@ def export_denoiser(pipe, out_dir, *, num_frames, latent_height, latent_width, b
     without).  Returns the manifest.  A plan holds for this size, these switches and this library build.
     per_frame_context (prompt travel: one text context per frame) is refused: the plans hold one context per sample."""
     _refuse_controlnet(pipe, "export_denoiser")
+    _refuse_sigma_scheduler(pipe, "export_denoiser")
     if per_frame_context:
         raise NotImplementedError("export_denoiser: per-frame text contexts (prompt travel) are not implemented for the C handle (its "
                                   "plans and the C host's inputs file hold one context per sample)")

@@ -1425,6 +1425,66 @@ def lcm_cfg_step(latents, noise, noise_pred, coef, step_index, guidance_scale, c
     return latents
 
 
+def sigma_prep(latents, cond, coef, step_index, c_pad, cfg_copies):
+    """`ddim_prep` with Euler's `scale_model_input`: latents fp32 [B, F, C, H, W] (frame 0 overwritten in place with cond [B, C, H, W],
+    unscaled) -> model input tokens fp16 [cfg_copies * B * F, H, W, c_pad] = fp16(v * coef[step][1]); coef fp32 [steps, >= 2] (the
+    samplers' `step_coefficients`: column 1 is 1 / sqrt(sigma^2 + 1)); step_index device int32 scalar, read and not advanced."""
+    lib = _lib.load()
+    _req(latents, "latents", dtype=torch.float32)
+    _req(cond, "cond", dtype=torch.float32)
+    _req(coef, "coef", dtype=torch.float32)
+    _req(step_index, "step_index", dtype=torch.int32)
+    if latents.dim() != 5 or not latents.is_contiguous() or not cond.is_contiguous():
+        raise ValueError("latents must be contiguous [B, F, C, H, W]; cond contiguous [B, C, H, W]")
+    b, f, c, h, w = latents.shape
+    if tuple(cond.shape) != (b, c, h, w):
+        raise ValueError(f"cond must be {(b, c, h, w)}, got {tuple(cond.shape)}")
+    if coef.dim() != 2 or coef.shape[0] < 1 or coef.shape[1] < 2 or not coef.is_contiguous():
+        raise ValueError("coef must be contiguous [steps >= 1, >= 2]")
+    out = torch.empty((cfg_copies * b * f, h, w, c_pad), dtype=f16, device=latents.device)
+    _lib.check(lib.i2v_sigma_prep(_p(latents), _p(cond), _p(out), _p(coef), coef.shape[1], coef.shape[0], _p(step_index), b, f, c, h * w,
+                                  c_pad, cfg_copies, _stream()),
+               "i2v_sigma_prep")
+    return out
+
+
+def euler_cfg_step(latents, noise, noise_pred, coef, step_index, guidance_scale, cfg_copies):
+    """In-place Euler / Euler-ancestral update of latents fp32 [B, F, C, H, W] from noise_pred tokens (fp32, or fp16)
+    [cfg_copies * B * F, H, W, ld]: x' = x + eps (sigma_to - sigma) + sigma_up z.  coef fp32 [steps, 4] rows {sigma,
+    1 / sqrt(sigma^2 + 1), sigma_to, sigma_up} (`EulerDiscreteScheduler.step_coefficients` / `EulerAncestralDiscreteScheduler.
+    step_coefficients`); noise fp32 [n >= steps, B, F, C, H, W] (`EulerAncestralDiscreteScheduler.step_noise`: row `step` is z), None for
+    Euler, whose rows all have sigma_up = 0; step_index device int32 scalar (advanced by one, wrapping to 0 at the end of the table).
+    noise=None with a table that has a non-zero sigma_up is refused here, where the table can be read: outside stream capture (a
+    captured step has had its eager warm-up step)."""
+    lib = _lib.load()
+    _req(latents, "latents", dtype=torch.float32)
+    _req(noise_pred, "noise_pred", dtype=None)
+    if noise_pred.dtype not in (torch.float32, f16):
+        raise TypeError("noise_pred must be fp32 or fp16")
+    _req(coef, "coef", dtype=torch.float32)
+    _req(step_index, "step_index", dtype=torch.int32)
+    if latents.dim() != 5 or not latents.is_contiguous():
+        raise ValueError("latents must be contiguous [B, F, C, H, W]")
+    b, f, c, h, w = latents.shape
+    if coef.dim() != 2 or coef.shape[1] != 4 or coef.shape[0] < 1 or not coef.is_contiguous():
+        raise ValueError("coef must be contiguous [steps, 4]")
+    if noise is not None:
+        _req(noise, "noise", dtype=torch.float32)
+        if noise.dim() != 6 or tuple(noise.shape[1:]) != tuple(latents.shape) or noise.shape[0] < coef.shape[0] or not noise.is_contiguous():
+            raise ValueError(f"noise must be contiguous [n >= {coef.shape[0]}, {', '.join(str(v) for v in latents.shape)}], "
+                             f"got {tuple(noise.shape)}")
+    elif not torch.cuda.is_current_stream_capturing() and bool((coef[:, 3] != 0).any()):
+        raise ValueError("noise is None and the coefficient table has a row with sigma_up != 0 (an ancestral table needs its noise table)")
+    if noise_pred.dim() != 4 or not noise_pred.is_contiguous() or noise_pred.shape[0] != cfg_copies * b * f or \
+            noise_pred.shape[1] != h or noise_pred.shape[2] != w or noise_pred.shape[3] < c:
+        raise ValueError(f"noise_pred must be contiguous [{cfg_copies * b * f}, {h}, {w}, >={c}]")
+    _lib.check(lib.i2v_euler_cfg_step(_p(latents), _p(noise) if noise is not None else None, noise.shape[0] if noise is not None else 0,
+                                      _p(noise_pred), 1 if noise_pred.dtype == torch.float32 else 0, noise_pred.shape[3], _p(coef),
+                                      coef.shape[0], _p(step_index), float(guidance_scale), b, f, c, h * w, cfg_copies, _stream()),
+               "i2v_euler_cfg_step")
+    return latents
+
+
 def freeu(hidden, skip, b, s):
     """FreeU on the operands of an up block's skip concatenation (i2v_freeu_f16; diffusers apply_freeu, unet:453-478): hidden
     [N, H, W, C1], skip [N, H, W, C2] fp16 token-major -> (hidden', skip'), new tensors.  hidden'[..., :C1 // 2] = hidden * b, the

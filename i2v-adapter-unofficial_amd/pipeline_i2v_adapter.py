@@ -5,7 +5,9 @@
 One DDIM step = frame-0 overwrite + CFG duplicate + layout edge (i2v_ddim_prep), timestep embedding, the UNet,
 CFG combine + DDIM update (i2v_ddim_cfg_step; with a DPMSolverMultistepScheduler the DPM-Solver++(2M) update,
 i2v_dpm_cfg_step, which also keeps the previous data prediction on the device; with an LCMScheduler the latent-consistency update,
-i2v_lcm_cfg_step, which re-noises with this step's row of a noise table drawn once per sample).  The whole step is captured ONCE as a hipGraph (through
+i2v_lcm_cfg_step, which re-noises with this step's row of a noise table drawn once per sample; with this package's EulerDiscreteScheduler /
+EulerAncestralDiscreteScheduler the prep scales the model input, i2v_sigma_prep, and the update is i2v_euler_cfg_step, the ancestral
+sampler's noise from such a table too).  The whole step is captured ONCE as a hipGraph (through
 torch.cuda.CUDAGraph on the stream the ctypes launches go to) and replayed for every timestep: the step's
 scalars (t, sqrt(a_t), ...) are read on the device from small tables indexed by a device-side step counter, so
 there is no per-step host<->device traffic and no per-step sync (the reference syncs once per step on
@@ -29,7 +31,8 @@ import torch
 from . import blocks
 from . import kernels as K
 from ._lib import HipLibraryError
-from .blocks import DDIMScheduler, DPMSolverMultistepScheduler, ImageProjection, LCMScheduler, Resampler
+from .blocks import (DDIMScheduler, DPMSolverMultistepScheduler, EulerAncestralDiscreteScheduler, EulerDiscreteScheduler, ImageProjection,
+                     LCMScheduler, Resampler)
 from .image_processor import VaeImageProcessor, tensor2vid
 from .unet_motion_cross_frame_attn import UNetMotionCrossFrameAttnModel
 
@@ -41,8 +44,10 @@ CFG_SHARED = os.environ.get("I2V_CFG_SHARED", "1") != "0"
 f16 = torch.float16
 logger = logging.getLogger(__name__)
 
-# diffusers schedulers the reference's pipeline accepts (pipe:25-32, 83-90) that this build does not: each needs what the
-# captured step has no room for (sigma-scaled inputs and prior, per-step host noise, 3-4 history tensors)
+# diffusers schedulers the reference's pipeline accepts (pipe:25-32, 83-90) that this build refuses by class name.  Only LMS and PNDM are
+# unsupported in principle (each needs 3-4 history tensors the captured step has no room for); the two Euler names are refused for a
+# FOREIGN object of that name (diffusers' own class: its tables are not this build's) -- this package's EulerDiscreteScheduler and
+# EulerAncestralDiscreteScheduler (blocks.py) run, recognised by isinstance before the name check
 UNSUPPORTED_SCHEDULERS = ("EulerDiscreteScheduler", "EulerAncestralDiscreteScheduler", "LMSDiscreteScheduler", "PNDMScheduler")
 
 
@@ -76,7 +81,7 @@ def _draw(fn, shape, generator, device):
 # (`_copy_sample_inputs`, in this order) and `_graph_key` holds the shape and dtype of exactly these, so what is copied in always
 # fits.  Not listed: `x0_prev` (DPM-Solver++) is the step's own history, not a sample input -- the first step of a sample does not
 # read it; `ctx_proj`, `temb_table` and the ControlNet's pair are projected from these into the static buffers (`_project_once`).
-SAMPLE_INPUTS = ("latents", "cond", "t_table", "coef", "ctx_text", "ctx_ip", "noise",      # (noise: this sample's LCM draws)
+SAMPLE_INPUTS = ("latents", "cond", "t_table", "coef", "ctx_text", "ctx_ip", "noise",      # (noise: this sample's LCM / Euler-a draws)
                  "cn_cond", "cn_scale", "t2i_scale",                                       # (this sample's control frames)
                  "v2v_source", "v2v_noise", "v2v_mask", "v2v_coef",                        # (this sample's clip and mask)
                  "t2i_feats")                                                              # (this sample's adapter features)
@@ -571,8 +576,13 @@ class I2VAdapterPipeline:
     # ------------------------------------------------------------------------------------------ one step
     def _scheduler_kind(self):
         """"dpmsolver++" for a DPMSolverMultistepScheduler (the i2v_dpm_cfg_step update), "lcm" for an LCMScheduler (the
-        i2v_lcm_cfg_step update), "ddim" for any other scheduler object (the DDIM update, as before); the reference's other schedulers
-        by class name raise."""
+        i2v_lcm_cfg_step update), "euler" / "euler_ancestral" for this package's EulerDiscreteScheduler / EulerAncestralDiscreteScheduler
+        (i2v_sigma_prep and the i2v_euler_cfg_step update), "ddim" for any other scheduler object (the DDIM update, as before); the
+        reference's other schedulers by class name raise -- a foreign object named like one of the Euler classes too."""
+        if isinstance(self.scheduler, EulerAncestralDiscreteScheduler):
+            return "euler_ancestral"
+        if isinstance(self.scheduler, EulerDiscreteScheduler):
+            return "euler"
         if isinstance(self.scheduler, LCMScheduler):
             return "lcm"
         if isinstance(self.scheduler, DPMSolverMultistepScheduler):
@@ -581,13 +591,19 @@ class I2VAdapterPipeline:
         if name in UNSUPPORTED_SCHEDULERS:
             raise NotImplementedError(f"{name} is not supported by this build: use DDIMScheduler or DPMSolverMultistepScheduler "
                                       "(e.g. DPMSolverMultistepScheduler.from_config(pipe.scheduler.config)), or LCMScheduler with an "
-                                      "LCM-LoRA")
+                                      "LCM-LoRA; Euler and Euler-ancestral sampling run with this package's own EulerDiscreteScheduler / "
+                                      "EulerAncestralDiscreteScheduler (e.g. EulerDiscreteScheduler.from_config(pipe.scheduler.config))")
         return "ddim"
 
     def _step(self, st):
         """One iteration of pipe:666-697 as kernel launches on the current stream (captured into a hipGraph)."""
         unet = self.unet
-        x = K.ddim_prep(st["latents"], st["cond"], unet.packed()["cin_pad"], st["copies"])    # pipe:668-673
+        sigma_space = isinstance(self.scheduler, (EulerDiscreteScheduler, EulerAncestralDiscreteScheduler))
+        if sigma_space:
+            # scale_model_input: the model input is the latents / sqrt(sigma^2 + 1), frame 0 included; the latents keep the bare condition
+            x = K.sigma_prep(st["latents"], st["cond"], st["coef"], st["step_idx"], unet.packed()["cin_pad"], st["copies"])
+        else:
+            x = K.ddim_prep(st["latents"], st["cond"], unet.packed()["cin_pad"], st["copies"])  # pipe:668-673
         # the time-embedding chain of this step's timestep: one row of the table computed once per sample (_time_table)
         temb_proj = K.select_row(st["temb_table"], st["step_idx"])
         control = {}
@@ -606,14 +622,16 @@ class I2VAdapterPipeline:
                              st["num_frames"], cfg_shared=CFG_SHARED and st["copies"] == 2, temb_proj=temb_proj,
                              forward_upsample_size=any(s % (2 ** unet.num_upsamplers) for s in st["latents"].shape[-2:]),
                              **control)                                                          # pipe:676-683, unet:1304-1311
-        if isinstance(self.scheduler, LCMScheduler):
+        if sigma_space:
+            K.euler_cfg_step(st["latents"], st.get("noise"), y, st["coef"], st["step_idx"], st["guidance"], st["copies"])
+        elif isinstance(self.scheduler, LCMScheduler):
             K.lcm_cfg_step(st["latents"], st["noise"], y, st["coef"], st["step_idx"], st["guidance"], st["copies"])
         elif isinstance(self.scheduler, DPMSolverMultistepScheduler):
             K.dpm_cfg_step(st["latents"], st["x0_prev"], y, st["coef"], st["step_idx"], st["guidance"], st["copies"])
         else:
             K.ddim_cfg_step(st["latents"], y, st["coef"], st["step_idx"], st["guidance"], st["copies"])  # pipe:686-691
         if st.get("v2v_mask") is not None:
-            # video-to-video with a mask: the same launch under the three schedulers.  The scheduler step has advanced the counter (and
+            # video-to-video with a mask: the same launch under every scheduler.  The scheduler step has advanced the counter (and
             # wrapped it after the last step), so the launch reads the row of the NEXT timestep -- row 0, the clean source, at the end
             K.masked_renoise(st["latents"], st["v2v_source"], st["v2v_noise"], st["v2v_mask"], st["v2v_coef"], st["step_idx"])
 
@@ -853,15 +871,27 @@ class I2VAdapterPipeline:
 
     def prepare_video_latents(self, video_latents, noise, timestep):
         """the initial latents of video-to-video: scheduler.add_noise(video_latents, noise, timestep) =
-        sqrt(abar_t) * video_latents + sqrt(1 - abar_t) * noise, on a copy of the source (fp32 [B, F, 4, h, w] on the device; K.axpby)"""
+        sqrt(abar_t) * video_latents + sqrt(1 - abar_t) * noise (a sigma-space sampler: video_latents + sigma_t * noise), on a copy of the
+        source (fp32 [B, F, 4, h, w] on the device; K.axpby)"""
         sa, sb = self._noise_level(timestep)
         return K.axpby(video_latents.detach().to(torch.float32).clone(memory_format=torch.contiguous_format),
                        noise.to(torch.float32).contiguous(), sa, sb)
 
     def _noise_level(self, timestep):
-        """(sqrt(abar_t), sqrt(1 - abar_t)) as `add_noise` computes them: in fp32"""
+        """(a, b) of `add_noise` = a x0 + b noise at `timestep`: (sqrt(abar_t), sqrt(1 - abar_t)) as `add_noise` computes them, in fp32; a
+        scheduler with a `noise_level` of its own (the Euler samplers: (1, sigma_t), fractional timesteps) is asked instead"""
+        if hasattr(self.scheduler, "noise_level"):
+            return self.scheduler.noise_level(timestep)
         a = self.scheduler.alphas_cumprod[int(timestep)].to(torch.float32)
         return float(a ** 0.5), float((1 - a) ** 0.5)
+
+    def _prior_level(self, timestep):
+        """(a, b) the prior and FreeInit's mix noise to: (abar_t^0.5, (1 - abar_t)^0.5) from abar_t as a Python float, as these two
+        always computed it; a scheduler with a `noise_level` of its own is asked instead"""
+        if hasattr(self.scheduler, "noise_level"):
+            return self.scheduler.noise_level(timestep)
+        a_t = float(self.scheduler.alphas_cumprod[int(timestep)])
+        return a_t ** 0.5, (1.0 - a_t) ** 0.5
 
     def renoise_table(self, timesteps):
         """fp32 [len(timesteps), 2]: the coefficient table of `K.masked_renoise`.  The scheduler-step kernels have already advanced the
@@ -1383,9 +1413,8 @@ class I2VAdapterPipeline:
         if has_clip:
             latents = self.prepare_video_latents(source, noise, timesteps[0])
         else:
-            a_t = float(self.scheduler.alphas_cumprod[int(timesteps[0])])
-            latents = K.first_frame_prior(cond_dev, mask_u.contiguous(), noise, blur_sigma, blurred_strength, a_t ** 0.5,
-                                          (1.0 - a_t) ** 0.5)
+            latents = K.first_frame_prior(cond_dev, mask_u.contiguous(), noise, blur_sigma, blurred_strength,
+                                          *self._prior_level(timesteps[0]))
         return latents, cond_dev, noise, source, timesteps
 
     def _schedule_tables(self, st, timesteps, eta):
@@ -1448,7 +1477,7 @@ class I2VAdapterPipeline:
         if kind == "dpmsolver++":
             # the previous step's data prediction: the first step of a sample is first order and does not read it
             st["x0_prev"] = torch.empty_like(latents)
-        if kind == "lcm":
+        if kind in ("lcm", "euler_ancestral"):
             # every step's fresh noise (diffusers draws it inside `step`, from `generator`, after prepare_latents' draw): one table per
             # sample, drawn after the prior's draws, read on the device by the step counter -- the steps stay captured
             st["noise"] = self.scheduler.step_noise(timesteps, tuple(latents.shape), generator, dev)
@@ -1461,7 +1490,7 @@ class I2VAdapterPipeline:
         straight into the graph's static buffers).  DPM-Solver++ has no stochastic form here (the reference passes `eta` only to a
         scheduler whose step takes it, pipe:184-199), and LCM's step takes no eta either, its noise is in the table: with both `eta`
         is ignored and the steps stay captured.  Returns the final latents."""
-        fixed = self._scheduler_kind() in ("dpmsolver++", "lcm")
+        fixed = self._scheduler_kind() in ("dpmsolver++", "lcm", "euler", "euler_ancestral")
         for rnd in range(len(round_steps)):
             if rnd > 0:
                 timesteps = self._free_init_round(st, rnd, round_steps, init_noise, generator, ratio, eta)
@@ -1501,9 +1530,8 @@ class I2VAdapterPipeline:
             self._schedule_tables(st, timesteps, eta)
         b, f, c, h, w = prev.shape
         lpf = free_init_filter((f, h, w), fi["method"], fi["order"], fi["spatial_stop_frequency"], fi["temporal_stop_frequency"], device=dev)
-        a_t = float(self.scheduler.alphas_cumprod[int(timesteps[0])])
-        st["latents"] = K.freeinit_mix(prev.contiguous(), init_noise.contiguous(), z_rand, lpf, a_t ** 0.5, (1.0 - a_t) ** 0.5)
-        if self._scheduler_kind() == "lcm":
+        st["latents"] = K.freeinit_mix(prev.contiguous(), init_noise.contiguous(), z_rand, lpf, *self._prior_level(timesteps[0]))
+        if self._scheduler_kind() in ("lcm", "euler_ancestral"):
             st["noise"] = self.scheduler.step_noise(timesteps, tuple(prev.shape), generator, dev)
         st["step_idx"] = torch.zeros(1, dtype=torch.int32, device=dev)
         return timesteps
@@ -1534,13 +1562,16 @@ class I2VAdapterPipeline:
 
 SCHEDULERS = ("ddim", "dpmsolver++")
 STOCHASTIC_SCHEDULERS = ("lcm",)       # samplers whose step draws noise (from a device table: still one captured step)
+SIGMA_SCHEDULERS = ("euler_discrete", "euler_ancestral")    # samplers in sigma space: Euler, and Euler-ancestral (noise from a table too)
 
 
-def load_scheduler(model_path, kind="ddim"):
+def load_scheduler(model_path, kind="ddim", karras_sigmas=False):
     """the evaluation driver's scheduler (`--scheduler`) from `<model_path>/scheduler/scheduler_config.json`: "ddim" as the
     reference builds it (pipe:755-757), "dpmsolver++" the same config as a DPMSolverMultistepScheduler (DPM-Solver++(2M),
     linspace spacing, steps_offset=1), "lcm" the same config as an LCMScheduler (the checkpoint's betas, diffusers' LCM defaults for the
-    rest: for a UNet with an LCM-LoRA or AnimateLCM merged in)."""
+    rest: for a UNet with an LCM-LoRA or AnimateLCM merged in), "euler_discrete" / "euler_ancestral" the same config as an
+    EulerDiscreteScheduler (`karras_sigmas`: with Karras et al.'s noise levels) / EulerAncestralDiscreteScheduler, linspace spacing and
+    steps_offset=1 as the DDIM line has."""
     if kind == "ddim":
         return DDIMScheduler.from_pretrained(model_path, subfolder="scheduler", clip_sample=False,
                                              timestep_spacing="linspace", steps_offset=1)          # pipe:755-757
@@ -1550,7 +1581,13 @@ def load_scheduler(model_path, kind="ddim"):
     if kind == "lcm":
         return LCMScheduler.from_pretrained(model_path, subfolder="scheduler", timestep_spacing="leading", steps_offset=0,
                                             set_alpha_to_one=True, clip_sample=False)
-    raise ValueError(f"unknown scheduler {kind!r}: one of {', '.join(SCHEDULERS + STOCHASTIC_SCHEDULERS)}")
+    if kind == "euler_discrete":
+        return EulerDiscreteScheduler.from_pretrained(model_path, subfolder="scheduler", timestep_spacing="linspace", steps_offset=1,
+                                                      use_karras_sigmas=bool(karras_sigmas))
+    if kind == "euler_ancestral":
+        return EulerAncestralDiscreteScheduler.from_pretrained(model_path, subfolder="scheduler", timestep_spacing="linspace",
+                                                               steps_offset=1)
+    raise ValueError(f"unknown scheduler {kind!r}: one of {', '.join(SCHEDULERS + STOCHASTIC_SCHEDULERS + SIGMA_SCHEDULERS)}")
 
 
 def load_text_encoder(model_path):
@@ -1613,6 +1650,11 @@ def build_parser():
     parser.add_argument("--scheduler", choices=SCHEDULERS + STOCHASTIC_SCHEDULERS, default="ddim",
                         help="ddim (the reference's), dpmsolver++ (DPM-Solver++(2M): 15-20 steps instead of 25-50) or lcm (latent-consistency "
                              "sampling for a UNet with an LCM-LoRA / AnimateLCM merged in (--lora): 4-8 steps, --guidance_scale 1-2)")
+    parser.add_argument("--sampler", choices=SIGMA_SCHEDULERS, default=None,
+                        help="a sampler in sigma space in place of --scheduler: euler_discrete (\"Euler\") or euler_ancestral (\"Euler a\": "
+                             "fresh noise every step, from --seed).  (An option of its own: the choices of --scheduler are fixed.)")
+    parser.add_argument("--karras_sigmas", action="store_true",
+                        help="with --sampler euler_discrete: Karras et al.'s noise levels (use_karras_sigmas=True)")
     parser.add_argument("--guidance_scale", type=float, default=7.5, help="classifier-free guidance scale (pipe:794); <= 1 runs one copy")
     parser.add_argument("--freeu", type=float, nargs=4, default=None, metavar=("S1", "S2", "B1", "B2"),
                         help="enable FreeU with these scales (SD-1.5: 0.9 0.2 1.2 1.4); off by default, as in the reference driver")
@@ -1750,6 +1792,9 @@ def main(argv=None):
     if args.prompt_weighting is not None and args.prompt_weighting < 1:
         logger.error(f"--prompt_weighting {args.prompt_weighting}: the number of chunks is at least 1.")
         return -1
+    if args.karras_sigmas and args.sampler != "euler_discrete":
+        logger.error("--karras_sigmas goes with --sampler euler_discrete.")
+        return -1
     if args.video_column is None and (args.strength is not None or args.mask_column is not None):
         logger.error("--strength and --mask_column need a source clip: --video_column.")
         return -1
@@ -1775,7 +1820,7 @@ def main(argv=None):
         logger.info(f"Successfully loaded AutoencoderTiny from {args.vae_tiny}.")
     else:
         vae = AutoencoderKL.from_pretrained(os.path.join(args.model_path, "vae"))                # pipe:754
-    scheduler = load_scheduler(args.model_path, args.scheduler)                                 # pipe:755-757
+    scheduler = load_scheduler(args.model_path, args.sampler or args.scheduler, karras_sigmas=args.karras_sigmas)   # pipe:755-757
 
     eval_data_dir = os.path.dirname(args.eval_data_path)                                         # pipe:759-768
     eval_data_df = pd.read_csv(args.eval_data_path)

@@ -142,6 +142,7 @@ _WRAPPED = {
     "nchw_to_tokens": _work_misc("elementwise"), "tokens_to_nchw": _work_misc("elementwise"),
     "lcm_cfg_step": _work_misc("elementwise"), "freenoise_gather": _work_misc("elementwise"),
     "freenoise_blend": _work_misc("elementwise"),
+    "sigma_prep": _work_misc("elementwise"), "euler_cfg_step": _work_misc("elementwise"),
     # the CLIP text tower's own kernels (once per prompt, not per step): one class, so that a profile of `pipe(prompt=...)` shows what
     # the prompt cost beside the step's classes; its GEMMs and LayerNorms are counted with theirs
     "clip_embed": _work_misc("clip_text"), "clip_attention": _work_clip_attn, "quick_gelu": _work_misc("clip_text"),

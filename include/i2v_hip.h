@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define I2V_ABI_VERSION 28
+#define I2V_ABI_VERSION 29
 
 #define I2V_OK 0
 #define I2V_ERR_INVALID_ARG (-1)
@@ -600,6 +600,27 @@ int i2v_dpm_cfg_step(float* latents, float* x0_prev, const void* noise_pred, int
 int i2v_lcm_cfg_step(float* latents, const float* noise, int32_t n_noise, const void* noise_pred, int32_t np_is_f32, int64_t ld_np,
                      const float* coef, int32_t n_steps, int32_t* step_index, float guidance_scale, int32_t b, int32_t f, int32_t c,
                      int32_t hw, int32_t cfg_copies, i2v_stream_t stream);
+
+/* (ABI 29) The sigma-space form of both halves of the step, for EulerDiscreteScheduler and EulerAncestralDiscreteScheduler (diffusers
+ * 0.24, epsilon prediction).  One coefficient table serves both launches:
+ *   coef fp32 [n_steps][4] = {sigma, 1 / sqrt(sigma^2 + 1), sigma_to, sigma_up}
+ * with sigma_to = sigma_next, sigma_up = 0 for Euler and sigma_to = sigma_down = sqrt(sigma_next^2 - sigma_up^2),
+ * sigma_up = sqrt(sigma_next^2 (sigma^2 - sigma_next^2) / sigma^2) for the ancestral sampler (its last row: both 0).
+ *   prep : i2v_ddim_prep with scale_model_input: latents[:, 0] = cond, UNSCALED (pipe:669); model_in = fp16(v * coef[step][1]), frame 0
+ *          included (the reference scales after the overwrite, pipe:669-673).  step = clamp(*step_index, 0, n_steps - 1); the counter
+ *          is read, not advanced.  ld_coef >= 2: the row stride of `coef` in floats (4 for the table above).
+ *   step : the same CFG combine and the same layouts as i2v_lcm_cfg_step, then in fp32
+ *            x' = x + eps (sigma_to - sigma) + sigma_up z,  z = noise[min(step, n_noise - 1)]
+ *          and *step_index advances / wraps as in the DDIM step.  noise fp32 [n_noise][b, f, c, hw], one row per step, n_noise >=
+ *          n_steps; a row with sigma_up == 0 does not read it.  noise may be NULL when no row has sigma_up != 0 (Euler): the table is
+ *          device memory, so that is the caller's to guarantee -- with NULL every row runs as if sigma_up were 0.  16-byte accesses when
+ *          hw % 4 == 0 and latents and noise are 16-byte aligned, scalar ones otherwise. */
+int i2v_sigma_prep(float* latents, const float* cond, void* model_in, const float* coef, int32_t ld_coef, int32_t n_steps,
+                   const int32_t* step_index, int32_t b, int32_t f, int32_t c, int32_t hw, int32_t c_pad, int32_t cfg_copies,
+                   i2v_stream_t stream);
+int i2v_euler_cfg_step(float* latents, const float* noise, int32_t n_noise, const void* noise_pred, int32_t np_is_f32, int64_t ld_np,
+                       const float* coef, int32_t n_steps, int32_t* step_index, float guidance_scale, int32_t b, int32_t f, int32_t c,
+                       int32_t hw, int32_t cfg_copies, i2v_stream_t stream);
 
 /* (ABI 11) FreeU (pipe:155-181 enable_freeu; unet:453-478, 1213-1227: diffusers 0.24 apply_freeu / fourier_filter with threshold 1) on the
  * two operands of an up block's skip concatenation, before `cat([hidden, skip], 1)` (unet:478); one launch, new tensors out (neither

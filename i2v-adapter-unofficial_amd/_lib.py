@@ -10,7 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # I2V_LIB_PATH selects another build of the same ABI (same-box A/B of two kernels, tools/ab_bench.sh); the in-tree
 # library is never overwritten by tooling
 LIB_PATH = os.environ.get("I2V_LIB_PATH") or os.path.join(_HERE, "libi2v_hip.so")
-ABI_VERSION = 29
+ABI_VERSION = 30
 
 I2V_EPI_NONE, I2V_EPI_GELU, I2V_EPI_GEGLU = 0, 1, 2
 I2V_STORE_ROWMAJOR, I2V_STORE_ROWPERM, I2V_STORE_VT, I2V_STORE_VT_T = 0, 1, 2, 3
@@ -373,6 +373,8 @@ SIGNATURES = {
     "i2v_add_broadcast_residual_f16": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, C.c_int64, _P, C.c_int32, _P, _P]),
     "i2v_interp_rows_f16": (C.c_int, [_P, C.c_int64, C.c_int32, _P, _P, _P, _P, C.c_int64, C.c_int32, C.c_int32, _P]),
     "i2v_masked_renoise_f32": (C.c_int, [_P, _P, _P, _P, _P, C.c_int32, _P, C.c_int64, C.c_int32, C.c_int32, _P]),
+    "i2v_resize_renoise_f32": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_float, C.c_float, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
+                                         C.c_int32, _P]),
     "i2v_weight_embeds_f16": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int32, _P]),
     # the model handle: configuration, weight registry, plan, one captured step
     "i2v_unet_create": (C.c_int, [C.POINTER(UnetConfig), C.POINTER(_P)]),

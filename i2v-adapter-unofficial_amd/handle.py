@@ -373,6 +373,14 @@ def _refuse_sigma_scheduler(pipe, what):
                                   "DPMSolverMultistepScheduler or LCMScheduler to export")
 
 
+def _refuse_hires_fix(pipe, what):
+    """the hires fix (`pipe.enable_hires_fix`) samples at two sizes with a latent upscale (i2v_resize_renoise_f32) between them: a plan
+    holds one size and has no entry id for the upscale"""
+    if getattr(pipe, "hires_fix_enabled", False):
+        raise NotImplementedError(f"{what}: the hires fix (two passes at two sizes with i2v_resize_renoise_f32 between them) is not "
+                                  "implemented for the C handle (a plan holds one size); disable_hires_fix() to export")
+
+
 def _step_problem(st):
     b, f, _c, hh, ww = st["latents"].shape
     return (st["copies"] * b, f, hh, ww, st["ctx_text"].shape[1], int(st["ctx_ip"] is not None))
@@ -389,6 +397,7 @@ def record_step_plan(pipe, st):
     With an LCMScheduler the step ends in i2v_lcm_cfg_step: STEP_COEF is fp32 [T, 6] and STEP_NOISE (the same slot) fp32
     [T - 1, B, F, C, H, W] (= st["noise"], read only: `LCMScheduler.step_noise`; absent for a single-step schedule)."""
     _refuse_controlnet(pipe, "record_step_plan")
+    _refuse_hires_fix(pipe, "record_step_plan")
     _refuse_per_frame_context(st, "record_step_plan")
     _refuse_mask(st, "record_step_plan")
     _refuse_sigma_scheduler(pipe, "record_step_plan")
@@ -430,6 +439,7 @@ def record_prepare_plan(pipe, st, image_embeds=None):
     time_emb_proj of every timestep of the schedule (unet:1336-1343) written into `temb_table` -- as a launch plan.
     io: PREP_CONTEXT fp16 [2 B, L, D] (= st["ctx_text"]), PREP_TIMESTEPS fp32 [T] (= st["t_table"]), PREP_IMAGE_EMBEDS fp16 [2 B, clip]."""
     _refuse_controlnet(pipe, "record_prepare_plan")
+    _refuse_hires_fix(pipe, "record_prepare_plan")
     _refuse_per_frame_context(st, "record_prepare_plan")
     _refuse_mask(st, "record_prepare_plan")
     unet = pipe.unet
@@ -584,6 +594,7 @@ def export_denoiser(pipe, out_dir, *, num_frames, latent_height, latent_width, b
     without).  Returns the manifest.  A plan holds for this size, these switches and this library build.
     per_frame_context (prompt travel: one text context per frame) is refused: the plans hold one context per sample."""
     _refuse_controlnet(pipe, "export_denoiser")
+    _refuse_hires_fix(pipe, "export_denoiser")
     _refuse_sigma_scheduler(pipe, "export_denoiser")
     if per_frame_context:
         raise NotImplementedError("export_denoiser: per-frame text contexts (prompt travel) are not implemented for the C handle (its "

@@ -1784,6 +1784,41 @@ def masked_renoise(latents, source, noise, mask, coef, step_index):
     return latents
 
 
+# ---------------------------------------------------------------------------------------------- hires fix: latent upscale + re-noise
+def resize_renoise(src, tables, noise=None, a=1.0, b=0.0):
+    """out[..., Y, X] = a * sum_ky sum_kx wy[Y, ky] wx[X, kx] src[..., iy[Y, ky], ix[X, kx]] + b * noise[..., Y, X]
+    (i2v_resize_renoise_f32): the hires fix's latent upscale with the second pass's re-noise fused in.  src fp32 [..., h, w] contiguous
+    (at least 2-D; the leading axes are planes); tables = (iy, wy, ix, wx) from `hires_fix.device_tables`: int32 / fp32 [H, 4] and
+    [W, 4] on src's device, H >= h and W >= w (upscaling only); noise None (then `b` is ignored) or fp32 [..., H, W] contiguous.  Returns
+    a new fp32 [..., H, W].  All fp32, a fixed-order 16-term sum, then a * r (+ b * noise): the operations of `axpby`, so the fused call
+    gives the bits of resize_renoise(src, tables) followed by axpby(out, noise, a, b)."""
+    lib = _lib.load()
+    iy, wy, ix, wx = tables
+    _req(src, "src", dtype=torch.float32)
+    for t, name, dt in ((iy, "iy", torch.int32), (wy, "wy", torch.float32), (ix, "ix", torch.int32), (wx, "wx", torch.float32)):
+        _req(t, name, dtype=dt)
+        if t.dim() != 2 or t.shape[1] != 4 or not t.is_contiguous() or t.device != src.device:
+            raise ValueError(f"resize_renoise: {name} must be a contiguous [n_out, 4] table on src's device, got {tuple(t.shape)}")
+    if src.dim() < 2 or src.numel() < 1 or not src.is_contiguous():
+        raise ValueError(f"resize_renoise: src must be a non-empty contiguous [..., h, w], got {tuple(src.shape)}")
+    if iy.shape != wy.shape or ix.shape != wx.shape:
+        raise ValueError("resize_renoise: the index and weight tables of an axis must have the same shape")
+    h, w = src.shape[-2:]
+    height, width = iy.shape[0], ix.shape[0]
+    if height < h or width < w:
+        raise ValueError(f"resize_renoise: {h} x {w} -> {height} x {width} is a downscale: upscaling only")
+    shape = tuple(src.shape[:-2]) + (height, width)
+    if noise is not None:
+        _req(noise, "noise", dtype=torch.float32)
+        if tuple(noise.shape) != shape or not noise.is_contiguous() or noise.device != src.device:
+            raise ValueError(f"resize_renoise: noise must be a contiguous {shape} on src's device, got {tuple(noise.shape)}")
+    out = torch.empty(shape, dtype=torch.float32, device=src.device)
+    planes = src.numel() // (h * w)
+    _lib.check(lib.i2v_resize_renoise_f32(_p(src), _p(out), _p(noise) if noise is not None else None, _p(iy), _p(wy), _p(ix), _p(wx),
+                                          float(a), float(b), planes, h, w, height, width, _stream()), "i2v_resize_renoise_f32")
+    return out
+
+
 _freeinit_ws = {}
 
 

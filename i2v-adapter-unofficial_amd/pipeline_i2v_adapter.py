@@ -106,6 +106,9 @@ def _sample_input_shapes(st):
     return tuple(shp(st.get(name)) for name in SAMPLE_INPUTS)
 
 
+_UNSET = object()      # an argument that was not passed, where None is a value of its own (`enable_hires_fix(scale=...)`)
+
+
 @contextlib.contextmanager
 def _set_for_call(setter, value):
     """`setter(value)` now and `setter(previous)` on the way out, exceptions included; `setter` returns the value it replaces"""
@@ -196,6 +199,7 @@ class I2VAdapterPipeline:
         self._graph = None
         self._graph_cache = {}
         self._free_init = None
+        self._hires_fix = None
         self._prompt_weighting = None
         self._textual_inversions = []
 
@@ -404,6 +408,57 @@ class I2VAdapterPipeline:
     @property
     def free_init_enabled(self):
         return self._free_init is not None
+
+    def enable_hires_fix(self, scale=_UNSET, size=None, strength: float = 0.6, num_inference_steps: Optional[int] = None,
+                         upscaler: str = "bicubic-antialiased"):
+        """The two-pass "hires fix" of the AnimateDiff / A1111 / ComfyUI front ends: every call samples at its `height` x
+        `width` as before -- the size the motion modules were trained at --, then upscales the latents, re-noises them to `strength`
+        of the schedule and refines them at the target size: `size` = (height, width), or 8 * round(side * `scale` / 8) per side
+        (`scale` 1.5 when neither is passed; passing both, or None for both, is refused).  The second pass is what a call with
+        `video_latents=upscale_latents(first pass), strength=strength, num_inference_steps=num_inference_steps or the call's,
+        height, width = the target` would do, with the same contexts, scheduler, guidance, control arguments and generator objects,
+        which go on from where the first pass left them: a `condition_image` is encoded again at the target size, condition latents
+        that were passed in are upscaled, control frames and the mask are prepared again.  Its initial latents are ONE launch of
+        `i2v_resize_renoise_f32` (upscale and add_noise fused).  `upscaler`: A1111's latent upscalers -- "nearest", "nearest-exact",
+        "bilinear", "bicubic", "bilinear-antialiased", "bicubic-antialiased" (torch.nn.functional.interpolate's modes); pixel-space
+        upscalers and ESRGAN-class networks are not implemented, and neither is downscaling.  The two sizes are two captured steps:
+        while the fix is enabled the graph cache keeps two (both workspaces stay allocated).  FreeInit's rounds belong to the first
+        pass.  The defaults are the front ends' usual ones and are unmeasured for quality here."""
+        from .hires_fix import DEFAULT_SCALE, check_hires_fix_args
+        if scale is _UNSET:
+            scale = DEFAULT_SCALE if size is None else None
+        self._hires_fix = check_hires_fix_args(scale, size, strength, num_inference_steps, upscaler)
+
+    def disable_hires_fix(self):
+        """one pass per call again: every path is what it was before `enable_hires_fix`"""
+        self._hires_fix = None
+
+    @property
+    def hires_fix_enabled(self):
+        return self._hires_fix is not None
+
+    def upscale_latents(self, latents, height, width, upscaler=None):
+        """latents fp32 [B, F, C, h, w] -> fp32 [B, F, C, height / 8, width / 8] on the UNet's device: the hires fix's latent upscale
+        (`K.resize_renoise` with a = 1 and no noise).  `upscaler`: one of `hires_fix.UPSCALERS`; None takes the enabled fix's, or
+        "bicubic-antialiased".  Upscaling only."""
+        from .hires_fix import UPSCALERS, device_tables
+        if upscaler is None:
+            upscaler = self._hires_fix.upscaler if self._hires_fix is not None else "bicubic-antialiased"
+        if upscaler not in UPSCALERS:
+            raise ValueError(f"unknown upscaler {upscaler!r}: one of {', '.join(UPSCALERS)}")
+        if not isinstance(latents, torch.Tensor) or latents.dim() != 5:
+            raise ValueError("`latents` must be a [B, F, C, h, w] tensor, got "
+                             f"{tuple(latents.shape) if isinstance(latents, torch.Tensor) else type(latents)}")
+        if height % self.vae_scale_factor or width % self.vae_scale_factor:
+            raise ValueError(f"`height` and `width` have to be divisible by {self.vae_scale_factor} but are {height} and {width}.")
+        h, w = latents.shape[-2:]
+        h2, w2 = height // self.vae_scale_factor, width // self.vae_scale_factor
+        if h2 < h or w2 < w:
+            raise ValueError(f"upscale_latents: {h} x {w} -> {h2} x {w2} latents is a downscale, which is not supported")
+        if self.unet.device.type != "cuda":
+            raise HipLibraryError(f"unet is on {self.unet.device}: the HIP path has no CPU fallback")
+        src = latents.detach().to(self.unet.device, torch.float32).contiguous()
+        return K.resize_renoise(src, device_tables(h, w, h2, w2, upscaler, src.device))
 
     def enable_free_noise(self, context_length: int = 16, context_stride: int = 4, weighting_scheme: str = "pyramid",
                           noise_type: str = "shuffle_context"):
@@ -679,12 +734,16 @@ class I2VAdapterPipeline:
         hit = cache.get(key)
         if hit is not None:
             graph, gst = hit
+            cache[key] = cache.pop(key)     # (most recently used last)
             _copy_sample_inputs(gst, st)
             self._project_once(gst, into=True)
         else:
             # one shape at a time (a graph pins its workspace): the old graph and its pool go before the new capture,
-            # so two pools never coexist at the peak
-            cache.clear()
+            # so two pools never coexist at the peak.  While the hires fix is enabled, two: its passes have one size each, and the
+            # most recently used graph stays beside the new one
+            keep = 1 if self._hires_fix is not None else 0
+            for old in list(cache)[:max(len(cache) - keep, 0)]:
+                del cache[old]
             self._graph = None
             self._project_once(st)
             # warm-up outside capture: packs weights, sizes the allocator; then restore the state it advanced
@@ -1179,6 +1238,10 @@ class I2VAdapterPipeline:
                 (adapter_image, num_frames, adapter_conditioning_scale, adapter_conditioning_factor),
                 video, video_latents, strength, mask_image)
             output_type, use_graph = self._resolve_call_defaults(output_type, callback, use_graph)
+            # the hires fix's target size and step count (None while it is disabled): its refusals come before anything is encoded
+            hires = self._hires_target(height, width, condition_image, condition_image_latents, video, video_latents,
+                                       num_inference_steps)
+            given_condition_latents = condition_image_latents
             do_cfg = guidance_scale > 1.0
             self.unet._sync_lora()      # before anything reads a weight, a pack or the weights' versions (_graph_key)
             prompt_embeds, negative_prompt_embeds, image_embeds, negative_image_embeds = self._encode_contexts(
@@ -1204,6 +1267,14 @@ class I2VAdapterPipeline:
                 (float(adapter_conditioning_scale), float(adapter_conditioning_factor)), mask_image, source, noise, generator)
             latents = self._run_rounds(st, timesteps, round_steps, noise, use_graph, callback, callback_steps, eta, generator,
                                        frame_similarity_sample_ratio)
+            if hires is not None:
+                first = frame_similarity_sample_ratio if video_latents is None else strength
+                steps_run = sum(min(int(n * first), n) for n in round_steps)
+                latents = self._hires_pass(
+                    hires, latents, steps_run, condition_image if given_condition_latents is None else None, condition_image_latents,
+                    batch_size, num_frames, frame_similarity_blurred_strength, generator, prior_mask_generator, prior_noise_generator,
+                    blur_sigma, eta, prompt_embeds, image_embeds, per_frame, 2 if do_cfg else 1, guidance_scale, control_image,
+                    st.get("cn_args"), adapter_image, st.get("t2i_args"), mask_image, use_graph, callback, callback_steps)
             return self._output(latents, output_type, return_dict)
 
     # the phases of a call, in the order `__call__` runs them
@@ -1371,17 +1442,20 @@ class I2VAdapterPipeline:
         return [num_inference_steps] * rounds
 
     def _initial_latents(self, condition_image_latents, video_latents, batch_size, num_frames, height, width, num_steps, strength,
-                         blurred_strength, generator, latents, prior_mask_generator, prior_noise_generator, blur_sigma):
+                         blurred_strength, generator, latents, prior_mask_generator, prior_noise_generator, blur_sigma, lowres=None):
         """Phase 4, the first round's schedule and the latents it starts from.  `strength`: the fraction of the `num_steps` schedule
         that runs (the similarity ratio without a source clip).  The draws, in this order: `prepare_latents` (`generator`), the blur
         sigma and the prior's mask (`prior_mask_generator`; neither with a source clip), the noise (`prior_noise_generator`;
         rescheduled by FreeNoise behind its first window).  Without a source clip the first-frame-similarity prior + add_noise
         (pipe:647-656) in ONE HIP kernel -- the reference overwrites the latents drawn above (its `latents = self.scheduler.
         add_noise(...)`, pipe:656), and so does this; its random draws take explicit generators (the reference uses the unseeded
-        global RNG) --, with one the source noised to the first timestep's level.  Returns (latents, cond, noise, source, timesteps):
+        global RNG) --, with one the source noised to the first timestep's level.  `lowres` (the hires fix's second pass, with
+        `video_latents` None): (clip, tables, keep) -- the source is `K.resize_renoise(clip, tables)`, materialised only when `keep`
+        (a mask's blend reads it), and the latents are ONE fused launch of the same kernel with the noise and the first timestep's
+        level, the bits of the upscale followed by `prepare_video_latents`.  Returns (latents, cond, noise, source, timesteps):
         fp32 on the UNet's device, `source` None without a clip."""
         dev = self.unet.device
-        has_clip = video_latents is not None
+        has_clip = video_latents is not None or lowres is not None
         self.scheduler.set_timesteps(num_steps)                                                 # pipe:630-631
         timesteps, _ = self.get_timesteps(num_steps, strength)
         cond_dev = condition_image_latents.detach().to(dev, torch.float32).contiguous()
@@ -1392,7 +1466,12 @@ class I2VAdapterPipeline:
                                          else prior_mask_generator)
         shape = (batch_size, num_frames) + tuple(cond_dev.shape[1:])
         source = None
-        if has_clip:
+        if lowres is not None:
+            clip, tables, keep = lowres
+            if tuple(clip.shape[:3]) != shape[:3] or (tables[0].shape[0], tables[2].shape[0]) != shape[3:]:
+                raise ValueError(f"the first pass's latents are {tuple(clip.shape)}, the second pass's are {shape}")
+            source = K.resize_renoise(clip, tables) if keep else None
+        elif has_clip:
             source = video_latents.detach().to(dev, torch.float32)
             if source.shape[0] == 1 and batch_size > 1:
                 source = source.expand(batch_size, -1, -1, -1, -1)
@@ -1410,7 +1489,9 @@ class I2VAdapterPipeline:
         else:
             noise = _draw(torch.randn, shape, prior_noise_generator, dev)                       # pipe:655
         noise = noise.contiguous()
-        if has_clip:
+        if lowres is not None:
+            latents = K.resize_renoise(lowres[0], lowres[1], noise.to(torch.float32), *self._noise_level(timesteps[0]))
+        elif has_clip:
             latents = self.prepare_video_latents(source, noise, timesteps[0])
         else:
             latents = K.first_frame_prior(cond_dev, mask_u.contiguous(), noise, blur_sigma, blurred_strength,
@@ -1510,6 +1591,75 @@ class I2VAdapterPipeline:
         if not return_dict:
             return (video,)
         return I2VAdapterPipelineOutput(frames=video)
+
+    def _hires_target(self, height, width, condition_image, condition_image_latents, video, video_latents, num_inference_steps):
+        """the hires fix of this call, checked on the host before anything is encoded: None while it is disabled, else (height, width,
+        steps) of the second pass.  The first pass's size is found as phase 3 finds it (the arguments, the UNet's sample size or the
+        latents that were passed in); what phase 3 itself refuses is left to it."""
+        hf = self._hires_fix
+        if hf is None:
+            return None
+        from .hires_fix import second_pass_steps, target_size
+        if (condition_image is not None and condition_image_latents is None) or video is not None:
+            height = height or self.unet.config.sample_size * self.vae_scale_factor
+            width = width or self.unet.config.sample_size * self.vae_scale_factor
+        else:
+            lat = condition_image_latents if condition_image_latents is not None else video_latents
+            if lat is None:
+                return None
+            height = height or lat.shape[-2] * self.vae_scale_factor
+            width = width or lat.shape[-1] * self.vae_scale_factor
+        steps = hf.num_inference_steps or num_inference_steps
+        second_pass_steps(steps, hf.strength)
+        return target_size(height, width, hf) + (steps,)
+
+    def _hires_pass(self, hires, first, steps_run, condition_image, condition_image_latents, batch_size, num_frames, blurred_strength,
+                    generator, prior_mask_generator, prior_noise_generator, blur_sigma, eta, prompt_embeds, image_embeds, per_frame,
+                    copies, guidance_scale, control_image, cn_args, adapter_image, t2i_args, mask_image, use_graph, callback,
+                    callback_steps):
+        """The hires fix's second pass (enable_hires_fix), after the first pass's rounds: what a call with
+        `video_latents=upscale_latents(first)`, `strength`, the target size and the condition at that size would do -- phases 4 to 6
+        again, the same draws in the same order from the same generator objects, one plain round whatever FreeInit is set to.  In the
+        order of the draws: a `condition_image` is encoded again at the target size (condition latents that were passed in, or that
+        came from a source clip's first frame, are upscaled), then `_initial_latents`' draws, then `_assemble_state`'s -- where the
+        control frames, the adapter's features and the mask are prepared again at the target size; with a mask the source the blend
+        keeps is the upscaled first pass.  The contexts are the first pass's.  `callback` goes on counting after the `steps_run`
+        steps of the first pass.  Returns the final latents."""
+        from .hires_fix import device_tables
+        height, width, steps = hires
+        hf, dev, vsf = self._hires_fix, self.unet.device, self.vae_scale_factor
+        if condition_image is not None:
+            cond = self.encode_condition_image(condition_image, height, width, generator)
+        else:
+            cond = self.upscale_latents(condition_image_latents[:, None], height, width, hf.upscaler)[:, 0]
+        clip = first.detach().to(dev, torch.float32).contiguous()
+        tables = device_tables(clip.shape[-2], clip.shape[-1], height // vsf, width // vsf, hf.upscaler, dev)
+        latents, cond, noise, source, timesteps = self._initial_latents(
+            cond, None, batch_size, num_frames, height, width, steps, hf.strength, blurred_strength, generator, None,
+            prior_mask_generator, prior_noise_generator, blur_sigma, lowres=(clip, tables, mask_image is not None))
+        control_image, adapter_image = (self._frames_at(t, height, width) for t in (control_image, adapter_image))
+        st = self._assemble_state(latents, cond, timesteps, eta, prompt_embeds, image_embeds, per_frame, copies, num_frames,
+                                  guidance_scale, batch_size, height, width, control_image, cn_args, adapter_image, t2i_args,
+                                  mask_image, source, noise, generator)
+        if callback is not None:
+            user_callback = callback
+            callback = lambda i, t, x: user_callback(steps_run + i, t, x)
+        fixed = self._scheduler_kind() in ("dpmsolver++", "lcm", "euler", "euler_ancestral")
+        self._sample_round(st, timesteps, use_graph, callback, callback_steps, eta, fixed, generator)
+        latents = st["latents"]
+        latents[:, 0] = st["cond"]
+        return latents
+
+    @staticmethod
+    def _frames_at(frames, height, width):
+        """control / adapter frames for the second pass: PIL images are resized where they are prepared; a tensor, which has to have
+        the call's size already, is resized here on the host (bilinear, as preprocessing) -- None and lists pass through"""
+        if not isinstance(frames, torch.Tensor) or tuple(frames.shape[-2:]) == (height, width):
+            return frames
+        import torch.nn.functional as F
+        t = frames.detach().float().cpu()
+        flat = F.interpolate(t.reshape(-1, *t.shape[-3:]), size=(height, width), mode="bilinear", align_corners=False)
+        return flat.reshape(*t.shape[:-2], height, width)
 
     def _free_init_round(self, st, rnd, round_steps, init_noise, generator, ratio, eta):
         """FreeInit between round rnd - 1 and round rnd >= 1 (diffusers `_apply_free_init`), in the order of the draws: the fresh noise
@@ -1714,6 +1864,20 @@ def build_parser():
     parser.add_argument("--mask_column", type=str, default=None, metavar="COL",
                         help="with --video_column: the CSV column that holds, per row, the mask -- one image for all frames, or a "
                              "directory / animated GIF of num_frames masks; white is regenerated, black keeps the source")
+    parser.add_argument("--hires_scale", type=float, default=None, metavar="S",
+                        help="hires fix (pipe.enable_hires_fix): after the pass at --height x --width, upscale the latents by S (>= 1; "
+                             "each side rounded to a multiple of 8), re-noise them and refine at that size; use --vae_tiling above 512 px")
+    parser.add_argument("--hires_size", type=int, nargs=2, default=None, metavar=("H", "W"),
+                        help="hires fix with the target size given in pixels (multiples of 8, not below the first pass); instead of "
+                             "--hires_scale")
+    parser.add_argument("--hires_strength", type=float, default=0.6, metavar="S",
+                        help="hires fix: the fraction of the schedule the upscaled latents are noised to, in (0, 1] (0.6)")
+    parser.add_argument("--hires_steps", type=int, default=None, metavar="N",
+                        help="hires fix: the schedule of the second pass, of which the last int(N * strength) steps run "
+                             "(default: --num_inference_steps)")
+    parser.add_argument("--hires_upscaler", type=str, default="bicubic-antialiased",
+                        help="hires fix: the latent upscaler -- nearest, nearest-exact, bilinear, bicubic, bilinear-antialiased or "
+                             "bicubic-antialiased (pixel-space upscalers and ESRGAN-class networks are not implemented)")
     return parser
 
 
@@ -1798,6 +1962,14 @@ def main(argv=None):
     if args.video_column is None and (args.strength is not None or args.mask_column is not None):
         logger.error("--strength and --mask_column need a source clip: --video_column.")
         return -1
+    hires = None
+    if args.hires_scale is not None or args.hires_size is not None:
+        from .hires_fix import check_hires_fix_args
+        try:
+            hires = check_hires_fix_args(args.hires_scale, args.hires_size, args.hires_strength, args.hires_steps, args.hires_upscaler)
+        except ValueError as e:
+            logger.error(f"--hires_scale / --hires_size: {e}")
+            return -1
     i2v_adapter = None
     motion_adapter = MotionAdapter.from_pretrained(args.motion_adapter_path)                     # pipe:734
     checkpoint_path = os.path.join(args.checkpoint_root, args.task_name, f"epoch_{args.checkpoint_epoch}")
@@ -1884,6 +2056,9 @@ def main(argv=None):
                                weighting_scheme=args.free_noise_weighting, noise_type=args.free_noise_noise)
     if args.free_init is not None:
         pipe.enable_free_init(num_iters=args.free_init, use_fast_sampling=args.free_init_fast, method=args.free_init_method)
+    if hires is not None:
+        pipe.enable_hires_fix(scale=hires.scale, size=hires.size, strength=hires.strength,
+                              num_inference_steps=hires.num_inference_steps, upscaler=hires.upscaler)
     if args.lora:
         names, weights = [], []
         for i, spec in enumerate(args.lora):

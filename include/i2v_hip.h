@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define I2V_ABI_VERSION 29
+#define I2V_ABI_VERSION 30
 
 #define I2V_OK 0
 #define I2V_ERR_INVALID_ARG (-1)
@@ -952,6 +952,29 @@ int i2v_interp_rows_f16(const void* src, int64_t ld_src, int32_t n_src, const in
  *       images * channels * hw >= 2^31 - 2^19. */
 int i2v_masked_renoise_f32(float* latents, const float* source, const float* noise, const float* mask, const float* coef, int32_t coef_rows,
                            const int32_t* step_idx, int64_t images, int32_t channels, int32_t hw, i2v_stream_t stream);
+
+/* (ABI 30) Hires fix (pipeline `enable_hires_fix` / `upscale_latents`): the latent upscale between the two passes with the second pass's
+ * re-noise fused in.  Once per sample, outside the captured step.
+ *       out[p, Y, X] = a * sum_ky sum_kx wy[Y][ky] * wx[X][kx] * src[p, iy[Y][ky], ix[X][kx]]  +  b * noise[p, Y, X]
+ *       src fp32 [planes, h, w]; out and noise fp32 [planes, H, W]; planes = batch * frames * channels; all contiguous.
+ *       noise may be NULL: then b is ignored and nothing is read for it.
+ *       Upscaling only, H >= h and W >= w: every mode then needs at most four taps per axis.  iy int32 [H, 4] / wy fp32 [H, 4] are the
+ *       source rows and weights of every output row, ix int32 [W, 4] / wx fp32 [W, 4] those of every output column, DEVICE memory, built
+ *       on the host in fp64 and rounded once (hires_fix.resize_tables).  An unused tap has weight 0 and a valid index.  The kernel does
+ *       no coordinate arithmetic; it clamps every index into the source plane before use, so a damaged table never reads out of bounds.
+ *       Arithmetic, all fp32, nothing contracted: term(ky, kx) = (wy * wx) * src; the 16 terms are added in the order ky outer, kx inner,
+ *       from the first term on (15 additions) to r; out = a * r without noise, (a * r) + (b * noise) with it -- the operations of
+ *       i2v_axpby_f32, so one fused launch gives the bits of a resize followed by i2v_axpby_f32(out, noise, a, b).
+ *       |out - exact| <= 2^-19 (|a| sum |wy| |wx| |src| + |b| |noise|) against fp64 from the same fp32 tables.  A weight of exactly 1
+ *       beside zeros (nearest modes; every mode at H == h, W == w) with a == 1 returns the source value (finite sources; -0 becomes +0).
+ *       Grid: at most 4096 workgroups of 256 lanes stride over tiles of 512 16-byte chunks of the flat output, one chunk per lane and
+ *       step: one 16-byte store and one 16-byte noise load per chunk, the taps through the caches.  With W % 4 != 0 a chunk may straddle
+ *       rows and every value finds its own row and column; the last numel % 4 values take a scalar path.  No workspace.
+ *       I2V_ERR_INVALID_ARG (nothing launched): a null src / out / table, planes / h / w < 1, H < h or W < w (a downscale), out / noise /
+ *       a table not 16-byte or src not 4-byte aligned, planes * H * W >= 2^31 - 2^19, out overlapping src, noise or a table. */
+int i2v_resize_renoise_f32(const float* src, float* out, const float* noise, const int32_t* iy, const float* wy, const int32_t* ix,
+                           const float* wx, float a, float b, int64_t planes, int32_t h, int32_t w, int32_t H, int32_t W,
+                           i2v_stream_t stream);
 
 /* (ABI 27) Prompt weighting (the `(text:1.3)` / `[text]` emphasis syntax of SD-1.5 front ends; pipeline `enable_prompt_weighting` /
  * `encode_weighted_prompt`): every token's embedding times its weight, then the prompt rescaled to its unweighted mean.  Once per sample.

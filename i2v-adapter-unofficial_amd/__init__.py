@@ -14,10 +14,10 @@ def __getattr__(name):
     import importlib
     if name in ("blocks", "handle", "checkpoint", "sharding", "vae", "training", "profiling", "i2v_adapter", "unet_motion_cross_frame_attn",
                 "pipeline_i2v_adapter", "image_processor", "lora", "free_init", "free_noise", "clip_text", "clip_vision", "controlnet", "t2i_adapter", "autoencoder_tiny", "prompt_travel",
-                "prompt_weighting", "textual_inversion"):
+                "prompt_weighting", "textual_inversion", "upscaler"):
         return importlib.import_module(f"{__name__}.{name}")
     for mod in ("i2v_adapter", "unet_motion_cross_frame_attn", "pipeline_i2v_adapter", "blocks", "sharding", "vae",
-                "image_processor", "checkpoint", "handle", "clip_text", "clip_vision", "controlnet", "t2i_adapter", "autoencoder_tiny"):
+                "image_processor", "checkpoint", "handle", "clip_text", "clip_vision", "controlnet", "t2i_adapter", "autoencoder_tiny", "upscaler"):
         m = importlib.import_module(f"{__name__}.{mod}")
         if hasattr(m, name):
             return getattr(m, name)

@@ -10,7 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # I2V_LIB_PATH selects another build of the same ABI (same-box A/B of two kernels, tools/ab_bench.sh); the in-tree
 # library is never overwritten by tooling
 LIB_PATH = os.environ.get("I2V_LIB_PATH") or os.path.join(_HERE, "libi2v_hip.so")
-ABI_VERSION = 30
+ABI_VERSION = 31
 
 I2V_EPI_NONE, I2V_EPI_GELU, I2V_EPI_GEGLU = 0, 1, 2
 I2V_STORE_ROWMAJOR, I2V_STORE_ROWPERM, I2V_STORE_VT, I2V_STORE_VT_T = 0, 1, 2, 3
@@ -20,7 +20,7 @@ I2V_ROUTE_GENERIC, I2V_ROUTE_CONV_THIN, I2V_ROUTE_BIG_TILE, I2V_ROUTE_BIG_DEEP, 
 I2V_EXTRA_NONE, I2V_EXTRA_LNF, I2V_EXTRA_HILO, I2V_EXTRA_GNS, I2V_EXTRA_UPF = 0, 1, 2, 4, 8
 I2V_TATTN_LDS_FORM, I2V_TATTN_REG_FORM = 0, 1
 I2V_ADD_RES_MAX = 16
-I2V_TAESD_PREP_IDENTITY, I2V_TAESD_PREP_UNIT, I2V_TAESD_PREP_CLAMP = 0, 1, 2
+I2V_TAESD_PREP_IDENTITY, I2V_TAESD_PREP_UNIT, I2V_TAESD_PREP_CLAMP, I2V_TAESD_PREP_UNIT_CLAMP = 0, 1, 2, 4
 
 
 class HipLibraryError(RuntimeError):
@@ -366,6 +366,9 @@ SIGNATURES = {
                                               C.c_float, _P]),
     "i2v_add_residuals_f16": (C.c_int, [C.POINTER(AddResidualsParams), _P]),
     "i2v_conv3x3_c64_f16": (C.c_int, [C.POINTER(ConvC64Params), _P]),
+    "i2v_conv3x3_c64_prelu_f16": (C.c_int, [C.POINTER(ConvC64Params), _P, _P]),
+    "i2v_pixel_shuffle_add_f32": (C.c_int, [_P, C.c_int64, _P, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                            C.c_int32, C.c_int32, _P]),
     "i2v_taesd_prep_f16": (C.c_int, [_P, C.c_int32, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),
     "i2v_pixel_unshuffle8_f16": (C.c_int, [_P, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),
     "i2v_avgpool2x_f16": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),

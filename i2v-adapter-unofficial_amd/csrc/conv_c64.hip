@@ -1,7 +1,11 @@
-// 3x3 / pad 1 / stride 1 convolution with Cin = Cout = 64 and a fused epilogue: the layer AutoencoderTiny (TAESD) is made of
-// (i2v_conv3x3_c64_f16), and that model's entry mover (i2v_taesd_prep_f16).
+// 3x3 / pad 1 / stride 1 convolution with Cin = Cout = 64 and a fused epilogue: the layer AutoencoderTiny (TAESD) and the Real-ESRGAN
+// compact upscaler (SRVGGNetCompact) are made of (i2v_conv3x3_c64_f16 / i2v_conv3x3_c64_prelu_f16), and their entry mover
+// (i2v_taesd_prep_f16).
 //
 //   out = act_out( act_mid(conv(x) + bias) + residual )            token-major fp16 [N, H, W, 64], fp32 arithmetic, one rounding
+//
+// act_mid is ReLU / identity (conv_c64_kernel<false>) or a per-channel PReLU v >= 0 ? v : slope[c] v (conv_c64_kernel<true>: the same
+// kernel with 16 more registers, the lane's slopes held like its bias; ReLU and leaky ReLU are slope 0 and 0.1).
 //
 // conv_thin.hip's scheme at 64 output channels.  A workgroup of four waves owns an 8 x 16 pixel tile of one image; the tile WITH its
 // halo (10 x 18 pixels x 128 B = 23 KB) is staged in LDS once and the nine taps are 16x16x32 MFMAs against SHIFTED reads of it:
@@ -40,7 +44,9 @@ constexpr int C6_PIECES = C6_HP * 8;                     // 16-byte pieces of a 
 constexpr int C6_NLD = (C6_PIECES + 255) / 256;          // per thread: 6
 static_assert((C6_HP - 1 | 6) < 192 && C6_PLANE % 256 == 0 && C6_LDS <= 160 * 1024, "LDS image");
 
-__global__ __launch_bounds__(256, 1) void conv_c64_kernel(const i2v_conv_c64_params p, const int tiles_x, const int tiles_y, const int ntiles) {
+template <bool PRELU>
+__global__ __launch_bounds__(256, 1) void conv_c64_kernel(const i2v_conv_c64_params p, const int tiles_x, const int tiles_y, const int ntiles,
+                                                          const float* __restrict__ slope) {
   extern __shared__ __attribute__((aligned(16))) char smem[];     // W fragments, then [2] halo tiles
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int g = lane >> 4, l15 = lane & 15;
@@ -93,6 +99,16 @@ __global__ __launch_bounds__(256, 1) void conv_c64_kernel(const i2v_conv_c64_par
     const f16x8 b = p.bias ? ld_global_16B(reinterpret_cast<const f16*>(p.bias) + 32 * h + 8 * g) : zero8();
 #pragma unroll
     for (int j = 0; j < 8; ++j) bv[h][j] = (float)b[j];
+  }
+  // ... and, for the PReLU epilogue, their slopes (fp32 [64]: two 16-byte loads per half)
+  float sv[2][8];
+  if constexpr (PRELU) {
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const f32x4 s0 = *reinterpret_cast<const f32x4*>(slope + 32 * h + 8 * g), s1 = *reinterpret_cast<const f32x4*>(slope + 32 * h + 8 * g + 4);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) sv[h][j] = s0[j], sv[h][4 + j] = s1[j];
+    }
   }
   const bool relu_mid = p.relu_mid != 0, relu_out = p.relu_out != 0;
   const f16* __restrict__ R = reinterpret_cast<const f16*>(p.residual);
@@ -166,7 +182,10 @@ __global__ __launch_bounds__(256, 1) void conv_c64_kernel(const i2v_conv_c64_par
 #pragma unroll
           for (int j = 0; j < 8; ++j) {
             float v = acc[2 * h + (j >> 2)][r][j & 3] + bv[h][j];
-            if (relu_mid) v = fmaxf(v, 0.f);
+            if constexpr (PRELU)
+              v = v >= 0.f ? v : sv[h][j] * v;
+            else if (relu_mid)
+              v = fmaxf(v, 0.f);
             v += (float)rr[r][h][j];              // (zeros without a residual: v + 0 is v, and -0 + 0 = +0 is the same fp16 number)
             o[j] = (f16)(relu_out ? fmaxf(v, 0.f) : v);
           }
@@ -180,7 +199,7 @@ __global__ __launch_bounds__(256, 1) void conv_c64_kernel(const i2v_conv_c64_par
   }
 }
 
-// NCHW fp32 / fp16 -> token-major fp16 [N, H, W, 64] (pixel stride ld_dst), channels >= c zero, through one of three maps
+// NCHW fp32 / fp16 -> token-major fp16 [N, H, W, 64] (pixel stride ld_dst), channels >= c zero, through one of four maps
 template <bool F32>
 __global__ __launch_bounds__(256) void taesd_prep_kernel(const void* __restrict__ src_, f16* __restrict__ dst, const int64_t ld_dst,
                                                          const int64_t items, const int c, const int hw, const int mode) {
@@ -198,6 +217,8 @@ __global__ __launch_bounds__(256) void taesd_prep_kernel(const void* __restrict_
         v = F32 ? reinterpret_cast<const float*>(src_)[s0 + (int64_t)j * hw] : (float)reinterpret_cast<const f16*>(src_)[s0 + (int64_t)j * hw];
         if (mode == I2V_TAESD_PREP_UNIT)
           v = (v + 1.0f) * 0.5f;
+        else if (mode == I2V_TAESD_PREP_UNIT_CLAMP)
+          v = fminf(fmaxf((v + 1.0f) * 0.5f, 0.0f), 1.0f);
         else if (mode == I2V_TAESD_PREP_CLAMP)
           v = 3.0f * tanhf(v / 3.0f);
       }
@@ -209,47 +230,72 @@ __global__ __launch_bounds__(256) void taesd_prep_kernel(const void* __restrict_
 
 }  // namespace
 
-extern "C" int i2v_conv3x3_c64_f16(const i2v_conv_c64_params* p, i2v_stream_t stream) {
-  I2V_CHECK_ARG(p != nullptr, "i2v_conv3x3_c64_f16: null params");
-  I2V_CHECK_ARG(p->x && p->w && p->out, "i2v_conv3x3_c64_f16: null pointer");
-  I2V_CHECK_ARG(p->cin == C6_C && p->cout == C6_C, "i2v_conv3x3_c64_f16: Cin %d, Cout %d: this kernel is the 64 -> 64 convolution", p->cin,
+namespace {
+
+// the argument checks and the launch of both entry points: `fn` names the entry in the messages, `prelu` selects the instantiation
+int conv_c64_launch(const char* fn, const i2v_conv_c64_params* p, const bool prelu, const void* slope, i2v_stream_t stream) {
+  I2V_CHECK_ARG(p != nullptr, "%s: null params", fn);
+  I2V_CHECK_ARG(p->x && p->w && p->out, "%s: null pointer", fn);
+  I2V_CHECK_ARG(p->cin == C6_C && p->cout == C6_C, "%s: Cin %d, Cout %d: this kernel is the 64 -> 64 convolution", fn, p->cin,
                 p->cout);
-  I2V_CHECK_ARG(p->n_img >= 1 && p->height >= 1 && p->width >= 1, "i2v_conv3x3_c64_f16: n %d, h %d, w %d", p->n_img, p->height, p->width);
+  I2V_CHECK_ARG(p->n_img >= 1 && p->height >= 1 && p->width >= 1, "%s: n %d, h %d, w %d", fn, p->n_img, p->height, p->width);
   const int64_t lim = (int64_t)1 << 31;
   I2V_CHECK_ARG(p->ldx >= C6_C && p->ldx % 8 == 0 && p->ldo >= C6_C && p->ldo % 8 == 0 && p->ldx < (1 << 20) && p->ldo < (1 << 20),
-                "i2v_conv3x3_c64_f16: pixel strides ldx %lld, ldo %lld must be >= 64 and multiples of 8", (long long)p->ldx, (long long)p->ldo);
+                "%s: pixel strides ldx %lld, ldo %lld must be >= 64 and multiples of 8", fn, (long long)p->ldx, (long long)p->ldo);
   I2V_CHECK_ARG(p->residual == nullptr || (p->ldr >= C6_C && p->ldr % 8 == 0 && p->ldr < (1 << 20)),
-                "i2v_conv3x3_c64_f16: residual pixel stride %lld must be >= 64 and a multiple of 8", (long long)p->ldr);
+                "%s: residual pixel stride %lld must be >= 64 and a multiple of 8", fn, (long long)p->ldr);
   I2V_CHECK_ARG(i2v_al16(p->x) && i2v_al16(p->w) && i2v_al16(p->out) && i2v_al16(p->bias) && i2v_al16(p->residual),
-                "i2v_conv3x3_c64_f16: operands must be 16-byte aligned");
+                "%s: operands must be 16-byte aligned", fn);
   const int64_t hw = (int64_t)p->height * p->width, pixels = hw * p->n_img;
-  I2V_CHECK_ARG(hw * p->ldx < lim && pixels < lim, "i2v_conv3x3_c64_f16: problem too large");
+  I2V_CHECK_ARG(hw * p->ldx < lim && pixels < lim, "%s: problem too large", fn);
   const int64_t xb = ((pixels - 1) * p->ldx + C6_C) * 2, ob = ((pixels - 1) * p->ldo + C6_C) * 2;      // bytes from the first to the last element
   // other workgroups read x as halo while this one stores: out may not be x
-  I2V_CHECK_ARG(!i2v_overlap(p->out, ob, p->x, xb), "i2v_conv3x3_c64_f16: out overlaps x (other workgroups read x as halo)");
+  I2V_CHECK_ARG(!i2v_overlap(p->out, ob, p->x, xb), "%s: out overlaps x (other workgroups read x as halo)", fn);
   I2V_CHECK_ARG(!i2v_overlap(p->out, ob, p->w, C6_WBYTES) && (p->bias == nullptr || !i2v_overlap(p->out, ob, p->bias, C6_C * 2)),
-                "i2v_conv3x3_c64_f16: out overlaps the weights");
+                "%s: out overlaps the weights", fn);
   // every element of the residual is read by the lane that then stores it: out may BE the residual, and nothing in between
   I2V_CHECK_ARG(p->residual == nullptr || (p->residual == p->out && p->ldr == p->ldo) || !i2v_overlap(p->out, ob, p->residual, ((pixels - 1) * p->ldr + C6_C) * 2),
-                "i2v_conv3x3_c64_f16: out overlaps the residual without being it");
-  I2V_CHECK_ARG(p->max_workgroups >= 0, "i2v_conv3x3_c64_f16: max_workgroups %d", p->max_workgroups);
+                "%s: out overlaps the residual without being it", fn);
+  I2V_CHECK_ARG(p->max_workgroups >= 0, "%s: max_workgroups %d", fn, p->max_workgroups);
+  if (prelu) {
+    I2V_CHECK_ARG(slope != nullptr && i2v_al16(slope), "%s: slope must be 64 fp32 values, non-null and 16-byte aligned", fn);
+    I2V_CHECK_ARG(p->relu_mid == 0, "%s: relu_mid must be 0 (act_mid is the PReLU)", fn);
+    I2V_CHECK_ARG(!i2v_overlap(p->out, ob, slope, C6_C * 4), "%s: out overlaps slope", fn);
+  }
   const int tiles_x = (int)i2v_cdiv(p->width, C6_TW), tiles_y = (int)i2v_cdiv(p->height, C6_TH);
   const int64_t ntiles = (int64_t)p->n_img * tiles_x * tiles_y;
-  I2V_CHECK_ARG(ntiles < lim - (1 << 20), "i2v_conv3x3_c64_f16: problem too large");
-  const int cus = i2v_big_lds_kernel_cus(reinterpret_cast<const void*>(conv_c64_kernel), C6_LDS);
-  if (cus <= 0) I2V_FAIL(I2V_ERR_UNSUPPORTED, "i2v_conv3x3_c64_f16: the device refuses %d bytes of LDS", C6_LDS);
+  I2V_CHECK_ARG(ntiles < lim - (1 << 20), "%s: problem too large", fn);
+  const void* kernel = prelu ? reinterpret_cast<const void*>(conv_c64_kernel<true>) : reinterpret_cast<const void*>(conv_c64_kernel<false>);
+  const int cus = i2v_big_lds_kernel_cus(kernel, C6_LDS);
+  if (cus <= 0) I2V_FAIL(I2V_ERR_UNSUPPORTED, "%s: the device refuses %d bytes of LDS", fn, C6_LDS);
   int64_t grid = p->max_workgroups > 0 ? p->max_workgroups : cus;
   if (grid > ntiles) grid = ntiles;
-  hipLaunchKernelGGL(conv_c64_kernel, dim3((unsigned)grid), dim3(256), C6_LDS, reinterpret_cast<hipStream_t>(stream), *p, tiles_x, tiles_y,
-                     (int)ntiles);
-  return i2v_check_launch("i2v_conv3x3_c64_f16");
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (prelu)
+    hipLaunchKernelGGL(conv_c64_kernel<true>, dim3((unsigned)grid), dim3(256), C6_LDS, st, *p, tiles_x, tiles_y, (int)ntiles,
+                       reinterpret_cast<const float*>(slope));
+  else
+    hipLaunchKernelGGL(conv_c64_kernel<false>, dim3((unsigned)grid), dim3(256), C6_LDS, st, *p, tiles_x, tiles_y, (int)ntiles,
+                       static_cast<const float*>(nullptr));
+  return i2v_check_launch(fn);
+}
+
+}  // namespace
+
+extern "C" int i2v_conv3x3_c64_f16(const i2v_conv_c64_params* p, i2v_stream_t stream) {
+  return conv_c64_launch("i2v_conv3x3_c64_f16", p, false, nullptr, stream);
+}
+
+extern "C" int i2v_conv3x3_c64_prelu_f16(const i2v_conv_c64_params* p, const void* slope, i2v_stream_t stream) {
+  return conv_c64_launch("i2v_conv3x3_c64_prelu_f16", p, true, slope, stream);
 }
 
 extern "C" int i2v_taesd_prep_f16(const void* src, int32_t src_is_f32, void* dst, int64_t ld_dst, int32_t n, int32_t c, int32_t hw, int32_t mode,
                                   i2v_stream_t stream) {
   I2V_CHECK_ARG(src && dst, "i2v_taesd_prep_f16: null pointer");
   I2V_CHECK_ARG(n >= 1 && hw >= 1 && c >= 1 && c <= C6_C, "i2v_taesd_prep_f16: n %d, c %d (1..64), hw %d", n, c, hw);
-  I2V_CHECK_ARG(mode == I2V_TAESD_PREP_IDENTITY || mode == I2V_TAESD_PREP_UNIT || mode == I2V_TAESD_PREP_CLAMP, "i2v_taesd_prep_f16: mode %d", mode);
+  I2V_CHECK_ARG(mode == I2V_TAESD_PREP_IDENTITY || mode == I2V_TAESD_PREP_UNIT || mode == I2V_TAESD_PREP_CLAMP || mode == I2V_TAESD_PREP_UNIT_CLAMP,
+                "i2v_taesd_prep_f16: mode %d", mode);
   I2V_CHECK_ARG(ld_dst >= C6_C && ld_dst % 8 == 0 && ld_dst < (1 << 20) && i2v_al16(dst),
                 "i2v_taesd_prep_f16: dst must be 16-byte aligned with a pixel stride >= 64 that is a multiple of 8");
   const int64_t pixels = (int64_t)n * hw;

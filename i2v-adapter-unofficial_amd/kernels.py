@@ -388,11 +388,13 @@ def _pixel_stride(t, name):
     return ld
 
 
-def conv3x3_c64(x, w_packed, bias=None, *, relu_mid=False, relu_out=False, residual=None, out=None, max_workgroups=None):
+def conv3x3_c64(x, w_packed, bias=None, *, relu_mid=False, relu_out=False, residual=None, out=None, max_workgroups=None, slope=None):
     """out = act_out(act_mid(conv3x3(x) + bias) + residual): the 64 -> 64, stride 1, pad 1 convolution of AutoencoderTiny with its
     epilogue in one launch (i2v_conv3x3_c64_f16).  x, out, residual: token-major fp16 [N, H, W, 64] views with a pixel stride >= 64
     (a multiple of 8); w_packed from `pack_conv_c64`; bias fp16 [64].  `out` may be `residual`, never `x`.  max_workgroups caps the
-    persistent grid (a dispatch override, like the library's other ones: the result does not depend on it)."""
+    persistent grid (a dispatch override, like the library's other ones: the result does not depend on it).
+    slope (fp32 [64]): act_mid is the per-channel PReLU v >= 0 ? v : slope[c] v instead (i2v_conv3x3_c64_prelu_f16, the layer of
+    `upscaler.SRVGGNetCompact`); relu_mid must then be False."""
     lib = _lib.load()
     ldx = _pixel_stride(x, "x")
     n, h, wd, c = x.shape
@@ -421,16 +423,24 @@ def conv3x3_c64(x, w_packed, bias=None, *, relu_mid=False, relu_out=False, resid
     p.max_workgroups = 0 if max_workgroups is None else int(max_workgroups)
     if max_workgroups is not None and p.max_workgroups < 1:
         raise ValueError(f"max_workgroups must be positive, got {max_workgroups}")
+    if slope is not None:
+        _req(slope, "slope", dtype=torch.float32)
+        if slope.numel() != 64 or not slope.is_contiguous():
+            raise ValueError("slope must be a contiguous fp32 vector of 64 elements")
+        _lib.check(lib.i2v_conv3x3_c64_prelu_f16(C.byref(p), _p(slope), _stream()), "i2v_conv3x3_c64_prelu_f16")
+        return out
     _lib.check(lib.i2v_conv3x3_c64_f16(C.byref(p), _stream()), "i2v_conv3x3_c64_f16")
     return out
 
 
-TAESD_PREP_MODES = {"identity": _lib.I2V_TAESD_PREP_IDENTITY, "unit": _lib.I2V_TAESD_PREP_UNIT, "clamp": _lib.I2V_TAESD_PREP_CLAMP}
+TAESD_PREP_MODES = {"identity": _lib.I2V_TAESD_PREP_IDENTITY, "unit": _lib.I2V_TAESD_PREP_UNIT, "clamp": _lib.I2V_TAESD_PREP_CLAMP,
+                    "unit_clamp": _lib.I2V_TAESD_PREP_UNIT_CLAMP}
 
 
 def taesd_prep(src, mode="identity", out=None):
     """AutoencoderTiny's entry mover (i2v_taesd_prep_f16): src [N, C <= 64, H, W] fp32 / fp16 through `mode` -- "identity",
-    "unit" (v + 1) / 2, "clamp" 3 tanh(v / 3) -- to token-major fp16 [N, H, W, 64] with channels C.. zero."""
+    "unit" (v + 1) / 2, "clamp" 3 tanh(v / 3), "unit_clamp" min(max((v + 1) / 2, 0), 1) (the upscaler's) -- to token-major fp16
+    [N, H, W, 64] with channels C.. zero."""
     lib = _lib.load()
     _req(src, "src", dtype=None)
     if src.dtype not in (torch.float32, f16) or src.dim() != 4:
@@ -446,6 +456,32 @@ def taesd_prep(src, mode="identity", out=None):
         raise ValueError(f"out must be {(n, h, w, 64)}, got {tuple(out.shape)}")
     _lib.check(lib.i2v_taesd_prep_f16(_p(src), 1 if src.dtype == torch.float32 else 0, _p(out), ld, n, c, h * w, TAESD_PREP_MODES[mode],
                                       _stream()), "i2v_taesd_prep_f16")
+    return out
+
+
+def pixel_shuffle_add(y, src, s, *, unit_in=False, clamp=True, signed_out=False, out=None):
+    """The upscaler's exit (i2v_pixel_shuffle_add_f32): out[n, col, s i + dy, s j + dx] = range(clamp(y[n, i, j, (col s + dy) s + dx] +
+    entry(src[n, col, i, j]))), PixelShuffle(s) of the exit convolution's result plus the nearest-upsampled source.  y: token-major
+    fp16 [N, H, W, 64] view (pixel stride >= 64, a multiple of 8) of which channels < 3 s^2 are read; src: contiguous NCHW [N, 3, H, W]
+    fp32 / fp16 BEFORE the entry map, which is the identity or, with unit_in, `taesd_prep`'s "unit_clamp"; clamp: to [0, 1];
+    signed_out: 2 v - 1 after it.  s in 1..4.  Returns fp32 [N, 3, s H, s W] (`out`: a contiguous tensor of that shape)."""
+    lib = _lib.load()
+    ld = _pixel_stride(y, "y")
+    n, h, w, c = y.shape
+    _req(src, "src", dtype=None)
+    if src.dtype not in (torch.float32, f16) or tuple(src.shape) != (n, 3, h, w) or not src.is_contiguous() or src.device != y.device:
+        raise ValueError(f"src must be a contiguous fp32 / fp16 {(n, 3, h, w)} on y's device, got {src.dtype} {tuple(src.shape)}")
+    s = int(s)
+    if c != 64:
+        raise ValueError(f"y must have 64 channels, got {c}")
+    if out is None:
+        out = torch.empty((n, 3, s * h, s * w), dtype=torch.float32, device=y.device)
+    _req(out, "out", dtype=torch.float32)
+    if tuple(out.shape) != (n, 3, s * h, s * w) or not out.is_contiguous():
+        raise ValueError(f"out must be a contiguous {(n, 3, s * h, s * w)}, got {tuple(out.shape)}")
+    mode = _lib.I2V_TAESD_PREP_UNIT_CLAMP if unit_in else _lib.I2V_TAESD_PREP_IDENTITY
+    _lib.check(lib.i2v_pixel_shuffle_add_f32(_p(y), ld, _p(src), 1 if src.dtype == torch.float32 else 0, _p(out), n, h, w, s, mode,
+                                             int(bool(clamp)), int(bool(signed_out)), _stream()), "i2v_pixel_shuffle_add_f32")
     return out
 
 

@@ -200,6 +200,7 @@ class I2VAdapterPipeline:
         self._graph_cache = {}
         self._free_init = None
         self._hires_fix = None
+        self._upscaler = None
         self._prompt_weighting = None
         self._textual_inversions = []
 
@@ -459,6 +460,54 @@ class I2VAdapterPipeline:
             raise HipLibraryError(f"unet is on {self.unet.device}: the HIP path has no CPU fallback")
         src = latents.detach().to(self.unet.device, torch.float32).contiguous()
         return K.resize_renoise(src, device_tables(h, w, h2, w2, upscaler, src.device))
+
+    def enable_upscaler(self, model_or_path, frames_per_batch: Optional[int] = None, act_type: Optional[str] = None):
+        """The pixel-space upscale the AnimateDiff front ends run after sampling: while enabled, the decoded frames of
+        every call go through a Real-ESRGAN compact model (`upscaler.SRVGGNetCompact`: realesr-animevideov3, realesr-general-x4v3)
+        before `tensor2vid` / "pt" -- s x the size, s the model's `upscale`.  `model_or_path`: a `SRVGGNetCompact`, a released `.pth`,
+        a `.safetensors` file or a state dict (`act_type` "relu" / "leakyrelu" for a dict without PReLU weights).  `frames_per_batch`
+        frames go through the network at a time (None: all of them; one under `enable_vae_slicing`): frames are independent, so the
+        result is the same bits for every chunking.  There is nothing to upscale in latents: a call with output_type="latent" is
+        refused while the upscaler is enabled.  The sampler and the captured step are untouched."""
+        from .upscaler import SRVGGNetCompact
+        if frames_per_batch is not None and (isinstance(frames_per_batch, bool) or not isinstance(frames_per_batch, int)
+                                             or frames_per_batch < 1):
+            raise ValueError(f"`frames_per_batch` must be a positive integer or None, got {frames_per_batch!r}")
+        if isinstance(model_or_path, SRVGGNetCompact):
+            if act_type is not None and act_type != model_or_path.act_type:
+                raise ValueError(f"act_type={act_type!r}, but the model was built with {model_or_path.act_type!r}")
+            model = model_or_path
+        else:
+            model = SRVGGNetCompact.from_pretrained(model_or_path, act_type=act_type)
+            unet = getattr(self, "unet", None)
+            if unet is not None and unet.device.type == "cuda":
+                model = model.to(unet.device)
+        self._upscaler = (model, frames_per_batch)
+
+    def disable_upscaler(self):
+        """the decoded frames are the output again: every path is what it was before `enable_upscaler`"""
+        self._upscaler = None
+
+    @property
+    def upscaler_enabled(self):
+        return self._upscaler is not None
+
+    def upscale_frames(self, video):
+        """video [B, F, 3, H, W] or [N, 3, H, W] in [-1, 1] (`decode_latents`' result) -> fp32 of the same rank at s x the size, in
+        [-1, 1], through the enabled upscaler, `frames_per_batch` frames (one under `enable_vae_slicing`) at a time."""
+        if self._upscaler is None:
+            raise ValueError("upscale_frames needs an upscaler: enable_upscaler(model_or_path) first")
+        model, per = self._upscaler
+        if not isinstance(video, torch.Tensor) or video.dim() not in (4, 5) or video.shape[-3] != 3:
+            raise ValueError("`video` must be a [B, F, 3, H, W] or [N, 3, H, W] tensor, got "
+                             f"{tuple(video.shape) if isinstance(video, torch.Tensor) else type(video)}")
+        if model.device.type != "cuda":
+            raise HipLibraryError(f"the upscaler is on {model.device}: the HIP path has no CPU fallback")
+        flat = video.detach().to(model.device).reshape((-1,) + tuple(video.shape[-3:]))
+        n = flat.shape[0]
+        per = 1 if self._vae_slicing else (per or n)
+        out = torch.cat([model(flat[i: i + per], signed=True) for i in range(0, n, per)])
+        return out.reshape(tuple(video.shape[:-2]) + tuple(out.shape[-2:]))
 
     def enable_free_noise(self, context_length: int = 16, context_stride: int = 4, weighting_scheme: str = "pyramid",
                           noise_type: str = "shuffle_context"):
@@ -1238,6 +1287,9 @@ class I2VAdapterPipeline:
                 (adapter_image, num_frames, adapter_conditioning_scale, adapter_conditioning_factor),
                 video, video_latents, strength, mask_image)
             output_type, use_graph = self._resolve_call_defaults(output_type, callback, use_graph)
+            if self._upscaler is not None and output_type == "latent":
+                raise ValueError("output_type='latent' with the upscaler enabled: nothing is decoded, so there is nothing to upscale "
+                                 "(disable_upscaler(), or ask for 'pt' / 'pil' / 'np')")
             # the hires fix's target size and step count (None while it is disabled): its refusals come before anything is encoded
             hires = self._hires_target(height, width, condition_image, condition_image_latents, video, video_latents,
                                        num_inference_steps)
@@ -1581,11 +1633,14 @@ class I2VAdapterPipeline:
         return latents
 
     def _output(self, latents, output_type, return_dict):
-        """Phase 7, the output: the latents as they are ("latent"), or decoded by the VAE to a tensor ("pt") or through `tensor2vid`"""
+        """Phase 7, the output: the latents as they are ("latent"), or decoded by the VAE -- and upscaled while `enable_upscaler` is
+        on -- to a tensor ("pt") or through `tensor2vid`"""
         if output_type == "latent":                                                             # pipe:702-703
             video = latents
         else:
             video_tensor = self.decode_latents(latents)                                         # pipe:706
+            if self._upscaler is not None:
+                video_tensor = self.upscale_frames(video_tensor)
             video = video_tensor if output_type == "pt" else tensor2vid(video_tensor, self.image_processor,
                                                                         output_type=output_type)  # pipe:708-711
         if not return_dict:
@@ -1818,6 +1873,11 @@ def build_parser():
     parser.add_argument("--vae_tiny", type=str, default=None, metavar="PATH",
                         help="an AutoencoderTiny (TAESD) folder (config.json + diffusion_pytorch_model.safetensors) loaded in place of "
                              "<model_path>/vae: the cheap decode that goes with --scheduler lcm (no tiling: not with --vae_tiling)")
+    parser.add_argument("--upscaler", type=str, default=None, metavar="PATH",
+                        help="a Real-ESRGAN compact model (realesr-animevideov3 / realesr-general-x4v3: .pth, .pt or .safetensors) run on "
+                             "the decoded frames (pipe.enable_upscaler()): the GIFs are `upscale` x the size")
+    parser.add_argument("--upscaler_act", type=str, default=None, choices=("prelu", "relu", "leakyrelu"),
+                        help="with --upscaler: the activation of a file without PReLU weights (relu or leakyrelu)")
     parser.add_argument("--free_init", type=int, nargs="?", const=3, default=None, metavar="N",
                         help="FreeInit (pipe.enable_free_init): sample every clip N times (3 when given without a value), re-initialising "
                              "the noise's low frequencies from the previous round; off by default")
@@ -2051,6 +2111,9 @@ def main(argv=None):
         pipe.enable_freeu(*args.freeu)
     if args.vae_tiling:
         pipe.enable_vae_tiling()
+    if args.upscaler is not None:
+        pipe.enable_upscaler(args.upscaler, act_type=args.upscaler_act)
+        logger.info(f"Successfully loaded the upscaler from {args.upscaler}.")
     if args.free_noise is not None:
         pipe.enable_free_noise(context_length=args.free_noise, context_stride=args.free_noise_stride,
                                weighting_scheme=args.free_noise_weighting, noise_type=args.free_noise_noise)

@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define I2V_ABI_VERSION 30
+#define I2V_ABI_VERSION 31
 
 #define I2V_OK 0
 #define I2V_ERR_INVALID_ARG (-1)
@@ -872,16 +872,40 @@ typedef struct i2v_conv_c64_params {
   int32_t max_workgroups;
 } i2v_conv_c64_params;
 int i2v_conv3x3_c64_f16(const i2v_conv_c64_params* p, i2v_stream_t stream);
+/* (ABI 31) The same layer with a per-channel PReLU in the middle -- the layer of the Real-ESRGAN compact upscaler (SRVGGNetCompact,
+ * upscaler.py):
+ *           act_mid(v) = v >= 0 ? v : slope[c] * v        in fp32, before the residual add and the single rounding
+ *       slope: fp32 [64], non-null, 16-byte aligned.  ReLU and leaky ReLU are this epilogue with slope 0 and 0.1 (slope 1: the plain layer).
+ *       The second instantiation of the kernel above: a lane holds the 16 slopes of its channels in registers beside their bias.  relu_mid
+ *       must be 0; relu_out, residual, strides, max_workgroups and every argument check are those of i2v_conv3x3_c64_f16.
+ *       I2V_ERR_INVALID_ARG in addition: a null or misaligned slope, relu_mid != 0, out overlapping slope. */
+int i2v_conv3x3_c64_prelu_f16(const i2v_conv_c64_params* p, const void* slope, i2v_stream_t stream);
 /* (ABI 23) AutoencoderTiny's entry mover: src NCHW [n, c, hw] fp32 (src_is_f32) or fp16, c <= 64, through
  *           I2V_TAESD_PREP_IDENTITY  v                 I2V_TAESD_PREP_UNIT  (v + 1) / 2  (the encoder's input)
  *           I2V_TAESD_PREP_CLAMP     3 tanh(v / 3)     (the decoder's latent clamp)
+ *           I2V_TAESD_PREP_UNIT_CLAMP  min(max((v + 1) / 2, 0), 1)     (ABI 31: the upscaler's input, [-1, 1] frames to RGB in [0, 1])
  *       in fp32, to token-major fp16 dst [n, hw, 64] with pixel stride ld_dst (>= 64, a multiple of 8, 16-byte aligned base); channels
- *       c .. 63 are written as zeros.  I2V_ERR_INVALID_ARG: null / misaligned / overlapping operands, c outside 1..64, an unknown mode. */
+ *       c .. 63 are written as zeros.  I2V_ERR_INVALID_ARG: null / misaligned / overlapping operands, c outside 1..64, an unknown mode.
+ *       (The value 3 stays an unknown mode: ABI 23 .. 30 refuse it and callers may rely on that.) */
 #define I2V_TAESD_PREP_IDENTITY 0
 #define I2V_TAESD_PREP_UNIT 1
 #define I2V_TAESD_PREP_CLAMP 2
+#define I2V_TAESD_PREP_UNIT_CLAMP 4
 int i2v_taesd_prep_f16(const void* src, int32_t src_is_f32, void* dst, int64_t ld_dst, int32_t n, int32_t c, int32_t hw, int32_t mode,
                        i2v_stream_t stream);
+/* (ABI 31) The upscaler's exit (SRVGGNetCompact.forward: PixelShuffle(s)(body(x)) + nearest-upsampled x, then the caller's clamp), one launch:
+ *       y: token-major fp16 [n, h, w] pixels of stride ld (>= 64, a multiple of 8, 16-byte aligned base), the exit convolution's result;
+ *          channel k = (col * s + dy) * s + dx (PyTorch's PixelShuffle order), k < 3 s^2 -- no other channel is read.
+ *       src: the network's NCHW source [n, 3, h, w], fp32 (src_is_f32) or fp16, BEFORE the entry map; entry_mode is that map,
+ *          I2V_TAESD_PREP_IDENTITY or I2V_TAESD_PREP_UNIT_CLAMP.       out: NCHW fp32 [n, 3, s h, s w], 16-byte aligned.
+ *       In fp32, in this order:   base = entry(src[n, col, y, x]);   v = float(y[n, y, x, k]) + base;   clamp != 0: v = min(max(v, 0), 1);
+ *          signed_out != 0: v = 2 v - 1;   out[n, col, s y + dy, s x + dx] = v.        |out - exact| <= 2^-22 (|y| + |base| + 1).
+ *       s = 1 .. 4.  One lane owns the s contiguous outputs of one (col, dy) of one input pixel (a 16-byte store at s = 4) and a wave 64
+ *       consecutive pixels of a row; a capped grid strides.  Nothing outside out's n * 3 * s h * s w values is written.  No workspace.
+ *       I2V_ERR_INVALID_ARG (nothing launched): null / misaligned operands, out overlapping y or src, s outside 1..4, a bad ld, an entry
+ *       map other than the two. */
+int i2v_pixel_shuffle_add_f32(const void* y, int64_t ld, const void* src, int32_t src_is_f32, float* out, int32_t n, int32_t h, int32_t w,
+                              int32_t s, int32_t entry_mode, int32_t clamp, int32_t signed_out, i2v_stream_t stream);
 
 /* (ABI 24) T2I-Adapter (diffusers 0.24 `T2IAdapter`, adapter_type "full_adapter"; t2i_adapter.py).  The adapter reads the control frames
  * only -- never the latents or the timestep -- so its network runs once per sample and a denoising step adds four stored feature maps to the

@@ -10,7 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # I2V_LIB_PATH selects another build of the same ABI (same-box A/B of two kernels, tools/ab_bench.sh); the in-tree
 # library is never overwritten by tooling
 LIB_PATH = os.environ.get("I2V_LIB_PATH") or os.path.join(_HERE, "libi2v_hip.so")
-ABI_VERSION = 31
+ABI_VERSION = 32
 
 I2V_EPI_NONE, I2V_EPI_GELU, I2V_EPI_GEGLU = 0, 1, 2
 I2V_STORE_ROWMAJOR, I2V_STORE_ROWPERM, I2V_STORE_VT, I2V_STORE_VT_T = 0, 1, 2, 3
@@ -19,6 +19,10 @@ I2V_LORA_MAX_ADAPTERS, I2V_LORA_MAX_RANK = 8, 256
 I2V_ROUTE_GENERIC, I2V_ROUTE_CONV_THIN, I2V_ROUTE_BIG_TILE, I2V_ROUTE_BIG_DEEP, I2V_ROUTE_BIG_SPLITK = 0, 1, 2, 3, 4
 I2V_EXTRA_NONE, I2V_EXTRA_LNF, I2V_EXTRA_HILO, I2V_EXTRA_GNS, I2V_EXTRA_UPF = 0, 1, 2, 4, 8
 I2V_TATTN_LDS_FORM, I2V_TATTN_REG_FORM = 0, 1
+I2V_ATTN_BWD_DQ1, I2V_ATTN_BWD_DQ2, I2V_ATTN_BWD_DQ2_LDS = 0, 1, 2
+I2V_ATTN_BWD_DKV1, I2V_ATTN_BWD_DKV2, I2V_ATTN_BWD_DKV2_LDS32, I2V_ATTN_BWD_DKV2_LDS64 = 0, 1, 2, 3
+I2V_ATTN_LSE, I2V_ATTN_LSE_LDS = 0, 1
+I2V_ATTN_BWD_KIND_DQ, I2V_ATTN_BWD_KIND_DKV, I2V_ATTN_BWD_KIND_LSE = 0, 1, 2
 I2V_ADD_RES_MAX = 16
 I2V_TAESD_PREP_IDENTITY, I2V_TAESD_PREP_UNIT, I2V_TAESD_PREP_CLAMP, I2V_TAESD_PREP_UNIT_CLAMP = 0, 1, 2, 4
 
@@ -100,6 +104,18 @@ class AttnBwdParams(C.Structure):
         ("lq", C.c_int32), ("lk", C.c_int32),
         ("scale", C.c_float), ("kv_partitions", C.c_int32), ("dkv_partial", C.c_void_p),
     ]
+
+
+class AttnBwdRoute(C.Structure):
+    """struct i2v_attn_bwd_route: the kernel instantiations an attention-backward problem takes"""
+    _fields_ = [
+        ("ks", C.c_int32), ("dt", C.c_int32),
+        ("dq_form", C.c_int32), ("dkv_form", C.c_int32), ("lse_form", C.c_int32),
+        ("kv_partitions", C.c_int32), ("dq_blocks", C.c_int32), ("dkv_blocks", C.c_int32),
+    ]
+
+    def as_dict(self):
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
 
 
 class TAttnParams(C.Structure):
@@ -308,6 +324,9 @@ SIGNATURES = {
                                             C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _P]),
     "i2v_attention_lse_f32": (C.c_int, [C.POINTER(AttnParams), _P, _P]),
     "i2v_attention_bwd_f16": (C.c_int, [C.POINTER(AttnBwdParams), _P]),
+    "i2v_attention_bwd_route": (C.c_int, [C.c_int32] * 7 + [C.POINTER(AttnBwdRoute)]),
+    "i2v_attention_bwd_last_route": (C.c_int, [C.POINTER(AttnBwdRoute)]),
+    "i2v_attn_bwd_kernel_exists": (C.c_int, [C.c_int32, C.POINTER(AttnBwdRoute)]),
     "i2v_transpose_f16": (C.c_int, [_P, C.c_int64, C.c_int64, _P, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P]),
     "i2v_rowdot_heads_f32": (C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P]),
     "i2v_layernorm_bwd_f16": (C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, _P, C.c_int64, _P, C.c_int64, C.c_int32, C.c_int32,

@@ -607,6 +607,23 @@ def last_tattn_route() -> dict:
     return r.as_dict()
 
 
+def attn_bwd_route(batch_q, kv_group, heads, head_dim, lq, lk, need_dkv=True) -> dict:
+    """the kernels `attention_bwd` / `attention_lse` take for these sizes, as the fields of i2v_attn_bwd_route (ks, dt, dq_form,
+    dkv_form, lse_form, kv_partitions, dq_blocks, dkv_blocks): host arithmetic, no GPU"""
+    r = _lib.AttnBwdRoute()
+    _lib.check(_lib.load().i2v_attention_bwd_route(batch_q, kv_group, heads, head_dim, lq, lk, int(need_dkv), C.byref(r)),
+               "i2v_attention_bwd_route")
+    return r.as_dict()
+
+
+def last_attn_bwd_route() -> dict:
+    """the kernels that this thread's most recent `attention_bwd` launch took, with the kv_partitions it ran with and the lse_form
+    of this thread's most recent `attention_lse` (-1 before one)"""
+    r = _lib.AttnBwdRoute()
+    _lib.check(_lib.load().i2v_attention_bwd_last_route(C.byref(r)), "i2v_attention_bwd_last_route")
+    return r.as_dict()
+
+
 def motion_attn_supported(rows, channels, heads, head_dim, frames):
     """is the fused LayerNorm + q / k / v + temporal attention kernel implemented for this shape?"""
     return bool(_lib.load().i2v_motion_attn_supported(rows, channels, heads, head_dim, frames))
@@ -2105,16 +2122,11 @@ def attention_bwd(q, k, v, o, dout, *, batch_q, lq, lk, heads, head_dim, kv_grou
 
 
 def dkv_partitions(batch_q, kv_group, heads, head_dim, lq, lk):
-    """how many workgroups share the frames of one K / V in the dK / dV sweep (1 = off): a power of two dividing kv_group that
-    brings the sweep to about one thousand workgroups."""
-    if os.environ.get("I2V_ATTN_BWD_PARTS", "1") == "0" or kv_group < 2 or lq < 32:
+    """how many workgroups share the frames of one K / V in the dK / dV sweep (1 = off): the count the library's dispatch rule
+    recommends (i2v_attn_bwd_route.kv_partitions); I2V_ATTN_BWD_PARTS=0 turns the partitions off."""
+    if os.environ.get("I2V_ATTN_BWD_PARTS", "1") == "0":
         return 1
-    two_k = lk >= 512 and head_dim <= 96                      # (the sweep's own choice of 128 or 64 keys per workgroup)
-    blocks = ((lk + 127) // 128 if two_k else (lk + 63) // 64) * heads * (batch_q // kv_group)
-    parts = 1
-    while parts * 2 <= min(kv_group, 8) and kv_group % (parts * 2) == 0 and blocks * parts < 1024:
-        parts *= 2
-    return parts
+    return attn_bwd_route(batch_q, kv_group, heads, head_dim, lq, lk)["kv_partitions"]
 
 
 def layernorm_bwd(x, dn, gamma, eps, add=None):

@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define I2V_ABI_VERSION 31
+#define I2V_ABI_VERSION 32
 
 #define I2V_OK 0
 #define I2V_ERR_INVALID_ARG (-1)
@@ -1085,6 +1085,41 @@ typedef struct i2v_attn_bwd_params {
   float* dkv_partial;    /* scratch, fp32 [2][kv_partitions][batch_q / kv_group * lk][heads * head_dim]                       */
 } i2v_attn_bwd_params;
 int i2v_attention_bwd_f16(const i2v_attn_bwd_params* p, i2v_stream_t stream);
+
+/* (ABI 32) Which kernels an attention-backward problem takes.  i2v_attention_bwd_f16 and i2v_attention_lse_f32 dispatch to 47 kernel
+   instantiations: 7 head-dim classes <ks, dt> (<1,2> <2,3> <2,4> <3,5> <3,6> <4,8> <5,10> for head_dim <= 32, 48, 64, 80, 96, 128,
+   160), the dQ sweep in the forms DQ1 (one 16-query tile per wave) | DQ2 (two tiles, lq >= 512) | DQ2_LDS (... with the key-side
+   operands staged in LDS, lk >= 64), the dK / dV sweep in DKV1 | DKV2 (lk >= 512) | DKV2_LDS32 (lq >= 64) | DKV2_LDS64 (lq >= 128,
+   64 staged queries per barrier), the two-tile forms in the classes with dt <= 6 only; the log-sum-exp in LSE (ks 1..5) | LSE_LDS
+   (lq >= 512, lk >= 64, ks <= 3).  I2V_ATTN_BWD_LDS=0 turns the LDS-staged forms off, I2V_ATTN_BWD_QB=32 the 64-query stage (both
+   read once per process).  The route is decided by the same function the launches follow (there is no second copy of the rules). */
+enum { I2V_ATTN_BWD_DQ1 = 0, I2V_ATTN_BWD_DQ2 = 1, I2V_ATTN_BWD_DQ2_LDS = 2 };
+enum { I2V_ATTN_BWD_DKV1 = 0, I2V_ATTN_BWD_DKV2 = 1, I2V_ATTN_BWD_DKV2_LDS32 = 2, I2V_ATTN_BWD_DKV2_LDS64 = 3 };
+enum { I2V_ATTN_LSE = 0, I2V_ATTN_LSE_LDS = 1 };
+enum { I2V_ATTN_BWD_KIND_DQ = 0, I2V_ATTN_BWD_KIND_DKV = 1, I2V_ATTN_BWD_KIND_LSE = 2 };   /* the kernel families of the launch table */
+
+/* (a struct tag only, as i2v_gemm_route) */
+struct i2v_attn_bwd_route {
+  int32_t ks, dt;         /* the head-dim class: 32-channel contraction steps, 16-channel output tiles                        */
+  int32_t dq_form;        /* I2V_ATTN_BWD_DQ*                                                                                 */
+  int32_t dkv_form;       /* I2V_ATTN_BWD_DKV*, -1 without the dK / dV sweep                                                  */
+  int32_t lse_form;       /* I2V_ATTN_LSE*: the form i2v_attention_lse_f32 takes for the same sizes                           */
+  int32_t kv_partitions;  /* the i2v_attn_bwd_params.kv_partitions the library recommends for the sizes (1 = off): a power of
+                             two <= 8 dividing kv_group that brings the dK / dV sweep to about one thousand workgroups        */
+  int32_t dq_blocks, dkv_blocks; /* grid x of the two sweeps (dkv_blocks 0 without the dK / dV sweep)                         */
+};
+
+/* The route i2v_attention_bwd_f16 (need_dkv = 0: called with dk = NULL) and i2v_attention_lse_f32 take for these sizes: pure host
+   arithmetic, no pointers, no device call.  The sizes are validated as the launches validate them (< 0: refused). */
+int i2v_attention_bwd_route(int32_t batch_q, int32_t kv_group, int32_t heads, int32_t head_dim, int32_t lq, int32_t lk,
+                            int32_t need_dkv, struct i2v_attn_bwd_route* route);
+/* The route of the calling thread's most recent i2v_attention_bwd_f16 that reached a launch (< 0: none yet).  kv_partitions is the
+   count that launch ran with (what the caller passed; 1 when off or without the dK / dV sweep); lse_form is that of the thread's
+   most recent i2v_attention_lse_f32, -1 before one. */
+int i2v_attention_bwd_last_route(struct i2v_attn_bwd_route* route);
+/* 1 if the instantiation that `route` names for the kernel family `kind` (I2V_ATTN_BWD_KIND_*: DQ reads ks, dt, dq_form; DKV ks, dt,
+   dkv_form; LSE ks, lse_form) is in the launch table, else 0.  Read from the launch table itself. */
+int i2v_attn_bwd_kernel_exists(int32_t kind, const struct i2v_attn_bwd_route* route);
 
 /* dst[b][c][r] = src[b][r][c] for r < rows, c < cols (fp16; strides in elements); dst columns [rows, rows rounded up to 8)
  * are zero-filled (ld_dst must cover them).  Channel-major copies of token-major activations: the K^T / Q^T / dO^T

@@ -1,12 +1,14 @@
-"""Host-side reference of the flash-attention backward (csrc/backward.hip: i2v_attention_bwd_f16, i2v_attention_lse_f32), the case
-tables of tests/test_attention_bwd_edges_gpu.py and a mirror of the kernels' launch choices.  No GPU import: the CPU suite
-(tests/test_attention_bwd_reference.py) checks the reference against autograd, the tables against the coverage they are meant to
-give, and the asserted bound against an emulation of the kernels' roundings on exactly the inputs the GPU tests use.
+"""Host-side reference of the flash-attention backward (csrc/attention_bwd.hip: i2v_attention_bwd_f16, i2v_attention_lse_f32), the
+case tables of tests/test_attention_bwd_edges_gpu.py and a helper that asks the library which kernels a case takes
+(i2v_attention_bwd_route: the launch choices live in the library alone).  No GPU import and nothing of the package at import time:
+the CPU suite (tests/test_attention_bwd_reference.py) checks the reference against autograd, the tables against the coverage they
+are meant to give, and the asserted bound against an emulation of the kernels' roundings on exactly the inputs the GPU tests use.
 
     P = softmax(s Q K^T)   dP = dO V^T   delta = rowsum(dO o O)   dS = P o (dP - delta)
     dQ = s dS K            dK = s sum_group dS^T Q                dV = sum_group P^T dO
 """
 import collections
+import ctypes as C
 import functools
 
 import torch
@@ -16,7 +18,7 @@ LOG2E = 1.4426950408889634
 Ref = collections.namedtuple("Ref", "dq dk dv o lse2")     # [bq, lq, C], [bkv, lk, C] x 2, [bq, lq, C], [bq, heads, lq] (log2)
 
 # ---------------------------------------------------------------------------------------------- case tables
-# (d, lq, lk, group, need_dkv): heads = 2, bkv = 2, bq = bkv * group.  What each row is there for (forms() below names the kernels):
+# (d, lq, lk, group, need_dkv): heads = 2, bkv = 2, bq = bkv * group.  What each row is there for (the forms as route_id() below names them):
 RAGGED = [
     (8, 70, 77, 1, True),       # class <= 32 (KS 1, DT 2), one-tile forms, attn_lse_kernel<1>; lq, lk not multiples of 8
     (16, 45, 515, 1, True),     # dkv2 (lk >= 512, lq < 64) with lq % 8 != 0: the zero-filled pad of Q^T / dO^T
@@ -35,6 +37,20 @@ RAGGED = [
     (40, 601, 77, 2, False),    # the text cross-attention through dq2_lds
     (40, 520, 4, 2, False),     # the IP-Adapter tokens through dq2
     (40, 260, 1000, 8, True),   # dkv2_lds64, 8 partitions, ragged lk
+    # every two-tile form in every class that has it (and the one-tile forms of classes (2, 4), (3, 6) beside them), at the smallest
+    # ragged lengths that reach the form: lq / lk just above 512, and below 64 | just above 64 | just above 128 on the other side
+    (24, 67, 517, 1, True),     # class (1, 2): dkv2_lds32
+    (40, 45, 517, 1, True),     # class (2, 3): dkv2
+    (64, 517, 45, 1, True),     # class (2, 4): dq2, dkv1
+    (56, 45, 517, 1, True),     # class (2, 4): dq1, dkv2
+    (64, 67, 517, 1, True),     # class (2, 4): dkv2_lds32
+    (80, 517, 45, 1, True),     # class (3, 5): dq2
+    (72, 517, 67, 1, True),     # class (3, 5): dq2_lds, attn_lse_lds_kernel<3> with partial d
+    (80, 45, 517, 1, True),     # class (3, 5): dkv2
+    (72, 67, 517, 1, True),     # class (3, 5): dkv2_lds32
+    (80, 131, 517, 1, True),    # class (3, 5): dkv2_lds64
+    (96, 517, 45, 1, True),     # class (3, 6): dq2, dkv1
+    (88, 45, 517, 1, True),     # class (3, 6): dkv2
 ]
 RAGGED_HEADS, RAGGED_BKV = 2, 2
 
@@ -143,39 +159,43 @@ def short_case(heads, d, frames):
     return (d, frames, frames, 1, heads, SHORT_PIXELS)
 
 
-# ---------------------------------------------------------------------------------------------- launch mirror
-def dkv_partitions(batch_q, kv_group, heads, head_dim, lq, lk):
-    """kernels.dkv_partitions without its environment switch, so that this module stays free of the package
-    (tests/test_attention_bwd_reference.py checks that the two agree on every case)."""
-    if kv_group < 2 or lq < 32:
-        return 1
-    two_k = lk >= 512 and head_dim <= 96
-    blocks = ((lk + 127) // 128 if two_k else (lk + 63) // 64) * heads * (batch_q // kv_group)
-    parts = 1
-    while parts * 2 <= min(kv_group, 8) and kv_group % (parts * 2) == 0 and blocks * parts < 1024:
-        parts *= 2
-    return parts
+# ---------------------------------------------------------------------------------------------- the library's route
+DQ_FORMS = ("dq1", "dq2", "dq2_lds")                          # I2V_ATTN_BWD_DQ* of include/i2v_hip.h, by value
+DKV_FORMS = ("dkv1", "dkv2", "dkv2_lds32", "dkv2_lds64")      # I2V_ATTN_BWD_DKV*
+LSE_FORMS = ("lse", "lse_lds")                                # I2V_ATTN_LSE*
+KIND_DQ, KIND_DKV, KIND_LSE = 0, 1, 2                         # I2V_ATTN_BWD_KIND_*
 
 
-CLASSES = [(32, 1, 2), (48, 2, 3), (64, 2, 4), (80, 3, 5), (96, 3, 6), (128, 4, 8), (160, 5, 10)]     # (max d, KS, DT)
+def ask_route(lib, d, lq, lk, group, bkv=RAGGED_BKV, need_dkv=True, heads=RAGGED_HEADS):
+    """i2v_attention_bwd_route for a case, as a dict of the fields of i2v_attn_bwd_route.  lib: the package's _lib module (this
+    module imports nothing of the package itself).  Host arithmetic only: no GPU."""
+    r = lib.AttnBwdRoute()
+    rc = lib.load().i2v_attention_bwd_route(bkv * group, group, heads, d, lq, lk, int(need_dkv), C.byref(r))
+    assert rc == 0, lib.load().i2v_last_error()
+    return r.as_dict()
 
 
-def forms(d, lq, lk, lds=True, qb64=True):
-    """(ks, dt, dq_form, dkv_form, lse_form): the template class and kernel forms launch_bwd / i2v_attention_lse_f32 of
-    csrc/backward.hip choose for (head_dim, lq, lk).  lds=False: I2V_ATTN_BWD_LDS=0; qb64=False: I2V_ATTN_BWD_QB=32."""
-    if d <= 0 or d % 8 != 0 or d > 160:
-        raise ValueError(f"head_dim {d}: a multiple of 8, <= 160")
-    ks, dt = next((ks, dt) for dmax, ks, dt in CLASSES if d <= dmax)
-    two_q, two_k = lq >= 512 and dt <= 6, lk >= 512 and dt <= 6
-    if two_q and lds and lk >= 64:
-        dq_form = "dq2_lds"
-    else:
-        dq_form = "dq2" if two_q else "dq1"
-    if two_k and lds and lq >= 128 and qb64:
-        dkv_form = "dkv2_lds64"
-    elif two_k and lds and lq >= 64:
-        dkv_form = "dkv2_lds32"
-    else:
-        dkv_form = "dkv2" if two_k else "dkv1"
-    lse_form = "lse_lds" if lds and lq >= 512 and lk >= 64 and (d + 31) // 32 <= 3 else "lse"
-    return ks, dt, dq_form, dkv_form, lse_form
+def route_forms(route):
+    """(ks, dt, dq_form, dkv_form, lse_form) of a route with the forms by name; dkv_form None without the dK / dV sweep, lse_form
+    None before the first log-sum-exp launch (a last route)"""
+    name = lambda names, v: names[v] if v >= 0 else None
+    return (route["ks"], route["dt"], name(DQ_FORMS, route["dq_form"]), name(DKV_FORMS, route["dkv_form"]),
+            name(LSE_FORMS, route["lse_form"]))
+
+
+def route_id(route):
+    """dq2_lds/dkv2_lds64/lse_lds"""
+    return "/".join(str(f) for f in route_forms(route)[2:])
+
+
+if __name__ == "__main__":
+    # the routes the library answers for ENV_CASES under this process's environment, as JSON [[ks, dt, dq, dkv, lse], ...]: the
+    # switches are read once per process, so tests/test_attention_bwd_reference.py asks each in a child that carries it.  No GPU.
+    import json
+    import os
+    import sys
+    if sys.argv[1:] != ["--routes"]:
+        sys.exit("usage: python tests/attn_bwd_reference.py --routes")
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    import i2v_adapter_unofficial_amd as pkg
+    print(json.dumps([route_forms(ask_route(pkg._lib, *c[:4])) for c in ENV_CASES]))

@@ -44,7 +44,8 @@ def test_ctypes_structs_match_header(lib):
     names = {"i2v_gemm_params": lib.GemmParams, "i2v_attn_params": lib.AttnParams, "i2v_tattn_params": lib.TAttnParams,
              "i2v_gn_params": lib.GnParams, "i2v_ln_params": lib.LnParams, "i2v_motion_attn_params": lib.MotionAttnParams,
              "i2v_cross_attn_fused_params": lib.CrossAttnFusedParams, "i2v_ff_fused_params": lib.FfFusedParams,
-             "struct i2v_gemm_route": lib.GemmRoute, "struct i2v_tattn_route": lib.TAttnRoute}
+             "struct i2v_gemm_route": lib.GemmRoute, "struct i2v_tattn_route": lib.TAttnRoute,
+             "i2v_attn_bwd_params": lib.AttnBwdParams, "struct i2v_attn_bwd_route": lib.AttnBwdRoute}
     prog = ['#include <stdio.h>', '#include <stddef.h>', f'#include "{HEADER}"', "int main(void){"]
     for cname, cls in names.items():
         prog.append(f'printf("{cname} %zu\\n", sizeof({cname}));')
@@ -103,6 +104,15 @@ def test_bad_arguments_return_error_codes_without_a_gpu(lib):
     qp.rows, qp.channels, qp.n_qk, qp.rows_per_image = 256, 320, 960, 128
     assert h.i2v_ln_qkv_f16(C.byref(qp), None) == -1 and b"null pointer" in h.i2v_last_error()
     assert h.i2v_ff_fused_f16(None, None) == -1
+    # (ABI 32) the attention backward's route queries: host arithmetic, the launch's own refusals
+    br = lib.AttnBwdRoute()
+    assert h.i2v_attention_bwd_route(32, 16, 8, 40, 4096, 4096, 1, C.byref(br)) == 0
+    assert br.as_dict() == dict(ks=2, dt=3, dq_form=lib.I2V_ATTN_BWD_DQ2_LDS, dkv_form=lib.I2V_ATTN_BWD_DKV2_LDS64,
+                                lse_form=lib.I2V_ATTN_LSE_LDS, kv_partitions=2, dq_blocks=32, dkv_blocks=32)
+    assert h.i2v_attn_bwd_kernel_exists(lib.I2V_ATTN_BWD_KIND_DKV, C.byref(br)) == 1
+    assert h.i2v_attention_bwd_route(32, 16, 8, 44, 4096, 4096, 1, C.byref(br)) == -1 and b"head_dim (44)" in h.i2v_last_error()
+    assert h.i2v_attention_bwd_route(32, 16, 8, 40, 4096, 4096, 1, None) == -1 and h.i2v_attention_bwd_last_route(None) == -1
+    assert h.i2v_attention_bwd_f16(None, None) == -1 and h.i2v_attention_lse_f32(None, None, None) == -1
     assert h.i2v_colsum_workspace_bytes(1000, 70) == 4 * 70 * 4 and h.i2v_colsum_det_f32(None, 0, None, 0, None, 0, 0, None, None) == -1
 
 

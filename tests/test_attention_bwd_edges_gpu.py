@@ -1,10 +1,12 @@
-"""The flash-attention backward (csrc/backward.hip) at every launch form, head-dim class and tail: the HIP kernels against the
-float64 reference of tests/attn_bwd_reference.py (explicit formulas, no autograd), on the case tables defined there.
-tests/test_attention_bwd_reference.py shows on the CPU that the tables reach every (KS, DT) class, every dQ / dK dV / log-sum-exp
-form, the lq / lk pads and the kv_partitions path, and that a kernel with the documented roundings sits within half of the bound.
+"""The flash-attention backward (csrc/attention_bwd.hip) at every kernel instantiation and tail: the HIP kernels against the
+float64 reference of tests/attn_bwd_reference.py (explicit formulas, no autograd), on the case tables defined there.  After every
+launch the library's own report of the kernels it took (kernels.last_attn_bwd_route()) must be the route written down by hand in
+tests/test_attention_bwd_reference.py, which also shows on the CPU that the tables reach every instantiation of the launch table,
+the lq / lk pads and the kv_partitions path, and that a kernel with the documented roundings sits within half of the bound.
 
 Bounds: gradients GRAD_REL_TOL (2.5e-3) of the largest reference entry, forward output 3e-3, log2-sum-exp 1e-3: the project's own
 (tests/parity.py, tests/test_training_gpu.py).  Measured on MI355X: profiles/attn_bwd_edges_errors.jsonl."""
+import json
 import os
 import subprocess
 import sys
@@ -14,6 +16,7 @@ import torch
 
 from tests import attn_bwd_reference as R
 from tests.parity import GRAD_REL_TOL, compare
+from tests.test_attention_bwd_reference import INTENDED, PARTS, SHORT_CLASS, SWITCHED
 
 pytestmark = pytest.mark.gpu
 FWD_REL_TOL, LSE_REL_TOL = 3e-3, 1e-3
@@ -24,9 +27,20 @@ def K():
     return p.kernels
 
 
-def _run(dev, inputs, *, heads, d, group, need_dkv=True, embed=None):
+def _assert_route(want, parts, need_dkv=True):
+    """the launch just made took the kernels the tables say: want = (ks, dt, dq_form, dkv_form, lse_form) by name, parts = the
+    kv_partitions it ran with"""
+    got = K().last_attn_bwd_route()
+    want = tuple(want) if need_dkv else tuple(want[:3]) + (None,) + tuple(want[4:])
+    parts = parts if need_dkv else 1
+    assert R.route_forms(got) == want and got["kv_partitions"] == parts, \
+        f"another kernel ran than the test is about: {R.route_forms(got)} x {got['kv_partitions']}, expected {want} x {parts}"
+
+
+def _run(dev, inputs, *, heads, d, group, want, parts, need_dkv=True, embed=None):
     """forward (with its log-sum-exp), attention_lse, and the backward from both statistics, on fp16 [b, l, C] host operands.
-    embed: a function that places a dense [rows, C] matrix on the device in the layout under test."""
+    embed: a function that places a dense [rows, C] matrix on the device in the layout under test.
+    want, parts: the route both backward launches must report (_assert_route)."""
     k_ = K()
     q, k, v, do = inputs
     (bq, lq, C), (bkv, lk, _) = q.shape, k.shape
@@ -39,7 +53,9 @@ def _run(dev, inputs, *, heads, d, group, need_dkv=True, embed=None):
     od_k, lse_k = k_.attention(qd, kd, k_.transpose_tokens(vd, lk), return_lse="fused", **kw)
     assert torch.equal(od, od_k)
     grads = k_.attention_bwd(qd, kd, vd, od, dod, need_dkv=need_dkv, **kw)                    # recomputes the log-sum-exp
+    _assert_route(want, parts, need_dkv)
     grads_f = k_.attention_bwd(qd, kd, vd, od, dod, need_dkv=need_dkv, lse=lse_f, **kw)      # the one the forward wrote
+    _assert_route(want, parts, need_dkv)
     return dict(o=od, lse=lse, lse_f=lse_f, lse_k=lse_k, grads=grads, grads_f=grads_f, dev=(qd, kd, vd, dod), kw=kw)
 
 
@@ -67,7 +83,12 @@ def _same(a, b):
 
 def _tag(case):
     d, lq, lk = case[:3]
-    return f"attn bwd d={d} lq={lq} lk={lk} group={case[3]} {'/'.join(R.forms(d, lq, lk)[2:])}"
+    return f"attn bwd d={d} lq={lq} lk={lk} group={case[3]} {'/'.join(INTENDED[(d, lq, lk)][2:])}"
+
+
+def _want(case):
+    """(forms, kv_partitions at bkv = 2) of a ragged / strided / scaled case, from the hand-written tables"""
+    return dict(want=INTENDED[case[:3]], parts=PARTS[case[:4]][1])
 
 
 @pytest.mark.parametrize("case", R.RAGGED, ids=R.case_id)
@@ -79,16 +100,18 @@ def test_ragged(dev, case):
     heads, bkv = R.RAGGED_HEADS, R.RAGGED_BKV
     k_ = K()
     inputs, ref = R.case_data(d, lq, lk, group)
-    run = _run(dev, inputs, heads=heads, d=d, group=group, need_dkv=need_dkv)
+    run = _run(dev, inputs, heads=heads, d=d, group=group, need_dkv=need_dkv, **_want(case))
     _check(run, ref, _tag(case), need_dkv)
     qd, kd, vd, dod = run["dev"]
     again = k_.attention_bwd(qd, kd, vd, run["o"], dod, need_dkv=need_dkv, **run["kw"])
+    _assert_route(INTENDED[case[:3]], PARTS[case[:4]][1], need_dkv)
     assert _same(run["grads"], again), "a second identical call differs"
     # batch independence, bit for bit: K / V entry 0 with its whole group of query batches
     assert k_.dkv_partitions(bkv * group, group, heads, d, lq, lk) == k_.dkv_partitions(group, group, heads, d, lq, lk)
     nq, nk = group * lq, lk
     one = k_.attention_bwd(qd[:nq].clone(), kd[:nk].clone(), vd[:nk].clone(), run["o"][:nq].clone(), dod[:nq].clone(),
                            need_dkv=need_dkv, **dict(run["kw"], batch_q=group))
+    _assert_route(INTENDED[case[:3]], PARTS[case[:4]][0], need_dkv)
     dq, dk, dv = run["grads"]
     assert torch.equal(dq[:nq], one[0]), "dQ of batch entry 0 depends on the other entries"
     if need_dkv:
@@ -101,16 +124,18 @@ def test_short_sequences(dev, case):
     """a motion module's shape: batch = pixels, lq = lk = frames <= 32, most of a 32-row block masked"""
     heads, d, f = case
     inputs, ref = R.case_data(*R.short_case(heads, d, f))
-    run = _run(dev, inputs, heads=heads, d=d, group=1)
+    want = SHORT_CLASS[d] + ("dq1", "dkv1", "lse")
+    run = _run(dev, inputs, heads=heads, d=d, group=1, want=want, parts=1)
     _check(run, ref, f"attn bwd short heads={heads} d={d} F={f}")
     qd, kd, vd, dod = run["dev"]
     assert _same(run["grads"], K().attention_bwd(qd, kd, vd, run["o"], dod, **run["kw"])), "a second identical call differs"
+    _assert_route(want, 1)
 
 
 def _one_frame(dev, key):
     heads, d, f = R.ONE_FRAME
     inputs, ref = R.case_data(*R.short_case(heads, d, f))
-    run = _run(dev, inputs, heads=heads, d=d, group=1)
+    run = _run(dev, inputs, heads=heads, d=d, group=1, want=SHORT_CLASS[d] + ("dq1", "dkv1", "lse"), parts=1)
     C = heads * d
     compare(run["o"], ref.o.reshape(-1, C), rel=FWD_REL_TOL, name="attn bwd one frame: forward output")
     lim = 1e-3 * ref.dv.abs().max().item()
@@ -151,8 +176,8 @@ def test_strided_operands(dev, case):
         buf[:, 8:8 + C] = t.to(dev)
         return buf[:, 8:8 + C]
 
-    dense = _run(dev, inputs, heads=heads, d=d, group=group)
-    strided = _run(dev, inputs, heads=heads, d=d, group=group, embed=embed)
+    dense = _run(dev, inputs, heads=heads, d=d, group=group, **_want(case))
+    strided = _run(dev, inputs, heads=heads, d=d, group=group, embed=embed, **_want(case))
     assert strided["dev"][0].stride(0) == C + 16 and not strided["dev"][0].is_contiguous()
     _check(strided, ref, _tag(case) + " strided", grads_only=True)
     assert torch.equal(dense["o"], strided["o"]) and torch.equal(dense["lse"], strided["lse"])
@@ -166,12 +191,12 @@ def test_gradient_scale(dev, case, exp):
     d, lq, lk, group, _ = case
     heads = R.RAGGED_HEADS
     inputs, ref = R.case_data(d, lq, lk, group, heads, R.RAGGED_BKV, exp)
-    run = _run(dev, inputs, heads=heads, d=d, group=group)
+    run = _run(dev, inputs, heads=heads, d=d, group=group, **_want(case))
     _check(run, ref, _tag(case) + f" dO*2^{exp}", grads_only=True)
 
 
 _CHILD = r"""
-import sys, torch
+import json, sys, torch
 sys.path.insert(0, %r)
 from tests import attn_bwd_reference as R
 import i2v_adapter_unofficial_amd as pkg
@@ -186,6 +211,8 @@ for d, lq, lk, group, _ in R.ENV_CASES:
     got = k_.attention_bwd(qd, kd, vd, od, dod, **kw)
     rel = [(g.double().cpu() - r.reshape(-1, C)).abs().max().item() / r.abs().max().item() for g, r in zip(got, (ref.dq, ref.dk, ref.dv))]
     assert all(torch.isfinite(g).all() for g in got)
+    route = k_.last_attn_bwd_route()
+    print("ROUTE", json.dumps([list(R.route_forms(route)), route["kv_partitions"]]))
     print("REL", d, lq, lk, group, *rel)
 print("OK")
 """
@@ -194,13 +221,20 @@ print("OK")
 @pytest.mark.parametrize("switch,value", R.ENV_SWITCHES)
 def test_environment_switches_in_child_process(dev, switch, value):
     """I2V_ATTN_BWD_LDS=0 (the L2-fed two-tile forms at long lengths) and I2V_ATTN_BWD_QB=32 (32 staged queries per barrier) are
-    read once per process, hence the child: the same bound against the same reference"""
+    read once per process, hence the child: the same bound against the same reference, and the switch really moved the case:
+    dq2 / dkv2 / lse under I2V_ATTN_BWD_LDS=0, dkv2_lds32 under I2V_ATTN_BWD_QB=32"""
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, "-c", _CHILD % root], env=dict(os.environ, **{switch: value}), capture_output=True,
                        text=True, timeout=300)
     assert r.returncode == 0 and "OK" in r.stdout, r.stdout + r.stderr
     lines = [ln.split()[1:] for ln in r.stdout.splitlines() if ln.startswith("REL ")]
     assert len(lines) == len(R.ENV_CASES)
+    routes = [json.loads(ln[len("ROUTE "):]) for ln in r.stdout.splitlines() if ln.startswith("ROUTE ")]
+    assert len(routes) == len(R.ENV_CASES)
+    for (forms, parts), case, want in zip(routes, R.ENV_CASES, SWITCHED[(switch, value)]):
+        assert tuple(forms) == want != INTENDED[case[:3]] and parts == PARTS[case[:4]][1], f"{switch}={value} {case}: ran {forms} x {parts}"
+    moved = {"I2V_ATTN_BWD_LDS": ("dq2", "dkv2", "lse"), "I2V_ATTN_BWD_QB": ("dq2_lds", "dkv2_lds32", "lse_lds")}[switch]
+    assert all(tuple(forms[2:]) == moved for forms, _ in routes)
     from tests.parity import log_error
     for (d, lq, lk, group, *rels), case in zip(lines, R.ENV_CASES):
         assert (int(d), int(lq), int(lk), int(group)) == case[:4]

@@ -10,7 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # I2V_LIB_PATH selects another build of the same ABI (same-box A/B of two kernels, tools/ab_bench.sh); the in-tree
 # library is never overwritten by tooling
 LIB_PATH = os.environ.get("I2V_LIB_PATH") or os.path.join(_HERE, "libi2v_hip.so")
-ABI_VERSION = 32
+ABI_VERSION = 33
 
 I2V_EPI_NONE, I2V_EPI_GELU, I2V_EPI_GEGLU = 0, 1, 2
 I2V_STORE_ROWMAJOR, I2V_STORE_ROWPERM, I2V_STORE_VT, I2V_STORE_VT_T = 0, 1, 2, 3
@@ -24,6 +24,7 @@ I2V_ATTN_BWD_DKV1, I2V_ATTN_BWD_DKV2, I2V_ATTN_BWD_DKV2_LDS32, I2V_ATTN_BWD_DKV2
 I2V_ATTN_LSE, I2V_ATTN_LSE_LDS = 0, 1
 I2V_ATTN_BWD_KIND_DQ, I2V_ATTN_BWD_KIND_DKV, I2V_ATTN_BWD_KIND_LSE = 0, 1, 2
 I2V_ADD_RES_MAX = 16
+I2V_ADD_RES_NETS_MAX = 4
 I2V_TAESD_PREP_IDENTITY, I2V_TAESD_PREP_UNIT, I2V_TAESD_PREP_CLAMP, I2V_TAESD_PREP_UNIT_CLAMP = 0, 1, 2, 4
 
 
@@ -258,6 +259,16 @@ class AddResidualsParams(C.Structure):
                 ("step_idx", C.c_void_p)]
 
 
+class AddMultiResidualsEntry(C.Structure):
+    _fields_ = [("dst", C.c_void_p), ("dst_lo", C.c_void_p), ("skip", C.c_void_p), ("skip_lo", C.c_void_p),
+                ("res", C.c_void_p * I2V_ADD_RES_NETS_MAX), ("numel", C.c_int64)]
+
+
+class AddMultiResidualsParams(C.Structure):
+    _fields_ = [("t", AddMultiResidualsEntry * I2V_ADD_RES_MAX), ("n", C.c_int32), ("n_nets", C.c_int32), ("scale_rows", C.c_int32),
+                ("scale_table", C.c_void_p), ("step_idx", C.c_void_p)]
+
+
 class ConvC64Params(C.Structure):
     _fields_ = [
         ("x", C.c_void_p), ("ldx", C.c_int64),
@@ -384,6 +395,7 @@ SIGNATURES = {
                                               C.c_int32, C.c_int32, C.c_int32, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                               C.c_float, _P]),
     "i2v_add_residuals_f16": (C.c_int, [C.POINTER(AddResidualsParams), _P]),
+    "i2v_add_multi_residuals_f16": (C.c_int, [C.POINTER(AddMultiResidualsParams), _P]),
     "i2v_conv3x3_c64_f16": (C.c_int, [C.POINTER(ConvC64Params), _P]),
     "i2v_conv3x3_c64_prelu_f16": (C.c_int, [C.POINTER(ConvC64Params), _P, _P]),
     "i2v_pixel_shuffle_add_f32": (C.c_int, [_P, C.c_int64, _P, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,

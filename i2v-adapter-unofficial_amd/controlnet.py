@@ -377,6 +377,18 @@ class ControlNetModel(SampleProjectionMixin, PretrainedMixin, HipModule):
                 guess_mode: bool = False, return_dict: bool = True):
         """sample (B, F, C, H, W) or (N, C, H, W); timestep a number, a scalar or [B]; encoder_hidden_states [B, L, D] with N % B == 0;
         controlnet_cond (N, 3, 8 H, 8 W) in [0, 1].  Returns NCHW tensors (N, C_i, h_i, w_i) in sample's dtype."""
+        down, mid, dt = self._forward_checked(sample, timestep, encoder_hidden_states, controlnet_cond, conditioning_scale, class_labels,
+                                              timestep_cond, attention_mask, added_cond_kwargs, guess_mode)
+        down = tuple(K.tokens_to_nchw(t, dtype=dt) for t in down)
+        mid = K.tokens_to_nchw(mid, dtype=dt)
+        if not return_dict:
+            return down, mid
+        return ControlNetOutput(down_block_res_samples=down, mid_block_res_sample=mid)
+
+    def _forward_checked(self, sample, timestep, encoder_hidden_states, controlnet_cond, conditioning_scale, class_labels, timestep_cond,
+                         attention_mask, added_cond_kwargs, guess_mode):
+        """`forward`'s argument checks and its launches up to the token-major outputs: (12 down tensors, mid tensor, the dtype `forward`
+        returns).  MultiControlNetModel runs every net through here."""
         if guess_mode:
             raise NotImplementedError("guess_mode=True is not implemented")
         if attention_mask is not None:
@@ -408,9 +420,88 @@ class ControlNetModel(SampleProjectionMixin, PretrainedMixin, HipModule):
         x = K.nchw_to_tokens(sample, p["cin_pad"])
         down, mid = self._fwd_tokens(x, self.project_time_table(timesteps), ctx, self.embed_condition(controlnet_cond),
                                      out_scale=conditioning_scale)
-        dt = sample.dtype if sample.dtype in (torch.float32, f16) else f16
-        down = tuple(K.tokens_to_nchw(t, dtype=dt) for t in down)
-        mid = K.tokens_to_nchw(mid, dtype=dt)
+        return down, mid, sample.dtype if sample.dtype in (torch.float32, f16) else f16
+
+
+class MultiControlNetModel(nn.Module):
+    """diffusers' MultiControlNetModel: 1 .. I2V_ADD_RES_NETS_MAX ControlNetModels in `.nets` whose outputs are summed.  The nets may
+    differ in their conditioning channels (a 1-channel edge net beside a 3-channel pose net); they serve one UNet, so their outputs
+    have one geometry.  The pipeline takes it as `controlnet=` and then takes one list entry per net for `control_image` (and a float
+    or a list for the scale and the window); its captured step runs the nets one after the other and adds all their residuals in one
+    launch (K.add_multi_residuals)."""
+
+    def __init__(self, controlnets):
+        super().__init__()
+        if not isinstance(controlnets, (list, tuple, nn.ModuleList)):
+            raise TypeError(f"MultiControlNetModel takes a list of ControlNetModels, got {type(controlnets)}")
+        nets = list(controlnets)
+        if not 1 <= len(nets) <= K._lib.I2V_ADD_RES_NETS_MAX:
+            raise ValueError(f"MultiControlNetModel holds 1 .. {K._lib.I2V_ADD_RES_NETS_MAX} ControlNets (the residuals of all of them are "
+                             f"added in one launch), got {len(nets)}")
+        for i, net in enumerate(nets):
+            if not isinstance(net, ControlNetModel):
+                raise TypeError(f"MultiControlNetModel: entry {i} is a {type(net).__name__}, not a ControlNetModel")
+        self.nets = nn.ModuleList(nets)
+
+    def __len__(self):
+        return len(self.nets)
+
+    @property
+    def dtype(self):
+        return self.nets[0].dtype
+
+    @property
+    def device(self):
+        return self.nets[0].device
+
+    def weight_signature(self):
+        """the nets' signatures, concatenated: what a captured step that launches all of them was captured against"""
+        return tuple(e for net in self.nets for e in net.weight_signature())
+
+    # ------------------------------------------------------------------ diffusers' folder names: dir, dir_1, dir_2, ...
+    def save_pretrained(self, save_directory: str, **kwargs):
+        for i, net in enumerate(self.nets):
+            net.save_pretrained(save_directory if i == 0 else f"{save_directory}_{i}", **kwargs)
+
+    @classmethod
+    def from_pretrained(cls, pretrained_model_path: str, **kwargs):
+        import os
+        nets, path = [], pretrained_model_path
+        while os.path.isdir(path):
+            nets.append(ControlNetModel.from_pretrained(path, **kwargs))
+            path = f"{pretrained_model_path}_{len(nets)}"
+        if not nets:
+            raise ValueError(f"No ControlNets found under {os.path.dirname(pretrained_model_path)}. Expected at least "
+                             f"{pretrained_model_path}.")
+        return cls(nets)
+
+    def _per_net(self, value, name):
+        if isinstance(value, (list, tuple)):
+            if len(value) != len(self.nets):
+                raise ValueError(f"`{name}` holds {len(value)} entries for {len(self.nets)} ControlNets")
+            return list(value)
+        return [value] * len(self.nets)
+
+    def forward(self, sample, timestep, encoder_hidden_states, controlnet_cond, conditioning_scale, class_labels=None,
+                timestep_cond=None, attention_mask=None, added_cond_kwargs=None, cross_attention_kwargs=None,
+                guess_mode: bool = False, return_dict: bool = True):
+        """diffusers' MultiControlNetModel.forward: `controlnet_cond` and `conditioning_scale` are lists with one entry per net (a
+        float is taken for all nets); the other arguments are ControlNetModel.forward's and are checked by every net.  Each net runs
+        unscaled; the scaled outputs are summed in fp32 in net order and rounded once (K.add_multi_residuals onto zeros).  Returns the
+        summed (down_block_res_samples, mid_block_res_sample), NCHW in sample's dtype."""
+        if not isinstance(controlnet_cond, (list, tuple)):
+            raise ValueError(f"`controlnet_cond` is a list with one entry per ControlNet, got {type(controlnet_cond)}")
+        conds = self._per_net(controlnet_cond, "controlnet_cond")
+        scales = [float(s) for s in self._per_net(conditioning_scale, "conditioning_scale")]
+        sets, dt = [], None
+        for net, cond in zip(self.nets, conds):
+            down, mid, dt = net._forward_checked(sample, timestep, encoder_hidden_states, cond, 1.0, class_labels, timestep_cond,
+                                                 attention_mask, added_cond_kwargs, guess_mode)
+            sets.append(list(down) + [mid])
+        table = torch.tensor(scales, dtype=torch.float32, device=sets[0][0].device).view(len(scales), 1)
+        summed = K.add_multi_residuals([torch.zeros_like(t) for t in sets[0]], sets, scale=(table, None))
+        outs = [K.tokens_to_nchw(t, dtype=dt) for t in summed]
+        down, mid = tuple(outs[:-1]), outs[-1]
         if not return_dict:
             return down, mid
         return ControlNetOutput(down_block_res_samples=down, mid_block_res_sample=mid)

@@ -1617,6 +1617,66 @@ def add_residuals(skips, residuals, scale=None, out=None):
     return outs
 
 
+def add_multi_residuals(skips, residual_sets, scale=None, out=None):
+    """The residuals of N ControlNets into skip tensors in one launch (i2v_add_multi_residuals_f16): out_i = skip_i + sum_k s_k *
+    residual_sets[k][i], summed in fp32 in net order and rounded once.  residual_sets: a list of N (1 .. I2V_ADD_RES_NETS_MAX) lists
+    shaped like `skips`.  scale = None (every s_k = 1) or (table fp32 [N, rows], step_idx int32 [1] or None):
+    s_k = table[k, clamp(*step_idx)], read on the device.  `out`, the precise residual stream's low halves and the split over several
+    launches beyond I2V_ADD_RES_MAX tensors are `add_residuals`'; with N = 1 so are the bits.  Returns the list of results."""
+    lib = _lib.load()
+    skips, sets = list(skips), [list(r) for r in residual_sets]
+    if not 1 <= len(sets) <= _lib.I2V_ADD_RES_NETS_MAX:
+        raise ValueError(f"add_multi_residuals: {len(sets)} residual sets, not 1 .. {_lib.I2V_ADD_RES_NETS_MAX}")
+    for k, rs in enumerate(sets):
+        if len(skips) != len(rs) or not skips:
+            raise ValueError(f"add_multi_residuals: {len(skips)} skip tensors and {len(rs)} residuals in set {k}")
+    if out is not None and len(out) != len(skips):
+        raise ValueError(f"add_multi_residuals: {len(out)} outputs for {len(skips)} skip tensors")
+    table = idx = None
+    if scale is not None:
+        table, idx = scale
+        _req(table, "scale table", dtype=torch.float32)
+        if table.dim() != 2 or table.shape[0] != len(sets) or table.shape[1] < 1 or not table.is_contiguous():
+            raise ValueError(f"add_multi_residuals: the scale table is a contiguous fp32 [{len(sets)}, rows] matrix, one row per set")
+        if idx is not None:
+            _req(idx, "step_idx", dtype=torch.int32)
+    outs, los = [], []
+    for i, s in enumerate(skips):
+        _req(s, f"skips[{i}]")
+        for k, rs in enumerate(sets):
+            r = _req(rs[i], f"residual_sets[{k}][{i}]")
+            if s.shape != r.shape or not s.is_contiguous() or not r.is_contiguous():
+                raise ValueError(f"add_multi_residuals: tensor {i}: skip {tuple(s.shape)} and residual {tuple(r.shape)} of set {k} must "
+                                 "be contiguous tensors of one shape")
+        if s.numel() == 0 or s.numel() % 8 != 0:
+            raise ValueError(f"add_multi_residuals: tensor {i} has {s.numel()} values, not a positive multiple of 8")
+        lo = lo_of(s)
+        if lo is not None and (lo.shape != s.shape or lo.stride() != s.stride() or lo.dtype != f16):
+            raise ValueError("the low half of a stream tensor must be laid out like the tensor")
+        o = torch.empty_like(s) if out is None else _req(out[i], f"out[{i}]")
+        if o.shape != s.shape or not o.is_contiguous():
+            raise ValueError(f"add_multi_residuals: out[{i}] must be contiguous {tuple(s.shape)}")
+        outs.append(o)
+        los.append(None if lo is None else (lo if o is s else torch.empty_like(s)))
+    for first in range(0, len(skips), _lib.I2V_ADD_RES_MAX):
+        p = _lib.AddMultiResidualsParams()
+        n = min(_lib.I2V_ADD_RES_MAX, len(skips) - first)
+        for j in range(n):
+            i, e = first + j, p.t[j]
+            e.dst, e.dst_lo, e.skip, e.skip_lo = _p(outs[i]), _p(los[i]), _p(skips[i]), _p(lo_of(skips[i]))
+            for k, rs in enumerate(sets):
+                e.res[k] = _p(rs[i])
+            e.numel = skips[i].numel()
+        p.n, p.n_nets = n, len(sets)
+        if table is not None:
+            p.scale_table, p.scale_rows, p.step_idx = _p(table), table.shape[1], _p(idx)
+        _lib.check(lib.i2v_add_multi_residuals_f16(C.byref(p), _stream()), "i2v_add_multi_residuals_f16")
+    for o, lo in zip(outs, los):
+        if lo is not None:
+            o._i2v_lo = lo
+    return outs
+
+
 # ---------------------------------------------------------------------------------------------- T2I-Adapter (t2i_adapter.py)
 def pixel_unshuffle8(src):
     """PixelUnshuffle(8) of [N, C, H, W] fp32 / fp16 images (C = 1 or 3; H, W multiples of 8) -> tokens fp16 [N, H / 8, W / 8, 64 C] in

@@ -77,7 +77,7 @@ def _draw(fn, shape, generator, device):
 
 
 # The per-sample device buffers a captured step reads, by their key in the state dict `st`: each a tensor, a tuple of tensors
-# (t2i_feats) or absent / None.  The ONE list of them: a graph-cache hit copies exactly these into the graph's static buffers
+# (t2i_feats; cn_cond with a MultiControlNetModel, one per net) or absent / None.  The ONE list of them: a graph-cache hit copies exactly these into the graph's static buffers
 # (`_copy_sample_inputs`, in this order) and `_graph_key` holds the shape and dtype of exactly these, so what is copied in always
 # fits.  Not listed: `x0_prev` (DPM-Solver++) is the step's own history, not a sample input -- the first step of a sample does not
 # read it; `ctx_proj`, `temb_table` and the ControlNet's pair are projected from these into the static buffers (`_project_once`).
@@ -177,7 +177,7 @@ class I2VAdapterPipeline:
         if unet is None:
             raise ValueError("`unet` is required")
         if isinstance(controlnet, (list, tuple)):
-            raise NotImplementedError("a list of ControlNets (diffusers' MultiControlNetModel) is not implemented: pass one ControlNetModel")
+            raise NotImplementedError("a list of ControlNets is not taken as it is: wrap it, `MultiControlNetModel([a, b])`")
         self.controlnet = controlnet
         if isinstance(t2i_adapter, (list, tuple)):
             raise NotImplementedError("a list of T2I-Adapters (diffusers' MultiAdapter) is not implemented: pass one T2IAdapter")
@@ -711,7 +711,14 @@ class I2VAdapterPipeline:
         # the time-embedding chain of this step's timestep: one row of the table computed once per sample (_time_table)
         temb_proj = K.select_row(st["temb_table"], st["step_idx"])
         control = {}
-        if st.get("cn_cond") is not None:
+        if isinstance(st.get("cn_cond"), tuple):
+            # several ControlNets: one after the other on this stream (no parallel branches in the captured graph), each on the step's
+            # model input with its own control frames, context projection and time table; the UNet adds all their residuals in one
+            # launch per add, each net at this step's value of its own row of the [N, steps] scale table
+            sets = [net._fwd_tokens(x, K.select_row(temb, st["step_idx"]), ctx, cond) for net, temb, ctx, cond in
+                    zip(self.controlnet.nets, st["cn_temb_table"], st["cn_ctx_proj"], st["cn_cond"])]
+            control = dict(residual_sets=sets, residual_scale=(st["cn_scale"], st["step_idx"]))
+        elif st.get("cn_cond") is not None:
             # the ControlNet reads the step's model input -- frame 0 already replaced by the condition latents, the tensor the UNet
             # reads -- and writes its 12 + 1 residuals; the UNet adds them at this step's row of the scale table
             down, mid = self.controlnet._fwd_tokens(x, K.select_row(st["cn_temb_table"], st["step_idx"]), st["cn_ctx_proj"], st["cn_cond"])
@@ -746,7 +753,12 @@ class I2VAdapterPipeline:
         old = (lambda name: st[name]) if into else (lambda name: None)
         st["ctx_proj"] = self.unet.project_context(st["ctx_text"], st["ctx_ip"], out=old("ctx_proj"))
         st["temb_table"] = self.unet.project_time_table(st["t_table"], out=old("temb_table"))
-        if st.get("cn_cond") is not None:
+        if isinstance(st.get("cn_cond"), tuple):                      # several ControlNets: one projection and one table per net
+            nets = self.controlnet.nets
+            olds = lambda name: old(name) or (None,) * len(nets)
+            st["cn_ctx_proj"] = tuple(net.project_context(st["ctx_text"], out=o) for net, o in zip(nets, olds("cn_ctx_proj")))
+            st["cn_temb_table"] = tuple(net.project_time_table(st["t_table"], out=o) for net, o in zip(nets, olds("cn_temb_table")))
+        elif st.get("cn_cond") is not None:
             st["cn_ctx_proj"] = self.controlnet.project_context(st["ctx_text"], out=old("cn_ctx_proj"))
             st["cn_temb_table"] = self.controlnet.project_time_table(st["t_table"], out=old("cn_temb_table"))
 
@@ -837,26 +849,66 @@ class I2VAdapterPipeline:
         if control_image is None:
             raise ValueError("the pipeline has a `controlnet`: `control_image` is required (one control frame per frame of the clip)")
         from .controlnet import controlnet_keep_table
+        if self._multi_controlnet():
+            nets = self.controlnet.nets
+            if not isinstance(control_image, (list, tuple)) or len(control_image) != len(nets):
+                n = len(control_image) if isinstance(control_image, (list, tuple)) else 1
+                raise ValueError(f"`control_image` holds {n} entries, the pipeline has {len(nets)} ControlNets: with a "
+                                 "MultiControlNetModel it is a list with one entry per net, each what a single ControlNet takes")
+            for k, (net, frames, args) in enumerate(zip(nets, control_image, self._control_args(scale, start, end))):
+                controlnet_keep_table(1, *args)                        # each net's own window
+                n = _frame_count(frames, f"control_image[{k}]", net.config.conditioning_channels, "the ControlNet's `conditioning_channels`")
+                if n != num_frames:
+                    raise ValueError(f"`control_image[{k}]` holds {n} frames, `num_frames` is {num_frames}: a ControlNet runs per frame "
+                                     "and needs one control frame for every frame of the clip")
+            return
         controlnet_keep_table(1, scale, start, end)                    # 0 <= start < end <= 1, else ValueError
         n = _frame_count(control_image, "control_image", 3)
         if n != num_frames:
             raise ValueError(f"`control_image` holds {n} frames, `num_frames` is {num_frames}: a ControlNet runs per frame and needs one "
                              "control frame for every frame of the clip")
 
-    def prepare_control_image(self, control_image, batch_size, num_frames, height, width):
+    def prepare_control_image(self, control_image, batch_size, num_frames, height, width, channels: int = 3):
         """-> fp32 [batch_size * num_frames, 3, height, width] in [0, 1] on the host: PIL images resized by the image processor WITHOUT
         the [-1, 1] normalisation (a ControlNet is trained on [0, 1] maps); tensors as they are (they must have that size); one clip
-        of control frames is shared by the batch."""
+        of control frames is shared by the batch.  channels: a net's `conditioning_channels` where it is not 3 (a net of a
+        MultiControlNetModel) -- tensors must have that many, PIL images are converted to "L" for 1."""
         if isinstance(control_image, torch.Tensor):
-            t = _frame_tensor(control_image, "control_image", height, width, batch_size, num_frames)
+            t = _frame_tensor(control_image, "control_image", height, width, batch_size, num_frames,
+                              *(() if channels == 3 else (channels, "the ControlNet's `conditioning_channels`")))
         else:
             if len(control_image) != num_frames:
                 raise ValueError(f"`control_image` holds {len(control_image)} frames, `num_frames` is {num_frames}")
-            t = self.control_image_processor.preprocess(list(control_image), height=height, width=width)
+            if channels == 1:
+                t = torch.stack([_pil_plane(im, "control_image", "L", height, width)[None] for im in control_image])
+            else:
+                t = self.control_image_processor.preprocess(list(control_image), height=height, width=width)
             if tuple(t.shape[-2:]) != (height, width):
                 raise ValueError(f"control frames of {tuple(t.shape[-2:])} after resizing, expected {height} x {width}")
             t = t[None].expand(batch_size, -1, -1, -1, -1)
-        return t.reshape(batch_size * num_frames, 3, height, width).contiguous()
+        return t.reshape(batch_size * num_frames, channels, height, width).contiguous()
+
+    def _multi_controlnet(self):
+        from .controlnet import MultiControlNetModel
+        return isinstance(self.controlnet, MultiControlNetModel)
+
+    def _control_args(self, scale, start, end):
+        """(scale, start, end) of a call as `_schedule_tables` keeps them: three floats, or with a MultiControlNetModel one such triple
+        per net -- each argument a number for all nets or a list with one entry per net (diffusers' rule); a list of another length
+        is a ValueError."""
+        if not self._multi_controlnet():
+            return float(scale), float(start), float(end)
+        n = len(self.controlnet.nets)
+        cols = []
+        for name, v in (("controlnet_conditioning_scale", scale), ("control_guidance_start", start), ("control_guidance_end", end)):
+            if isinstance(v, (list, tuple)):
+                if len(v) != n:
+                    raise ValueError(f"`{name}` holds {len(v)} values, the pipeline has {n} ControlNets: pass one number for all "
+                                     "nets or a list with one per net")
+                cols.append([float(x) for x in v])
+            else:
+                cols.append([float(v)] * n)
+        return tuple(zip(*cols))
 
     # ------------------------------------------------------------------------------------------ T2I-Adapter
     def _check_adapter_args(self, adapter_image, num_frames, scale, factor):
@@ -1253,7 +1305,9 @@ class I2VAdapterPipeline:
         `precise_stream` are additions, and so are the ControlNet arguments, which carry the names of diffusers'
         StableDiffusionControlNetPipeline: `control_image` -- `num_frames` PIL images, a [F, 3, H, W] tensor in [0, 1] shared by the
         batch or a [B, F, 3, H, W] tensor in [0, 1] --, `controlnet_conditioning_scale`, and the window
-        `control_guidance_start` .. `control_guidance_end` of the schedule, as fractions, in which the control acts; and the
+        `control_guidance_start` .. `control_guidance_end` of the schedule, as fractions, in which the control acts -- with a
+        `MultiControlNetModel` of N nets `control_image` is a list of N such entries, each with its net's `conditioning_channels`,
+        and the scale and the two window arguments are each a number for all nets or a list of N --; and the
         T2I-Adapter arguments of diffusers' StableDiffusionAdapterPipeline: `adapter_image` -- as `control_image`, with the adapter's
         `in_channels` --, `adapter_conditioning_scale`, and `adapter_conditioning_factor`, the fraction of the steps, from the
         first, on which the adapter's features are added).
@@ -1315,7 +1369,7 @@ class I2VAdapterPipeline:
             st = self._assemble_state(
                 latents, cond, timesteps, eta, prompt_embeds, image_embeds, per_frame, 2 if do_cfg else 1, num_frames, guidance_scale,
                 batch_size, height, width, control_image,
-                (float(controlnet_conditioning_scale), float(control_guidance_start), float(control_guidance_end)), adapter_image,
+                self._control_args(controlnet_conditioning_scale, control_guidance_start, control_guidance_end), adapter_image,
                 (float(adapter_conditioning_scale), float(adapter_conditioning_factor)), mask_image, source, noise, generator)
             latents = self._run_rounds(st, timesteps, round_steps, noise, use_graph, callback, callback_steps, eta, generator,
                                        frame_similarity_sample_ratio)
@@ -1562,7 +1616,11 @@ class I2VAdapterPipeline:
         st["coef"] = self.scheduler.step_coefficients(timesteps, eta).to(dev)
         if st.get("cn_cond") is not None:
             from .controlnet import controlnet_keep_table
-            st["cn_scale"] = torch.tensor(controlnet_keep_table(len(timesteps), *st["cn_args"]), dtype=torch.float32, device=dev)
+            if isinstance(st["cn_cond"], tuple):                  # several ControlNets: [N, steps], one row per net
+                rows = [controlnet_keep_table(len(timesteps), *args) for args in st["cn_args"]]
+            else:
+                rows = controlnet_keep_table(len(timesteps), *st["cn_args"])
+            st["cn_scale"] = torch.tensor(rows, dtype=torch.float32, device=dev)
         if st.get("t2i_feats") is not None:
             from .t2i_adapter import adapter_scale_table
             st["t2i_scale"] = torch.tensor(adapter_scale_table(len(timesteps), *st["t2i_args"]), dtype=torch.float32, device=dev)
@@ -1589,7 +1647,15 @@ class I2VAdapterPipeline:
             # (the fused kernel indexes them with the text's context index)
             st["ctx_text"] = st["ctx_text"].view(-1, *st["ctx_text"].shape[2:])
             st["ctx_ip"] = self.unet._expand_image_tokens(st["ctx_ip"], st["ctx_text"].shape[0])
-        if self.controlnet is not None:
+        if self._multi_controlnet():
+            # several ControlNets: as below per net, each with its own frames and channel count; `cn_cond` is the tuple of their tokens
+            conds = []
+            for net, image in zip(self.controlnet.nets, control_image):
+                frames = self.prepare_control_image(image, batch_size, num_frames, height, width, net.config.conditioning_channels)
+                tokens = net.embed_condition(frames.to(dev, f16))
+                conds.append(K.duplicate_batch(tokens) if copies == 2 else tokens)
+            st["cn_cond"], st["cn_args"] = tuple(conds), cn_args
+        elif self.controlnet is not None:
             # once per sample: the embedding of the B * F control frames (duplicated for the second CFG half); the scale table comes
             # with the schedule's, and the ControlNet's context projection and time table are made where the UNet's are (_project_once)
             frames = self.prepare_control_image(control_image, batch_size, num_frames, height, width).to(dev, f16)
@@ -1692,6 +1758,8 @@ class I2VAdapterPipeline:
         latents, cond, noise, source, timesteps = self._initial_latents(
             cond, None, batch_size, num_frames, height, width, steps, hf.strength, blurred_strength, generator, None,
             prior_mask_generator, prior_noise_generator, blur_sigma, lowres=(clip, tables, mask_image is not None))
+        if self._multi_controlnet():                     # one entry per net, each resized like a single net's
+            control_image = [self._frames_at(t, height, width) for t in control_image]
         control_image, adapter_image = (self._frames_at(t, height, width) for t in (control_image, adapter_image))
         st = self._assemble_state(latents, cond, timesteps, eta, prompt_embeds, image_embeds, per_frame, copies, num_frames,
                                   guidance_scale, batch_size, height, width, control_image, cn_args, adapter_image, t2i_args,
@@ -1893,17 +1961,26 @@ def build_parser():
                         help="FreeNoise's initial noise behind the first window (diffusers' default: shuffle_context)")
     parser.add_argument("--free_init_fast", action="store_true",
                         help="FreeInit's use_fast_sampling: earlier rounds take fewer steps (every round re-captures the step)")
-    parser.add_argument("--controlnet", type=str, default=None, metavar="PATH",
+    class OneOrList(argparse.Action):
+        """a repeatable option: given once it is the value, as it always was; given again the values become a list"""
+
+        def __call__(self, parser, namespace, value, option_string=None):
+            seen = getattr(namespace, self.dest)
+            setattr(namespace, self.dest, value if seen is None else (seen if isinstance(seen, list) else [seen]) + [value])
+
+    parser.add_argument("--controlnet", type=str, default=None, metavar="PATH", action=OneOrList,
                         help="an SD-1.5 ControlNet folder (config.json + diffusion_pytorch_model.safetensors, e.g. "
-                             "control_v11p_sd15_openpose): every clip follows the control frames of --control_column")
-    parser.add_argument("--control_column", type=str, default=None, metavar="NAME",
+                             "control_v11p_sd15_openpose): every clip follows the control frames of --control_column.  Repeatable "
+                             "(Multi-ControlNet, up to 4): the n-th --controlnet reads the n-th --control_column")
+    parser.add_argument("--control_column", type=str, default=None, metavar="NAME", action=OneOrList,
                         help="the CSV column that holds, per row, a directory of at least num_frames control images (taken in sorted "
-                             "order) or an animated GIF, relative to the CSV")
-    parser.add_argument("--controlnet_scale", type=float, default=1.0, metavar="S", help="controlnet_conditioning_scale (1.0)")
-    parser.add_argument("--control_guidance_start", type=float, default=0.0, metavar="A",
-                        help="fraction of the schedule at which the control starts to act (0.0)")
-    parser.add_argument("--control_guidance_end", type=float, default=1.0, metavar="B",
-                        help="fraction of the schedule at which the control stops acting (1.0)")
+                             "order) or an animated GIF, relative to the CSV; one per --controlnet")
+    parser.add_argument("--controlnet_scale", type=float, default=1.0, metavar="S", nargs="+",
+                        help="controlnet_conditioning_scale (1.0): one value for all nets or one per --controlnet")
+    parser.add_argument("--control_guidance_start", type=float, default=0.0, metavar="A", nargs="+",
+                        help="fraction of the schedule at which the control starts to act (0.0): one value or one per --controlnet")
+    parser.add_argument("--control_guidance_end", type=float, default=1.0, metavar="B", nargs="+",
+                        help="fraction of the schedule at which the control stops acting (1.0): one value or one per --controlnet")
     parser.add_argument("--t2i_adapter", type=str, default=None, metavar="PATH",
                         help="an SD-1.5 T2I-Adapter folder (config.json + diffusion_pytorch_model.safetensors, e.g. "
                              "t2iadapter_depth_sd15v2): every clip follows the control frames of --adapter_column, at no per-step "
@@ -2003,6 +2080,19 @@ def main(argv=None):
     if (args.controlnet is None) != (args.control_column is None):
         logger.error("--controlnet and --control_column come together.")
         return -1
+    as_list = lambda v: [] if v is None else v if isinstance(v, list) else [v]
+    args.controlnet, args.control_column = as_list(args.controlnet) or None, as_list(args.control_column) or None
+    n_nets = len(args.controlnet or [])
+    if n_nets != len(args.control_column or []):
+        logger.error(f"{n_nets} --controlnet and {len(args.control_column)} --control_column: each ControlNet reads its own column.")
+        return -1
+    for flag in ("controlnet_scale", "control_guidance_start", "control_guidance_end"):
+        values = as_list(getattr(args, flag))
+        if len(values) not in (1, max(n_nets, 1)):
+            logger.error(f"--{flag} takes one value or one per --controlnet ({n_nets}), got {len(values)}.")
+            return -1
+        if n_nets <= 1 or len(values) == 1:                # one net, or one value for all nets: the plain number
+            setattr(args, flag, values[0])
     if (args.t2i_adapter is None) != (args.adapter_column is None):
         logger.error("--t2i_adapter and --adapter_column come together.")
         return -1
@@ -2078,10 +2168,14 @@ def main(argv=None):
 
     controlnet = control_paths = None
     if args.controlnet is not None:
-        from .controlnet import ControlNetModel
-        controlnet = ControlNetModel.from_pretrained(args.controlnet)
-        control_paths = [os.path.join(eval_data_dir, str(p)) for p in eval_data_df[args.control_column]]
-        logger.info(f"Successfully loaded ControlNetModel from {args.controlnet}.")
+        from .controlnet import ControlNetModel, MultiControlNetModel
+        nets = [ControlNetModel.from_pretrained(path) for path in args.controlnet]
+        columns = [[os.path.join(eval_data_dir, str(p)) for p in eval_data_df[col]] for col in args.control_column]
+        if len(nets) == 1:
+            controlnet, control_paths = nets[0], columns[0]
+        else:                                              # per row: one path per net
+            controlnet, control_paths = MultiControlNetModel(nets), list(zip(*columns))
+        logger.info(f"Successfully loaded ControlNetModel from {', '.join(args.controlnet)}.")
     t2i_adapter = adapter_paths = None
     if args.t2i_adapter is not None:
         from .t2i_adapter import T2IAdapter
@@ -2150,7 +2244,9 @@ def main(argv=None):
             image = dict(ip_adapter_image=condition_images[ind]) if args.ip_adapter else {}      # pipe:796
         control = {}
         if controlnet is not None:
-            control = dict(control_image=load_control_frames(control_paths[ind], args.num_frames),
+            paths = control_paths[ind]
+            control = dict(control_image=load_control_frames(paths, args.num_frames) if isinstance(paths, str) else
+                           [load_control_frames(p, args.num_frames) for p in paths],
                            controlnet_conditioning_scale=args.controlnet_scale, control_guidance_start=args.control_guidance_start,
                            control_guidance_end=args.control_guidance_end)
         if t2i_adapter is not None:

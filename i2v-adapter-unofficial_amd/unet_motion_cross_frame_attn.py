@@ -762,13 +762,16 @@ class UNetMotionCrossFrameAttnModel(UNetLoraMixin, SampleProjectionMixin, Pretra
 
     def _fwd_tokens(self, x, temb, enable_cross_frame_attn, ctx_text, ctx_ip, num_frames, cfg_shared=False, temb_proj=None,
                     forward_upsample_size=False, down_residuals=None, mid_residual=None, residual_scale=None,
-                    intrablock_residuals=None, intrablock_scale=None):
+                    intrablock_residuals=None, intrablock_scale=None, residual_sets=None):
         """x: model-input tokens [B*F, H, W, cin_pad] fp16; temb [B, 4*C0] fp16 (pre-SiLU) -- or temb_proj [B or 1, sum Cout]:
         the resnets' time-embedding projections already computed (project_time_table); ctx_text [B, Lt, D]
         (+ ctx_ip [B, 4, D]) or a ProjectedContext; returns noise-prediction tokens [B*F, H, W, out_channels].
         down_residuals / mid_residual (a ControlNet's outputs, unet:1299-1300): token tensors shaped like the skip tensors (full
         batch, also under cfg_shared) and like the mid block's output; residual_scale = (fp32 table, int32 step counter) on the
         device, or None for scale 1 (K.add_residuals).
+        residual_sets (several ControlNets' outputs, instead of down_residuals / mid_residual): a list of N (down tensors, mid
+        tensor) pairs, each as above; residual_scale then carries an fp32 [N, rows] table, one row per set.  All sets are added in
+        one launch for the skip tensors and one for the mid tensor (K.add_multi_residuals): summed in fp32, rounded once.
         intrablock_residuals (a T2I-Adapter's features, diffusers' down_intrablock_additional_residuals): one token tensor per down
         block, [n, h, w, C] of that block's level with n dividing the full batch (also under cfg_shared); intrablock_scale as
         residual_scale.  A block with cross-attention adds its tensor to the output of its last layer, before that is recorded as a
@@ -780,6 +783,8 @@ class UNetMotionCrossFrameAttnModel(UNetLoraMixin, SampleProjectionMixin, Pretra
         if intrablock_residuals is not None:
             intrablock_residuals = list(intrablock_residuals)
             self._check_intrablock_residuals(intrablock_residuals, tuple(x.shape))
+        if residual_sets is not None and (down_residuals is not None or mid_residual is not None):
+            raise ValueError("residual_sets comes instead of down_residuals / mid_residual, not beside them")
         p = self.packed()
         wt, bt, slices = self._temb_pack()
         # ResnetBlock2D: time_emb_proj(nonlinearity(temb)) of all 22 resnets in one GEMM
@@ -812,9 +817,16 @@ class UNetMotionCrossFrameAttnModel(UNetLoraMixin, SampleProjectionMixin, Pretra
             # new tensors: the last skip tensor IS the mid block's input, which takes no residual (no down-sampler after the last
             # block); an in-place add would change what the mid block reads
             res = tuple(K.add_residuals(res, down_residuals, scale=residual_scale))
+        elif residual_sets is not None:
+            for k, (down, _) in enumerate(residual_sets):
+                if len(down) != len(res):
+                    raise ValueError(f"residual set {k}: {len(down)} tensors for {len(res)} skip tensors")
+            res = tuple(K.add_multi_residuals(res, [down for down, _ in residual_sets], scale=residual_scale))
         x = self.mid_block._fwd(x, temb_act, enable_cross_frame_attn, ctx_text, ctx_ip, num_frames)
         if mid_residual is not None:                                                    # unet:1402-1403
             x, = K.add_residuals([x], [mid_residual], scale=residual_scale, out=[x])
+        elif residual_sets is not None:
+            x, = K.add_multi_residuals([x], [[mid] for _, mid in residual_sets], scale=residual_scale, out=[x])
         upsample_size = None
         for bi, blk in enumerate(self.up_blocks):                                       # unet:1406-1436
             r = res[-len(blk.resnets):]

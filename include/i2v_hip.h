@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define I2V_ABI_VERSION 32
+#define I2V_ABI_VERSION 33
 
 #define I2V_OK 0
 #define I2V_ERR_INVALID_ARG (-1)
@@ -842,6 +842,44 @@ typedef struct i2v_add_residuals_params {
   const int32_t* step_idx;
 } i2v_add_residuals_params;
 int i2v_add_residuals_f16(const i2v_add_residuals_params* p, i2v_stream_t stream);
+
+/* (ABI 33) The residuals of several ControlNets (diffusers' MultiControlNetModel) into the UNet's skip tensors in ONE launch: for up to
+ * I2V_ADD_RES_MAX tensors and n_nets in 1..I2V_ADD_RES_NETS_MAX nets,
+ *           dst_i = skip_i + sum_k s_k * res_k_i,     s_k = scale_table[k * scale_rows + min(max(step_idx[0], 0), scale_rows - 1)]
+ *       scale_table fp32 [n_nets, scale_rows] (one row of scale_rows values per net) and step_idx (one int32) are DEVICE memory, read
+ *       by the kernel.  step_idx NULL: row 0.  scale_table NULL: every s_k = 1.  res[k] for k >= n_nets is not read.
+ *       The skip is read once and written once whatever n_nets is: (n_nets + 2) streams, not the 3 n_nets of one
+ *       i2v_add_residuals_f16 launch per net, and one rounding to fp16, not n_nets.
+ *       Arithmetic in fp32, every operation rounded on its own (no fused multiply-add): p_k = s_k * res_k, acc = p_0 + p_1 + ... in
+ *       net order, dst = rn16(skip + acc); with the precise residual stream (skip_lo / dst_lo both given)
+ *       sum = (skip + skip_lo) + acc, dst = rn16(sum), dst_lo = rn16(sum - dst).  Where every p_k is exactly zero the skip's bits (and
+ *       its low half's) are kept, -0 included.  Hence, bit for bit: n_nets = 1 is i2v_add_residuals_f16 on the same operands, and a
+ *       net whose products are all exactly zero (s_k = 0) changes no bit of what the remaining nets give.
+ *       All tensors fp16, dense, numel values each; dst may be skip (in place) and may not overlap anything else, no res in particular.
+ *       Grid and tile walk as i2v_add_residuals_f16: at most 2048 workgroups of 256 lanes over 16 KB tiles, the tensor of a tile found
+ *       through prefix sums in the launch's own parameter block; one kernel per n_nets.
+ *       I2V_ERR_INVALID_ARG (nothing launched): n outside 1..I2V_ADD_RES_MAX, n_nets outside 1..I2V_ADD_RES_NETS_MAX, a null dst / skip /
+ *       res[k < n_nets], numel not a positive multiple of 8, a pointer that is not 16-byte aligned, skip_lo and dst_lo not both given or
+ *       both null, dst_lo == dst, dst or dst_lo equal to a res, scale_table with scale_rows < 1, scale_table / step_idx not 4-byte
+ *       aligned. */
+#define I2V_ADD_RES_NETS_MAX 4
+typedef struct i2v_add_multi_residuals_entry {
+  void* dst;
+  void* dst_lo;
+  const void* skip;
+  const void* skip_lo;
+  const void* res[I2V_ADD_RES_NETS_MAX];
+  int64_t numel;
+} i2v_add_multi_residuals_entry;
+typedef struct i2v_add_multi_residuals_params {
+  i2v_add_multi_residuals_entry t[I2V_ADD_RES_MAX];
+  int32_t n;
+  int32_t n_nets;
+  int32_t scale_rows;
+  const float* scale_table;
+  const int32_t* step_idx;
+} i2v_add_multi_residuals_params;
+int i2v_add_multi_residuals_f16(const i2v_add_multi_residuals_params* p, i2v_stream_t stream);
 
 /* (ABI 23) The layer of AutoencoderTiny (TAESD, diffusers' AutoencoderTiny): a 3x3 / pad 1 / stride 1 convolution with Cin = Cout = 64 on
  * token-major fp16 images [n_img, height, width, 64] and its epilogue in one launch,

@@ -10,7 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # I2V_LIB_PATH selects another build of the same ABI (same-box A/B of two kernels, tools/ab_bench.sh); the in-tree
 # library is never overwritten by tooling
 LIB_PATH = os.environ.get("I2V_LIB_PATH") or os.path.join(_HERE, "libi2v_hip.so")
-ABI_VERSION = 33
+ABI_VERSION = 34
 
 I2V_EPI_NONE, I2V_EPI_GELU, I2V_EPI_GEGLU = 0, 1, 2
 I2V_STORE_ROWMAJOR, I2V_STORE_ROWPERM, I2V_STORE_VT, I2V_STORE_VT_T = 0, 1, 2, 3
@@ -282,6 +282,20 @@ class ConvC64Params(C.Structure):
     ]
 
 
+class ConvDenseParams(C.Structure):
+    _fields_ = [
+        ("x", C.c_void_p), ("ldx", C.c_int64),
+        ("w", C.c_void_p), ("bias", C.c_void_p),
+        ("r1", C.c_void_p), ("ldr1", C.c_int64),
+        ("r2", C.c_void_p), ("ldr2", C.c_int64),
+        ("out", C.c_void_p), ("ldo", C.c_int64),
+        ("n_img", C.c_int32), ("height", C.c_int32), ("width", C.c_int32),
+        ("cin", C.c_int32), ("cout", C.c_int32),
+        ("slope", C.c_float), ("s1", C.c_float), ("s2", C.c_float),
+        ("max_workgroups", C.c_int32),
+    ]
+
+
 # every symbol include/i2v_hip.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 SIGNATURES = {
@@ -400,6 +414,9 @@ SIGNATURES = {
     "i2v_conv3x3_c64_prelu_f16": (C.c_int, [C.POINTER(ConvC64Params), _P, _P]),
     "i2v_pixel_shuffle_add_f32": (C.c_int, [_P, C.c_int64, _P, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                             C.c_int32, C.c_int32, _P]),
+    "i2v_conv3x3_dense_f16": (C.c_int, [C.POINTER(ConvDenseParams), _P]),
+    "i2v_conv3x3_c64_up2_prelu_f16": (C.c_int, [C.POINTER(ConvC64Params), _P, _P]),
+    "i2v_rgb_exit_f32": (C.c_int, [_P, C.c_int64, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),
     "i2v_taesd_prep_f16": (C.c_int, [_P, C.c_int32, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),
     "i2v_pixel_unshuffle8_f16": (C.c_int, [_P, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),
     "i2v_avgpool2x_f16": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),

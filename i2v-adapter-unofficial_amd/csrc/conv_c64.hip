@@ -44,7 +44,10 @@ constexpr int C6_PIECES = C6_HP * 8;                     // 16-byte pieces of a 
 constexpr int C6_NLD = (C6_PIECES + 255) / 256;          // per thread: 6
 static_assert((C6_HP - 1 | 6) < 192 && C6_PLANE % 256 == 0 && C6_LDS <= 160 * 1024, "LDS image");
 
-template <bool PRELU>
+// UP2 (conv_c64_kernel<true, true>, i2v_conv3x3_c64_up2_prelu_f16): x is the image at HALF the size and the convolution runs on its
+// nearest-2x upsampling, which is never written: halo pixel (y, x) of the 2H x 2W grid is source pixel (y >> 1, x >> 1), zero outside
+// the grid.  Only the fetch differs.
+template <bool PRELU, bool UP2 = false>
 __global__ __launch_bounds__(256, 1) void conv_c64_kernel(const i2v_conv_c64_params p, const int tiles_x, const int tiles_y, const int ntiles,
                                                           const float* __restrict__ slope) {
   extern __shared__ __attribute__((aligned(16))) char smem[];     // W fragments, then [2] halo tiles
@@ -54,7 +57,7 @@ __global__ __launch_bounds__(256, 1) void conv_c64_kernel(const i2v_conv_c64_par
   const f16* __restrict__ X = reinterpret_cast<const f16*>(p.x);
   const int H = p.height, Wd = p.width;
   const int ldx = (int)p.ldx;
-  const int64_t img_stride = (int64_t)H * Wd * p.ldx;
+  const int64_t img_stride = UP2 ? (int64_t)(H >> 1) * (Wd >> 1) * p.ldx : (int64_t)H * Wd * p.ldx;
 
   // ---- weights into LDS: a straight copy of the packed image
   {
@@ -83,7 +86,10 @@ __global__ __launch_bounds__(256, 1) void conv_c64_kernel(const i2v_conv_c64_par
     for (int i = 0; i < C6_NLD; ++i) {
       const int y = ty * C6_TH + (hyx[i] >> 8) - 1, x = tx * C6_TW + (hyx[i] & 255) - 1;
       const bool in = dst_off[i] >= 0 && y >= 0 && y < H && x >= 0 && x < Wd;
-      st[i] = in ? ld_global_16B(Xi + (y * Wd + x) * ldx) : zero8();
+      if constexpr (UP2)
+        st[i] = in ? ld_global_16B(Xi + ((y >> 1) * (Wd >> 1) + (x >> 1)) * ldx) : zero8();
+      else
+        st[i] = in ? ld_global_16B(Xi + (y * Wd + x) * ldx) : zero8();
     }
   };
   auto commit = [&](const int buf) {
@@ -232,8 +238,10 @@ __global__ __launch_bounds__(256) void taesd_prep_kernel(const void* __restrict_
 
 namespace {
 
-// the argument checks and the launch of both entry points: `fn` names the entry in the messages, `prelu` selects the instantiation
-int conv_c64_launch(const char* fn, const i2v_conv_c64_params* p, const bool prelu, const void* slope, i2v_stream_t stream) {
+// the argument checks and the launch of the entry points: `fn` names the entry in the messages, `prelu` / `up2` select the instantiation
+// (up2: height and width are the OUTPUT's, both even; x holds n_img images of half that size)
+int conv_c64_launch(const char* fn, const i2v_conv_c64_params* p, const bool prelu, const void* slope, i2v_stream_t stream,
+                    const bool up2 = false) {
   I2V_CHECK_ARG(p != nullptr, "%s: null params", fn);
   I2V_CHECK_ARG(p->x && p->w && p->out, "%s: null pointer", fn);
   I2V_CHECK_ARG(p->cin == C6_C && p->cout == C6_C, "%s: Cin %d, Cout %d: this kernel is the 64 -> 64 convolution", fn, p->cin,
@@ -246,9 +254,11 @@ int conv_c64_launch(const char* fn, const i2v_conv_c64_params* p, const bool pre
                 "%s: residual pixel stride %lld must be >= 64 and a multiple of 8", fn, (long long)p->ldr);
   I2V_CHECK_ARG(i2v_al16(p->x) && i2v_al16(p->w) && i2v_al16(p->out) && i2v_al16(p->bias) && i2v_al16(p->residual),
                 "%s: operands must be 16-byte aligned", fn);
+  I2V_CHECK_ARG(!up2 || (p->height % 2 == 0 && p->width % 2 == 0), "%s: output height %d and width %d must be even (twice the source's)", fn,
+                p->height, p->width);
   const int64_t hw = (int64_t)p->height * p->width, pixels = hw * p->n_img;
   I2V_CHECK_ARG(hw * p->ldx < lim && pixels < lim, "%s: problem too large", fn);
-  const int64_t xb = ((pixels - 1) * p->ldx + C6_C) * 2, ob = ((pixels - 1) * p->ldo + C6_C) * 2;      // bytes from the first to the last element
+  const int64_t xb = (((up2 ? pixels / 4 : pixels) - 1) * p->ldx + C6_C) * 2, ob = ((pixels - 1) * p->ldo + C6_C) * 2;      // bytes from the first to the last element
   // other workgroups read x as halo while this one stores: out may not be x
   I2V_CHECK_ARG(!i2v_overlap(p->out, ob, p->x, xb), "%s: out overlaps x (other workgroups read x as halo)", fn);
   I2V_CHECK_ARG(!i2v_overlap(p->out, ob, p->w, C6_WBYTES) && (p->bias == nullptr || !i2v_overlap(p->out, ob, p->bias, C6_C * 2)),
@@ -265,13 +275,18 @@ int conv_c64_launch(const char* fn, const i2v_conv_c64_params* p, const bool pre
   const int tiles_x = (int)i2v_cdiv(p->width, C6_TW), tiles_y = (int)i2v_cdiv(p->height, C6_TH);
   const int64_t ntiles = (int64_t)p->n_img * tiles_x * tiles_y;
   I2V_CHECK_ARG(ntiles < lim - (1 << 20), "%s: problem too large", fn);
-  const void* kernel = prelu ? reinterpret_cast<const void*>(conv_c64_kernel<true>) : reinterpret_cast<const void*>(conv_c64_kernel<false>);
+  const void* kernel = up2     ? reinterpret_cast<const void*>(conv_c64_kernel<true, true>)
+                       : prelu ? reinterpret_cast<const void*>(conv_c64_kernel<true>)
+                               : reinterpret_cast<const void*>(conv_c64_kernel<false>);
   const int cus = i2v_big_lds_kernel_cus(kernel, C6_LDS);
   if (cus <= 0) I2V_FAIL(I2V_ERR_UNSUPPORTED, "%s: the device refuses %d bytes of LDS", fn, C6_LDS);
   int64_t grid = p->max_workgroups > 0 ? p->max_workgroups : cus;
   if (grid > ntiles) grid = ntiles;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (prelu)
+  if (up2)
+    hipLaunchKernelGGL((conv_c64_kernel<true, true>), dim3((unsigned)grid), dim3(256), C6_LDS, st, *p, tiles_x, tiles_y, (int)ntiles,
+                       reinterpret_cast<const float*>(slope));
+  else if (prelu)
     hipLaunchKernelGGL(conv_c64_kernel<true>, dim3((unsigned)grid), dim3(256), C6_LDS, st, *p, tiles_x, tiles_y, (int)ntiles,
                        reinterpret_cast<const float*>(slope));
   else
@@ -288,6 +303,10 @@ extern "C" int i2v_conv3x3_c64_f16(const i2v_conv_c64_params* p, i2v_stream_t st
 
 extern "C" int i2v_conv3x3_c64_prelu_f16(const i2v_conv_c64_params* p, const void* slope, i2v_stream_t stream) {
   return conv_c64_launch("i2v_conv3x3_c64_prelu_f16", p, true, slope, stream);
+}
+
+extern "C" int i2v_conv3x3_c64_up2_prelu_f16(const i2v_conv_c64_params* p, const void* slope, i2v_stream_t stream) {
+  return conv_c64_launch("i2v_conv3x3_c64_up2_prelu_f16", p, true, slope, stream, true);
 }
 
 extern "C" int i2v_taesd_prep_f16(const void* src, int32_t src_is_f32, void* dst, int64_t ld_dst, int32_t n, int32_t c, int32_t hw, int32_t mode,

@@ -123,3 +123,41 @@ extern "C" int i2v_pixel_shuffle_add_f32(const void* y, int64_t ld, const void* 
     ps_launch<4>(a, f32, grid, st);
   return i2v_check_launch("i2v_pixel_shuffle_add_f32");
 }
+
+// The exit of RRDBNet (upscaler.RRDBNet): there is no shuffle and no base, only the layout change, the caller's clamp and the range map,
+//   out[n, col, y, x] = range( clamp( float(y[n, y, x, col]) ) ),      token-major fp16 (pixel stride >= 3, any) -> NCHW fp32.
+// One lane per pixel: three 2-byte loads of one pixel, three stores that are contiguous across the wave (one per colour plane).
+namespace {
+
+__global__ __launch_bounds__(256) void rgb_exit_kernel(const f16* __restrict__ y, const int64_t ld, float* __restrict__ out, const int64_t pixels,
+                                                       const int64_t hw, const int clamp, const int signed_out) {
+  const int64_t stride = (int64_t)gridDim.x * 256;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < pixels; i += stride) {
+    const int64_t img = i / hw, px = i - img * hw;
+#pragma unroll
+    for (int col = 0; col < 3; ++col) {
+      float v = (float)y[i * ld + col];
+      if (clamp) v = fminf(fmaxf(v, 0.0f), 1.0f);
+      if (signed_out) v = 2.0f * v - 1.0f;
+      out[(img * 3 + col) * hw + px] = v;
+    }
+  }
+}
+
+}  // namespace
+
+extern "C" int i2v_rgb_exit_f32(const void* y, int64_t ld, float* out, int32_t n, int32_t h, int32_t w, int32_t clamp, int32_t signed_out,
+                                i2v_stream_t stream) {
+  I2V_CHECK_ARG(y && out, "i2v_rgb_exit_f32: null pointer");
+  I2V_CHECK_ARG(n >= 1 && h >= 1 && w >= 1, "i2v_rgb_exit_f32: n %d, h %d, w %d must be positive", n, h, w);
+  I2V_CHECK_ARG(ld >= 3 && ld < (1 << 20), "i2v_rgb_exit_f32: pixel stride ld %lld must be >= 3", (long long)ld);
+  I2V_CHECK_ARG((reinterpret_cast<uintptr_t>(y) & 1) == 0 && (reinterpret_cast<uintptr_t>(out) & 3) == 0,
+                "i2v_rgb_exit_f32: y and out must be aligned to their elements");
+  const int64_t hw = (int64_t)h * w, pixels = hw * n;
+  I2V_CHECK_ARG(pixels < ((int64_t)1 << 36), "i2v_rgb_exit_f32: problem too large");
+  I2V_CHECK_ARG(!i2v_overlap(out, pixels * 12, y, ((pixels - 1) * ld + 3) * 2), "i2v_rgb_exit_f32: out overlaps y");
+  const unsigned grid = i2v_ew_grid(pixels, 256, 8192);
+  hipLaunchKernelGGL(rgb_exit_kernel, dim3(grid), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), reinterpret_cast<const f16*>(y), ld, out,
+                     pixels, hw, clamp != 0, signed_out != 0);
+  return i2v_check_launch("i2v_rgb_exit_f32");
+}

@@ -433,6 +433,121 @@ def conv3x3_c64(x, w_packed, bias=None, *, relu_mid=False, relu_out=False, resid
     return out
 
 
+def conv3x3_c64_up2(x, w_packed, bias, slope, *, out=None, max_workgroups=None):
+    """out = prelu(conv3x3(nearest_2x(x)) + bias; slope) without the upsampled tensor (i2v_conv3x3_c64_up2_prelu_f16): the 64-channel
+    kernel's halo fetch reads source pixel (y >> 1, x >> 1).  x: token-major fp16 [N, H, W, 64] view; out: [N, 2 H, 2 W, 64];
+    w_packed from `pack_conv_c64`; bias fp16 [64] or None; slope fp32 [64]."""
+    lib = _lib.load()
+    ldx = _pixel_stride(x, "x")
+    n, h, wd, c = x.shape
+    _req(w_packed, "w_packed")
+    if w_packed.numel() != 9 * 64 * 64 or not w_packed.is_contiguous():
+        raise ValueError(f"w_packed must be the {9 * 64 * 64} values of pack_conv_c64, got {tuple(w_packed.shape)}")
+    if out is None:
+        out = torch.empty((n, 2 * h, 2 * wd, c), dtype=f16, device=x.device)
+    ldo = _pixel_stride(out, "out")
+    if tuple(out.shape) != (n, 2 * h, 2 * wd, c):
+        raise ValueError(f"out must be {(n, 2 * h, 2 * wd, c)}, got {tuple(out.shape)}")
+    p = _lib.ConvC64Params()
+    p.x, p.ldx, p.w, p.out, p.ldo = _p(x), ldx, _p(w_packed), _p(out), ldo
+    if bias is not None:
+        _req(bias, "bias")
+        if bias.numel() != c or not bias.is_contiguous():
+            raise ValueError("bias must be a contiguous vector of Cout elements")
+        p.bias = _p(bias)
+    p.n_img, p.height, p.width, p.cin, p.cout = n, 2 * h, 2 * wd, c, c
+    p.max_workgroups = 0 if max_workgroups is None else int(max_workgroups)
+    if max_workgroups is not None and p.max_workgroups < 1:
+        raise ValueError(f"max_workgroups must be positive, got {max_workgroups}")
+    _req(slope, "slope", dtype=torch.float32)
+    if slope.numel() != 64 or not slope.is_contiguous():
+        raise ValueError("slope must be a contiguous fp32 vector of 64 elements")
+    _lib.check(lib.i2v_conv3x3_c64_up2_prelu_f16(C.byref(p), _p(slope), _stream()), "i2v_conv3x3_c64_up2_prelu_f16")
+    return out
+
+
+DENSE_CIN = (64, 96, 128, 160, 192)
+DENSE_TILE = (16, 16)          # the dense kernel's output tile (rows, columns): the tests' sizes are built on it
+
+
+def pack_conv_dense(weight: torch.Tensor) -> torch.Tensor:
+    """[Cout in (32, 64), Cin in DENSE_CIN, 3, 3] -> the 9 Cin Cout fp16 of `conv3x3_dense`'s weight in the kernel's MFMA-fragment
+    order (include/i2v_hip.h, i2v_conv_dense_params.w), 32 output channels after 32:
+        packed[half, chunk, tap, b, 16 g + l, j] = W[32 half + 8 (l >> 2) + 4 b + (l & 3), 32 chunk + 8 g + j, tap]."""
+    co, ci = weight.shape[:2]
+    if co not in (32, 64) or ci not in DENSE_CIN or tuple(weight.shape[2:]) != (3, 3):
+        raise ValueError(f"pack_conv_dense takes a [32 | 64, {' | '.join(map(str, DENSE_CIN))}, 3, 3] weight, got {tuple(weight.shape)}")
+    # cout = 32 half + 8 q + 4 b + e, cin = 32 chunk + 8 g + j  ->  [half, chunk, tap, b, (g, (q, e)), j]
+    w = weight.detach().reshape(co // 32, 4, 2, 4, ci // 32, 4, 8, 9)                         # [half, q, b, e, chunk, g, j, tap]
+    return w.permute(0, 4, 7, 2, 5, 1, 3, 6).reshape(-1).to(f16).contiguous()
+
+
+def conv3x3_dense(buf, cin, w_packed, bias=None, *, out, slope=0.2, s1=1.0, r1=None, s2=1.0, r2=None, max_workgroups=None):
+    """out = fp16(s2 (s1 lrelu(conv3x3(buf[..., :cin]) + bias; slope) + r1) + r2): a layer of an RRDBNet dense block in one launch
+    (i2v_conv3x3_dense_f16).  buf: token-major fp16 [N, H, W, >= cin] view (pixel stride a multiple of 8) of which only channels
+    < cin are read; cin in DENSE_CIN; w_packed from `pack_conv_dense` (Cout = numel / (9 cin): 32 or 64); bias fp16 [Cout];
+    out, r1, r2: [N, H, W, Cout] views.  out may be other channels of buf's pixels (`buf[..., cin: cin + 32]`: the block's
+    concatenation is never built) and may be r1 or r2; any other overlap is refused.  slope 1: no activation.  max_workgroups caps
+    the persistent grid and never changes the result."""
+    lib = _lib.load()
+    ldx = _pixel_stride(buf, "buf")
+    n, h, wd, c = buf.shape
+    cin = int(cin)
+    if cin not in DENSE_CIN:
+        raise ValueError(f"cin must be one of {DENSE_CIN}, got {cin}")
+    if c < cin:
+        raise ValueError(f"buf has {c} channels, fewer than cin {cin}")
+    _req(w_packed, "w_packed")
+    cout = w_packed.numel() // (9 * cin)
+    if cout not in (32, 64) or w_packed.numel() != 9 * cin * cout or not w_packed.is_contiguous():
+        raise ValueError(f"w_packed must be the 9 x {cin} x (32 | 64) values of pack_conv_dense, got {tuple(w_packed.shape)}")
+    p = _lib.ConvDenseParams()
+    p.x, p.ldx, p.w = _p(buf), ldx, _p(w_packed)
+    for name, t in (("out", out), ("r1", r1), ("r2", r2)):
+        if t is None:
+            continue
+        ld = _pixel_stride(t, name)
+        if tuple(t.shape) != (n, h, wd, cout) or t.device != buf.device:
+            raise ValueError(f"{name} must be {(n, h, wd, cout)} on buf's device, got {tuple(t.shape)}")
+        if name == "out":
+            p.out, p.ldo = _p(t), ld
+        elif name == "r1":
+            p.r1, p.ldr1 = _p(t), ld
+        else:
+            p.r2, p.ldr2 = _p(t), ld
+    if out is None:
+        raise ValueError("out is required (a view of the block's buffer, or of the next block's)")
+    if bias is not None:
+        _req(bias, "bias")
+        if bias.numel() != cout or not bias.is_contiguous():
+            raise ValueError("bias must be a contiguous vector of Cout elements")
+        p.bias = _p(bias)
+    p.n_img, p.height, p.width, p.cin, p.cout = n, h, wd, cin, cout
+    p.slope, p.s1, p.s2 = float(slope), float(s1), float(s2)
+    p.max_workgroups = 0 if max_workgroups is None else int(max_workgroups)
+    if max_workgroups is not None and p.max_workgroups < 1:
+        raise ValueError(f"max_workgroups must be positive, got {max_workgroups}")
+    _lib.check(lib.i2v_conv3x3_dense_f16(C.byref(p), _stream()), "i2v_conv3x3_dense_f16")
+    return out
+
+
+def rgb_exit(y, *, clamp=True, signed_out=False, out=None):
+    """RRDBNet's exit (i2v_rgb_exit_f32): y token-major fp16 [N, H, W, >= 3] view -> fp32 NCHW [N, 3, H, W] of channels 0..2, clamped
+    to [0, 1] (clamp), then 2 v - 1 (signed_out)."""
+    lib = _lib.load()
+    ld = _pixel_stride(y, "y")
+    n, h, w, c = y.shape
+    if c < 3:
+        raise ValueError(f"y must have at least 3 channels, got {c}")
+    if out is None:
+        out = torch.empty((n, 3, h, w), dtype=torch.float32, device=y.device)
+    _req(out, "out", dtype=torch.float32)
+    if tuple(out.shape) != (n, 3, h, w) or not out.is_contiguous():
+        raise ValueError(f"out must be a contiguous {(n, 3, h, w)}, got {tuple(out.shape)}")
+    _lib.check(lib.i2v_rgb_exit_f32(_p(y), ld, _p(out), n, h, w, int(bool(clamp)), int(bool(signed_out)), _stream()), "i2v_rgb_exit_f32")
+    return out
+
+
 TAESD_PREP_MODES = {"identity": _lib.I2V_TAESD_PREP_IDENTITY, "unit": _lib.I2V_TAESD_PREP_UNIT, "clamp": _lib.I2V_TAESD_PREP_CLAMP,
                     "unit_clamp": _lib.I2V_TAESD_PREP_UNIT_CLAMP}
 

@@ -463,13 +463,18 @@ class I2VAdapterPipeline:
 
     def enable_upscaler(self, model_or_path, frames_per_batch: Optional[int] = None, act_type: Optional[str] = None):
         """The pixel-space upscale the AnimateDiff front ends run after sampling: while enabled, the decoded frames of
-        every call go through a Real-ESRGAN compact model (`upscaler.SRVGGNetCompact`: realesr-animevideov3, realesr-general-x4v3)
-        before `tensor2vid` / "pt" -- s x the size, s the model's `upscale`.  `model_or_path`: a `SRVGGNetCompact`, a released `.pth`,
-        a `.safetensors` file or a state dict (`act_type` "relu" / "leakyrelu" for a dict without PReLU weights).  `frames_per_batch`
+        every call go through a Real-ESRGAN model -- a compact one (`upscaler.SRVGGNetCompact`: realesr-animevideov3,
+        realesr-general-x4v3) or an RRDBNet (`upscaler.RRDBNet`: RealESRGAN_x4plus, RealESRGAN_x4plus_anime_6B), picked by
+        the file's keys (`upscaler.load_upscaler`) -- before `tensor2vid` / "pt": s x the size, s the model's `upscale`.
+        `model_or_path`: a `SRVGGNetCompact`, an `RRDBNet`, a released `.pth`, a `.safetensors` file or a state dict (`act_type` "relu" /
+        "leakyrelu" for a compact dict without PReLU weights; with an RRDBNet it is a ValueError).  `frames_per_batch`
         frames go through the network at a time (None: all of them; one under `enable_vae_slicing`): frames are independent, so the
         result is the same bits for every chunking.  There is nothing to upscale in latents: a call with output_type="latent" is
-        refused while the upscaler is enabled.  The sampler and the captured step are untouched."""
-        from .upscaler import SRVGGNetCompact
+        refused while the upscaler is enabled.  The sampler and the captured step are untouched.
+        Memory of an RRDBNet: three dense-block buffers of 192 channels at the input size plus two 64-channel activations at 4 x the
+        size are alive at the peak -- for 16 frames of 512 x 512, 3 x 1.6 GB = 4.8 GB and 2 x 8.6 GB at 2048 x 2048 (fp16), next to the
+        fp32 result (3.2 GB).  `frames_per_batch` bounds it: the peak is per chunk."""
+        from .upscaler import RRDBNet, SRVGGNetCompact, load_upscaler
         if frames_per_batch is not None and (isinstance(frames_per_batch, bool) or not isinstance(frames_per_batch, int)
                                              or frames_per_batch < 1):
             raise ValueError(f"`frames_per_batch` must be a positive integer or None, got {frames_per_batch!r}")
@@ -477,8 +482,12 @@ class I2VAdapterPipeline:
             if act_type is not None and act_type != model_or_path.act_type:
                 raise ValueError(f"act_type={act_type!r}, but the model was built with {model_or_path.act_type!r}")
             model = model_or_path
+        elif isinstance(model_or_path, RRDBNet):
+            if act_type is not None:
+                raise ValueError(f"act_type={act_type!r} with an RRDBNet: the architecture's activation is LeakyReLU(0.2)")
+            model = model_or_path
         else:
-            model = SRVGGNetCompact.from_pretrained(model_or_path, act_type=act_type)
+            model = load_upscaler(model_or_path, act_type=act_type)
             unet = getattr(self, "unet", None)
             if unet is not None and unet.device.type == "cuda":
                 model = model.to(unet.device)
@@ -1942,8 +1951,9 @@ def build_parser():
                         help="an AutoencoderTiny (TAESD) folder (config.json + diffusion_pytorch_model.safetensors) loaded in place of "
                              "<model_path>/vae: the cheap decode that goes with --scheduler lcm (no tiling: not with --vae_tiling)")
     parser.add_argument("--upscaler", type=str, default=None, metavar="PATH",
-                        help="a Real-ESRGAN compact model (realesr-animevideov3 / realesr-general-x4v3: .pth, .pt or .safetensors) run on "
-                             "the decoded frames (pipe.enable_upscaler()): the GIFs are `upscale` x the size")
+                        help="a Real-ESRGAN model -- compact (realesr-animevideov3 / realesr-general-x4v3) or RRDBNet (RealESRGAN_x4plus, "
+                             "RealESRGAN_x4plus_anime_6B), picked by the file's keys: .pth, .pt or .safetensors -- run on the decoded "
+                             "frames (pipe.enable_upscaler()): the GIFs are `upscale` x the size")
     parser.add_argument("--upscaler_act", type=str, default=None, choices=("prelu", "relu", "leakyrelu"),
                         help="with --upscaler: the activation of a file without PReLU weights (relu or leakyrelu)")
     parser.add_argument("--free_init", type=int, nargs="?", const=3, default=None, metavar="N",

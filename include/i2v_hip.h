@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define I2V_ABI_VERSION 33
+#define I2V_ABI_VERSION 34
 
 #define I2V_OK 0
 #define I2V_ERR_INVALID_ARG (-1)
@@ -944,6 +944,53 @@ int i2v_taesd_prep_f16(const void* src, int32_t src_is_f32, void* dst, int64_t l
  *       map other than the two. */
 int i2v_pixel_shuffle_add_f32(const void* y, int64_t ld, const void* src, int32_t src_is_f32, float* out, int32_t n, int32_t h, int32_t w,
                               int32_t s, int32_t entry_mode, int32_t clamp, int32_t signed_out, i2v_stream_t stream);
+
+/* (ABI 34) The layer of an RRDBNet dense block (Real-ESRGAN x4plus; upscaler.RRDBNet): a 3x3 / pad 1 / stride 1 convolution of the FIRST cin
+ * channels of a token-major fp16 image x [n_img, height, width] (pixel stride ldx >= cin) to cout channels, with a leaky ReLU and two scaled
+ * residual stages, one launch:
+ *           v = conv(x[..., 0:cin]) + bias;   v = v >= 0 ? v : slope v;   out = fp16( s2 * (s1 * v + r1) + r2 )
+ *       fp32 arithmetic in this order, one rounding.  cin: 64, 96, 128, 160 or 192; cout: 32 or 64; slope 1: no activation.  bias (fp16
+ *       [cout]), r1 and r2 (token-major fp16, cout channels, strides ldr1 / ldr2) are optional: an absent residual adds 0.  Strides are in
+ *       elements, multiples of 8; bases 16-byte aligned.  No channel >= cin of x is read, only the cout channels of out's pixels are written.
+ *       A dense block lives in one buffer of 192 channels (no concatenation): out may be OTHER CHANNELS OF x's PIXELS -- the same stride and
+ *       a channel offset c0 = ((out - x) mod ldx) with c0 >= cin and c0 + cout <= ldx; any other overlap of out with x is refused (other
+ *       workgroups read x as halo).  out may BE r1 or r2 (same base and stride); any other overlap with them, w or bias is refused.
+ *       w: [cout, cin, 3, 3] in the kernel's MFMA-fragment order, 9 cin cout fp16 (`kernels.pack_conv_dense`), 32 output channels after 32:
+ *           w[((((half * (cin / 32) + chunk) * 9 + tap) * 2 + b) * 64 + 16 g + l) * 8 + j]
+ *               = W[cout = 32 half + 8 (l >> 2) + 4 b + (l & 3)][cin = 32 chunk + 8 g + j][tap]
+ *       A halo-tile kernel, persistent over 16 x 16-pixel tiles, with the weight of 32 output channels resident in LDS (576 cin bytes) and
+ *       the halo staged in double-buffered 32-channel chunks (2 x 21504 bytes): 78 .. 150 KB, one workgroup per CU.  cout 64: even and
+ *       odd workgroups own one half each (a single workgroup walks the tiles twice).  max_workgroups > 0 caps the grid, 0: one per CU;
+ *       the result does not depend on the grid.
+ *       I2V_ERR_INVALID_ARG (nothing launched): null / misaligned operands, cin or cout outside the lists, a bad stride, a refused overlap,
+ *       a NaN scalar.  I2V_ERR_UNSUPPORTED: the device refuses the kernel its LDS. */
+typedef struct i2v_conv_dense_params {
+  const void* x;
+  int64_t ldx;
+  const void* w;
+  const void* bias;
+  const void* r1;
+  int64_t ldr1;
+  const void* r2;
+  int64_t ldr2;
+  void* out;
+  int64_t ldo;
+  int32_t n_img, height, width;
+  int32_t cin, cout;
+  float slope, s1, s2;
+  int32_t max_workgroups;
+} i2v_conv_dense_params;
+int i2v_conv3x3_dense_f16(const i2v_conv_dense_params* p, i2v_stream_t stream);
+/* (ABI 34) i2v_conv3x3_c64_prelu_f16 on the nearest-2x upsampling of x, which is never written: p->height and p->width are the OUTPUT's (both
+ *       even), x holds n_img images of half that size, and halo pixel (y, x) of the output grid reads source pixel (y >> 1, x >> 1) -- zero
+ *       outside the grid.  The third instantiation of the 64-channel kernel; only its fetch differs.  residual and out are at the output size.
+ *       Every argument check is that entry's, with x's extent taken at the source size; in addition an odd height or width is refused. */
+int i2v_conv3x3_c64_up2_prelu_f16(const i2v_conv_c64_params* p, const void* slope, i2v_stream_t stream);
+/* (ABI 34) RRDBNet's exit: y token-major fp16 [n, h, w] pixels of stride ld (>= 3, any), channels 0..2 read -> out NCHW fp32 [n, 3, h, w]:
+ *           v = float(y[n, y, x, col]);   clamp != 0: v = min(max(v, 0), 1);   signed_out != 0: v = 2 v - 1        (exact but for 2 v - 1: 2^-24)
+ *       I2V_ERR_INVALID_ARG: null / misaligned operands, out overlapping y, ld < 3. */
+int i2v_rgb_exit_f32(const void* y, int64_t ld, float* out, int32_t n, int32_t h, int32_t w, int32_t clamp, int32_t signed_out,
+                     i2v_stream_t stream);
 
 /* (ABI 24) T2I-Adapter (diffusers 0.24 `T2IAdapter`, adapter_type "full_adapter"; t2i_adapter.py).  The adapter reads the control frames
  * only -- never the latents or the timestep -- so its network runs once per sample and a denoising step adds four stored feature maps to the

@@ -10,7 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # I2V_LIB_PATH selects another build of the same ABI (same-box A/B of two kernels, tools/ab_bench.sh); the in-tree
 # library is never overwritten by tooling
 LIB_PATH = os.environ.get("I2V_LIB_PATH") or os.path.join(_HERE, "libi2v_hip.so")
-ABI_VERSION = 34
+ABI_VERSION = 35
 
 I2V_EPI_NONE, I2V_EPI_GELU, I2V_EPI_GEGLU = 0, 1, 2
 I2V_STORE_ROWMAJOR, I2V_STORE_ROWPERM, I2V_STORE_VT, I2V_STORE_VT_T = 0, 1, 2, 3
@@ -86,6 +86,18 @@ class AttnParams(C.Structure):
         ("scale", C.c_float), ("accumulate", C.c_int32), ("acc_scale", C.c_float),
         ("lse", C.c_void_p),
     ]
+
+
+class AttnRoute(C.Structure):
+    """struct i2v_attn_route: the kernel instantiation an attention-forward problem takes, and its launch"""
+    _fields_ = [
+        ("dqk", C.c_int32), ("dpv", C.c_int32), ("spare", C.c_int32), ("qt", C.c_int32), ("kvt", C.c_int32),
+        ("walk", C.c_int32), ("qbw", C.c_int32),
+        ("grid_x", C.c_int32), ("grid_y", C.c_int32), ("grid_z", C.c_int32), ("remap", C.c_int32),
+    ]
+
+    def as_dict(self):
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
 
 
 class AttnBwdParams(C.Structure):
@@ -311,6 +323,9 @@ SIGNATURES = {
     "i2v_gemm_last_route": (C.c_int, [C.POINTER(GemmRoute)]),
     "i2v_gemm_kernel_exists": (C.c_int, [C.POINTER(GemmRoute)]),
     "i2v_attention_f16": (C.c_int, [C.POINTER(AttnParams), _P]),
+    "i2v_attention_route": (C.c_int, [C.c_int32] * 6 + [C.POINTER(AttnRoute)]),
+    "i2v_attention_last_route": (C.c_int, [C.POINTER(AttnRoute)]),
+    "i2v_attn_kernel_exists": (C.c_int, [C.POINTER(AttnRoute)]),
     "i2v_temporal_attention_f16": (C.c_int, [C.POINTER(TAttnParams), _P]),
     "i2v_temporal_attention_route": (C.c_int, [C.POINTER(TAttnParams), C.POINTER(TAttnRoute)]),
     "i2v_temporal_attention_last_route": (C.c_int, [C.POINTER(TAttnRoute)]),

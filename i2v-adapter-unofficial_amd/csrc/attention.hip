@@ -69,6 +69,20 @@ __device__ __forceinline__ uint32_t pack_rn(float a, float b) {
 #ifndef I2V_ATTN_OCC_D80
 #define I2V_ATTN_OCC_D80 1
 #endif
+// Which workgroup-to-(query block, head, batch) mapping a launch of `gx x gy x gz` workgroups over `lk` keys uses: the short-key
+// re-deal (remap 1), else the pair re-deal (remap 2), else the natural order (remap 0); both re-deals are described where the kernel
+// applies them.  THE condition, written once: the kernel passes its gridDim and the two re-deals as callables, the host's plan
+// (attn_plan) the grid it is about to launch and callables that note which one applies.  (Callables and not a returned mode: inlined
+// into the kernel they leave it, instruction for instruction, the if / else-if it had.)
+template <class Short, class Pairs>
+__host__ __device__ __forceinline__ void attn_remap(int lk, int gx, int gz, int n_pairs, Short&& short_keys, Pairs&& pairs) {
+  if (I2V_ATTN_XCD_REMAP && lk <= 128 && (gx * gz) % 8 == 0) {
+    short_keys();
+  } else if (I2V_ATTN_XCD_REMAP && n_pairs % 8 == 0) {   // n_pairs = gy gz: the (batch, head) pairs
+    pairs();
+  }
+}
+
 template <int DQK, int DPV, int QT, int KVT, bool SPARE, bool WALK = false>
 __global__ __launch_bounds__(256)
 __attribute__((amdgpu_waves_per_eu(DQK == 64 && DPV == 48 && QT == 2 && KVT == 64 && !WALK ? 4 : (DQK == 96 && DPV == 80 && !WALK ? I2V_ATTN_OCC_D80 : 1))))
@@ -99,24 +113,27 @@ void attn_kernel(const i2v_attn_params p, const float scale_log2, const int qbw_
   int qb = blockIdx.x, h = blockIdx.y, bq = blockIdx.z;
   {
     const int nqb = gridDim.x, pairs = gridDim.y * gridDim.z;
-    if (I2V_ATTN_XCD_REMAP && p.lk <= 128 && (nqb * (int)gridDim.z) % 8 == 0) {
-      // short key sequences (the 77 text tokens): K / V^T are a few KB, the traffic is Q and O, whose rows interleave the
-      // heads (80-byte slices of 640-byte rows at d = 40).  Here an XCD walks the HEADS of one query block back to back, so
-      // that the slices of a row meet in one L2: each line of Q is fetched from HBM once and each line of O leaves whole.
-      const int lin = blockIdx.x + nqb * (blockIdx.y + gridDim.y * blockIdx.z);
-      const int xcd = lin & 7, slot = lin >> 3;
-      h = slot % (int)gridDim.y;
-      const int unit = (slot / (int)gridDim.y) * 8 + xcd;
-      qb = unit % nqb;
-      bq = unit / nqb;
-    } else if (I2V_ATTN_XCD_REMAP && pairs % 8 == 0) {
-      const int lin = blockIdx.x + nqb * (blockIdx.y + gridDim.y * blockIdx.z);
-      const int xcd = lin & 7, slot = lin >> 3;
-      const int pair = (slot / nqb) * 8 + xcd;
-      qb = slot % nqb;
-      h = pair % (int)gridDim.y;
-      bq = pair / (int)gridDim.y;
-    }
+    attn_remap(
+        p.lk, nqb, (int)gridDim.z, pairs,
+        [&] {
+          // short key sequences (the 77 text tokens): K / V^T are a few KB, the traffic is Q and O, whose rows interleave the
+          // heads (80-byte slices of 640-byte rows at d = 40).  Here an XCD walks the HEADS of one query block back to back, so
+          // that the slices of a row meet in one L2: each line of Q is fetched from HBM once and each line of O leaves whole.
+          const int lin = blockIdx.x + nqb * (blockIdx.y + gridDim.y * blockIdx.z);
+          const int xcd = lin & 7, slot = lin >> 3;
+          h = slot % (int)gridDim.y;
+          const int unit = (slot / (int)gridDim.y) * 8 + xcd;
+          qb = unit % nqb;
+          bq = unit / nqb;
+        },
+        [&] {
+          const int lin = blockIdx.x + nqb * (blockIdx.y + gridDim.y * blockIdx.z);
+          const int xcd = lin & 7, slot = lin >> 3;
+          const int pair = (slot / nqb) * 8 + xcd;
+          qb = slot % nqb;
+          h = pair % (int)gridDim.y;
+          bq = pair / (int)gridDim.y;
+        });
   }
   const int bkv = bq / p.kv_group;
   const int d = p.head_dim, lq = p.lq, lk = p.lk;
@@ -460,72 +477,105 @@ void attn_kernel(const i2v_attn_params p, const float scale_log2, const int qbw_
 
 inline bool al(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0; }
 
-template <int DQK, int DPV, bool SPARE>
-int launch_q(const i2v_attn_params& p, hipStream_t s) {
-  const float scale_log2 = p.scale * 1.4426950408889634f;
+using Route = struct i2v_attn_route;   // (include/i2v_hip.h)
+
+// ---- THE launch table: every attn_kernel instantiation the library holds, keyed by its template arguments.  The launch
+// (i2v_attention_f16) and the existence query (i2v_attn_kernel_exists) both walk this array.
+struct Entry {
+  int dqk, dpv, spare, qt, kvt, walk;
+  void (*launch)(const i2v_attn_params& p, float scale_log2, int qbw, dim3 grid, hipStream_t s);
+};
+#define ONE(DQK, DPV, SPARE, QT, KVT, WALK)                                                         \
+  {DQK, DPV, SPARE, QT, KVT, WALK, [](const i2v_attn_params& p, float scale_log2, int qbw, dim3 grid, hipStream_t s) { \
+     hipLaunchKernelGGL((attn_kernel<DQK, DPV, QT, KVT, SPARE, WALK>), grid, dim3(256), 0, s, p, scale_log2, qbw); \
+   }}
+#define TILE(DQK, DPV, KVT)                                                                                  \
+  ONE(DQK, DPV, false, 1, KVT, false), ONE(DQK, DPV, false, 1, KVT, true), ONE(DQK, DPV, false, 2, KVT, false), \
+  ONE(DQK, DPV, false, 2, KVT, true), ONE(DQK, DPV, true, 1, KVT, false), ONE(DQK, DPV, true, 1, KVT, true),  \
+  ONE(DQK, DPV, true, 2, KVT, false), ONE(DQK, DPV, true, 2, KVT, true)
+// head-dim classes <DQK, DPV> in ascending order: a head_dim takes the first class whose DPV holds it (SPARE: head_dim < DPV).
+// 64-key tiles for every class; 96-key tiles where 96 keys x DQK / 8 chunks are a multiple of the 256 threads (DQK 64); 128-key
+// tiles up to DQK 64 (reached through I2V_ATTN_KVT=128 only)
+const Entry TABLE[] = {TILE(32, 16, 64),  TILE(32, 32, 64),  TILE(64, 48, 64),    TILE(64, 64, 64),   TILE(96, 80, 64), TILE(96, 96, 64),
+                       TILE(128, 128, 64), TILE(160, 160, 64), TILE(64, 48, 96),    TILE(64, 64, 96),
+                       TILE(32, 16, 128), TILE(32, 32, 128), TILE(64, 48, 128),   TILE(64, 64, 128)};
+#undef ONE
+#undef TILE
+constexpr int CLASSES[][2] = {{32, 16}, {32, 32}, {64, 48}, {64, 64}, {96, 80}, {96, 96}, {128, 128}, {160, 160}};
+constexpr int MAX_HEAD_DIM = 160;
+
+const Entry* find_entry(int dqk, int dpv, int spare, int qt, int kvt, int walk) {
+  for (const Entry& e : TABLE)
+    if (e.dqk == dqk && e.dpv == dpv && e.spare == spare && e.qt == qt && e.kvt == kvt && e.walk == walk) return &e;
+  return nullptr;
+}
+
+// the sizes of a problem: what the route depends on
+struct Sizes {
+  int batch_q, kv_group, heads, head_dim, lq, lk;
+};
+
+// what the kernels assume of the sizes
+int check_sizes(const Sizes& z, const char* who) {
+  I2V_CHECK_ARG(z.batch_q > 0 && z.kv_group > 0 && z.batch_q % z.kv_group == 0,
+                "%s: batch_q (%d) must be a positive multiple of kv_group (%d)", who, z.batch_q, z.kv_group);
+  I2V_CHECK_ARG(z.heads > 0 && z.lq > 0 && z.lk > 0, "%s: heads, lq, lk must be positive", who);
+  I2V_CHECK_ARG(z.head_dim > 0 && z.head_dim % 8 == 0 && z.head_dim <= MAX_HEAD_DIM,
+                "%s: head_dim (%d) must be a multiple of 8 and <= %d", who, z.head_dim, MAX_HEAD_DIM);
+  I2V_CHECK_ARG(z.heads <= 65535 && z.batch_q <= 65535, "%s: heads / batch_q exceed the grid limits", who);
+  return I2V_OK;
+}
+
+// THE dispatch rule: which instantiation runs a problem that passed check_sizes, with which grid.  i2v_attention_f16 launches
+// what this answers and i2v_attention_route reports it; pure host arithmetic.
+Route attn_plan(const Sizes& z) {
+  Route r{};
+  for (const auto& c : CLASSES)
+    if (z.head_dim <= c[1]) {
+      r.dqk = c[0], r.dpv = c[1];
+      break;
+    }
+  r.spare = z.head_dim < r.dpv;
   // measured (profiles/r1_tile_sweep.txt): 2 query tiles per wave keep 2 waves / SIMD resident, so one wave's
   // softmax VALU overlaps the other's MFMAs; 4 tiles drop to 1 wave / SIMD and serialise the two pipes.
   // head_dim 160 (round 3, tools/attn_only.py): two tiles per wave win there too, although they leave one wave per SIMD
   // (256 + 52 registers): 256 x 256 keys 37 -> 32 us, 1024 x 1024 409 -> 330 us; 128 left at one tile (not on the UNet's path).
-  int qt = 1;
-  if (p.lq >= 128 && (DQK <= 96 || DQK == 160)) qt = 2;
+  r.qt = 1;
+  if (z.lq >= 128 && (r.dqk <= 96 || r.dqk == 160)) r.qt = 2;
   static const int qt_env = getenv("I2V_ATTN_QT") ? atoi(getenv("I2V_ATTN_QT")) : 0;   // tuning overrides
   static const int kvt_env = getenv("I2V_ATTN_KVT") ? atoi(getenv("I2V_ATTN_KVT")) : 0;
-  if (qt_env == 1 || qt_env == 2) qt = qt_env;
-  int kvt = 64;   // 128-key tiles (half the barriers per key) measured 2-4 % slower: the loop is VALU-bound, not sync-bound
+  if (qt_env == 1 || qt_env == 2) r.qt = qt_env;
+  r.kvt = 64;   // 128-key tiles (half the barriers per key) measured 2-4 % slower: the loop is VALU-bound, not sync-bound
   // the 77 text tokens (+ padding) fit ONE 96-key tile: a single trip through the key loop -- no second barrier round trip --
   // and 42 MFMAs / 24 exponentials per 32 queries instead of the 56 / 32 of two 64-key tiles (these launches are 8192
   // workgroups of almost nothing but prologue: 99.6 us at 64 x 64 for 168 MB of Q + O)
   // (head_dim 40 .. 64 only: 96 keys x DQK / 8 chunks must be a multiple of the 256 threads)
-  if (DQK == 64 && p.lk > 64 && p.lk <= 96) kvt = 96;
-  if (kvt_env == 64 || (kvt_env == 128 && DQK <= 64) || (kvt_env == 96 && DQK == 64)) kvt = kvt_env;
-  const dim3 block(256);
-  const int nqb = (int)i2v_cdiv(p.lq, 64 * qt);
+  if (r.dqk == 64 && z.lk > 64 && z.lk <= 96) r.kvt = 96;
+  if (kvt_env == 64 || (kvt_env == 128 && r.dqk <= 64) || (kvt_env == 96 && r.dqk == 64)) r.kvt = kvt_env;
+  const int nqb = (int)i2v_cdiv(z.lq, 64 * r.qt);
   // one key tile covers the whole sequence (the text / image-prompt tokens): walk several query blocks per workgroup so that
   // about 1024 workgroups remain (see WALK)
   static const int walk_off = getenv("I2V_ATTN_WALK") ? (atoi(getenv("I2V_ATTN_WALK")) == 0) : 0;
-  int qbw = 1;
-  if (!walk_off && p.lk <= kvt) {
-    const int64_t wgs = (int64_t)nqb * p.heads * p.batch_q;
-    qbw = (int)(wgs / 1024);
-    if (qbw > 8) qbw = 8;
-    if (qbw > nqb) qbw = nqb;
-    if (qbw < 1) qbw = 1;
+  r.qbw = 1;
+  if (!walk_off && z.lk <= r.kvt) {
+    const int64_t wgs = (int64_t)nqb * z.heads * z.batch_q;
+    r.qbw = (int)(wgs / 1024 > 8 ? 8 : wgs / 1024);
+    if (r.qbw > nqb) r.qbw = nqb;
+    if (r.qbw < 1) r.qbw = 1;
   }
   // (measured and removed: O staged through a per-wave LDS slab and stored as 16-byte row chunks instead of the accumulator
   //  layout's 8-byte pieces -- 77.7 vs 73.6 us; a head-major layout of q / o (80-byte rows contiguous) -- 72.7 vs 73.6 us;
   //  with 4 keys instead of 77 the launch still takes 56 us against 24 us for a copy of Q to O: what is left is the per-block
   //  instruction count of the single-tile path, tools/attn77_probe.py)
-  const bool walk = qbw > 1;
-  const dim3 grid((unsigned)i2v_cdiv(nqb, qbw), (unsigned)p.heads, (unsigned)p.batch_q);
-#define I2V_ATTN_LAUNCH(QTV, KVTV)                                                                                       \
-  do {                                                                                                                   \
-    if (walk)                                                                                                            \
-      hipLaunchKernelGGL((attn_kernel<DQK, DPV, QTV, KVTV, SPARE, true>), grid, block, 0, s, p, scale_log2, qbw);        \
-    else                                                                                                                 \
-      hipLaunchKernelGGL((attn_kernel<DQK, DPV, QTV, KVTV, SPARE, false>), grid, block, 0, s, p, scale_log2, 1);         \
-  } while (0)
-  if constexpr (DQK == 64) {
-    if (kvt == 96) {
-      if (qt == 2) I2V_ATTN_LAUNCH(2, 96); else I2V_ATTN_LAUNCH(1, 96);
-      return i2v_check_launch("i2v_attention_f16");
-    }
-  }
-  if constexpr (DQK <= 64) {
-    if (kvt == 128) {
-      if (qt == 2) I2V_ATTN_LAUNCH(2, 128); else I2V_ATTN_LAUNCH(1, 128);
-      return i2v_check_launch("i2v_attention_f16");
-    }
-  }
-  if (qt == 2) I2V_ATTN_LAUNCH(2, 64); else I2V_ATTN_LAUNCH(1, 64);
-#undef I2V_ATTN_LAUNCH
-  return i2v_check_launch("i2v_attention_f16");
+  r.walk = r.qbw > 1;
+  r.grid_x = (int32_t)i2v_cdiv(nqb, r.qbw), r.grid_y = z.heads, r.grid_z = z.batch_q;
+  r.remap = 0;
+  attn_remap(z.lk, r.grid_x, r.grid_z, r.grid_y * r.grid_z, [&] { r.remap = 1; }, [&] { r.remap = 2; });
+  return r;
 }
 
-template <int DQK, int DPV>
-int launch_d(const i2v_attn_params& p, hipStream_t s) {
-  return p.head_dim < DPV ? launch_q<DQK, DPV, true>(p, s) : launch_q<DQK, DPV, false>(p, s);
-}
+thread_local Route last_route;
+thread_local bool have_last_route = false;
 
 }  // namespace
 
@@ -541,12 +591,9 @@ extern "C" int i2v_attention_f16(const i2v_attn_params* pp, i2v_stream_t stream)
   I2V_CHECK_ARG(pp != nullptr, "i2v_attention_f16: null params");
   const i2v_attn_params& p = *pp;
   I2V_CHECK_ARG(p.q && p.k && p.vt && p.o, "i2v_attention_f16: null pointer");
-  I2V_CHECK_ARG(p.batch_q > 0 && p.kv_group > 0 && p.batch_q % p.kv_group == 0,
-                "i2v_attention_f16: batch_q (%d) must be a positive multiple of kv_group (%d)", p.batch_q, p.kv_group);
-  I2V_CHECK_ARG(p.heads > 0 && p.lq > 0 && p.lk > 0, "i2v_attention_f16: heads, lq, lk must be positive");
+  const Sizes z{p.batch_q, p.kv_group, p.heads, p.head_dim, p.lq, p.lk};
+  if (const int rc = check_sizes(z, "i2v_attention_f16")) return rc;
   I2V_CHECK_ARG(!(p.lse != nullptr && p.accumulate), "i2v_attention_f16: lse output is not combined with accumulate");
-  I2V_CHECK_ARG(p.head_dim > 0 && p.head_dim % 8 == 0 && p.head_dim <= 160,
-                "i2v_attention_f16: head_dim (%d) must be a multiple of 8 and <= 160", p.head_dim);
   I2V_CHECK_ARG(p.q_row_stride % 8 == 0 && p.k_row_stride % 8 == 0 && p.q_batch_stride % 8 == 0 &&
                     p.k_batch_stride % 8 == 0,
                 "i2v_attention_f16: q / k strides must be multiples of 8 elements");
@@ -554,16 +601,13 @@ extern "C" int i2v_attention_f16(const i2v_attn_params* pp, i2v_stream_t stream)
                 "i2v_attention_f16: vt_row_stride must be a multiple of 8 and >= lk rounded up to 8");
   I2V_CHECK_ARG(p.o_row_stride % 4 == 0 && p.o_batch_stride % 4 == 0, "i2v_attention_f16: o strides must be multiples of 4");
   I2V_CHECK_ARG(al(p.q, 16) && al(p.k, 16) && al(p.vt, 16) && al(p.o, 8), "i2v_attention_f16: pointer alignment");
-  I2V_CHECK_ARG(p.heads <= 65535 && p.batch_q <= 65535, "i2v_attention_f16: heads / batch_q exceed the grid limits");
   // the kernel addresses one (batch, head) slice of K and of V^T with 32-bit byte offsets (buffer loads)
   I2V_CHECK_ARG(p.k_row_stride > 0 && ((int64_t)p.lk + 128) * p.k_row_stride * 2 < (1ll << 30) &&
                     p.vt_row_stride > 0 && ((int64_t)p.head_dim * p.vt_row_stride + 256) * 2 < (1ll << 30),
                 "i2v_attention_f16: one (batch, head) slice of K / V^T must span less than 1 GiB");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const int d = p.head_dim;
-  if (d <= 16) return launch_d<32, 16>(p, s);
-  if (d <= 32) return launch_d<32, 32>(p, s);
 #ifdef I2V_VARIANTS
+  const int d = p.head_dim;
   if (d > 32 && d < 48) {
     const int rc = i2v_attention_pipe_try(p, s);
     if (rc != 0) return rc < 0 ? rc : I2V_OK;
@@ -573,10 +617,33 @@ extern "C" int i2v_attention_f16(const i2v_attn_params* pp, i2v_stream_t stream)
     if (rc != 0) return rc < 0 ? rc : I2V_OK;
   }
 #endif
-  if (d <= 48) return launch_d<64, 48>(p, s);
-  if (d <= 64) return launch_d<64, 64>(p, s);
-  if (d <= 80) return launch_d<96, 80>(p, s);
-  if (d <= 96) return launch_d<96, 96>(p, s);
-  if (d <= 128) return launch_d<128, 128>(p, s);
-  return launch_d<160, 160>(p, s);
+  const Route r = attn_plan(z);
+  const Entry* en = find_entry(r.dqk, r.dpv, r.spare, r.qt, r.kvt, r.walk);
+  if (en == nullptr)
+    I2V_FAIL(I2V_ERR_UNSUPPORTED, "i2v_attention_f16: no kernel <%d, %d> spare %d, qt %d, kvt %d, walk %d", r.dqk, r.dpv, r.spare, r.qt,
+             r.kvt, r.walk);
+  last_route = r;
+  have_last_route = true;
+  en->launch(p, p.scale * 1.4426950408889634f, r.qbw, dim3((unsigned)r.grid_x, (unsigned)r.grid_y, (unsigned)r.grid_z), s);
+  return i2v_check_launch("i2v_attention_f16");
+}
+
+extern "C" int i2v_attention_route(int32_t batch_q, int32_t kv_group, int32_t heads, int32_t head_dim, int32_t lq, int32_t lk,
+                                   Route* route) {
+  I2V_CHECK_ARG(route != nullptr, "i2v_attention_route: null argument");
+  const Sizes z{batch_q, kv_group, heads, head_dim, lq, lk};
+  if (const int rc = check_sizes(z, "i2v_attention_route")) return rc;
+  *route = attn_plan(z);
+  return I2V_OK;
+}
+
+extern "C" int i2v_attention_last_route(Route* route) {
+  I2V_CHECK_ARG(route != nullptr, "i2v_attention_last_route: null argument");
+  I2V_CHECK_ARG(have_last_route, "i2v_attention_last_route: this thread has launched no i2v_attention_f16 yet");
+  *route = last_route;
+  return I2V_OK;
+}
+
+extern "C" int i2v_attn_kernel_exists(const Route* r) {
+  return r != nullptr && find_entry(r->dqk, r->dpv, r->spare, r->qt, r->kvt, r->walk) != nullptr ? 1 : 0;
 }

@@ -681,6 +681,21 @@ def attention(q, k, vt, *, batch_q, lq, lk, heads, head_dim, kv_group=1, scale=N
     return (out, lse) if return_lse else out
 
 
+def attn_route(batch_q, kv_group, heads, head_dim, lq, lk) -> dict:
+    """the kernel `attention` takes for these sizes and its launch, as the fields of i2v_attn_route (dqk, dpv, spare, qt, kvt, walk,
+    qbw, grid_x, grid_y, grid_z, remap): host arithmetic, no GPU"""
+    r = _lib.AttnRoute()
+    _lib.check(_lib.load().i2v_attention_route(batch_q, kv_group, heads, head_dim, lq, lk, C.byref(r)), "i2v_attention_route")
+    return r.as_dict()
+
+
+def last_attn_route() -> dict:
+    """the route of this thread's most recent `attention` launch"""
+    r = _lib.AttnRoute()
+    _lib.check(_lib.load().i2v_attention_last_route(C.byref(r)), "i2v_attention_last_route")
+    return r.as_dict()
+
+
 def temporal_attention(q, k, vt, *, n_pixels, frames, heads, head_dim, scale=None, out=None):
     """Motion-module attention over the frame axis; tokens in (b, pixel, frame) order.
     q, k [n_pixels * frames, >= C]; vt [n_pixels, C, >= pad8(frames)].

@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define I2V_ABI_VERSION 34
+#define I2V_ABI_VERSION 35
 
 #define I2V_OK 0
 #define I2V_ERR_INVALID_ARG (-1)
@@ -250,6 +250,35 @@ typedef struct i2v_attn_params {
 } i2v_attn_params;
 
 int i2v_attention_f16(const i2v_attn_params* p, i2v_stream_t stream);
+
+/* (ABI 35) Which kernel an attention-forward problem takes.  i2v_attention_f16 dispatches to 112 kernel instantiations: 8 head-dim
+   classes <dqk, dpv> (<32,16> <32,32> <64,48> <64,64> <96,80> <96,96> <128,128> <160,160>: head_dim takes the first whose dpv
+   holds it), each with or without a spare V^T row (spare: head_dim < dpv, the PV MFMA computes the row sum), with qt = 1 | 2
+   16-row query tiles per wave (2 from lq >= 128 on, except the <128,128> class; I2V_ATTN_QT overrides), as a one-trip kernel or as
+   one that walks qbw query blocks per workgroup (walk: a single key tile and at least 2048 workgroups; I2V_ATTN_WALK=0 turns it
+   off), on kvt = 64-key tiles; dqk = 64 also on 96-key tiles (64 < lk <= 96) and dqk <= 64 on 128-key tiles (I2V_ATTN_KVT=128
+   only).  The route is decided by the same function the launch follows, and `remap` by the function the kernel itself calls. */
+struct i2v_attn_route {
+  int32_t dqk, dpv;   /* the head-dim class: head_dim padded to the QK^T contraction (32) and to the PV tile (16)             */
+  int32_t spare;      /* 1: head_dim < dpv                                                                                    */
+  int32_t qt;         /* 16-row query tiles per wave, 1 | 2: a workgroup owns 64 qt query rows per block                      */
+  int32_t kvt;        /* keys per tile: 64 | 96 | 128                                                                         */
+  int32_t walk;       /* 1: the kernel that walks qbw (> 1) consecutive query blocks per workgroup                            */
+  int32_t qbw;        /* query blocks per workgroup, 1..8 (a run-time argument)                                               */
+  int32_t grid_x, grid_y, grid_z; /* the launch: ceil(ceil(lq / (64 qt)) / qbw) x heads x batch_q workgroups                  */
+  int32_t remap;      /* how a workgroup finds its (query block, head, batch): 0 natural order, 1 the short-key re-deal
+                         (lk <= 128, grid_x grid_z % 8 == 0), 2 the pair re-deal (grid_y grid_z % 8 == 0)                     */
+};
+
+/* The route i2v_attention_f16 would take for these sizes: pure host arithmetic, no device call.  The sizes are validated as the
+   launch validates them (< 0: the launch would refuse them, or a null argument). */
+int i2v_attention_route(int32_t batch_q, int32_t kv_group, int32_t heads, int32_t head_dim, int32_t lq, int32_t lk,
+                        struct i2v_attn_route* route);
+/* The route of the calling thread's most recent i2v_attention_f16 that reached a launch (< 0: none yet). */
+int i2v_attention_last_route(struct i2v_attn_route* route);
+/* 1 if the kernel instantiation that `route` names (dqk, dpv, spare, qt, kvt, walk; qbw, the grid and remap are run-time values
+   and are not read) is in the launch table, else 0.  Read from the launch table itself. */
+int i2v_attn_kernel_exists(const struct i2v_attn_route* route);
 
 /* ------------------------------------------------------------------------------------------------
  * Temporal (motion-module) self-attention: sequence = frames (<= 32) of one pixel; tokens are in

@@ -45,7 +45,8 @@ def test_ctypes_structs_match_header(lib):
              "i2v_gn_params": lib.GnParams, "i2v_ln_params": lib.LnParams, "i2v_motion_attn_params": lib.MotionAttnParams,
              "i2v_cross_attn_fused_params": lib.CrossAttnFusedParams, "i2v_ff_fused_params": lib.FfFusedParams,
              "struct i2v_gemm_route": lib.GemmRoute, "struct i2v_tattn_route": lib.TAttnRoute,
-             "i2v_attn_bwd_params": lib.AttnBwdParams, "struct i2v_attn_bwd_route": lib.AttnBwdRoute}
+             "i2v_attn_bwd_params": lib.AttnBwdParams, "struct i2v_attn_bwd_route": lib.AttnBwdRoute,
+             "struct i2v_attn_route": lib.AttnRoute}
     prog = ['#include <stdio.h>', '#include <stddef.h>', f'#include "{HEADER}"', "int main(void){"]
     for cname, cls in names.items():
         prog.append(f'printf("{cname} %zu\\n", sizeof({cname}));')
@@ -113,6 +114,15 @@ def test_bad_arguments_return_error_codes_without_a_gpu(lib):
     assert h.i2v_attention_bwd_route(32, 16, 8, 44, 4096, 4096, 1, C.byref(br)) == -1 and b"head_dim (44)" in h.i2v_last_error()
     assert h.i2v_attention_bwd_route(32, 16, 8, 40, 4096, 4096, 1, None) == -1 and h.i2v_attention_bwd_last_route(None) == -1
     assert h.i2v_attention_bwd_f16(None, None) == -1 and h.i2v_attention_lse_f32(None, None, None) == -1
+    # (ABI 35) the attention forward's route queries: host arithmetic, the launch's own refusals
+    ar = lib.AttnRoute()
+    assert h.i2v_attention_route(32, 1, 8, 40, 4096, 77, C.byref(ar)) == 0
+    assert ar.as_dict() == dict(dqk=64, dpv=48, spare=1, qt=2, kvt=96, walk=1, qbw=8, grid_x=4, grid_y=8, grid_z=32, remap=1)
+    assert h.i2v_attn_kernel_exists(C.byref(ar)) == 1
+    ar.kvt = 32
+    assert h.i2v_attn_kernel_exists(C.byref(ar)) == 0
+    assert h.i2v_attention_route(32, 1, 8, 44, 4096, 77, C.byref(ar)) == -1 and b"head_dim (44)" in h.i2v_last_error()
+    assert h.i2v_attention_route(32, 1, 8, 40, 4096, 77, None) == -1 and h.i2v_attention_last_route(None) == -1
     assert h.i2v_colsum_workspace_bytes(1000, 70) == 4 * 70 * 4 and h.i2v_colsum_det_f32(None, 0, None, 0, None, 0, 0, None, None) == -1
 
 
